@@ -2,7 +2,8 @@
 """bench.py -- element stiffness assemblies per second, 3-D p=3 Poisson on 256^3 elements
 (BASELINE.json metric), one process per GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  --dump-outputs DIR: after the timed steps, a fixed sample of the last step's A and b goes to DIR/*.npy (dump_outputs).
   N>1: either way works -- `python bench.py --gpus N ...` starts its own N ranks (launch_ranks: children of a process that has
   not touched the GPU) and relays rank 0's line; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
   the ranks are the launcher's.
@@ -300,6 +301,66 @@ def build_problem(P, name, size, degree, world, rank, kernel, geometry, source=F
     return g, A, b, U, V, p
 
 
+DUMP_MAT_SCALARS = 1 << 20         # --dump-outputs: matrix entries kept (value, row, column: 24 MB in float64)
+DUMP_VEC_ENTRIES = 1 << 20         # ... and vector entries (value, index: 16 MB)
+
+
+def dump_outputs(outdir, g, A, b):
+    """--dump-outputs: what the timed path handed its caller after the last step -- the assembled matrix A and vector b of this
+    rank -- as float64 .npy files.  A (up to 70 GB at the headline size) and b are sampled on the device: a fixed, seeded set of
+    whole block rows of A and of entries of b, the same for every run with the same arguments, with their global natural
+    indices (node*dof+field) next to the values, so that two builds can be compared entry for entry."""
+    import numpy as np
+    import torch
+
+    def view(ptr, count, typestr):          # a torch tensor over device memory of the library (no copy)
+        class _A:
+            pass
+        a = _A()
+        a.__cuda_array_interface__ = dict(shape=(int(count),), typestr=typestr, data=(int(ptr), False), version=3)
+        return torch.as_tensor(a, device="cuda")
+
+    os.makedirs(outdir, exist_ok=True)
+    g.synchronize()
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(20240611)
+    bs = A.bs
+    p_rp, p_ci, p_val = A.device_ptrs()
+    rp = view(p_rp, A.nbrows + 1, "<i8").cpu().numpy()
+    ci = view(p_ci, A.nblocks, "<i4")
+    val = view(p_val, A.nblocks * bs * bs, "<f8")
+    # whole block rows, drawn without replacement until the scalar budget is spent
+    order = rng.permutation(A.nbrows)
+    blocks = np.diff(rp)
+    take = np.sort(order[: max(1, int(np.searchsorted(np.cumsum(blocks[order]) * bs * bs, DUMP_MAT_SCALARS, side="right")))])
+    starts, counts = rp[:-1][take], blocks[take]
+    first = np.cumsum(counts) - counts                       # offset of each taken row in the gathered list
+    bidx = np.repeat(starts - first, counts) + np.arange(int(counts.sum()))
+    assert bidx.size == 0 or (bidx.min() >= 0 and bidx.max() < A.nblocks)
+    bidx_t = torch.from_numpy(bidx).cuda()
+    cols_b = ci.index_select(0, bidx_t).long().cpu().numpy()
+    sidx = (bidx_t[:, None] * (bs * bs) + torch.arange(bs * bs, device="cuda")[None, :]).reshape(-1)
+    vals = val.index_select(0, sidx).cpu().numpy()
+    nrow, ncol, maps = A.layout()
+    ns = g.sizes()["node_sizes"]
+    r = np.repeat(take.astype(np.int64), counts)
+    grow = maps[0][0][r % nrow[0]].astype(np.int64) + ns[0] * (maps[1][0][(r // nrow[0]) % nrow[1]].astype(np.int64) + ns[1] * maps[2][0][r // (nrow[0] * nrow[1])].astype(np.int64))
+    c = cols_b
+    gcol = maps[0][1][c % ncol[0]].astype(np.int64) + ns[0] * (maps[1][1][(c // ncol[0]) % ncol[1]].astype(np.int64) + ns[1] * maps[2][1][c // (ncol[0] * ncol[1])].astype(np.int64))
+    ii, jj = np.meshgrid(np.arange(bs), np.arange(bs), indexing="ij")
+    rows = (grow[:, None, None] * bs + ii[None]).reshape(-1)
+    cols = (gcol[:, None, None] * bs + jj[None]).reshape(-1)
+    np.save(os.path.join(outdir, "A_values.npy"), vals.astype(np.float64))
+    np.save(os.path.join(outdir, "A_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(outdir, "A_cols.npy"), cols.astype(np.float64))
+    # b: a seeded sample of its entries (all of them when it is small)
+    n = b.n
+    pick = np.arange(n) if n <= DUMP_VEC_ENTRIES else np.sort(rng.choice(n, DUMP_VEC_ENTRIES, replace=False))
+    bv = view(b.device_ptr(), n, "<f8").index_select(0, torch.from_numpy(pick).cuda()).cpu().numpy()
+    np.save(os.path.join(outdir, "b_values.npy"), bv.astype(np.float64))
+    np.save(os.path.join(outdir, "b_index.npy"), b.indices(0)[pick].astype(np.float64))
+
+
 def launch_ranks(n):
     """Starts the n ranks of `bench.py --gpus n` as children of this (GPU-free, torch-free) process: the same command line with
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, rank 0's stdout relayed, the others' kept on stderr.
@@ -354,7 +415,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the N>1 checksum against a single-rank assembly on rank 0")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not spawn the rocprofv3 --pmc passes that measure roofline.traffic (N = 1); replay profiles/traffic.json instead")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's A and b (rank 0's rows) to DIR/*.npy in float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = WORKLOADS[args.form]
     # (NavierStokesVMS at 192^3 is an 8-GPU configuration -- 313 GB of matrix values; on fewer than 4 GPUs the default mesh is
     #  one GPU's share of it, 96^3, and the workload string says so)
@@ -481,6 +546,8 @@ def main():
         dt = float(tmax.item())
     total_elems = size ** 3
     value = total_elems * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g, A, b)
 
     # checksums over the owned rows: partition-independent up to rounding.  N > 1: rank 0 also assembles the whole mesh as a
     # single rank (it fits next to its share on a 288 GB GPU for the headline) and the sums must agree: a lost or doubled

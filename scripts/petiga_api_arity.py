@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates tests/golden/petiga_api_arity.json from the reference's public header (include/petiga.h): the argument count of
 every PETSC_EXTERN function and function-like macro, and the field names of struct _p_IGA / _n_IGAAxis / _n_IGABasis / _n_IGARule /
-_n_IGAForm.  Data about the interface, not its text: tests/test_adapter_signatures.py checks every PetIGA call and every struct
+_n_IGAForm, plus the sha256 of that parse (digest()).  Data about the interface, not its text: tests/test_adapter_signatures.py checks every PetIGA call and every struct
 field the adapter (adapter/petiga_amd_petsc.c, never compiled here: no PETSc) uses against it."""
 import json
 import os
@@ -49,10 +49,19 @@ def parse_header(text):
     return dict(functions=funcs, macros=macros, structs=structs)
 
 
+def digest(data):
+    """sha256 of the parsed interface (functions, macros, structs) in a canonical JSON form: committed next to the fixture as
+    tests/golden/petiga_api_arity.sha256, so that the fixture can be checked against the header it came from without the header."""
+    import hashlib
+    canon = json.dumps({k: data[k] for k in ("functions", "macros", "structs")}, sort_keys=True, separators=(",", ":"))
+    return hashlib.sha256(canon.encode()).hexdigest()
+
+
 if __name__ == "__main__":
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference/include/petiga.h"
+    ref = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.environ.get("PETIGA_DIR", "."), "include", "petiga.h")
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "petiga_api_arity.json")
     data = parse_header(open(ref).read())
     data["source"] = "include/petiga.h of dalcinl/PetIGA (argument counts and field names only)"
     json.dump(data, open(out, "w"), indent=0, sort_keys=True)
+    open(out[:-len(".json")] + ".sha256", "w").write(digest(data) + "\n")
     print(out, len(data["functions"]), "functions", len(data["macros"]), "macros", {k: len(v) for k, v in data["structs"].items()})

@@ -1,7 +1,7 @@
 // fake_rccl.hip -- a TEST DOUBLE for librccl.so's point-to-point API (test infrastructure, not product code).
 //
 // Why: the product transport of the ghost-row exchange (petiga_amd/csrc/comm.hpp, kind == 1) is grouped ncclSend / ncclRecv on a
-// stream, in up to three stream-ordered phases with receives posted ahead of the local assembly.  A gpurun box has ONE GPU, and
+// stream, in up to three stream-ordered phases with receives posted ahead of the local assembly.  A GPU test machine has ONE GPU, and
 // real RCCL refuses several ranks on one device, so that branch could only ever run as a one-rank loopback.  This library
 // exports the same symbols and moves the data between PROCESSES THAT SHARE ONE GPU, keeping the semantics a schedule can
 // depend on (and deadlock on):
@@ -15,9 +15,7 @@
 //     not rely on eager buffering);
 //   * messages between one (sender, receiver) pair match in issue order; a count mismatch is an error (ncclInvalidUsage);
 //   * ncclCommInitRank is a blocking collective over all ranks of the id.
-// FAKE_RCCL_BREAK=recv_first makes every group finish its receives before it starts its sends (what splitting a phase into a
-// receive group followed by a send group on one stream would do): the tests use it to show that the double DOES hang on a
-// schedule that real RCCL would hang on.  FAKE_RCCL_TIMEOUT_S (default 120): a watchdog thread (host memory only, no HIP calls)
+// FAKE_RCCL_TIMEOUT_S (default 120): a watchdog thread (host memory only, no HIP calls)
 // turns a group that stops making progress into a loud abort of the rank (exit code 86) that names the pending operations.
 //
 // Mechanics: a POSIX shared-memory control block per communicator id (one mailbox ring per ordered rank pair), mapped into the
@@ -89,7 +87,6 @@ struct Comm {
   std::atomic<unsigned> issued{0};
   std::mutex mu; std::deque<GroupRec> live;       // groups not yet cleaned up (watchdog reads the op lists)
   std::thread watchdog; std::atomic<bool> stop{false};
-  bool break_recv_first = false;
   double timeout_s = 120.0;
 };
 
@@ -307,11 +304,7 @@ static int launch_group(Comm *c, hipStream_t stream, const std::vector<PendingOp
 
 static int enqueue_group(Comm *c, hipStream_t stream, std::vector<PendingOp> &&ops) {
   reap(c, false);
-  if (!c->break_recv_first) return launch_group(c, stream, ops);
-  std::vector<PendingOp> r, s;
-  for (const PendingOp &p : ops) (p.send ? s : r).push_back(p);
-  if (int rc = launch_group(c, stream, r)) return rc;
-  return launch_group(c, stream, s);
+  return launch_group(c, stream, ops);
 }
 
 static size_t type_bytes(int datatype) {
@@ -362,7 +355,6 @@ int ncclCommInitRank(ncclComm_t *comm, int nranks, ncclUniqueId id, int rank) {
   std::unique_ptr<Comm> c(new Comm());
   c->nranks = nranks; c->rank = rank; c->name = id.internal;
   if (hipGetDevice(&c->device) != hipSuccess) return kUnhandledCudaError;
-  if (const char *e = getenv("FAKE_RCCL_BREAK")) c->break_recv_first = strcmp(e, "recv_first") == 0;
   if (const char *e = getenv("FAKE_RCCL_TIMEOUT_S")) c->timeout_s = atof(e) > 0 ? atof(e) : c->timeout_s;
   c->ctl_bytes = sizeof(Control) + sizeof(Slot) * (size_t)nranks * nranks * kRing;
   // whoever comes first creates and sizes the control block; the others wait for its magic

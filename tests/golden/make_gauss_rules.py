@@ -2,7 +2,7 @@
 
 Run in the build container (the reference tree is not on the GPU box):
 
-    python tests/golden/make_gauss_rules.py [/root/reference]
+    python tests/golden/make_gauss_rules.py [PETIGA_DIR]
 
 It reads `src/petigarule.c` as TEXT, finds the two tabulating functions (`IGA_Rule_GaussLegendre`, :182-319, and
 `IGA_Rule_GaussLobatto`, :321-end), and evaluates the `X[i] = ...; W[i] = ...;` assignments of every `case (q):` with a
@@ -43,7 +43,7 @@ def parse_function(text, name):
 
 
 def main():
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+    ref = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("PETIGA_DIR", ".")
     text = open(os.path.join(ref, "src", "petigarule.c")).read()
     out = {
         "provenance": "dalcinl/PetIGA src/petigarule.c: constants of IGA_Rule_GaussLegendre (q = 1..10) and "

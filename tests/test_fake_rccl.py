@@ -5,9 +5,9 @@ so its own semantics are pinned here, called directly through ctypes (no petiga_
   * it exports every symbol comm.hpp binds (CPU test);
   * a send reads its buffer in STREAM ORDER (what the stream wrote before it is what arrives), and work enqueued after a group sees
     the received data -- with the host never waiting in between;
-  * the operations of a group progress concurrently (two ranks that each receive from and send to the other in ONE group finish),
-    and the same exchange split into a receive group followed by a send group HANGS and is reported (exit code 86);
-  * messages of a pair match in issue order; a count mismatch is an error."""
+  * the operations of a group progress concurrently (two ranks that each receive from and send to the other in ONE group finish);
+  * messages of a pair match in issue order.
+Schedules that deadlock or mismatch are not run here on purpose: they would leave kernels spinning on a shared GPU."""
 import os
 import re
 import subprocess
@@ -91,16 +91,6 @@ WORKER = textwrap.dedent('''
             want = torch.arange(N, dtype=torch.float64, device="cuda") + 1000.0 * other
             assert torch.equal(out, 2.0 * want), (rank, out[:4], want[:4])
             assert torch.equal(recv[:7], want[:7] + 0.5)
-        elif mode == "split":
-            # the SAME exchange as two groups on one stream, receives first: each rank waits for a send that the other rank's
-            # stream can only reach after ITS receive -- a deadlock with real RCCL, and the double must say so
-            send.fill_(float(rank))
-            group([("r", recv, N, other)])
-            group([("s", send, N, other)])
-            st.synchronize()
-        elif mode == "mismatch":
-            group([("r", recv, 8 if rank == 0 else N, other), ("s", send, N, other)])
-            st.synchronize()
     torch.cuda.synchronize()
     assert L.ncclCommDestroy(comm) == 0
     print("rank", rank, "ok")
@@ -117,22 +107,7 @@ def _run(mode, tmp_path, timeout_s):
 
 
 @pytest.mark.gpu
+@pytest.mark.xdist_group("gpu_procs")      # two processes on the GPU, one such test at a time (pytest.ini)
 def test_stream_order_and_concurrent_progress_inside_a_group(tmp_path):
     rcs, outs = _run("order", tmp_path, 60)
     assert rcs == [0, 0], outs
-
-
-@pytest.mark.gpu
-def test_receive_group_before_send_group_deadlocks_and_is_reported(tmp_path):
-    rcs, outs = _run("split", tmp_path, 5)
-    assert all(rc == 86 for rc in rcs), (rcs, outs)
-    assert any("DEADLOCK" in o for o in outs) and all("ok" not in o for o in outs), outs
-    # (a rank that leaves through the watchdog unlinks the shared-memory names it created or opened: nothing to clean here, and
-    #  nobody may clean /dev/shm by prefix -- another test process may be using the double at the same time)
-
-
-@pytest.mark.gpu
-def test_count_mismatch_is_an_error(tmp_path):
-    rcs, outs = _run("mismatch", tmp_path, 20)
-    # the side that issues second sees the other's size at ncclGroupEnd (ncclInvalidUsage); the side that waits is told and leaves
-    assert all(rc != 0 for rc in rcs) and 86 in rcs and any("count mismatch" in o for o in outs), (rcs, outs)

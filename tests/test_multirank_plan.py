@@ -96,6 +96,7 @@ print("rank", rank, "ok", len(s), len(r))
 '''
 
 
+@pytest.mark.xdist_group("gpu_procs")      # the ranks open the GPU on a GPU machine: one such test at a time (pytest.ini)
 @pytest.mark.parametrize("world", [2])
 def test_p2p_pattern_on_gloo(world, tmp_path):
     script = tmp_path / "worker.py"
@@ -145,7 +146,7 @@ def test_a_periodic_ghost_layer_never_wraps_onto_its_own_rank():
     others own at least floor(N / 2) >= p nodes once the axis has the 2p + 1 functions a split periodic axis needs to hold its own
     stencil (refused at IGXSetUp otherwise).  Swept here: every degree, element count and rank count -- never refused; every ghost
     node is sent exactly once and the send / receive lists of all ranks agree.  (The wrapped thin-rank case runs against the oracle
-    on the GPU: tests/test_gpu_comm.py, poisson-p2-5ranks-periodic-wrap.)"""
+    on the GPU: tests/test_gpu_comm.py, poisson-p2-4ranks-periodic-wrap.)"""
     import petiga_amd as P
     for p in (1, 2, 3, 4):
         for N in range(2 * p + 1, 2 * p + 8):
