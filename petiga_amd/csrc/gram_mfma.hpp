@@ -260,7 +260,9 @@ struct PencilArgs {
   int open_hi;             // 1: elements beyond w_hi exist and belong to another pass: the last segment owns no rows past its elements
   int free_run;            // 1: no s_barrier ping-pong between the two wave groups: the SIMD's own arbitration interleaves MFMA and flush phases (IGX_FREE_RUN; default: p = 2 on the identity geometry)
   int wpb;                 // wavefronts (= pencils) per workgroup: 8; 6 for the free-running p = 2 walk on the identity geometry (gram_pencil_w6: three waves per SIMD)
-  int debug_noflush;       // experiment switch: 1 = skip the read-modify-write (timing of the MFMA walk alone)
+  int debug_noflush;       // experiment switch: 1 = skip the read-modify-write (timing of the MFMA walk alone); 3 = skip the MFMA phase of
+                           // the built-in Gram walk (the flush alone: the accumulators keep whatever they hold)
+  int debug_noprio;        // experiment switch: 1 = no s_setprio 3 around the flush
   long long *debug_buf;    // experiment: cycle stamps [block][wave 0 and 4][64 steps][4]
 };
 
@@ -337,6 +339,38 @@ __device__ __forceinline__ void pencil_mfma(d4_t (&acc)[4][4], const PencilLane 
       }
     }
   }
+}
+
+// The same Gram block, sum-factorised along the walk axis.  In pencil_mfma the walk-axis factor of an operand, z_alpha(qw, t), is
+// wave-uniform and uv(qy, alpha) does not depend on qw, so every MFMA is z_alpha(qw, ta) z_alpha(qw, tb) MFMA(uv, uv) and
+//   K_e[ta][tb] = G1[ta][tb] M_w + G0[ta][tb] M_xy,    G_k[ta][tb] = sum_qw z_k(qw, ta) z_k(qw, tb)   (1-D, staged per segment),
+//   M_w = sum_qy MFMA(u0 vy0, u0 vy0),  M_xy = sum_qy MFMA(u1 vy0, u1 vy0) + MFMA(u0 vy1, u0 vy1).
+// M_w and M_xy depend on the pencil only (its X and Y rows): 12 MFMAs once per pencil (pencil_sf_planes); an element is then
+// 2 x 4 v_fma_f64 per tile with wave-uniform G entries (pencil_mfma_sf) instead of 480 MFMAs.  Only the summation order changes.
+template <int NB>
+__device__ __forceinline__ void pencil_sf_planes(const PencilLane &L, d4_t &mw, d4_t &mxy) {
+  d4_t mx = (d4_t){0, 0, 0, 0}, my = mx;
+  mw = mx;
+#pragma unroll
+  for (int qy = 0; qy < NB; ++qy) {   // three independent chains
+    const double vy0 = L.vy[qy * 2 + 0], vy1 = L.vy[qy * 2 + 1];
+    const double cw = L.u0 * vy0, cx = L.u1 * vy0, cy = L.u0 * vy1;
+    mw = __builtin_amdgcn_mfma_f64_16x16x4f64(cw, cw, mw, 0, 0, 0);
+    mx = __builtin_amdgcn_mfma_f64_16x16x4f64(cx, cx, mx, 0, 0, 0);
+    my = __builtin_amdgcn_mfma_f64_16x16x4f64(cy, cy, my, 0, 0, 0);
+  }
+  mxy = mx + my;
+}
+template <bool SYM, int NB>
+__device__ __forceinline__ void pencil_mfma_sf(d4_t (&acc)[4][4], const d4_t &mw, const d4_t &mxy, const double *g /*LDS [4 ta][4 tb][2]: G0, G1*/) {
+#pragma unroll
+  for (int ta = 0; ta < NB; ++ta)
+#pragma unroll
+    for (int tb = SYM ? ta : 0; tb < NB; ++tb) {   // SYM: K_e is symmetric, tile (tb,ta) is the transpose of (ta,tb)
+      const double g0 = g[(ta * 4 + tb) * 2 + 0], g1 = g[(ta * 4 + tb) * 2 + 1];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[ta][tb][r] = __builtin_fma(g0, mxy[r], __builtin_fma(g1, mw[r], acc[ta][tb][r]));
+    }
 }
 
 // p = 2: the k-step (qw, qy, alpha) with k slot qx leaves one slot in four empty (27 x 6 = 162 MFMAs per element); numbering the 27
@@ -1940,8 +1974,9 @@ __device__ __forceinline__ void pencil_mfma_state_geo_p2(d4_t (&acc)[4][4], cons
 
 // ALIAS: the wrapped walk axis (PencilArgs::alias0) known at compile time -- 0: not wrapped, 1: wrapped, -1: read from the arguments.
 // The identity-geometry Gram instantiations come in both fixed flavours, so the headline kernel carries none of the modulo logic.
-template <bool SYSTEM, int W, int P, bool GEO, bool RAT, bool FIXT, class Form, bool IDENT, int ALIAS = -1, bool PACK = false, bool RESID = false>
+template <bool SYSTEM, int W, int P, bool GEO, bool RAT, bool FIXT, class Form, bool IDENT, int ALIAS = -1, bool PACK = false, bool RESID = false, bool SF = false>
 __device__ __forceinline__ void gram_pencil_body(const SpaceDev &S, const OutDev &out, const PencilArgs &pa, const double *prm) {
+  static_assert(!SF || (P == 3 && !GEO && !PACK && is_builtin_gram<Form>::v), "the sum-factorised walk: the p = 3 Gram matrix on the identity geometry");
   static_assert(!RESID || (PACK && IDENT && pencil_state_of<Form>::v && pencil_resid_of<Form>::v), "the fused Residual: a packed Tangent on the identity geometry of a form with the PENCIL_NCR hooks");
   static_assert(!GEO || W == 0, "the mapped-geometry variant walks axis 0");
   static_assert(!PACK || (P == 2 && W == 0 && !FIXT && ((!GEO && is_builtin_gram<Form>::v) || pencil_state_of<Form>::v)),
@@ -1981,12 +2016,30 @@ __device__ __forceinline__ void gram_pencil_body(const SpaceDev &S, const OutDev
   T.lay0 = alias0 ? AW.off[0] + wh : AW.off[wh];             // (alias0: a virtual layer number; rows and tables are taken modulo the axis)
   {
     const int tid = threadIdx.x, nthr = pa.wpb * 64;
+    if constexpr (SF) {      // zt holds the element's 1-D Gram sums G_k[ta][tb] at (ta*4 + tb)*2 + k (pencil_mfma_sf), wq its F factors
+      for (int i = tid; i < ne * 32; i += nthr) {             // of the walk axis sum_q sqrt(wJ) (sqrt(wJ) N_a) -- what the F sum below forms from zt
+        const int e = i >> 5, j = i & 31, ta = j >> 3, tb = (j >> 1) & 3, k = j & 1, eg = ew(e);
+        const double *tw = AW.tab + (size_t)eg * NB * NB * NDER;
+        double g = 0;
+#pragma unroll
+        for (int q = 0; q < NB; ++q) { const double sq = sqrt(AW.w[eg * NB + q] * AW.J[eg]); g += (tw[(q * NB + ta) * NDER + k] * sq) * (tw[(q * NB + tb) * NDER + k] * sq); }
+        T.zt[i] = g;
+      }
+      for (int i = tid; i < ne * 4; i += nthr) {
+        const int e = i >> 2, a = i & 3, eg = ew(e);
+        double sw = 0;
+#pragma unroll
+        for (int q = 0; q < NB; ++q) { const double sq = sqrt(AW.w[eg * NB + q] * AW.J[eg]); sw += sq * (AW.tab[((size_t)eg * NB * NB + q * NB + a) * NDER] * sq); }
+        T.wq[i] = sw;
+      }
+    } else {
     if (!GEO) for (int i = tid; i < ne * 32; i += nthr) {   // i = e*32 + (q*4 + a)*2 + k ; rows scaled by sqrt(w_q * J_e)
       const int e = i >> 5, j = i & 31, q = j >> 3, aa = (j >> 1) & 3, k = j & 1, eg = ew(e);
       T.zt[i] = (q < NB && aa < NB) ? AW.tab[((size_t)eg * NB * NB + q * NB + aa) * NDER + k] * sqrt(AW.w[eg * NB + q] * AW.J[eg]) : 0.0;
     }
     // (GEO: the weight itself, not its root: the metric carries the whole JW)
     for (int i = tid; i < ne * 4; i += nthr) { const int e = i >> 2, q = i & 3, eg = ew(e); const double wj = (q < NB) ? AW.w[eg * NB + q] * AW.J[eg] : 0.0; T.wq[i] = GEO ? wj : sqrt(wj); }
+    }
     for (int i = tid; i < ne; i += nthr) T.Jz[i] = AW.J[ew(i)];
     for (int i = tid; i < nl; i += nthr) {
       int lay = T.lay0 + i;
@@ -2085,6 +2138,8 @@ __device__ __forceinline__ void gram_pencil_body(const SpaceDev &S, const OutDev
 #pragma unroll
     for (int tb = 0; tb < 4; ++tb) acc[ta][tb] = (d4_t){0, 0, 0, 0};
   double Facc = 0;
+  d4_t sf_mw = (d4_t){0, 0, 0, 0}, sf_mxy = sf_mw;      // SF: the pencil's x-y planes of the Gram block (pencil_sf_planes)
+  if constexpr (SF) pencil_sf_planes<NB>(L, sf_mw, sf_mxy);
   double *hold = nullptr;
   if (W == 0) {
     constexpr int HS = WINMODE == 2 ? WINC_DOUBLES : (WINMODE == 1 ? WIN_DOUBLES : (P * (P + 1) / 2) * 4 * HOLD_LD);      // (PACK: the window of band rows takes the place of the hold area)
@@ -2263,20 +2318,25 @@ __device__ __forceinline__ void gram_pencil_body(const SpaceDev &S, const OutDev
       pencil_win_add(hold, pk, K2, ei);
     }
     else if constexpr (P == 2 && W == 0) pencil_mfma_p2(acc, L.vy - ((lane >> 2) & 3) * 8 + pa.wpb * 32, L.vy, zt, lane);
+    else if (kDebug && pa.debug_noflush == 3) {}      // (IGX_DEBUG_NOFLUSH=3: the flush alone)
+    else if constexpr (SF) pencil_mfma_sf<W == 0, NB>(acc, sf_mw, sf_mxy, zt);
     else pencil_mfma<W, W == 0, NB>(acc, L, zt);
     if (kDebug && pa.debug_buf) tq1 = __builtin_readcyclecounter();
     if (SYSTEM && !GEO) {   // F_a += f * J * prod_d sum_q w N : the walk-axis factor is sum_q sqrt(wJ) * (sqrt(wJ) N)
       double sw = 0;
       const int fs = L.fslot < NB ? L.fslot : 0;
+      if constexpr (SF) sw = wqs[fs];      // (staged with the G sums)
+      else {
 #pragma unroll
       for (int q = 0; q < NB; ++q) sw += wqs[q] * zt[(q * 4 + fs) * 2];
+      }
       if (L.fslot < NB) Facc += L.sxy * sw;
     }
     if (pingpong) __builtin_amdgcn_s_barrier();
     if (kDebug && pa.debug_buf) tq2 = __builtin_readcyclecounter();
     // the partner wavefront on this SIMD now streams MFMAs (one issue slot per 64 cycles); without priority
     // the younger wavefront's address arithmetic only gets the left-over VALU slots (measured: 12k vs 60k cycles)
-    __builtin_amdgcn_s_setprio(3);
+    if (!(kDebug && pa.debug_noprio)) __builtin_amdgcn_s_setprio(3);
     StatePre spn;
     if constexpr (SPLIT) { if (ei + 1 < ne) state_load(ei + 1, spn); }
 #pragma unroll
@@ -2323,10 +2383,10 @@ __device__ __forceinline__ void gram_pencil_body(const SpaceDev &S, const OutDev
   }
 }
 
-template <bool SYSTEM, int W, int P, bool GEO = false, bool RAT = false, bool FIXT = false, int ALIAS = -1>
+template <bool SYSTEM, int W, int P, bool GEO = false, bool RAT = false, bool FIXT = false, int ALIAS = -1, bool SF = false>
 __global__ void __launch_bounds__(512, 2)
 gram_pencil(SpaceDev S, OutDev out, PencilArgs pa) {
-  gram_pencil_body<SYSTEM, W, P, GEO, RAT, FIXT, void, false, ALIAS>(S, out, pa, nullptr);
+  gram_pencil_body<SYSTEM, W, P, GEO, RAT, FIXT, void, false, ALIAS, false, false, SF>(S, out, pa, nullptr);
 }
 
 // Twelve-wave workgroups for the free-running p = 2 walk on the identity geometry (config 2): without the ping-pong nothing ties the
@@ -2500,6 +2560,7 @@ static void launch_pencils(const Space &s, const SpaceDev &S, const OutDev &out,
     if (!color_range(s.lay[X], cx, bx.lo[X], bx.hi[X], pa.ex_start, pa.ex_step, pa.ex_count)) continue;
     if (!color_range(s.lay[Y], cy, bx.lo[Y], bx.hi[Y], pa.ey_start, pa.ey_step, pa.ey_count)) continue;
     const long long pencils = (long long)pa.ex_count * pa.ey_count;
+    const bool sf = P == 3 && !GEO && !mod && s.env.gram_sumfact != 0;
     // p = 2 on the identity geometry: the flush is the longer phase and the rigid ping-pong makes the MFMA wave wait for it; left to
     // the SIMD's own arbitration the walk gains 5 % (128^3: 166.7 -> 175.3 M el/s).  Everything at p = 3, mapped geometries and
     // Tangents lose 6-8 % without the barriers (256^3: 64.8 -> 59.5).  IGX_FREE_RUN=0/1 overrides.
@@ -2544,7 +2605,7 @@ static void launch_pencils(const Space &s, const SpaceDev &S, const OutDev &out,
       pa.blocks_per_seg = (int)((pencils + pa.wpb - 1) / pa.wpb);
     }
     pa.ne_max = pa.seg_len + 3;
-    pa.debug_noflush = s.env.debug_noflush;
+    pa.debug_noflush = s.env.debug_noflush; pa.debug_noprio = s.env.debug_noprio;
     pa.debug_buf = nullptr;
     static int dbg_done = 0, dbg_seen = 0;
     // IGX_DEBUG_TIMING=n: the n-th pencil launch of the process is the one that is stamped (1: the first)
@@ -2565,8 +2626,13 @@ static void launch_pencils(const Space &s, const SpaceDev &S, const OutDev &out,
       void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
       if (hipModuleLaunchKernel(mod->fn, (unsigned)(pa.blocks_per_seg * pa.nseg), 1, 1, 512, 1, 1, (unsigned)lds, stream, nullptr, cfg) != hipSuccess) { pencil_launch_error() = "launch of the run-time instantiation of the pencil walk failed"; return; }
     } else {
+    constexpr bool SFOK = P == 3 && !GEO;      // the sum-factorised Gram walk (pencil_mfma_sf; IGX_GRAM_SUMFACT=0: pencil_mfma)
     void (*kern)(SpaceDev, OutDev, PencilArgs) = gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT>;
-    if constexpr (W == 0 && !GEO) kern = pa.alias0 ? gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 1> : gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 0>;
+    if constexpr (SFOK && W != 0) { if (sf) kern = gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, -1, true>; }
+    if constexpr (W == 0 && !GEO) {
+      if (sf) kern = pa.alias0 ? gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 1, SFOK> : gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 0, SFOK>;
+      else kern = pa.alias0 ? gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 1> : gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 0>;
+    }
     if constexpr (W == 0 && P == 2 && !GEO && !FIXT) {
       if (pack) kern = pa.alias0 ? gram_pencil_w6<SYSTEM, P, 1, true> : gram_pencil_w6<SYSTEM, P, 0, true>;
       else if (w6) kern = pa.alias0 ? gram_pencil_w6<SYSTEM, P, 1> : gram_pencil_w6<SYSTEM, P, 0>;
@@ -2992,6 +3058,9 @@ static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, h
     // (p = 2: 21 k-steps x 6 layer-pair tiles, or x 3 packed tiles)
     dom.flop_per_element = 2048.0 * (deg == 3 ? 48 * (walk_axis == 0 ? 10 : 16) : 21 * ((walk_axis == 0 && pencil_p2_pack(s, deg, geo, fixt, mod != nullptr)) ? 3 : 6));
     if (state) dom.flop_per_element = mod->flop_per_element;
+    // the sum-factorised p = 3 Gram walk (pencil_mfma_sf): 2 fp64 FMAs on each of the 4 accumulator doubles of a tile, 64 lanes (its 12
+    // MFMAs are once per pencil)
+    else if (deg == 3 && !geo && !mod && s.env.gram_sumfact != 0) dom.flop_per_element = 2.0 * 2 * 4 * 64 * (walk_axis == 0 ? 10 : 16);
     // E as disjoint slabs: axis 0 faces (full), axis 1 faces (inside P along 0), axis 2 faces (inside P along 0,1)
     for (int d = 0; d < 3; ++d) for (int side = 0; side < 2; ++side) {
       Box b = all;

@@ -50,8 +50,10 @@ struct EnvSwitches {
   int fuse_resid = 0;        // IGX_FUSE_RESID=1: IGXComputeIFunctionIJacobian takes the fused walk (state_pencil_kr) where it exists; default: the two
                              // drivers one after the other -- measured in round 6: the fused launch costs 2.5 ms more than the Tangent's, the
                              // Residual's own pass 2.1 ms per launch
+  int gram_sumfact = 1;      // IGX_GRAM_SUMFACT=0: the p = 3 Gram walk on the identity geometry keeps its 480 MFMAs per element (pencil_mfma) instead of
+                             // the sum-factorised walk-axis contraction (pencil_mfma_sf)
   int combine = -1;          // IGX_COMBINE: element bricks of the feature kernel (-1 = automatic, 0 = one element per workgroup)
-  int debug_feature = 0, debug_noflush = 0, debug_timing = 0;   // only honoured by -DIGX_DEBUG builds
+  int debug_feature = 0, debug_noflush = 0, debug_timing = 0, debug_noprio = 0;   // only honoured by -DIGX_DEBUG builds
 };
 EnvSwitches read_env_switches();
 
