@@ -88,10 +88,41 @@ def _sampled_rows_vs_scaled_oracle(A, p, N, dof, A_small, Ns, scale, tol=1e-11):
     return rows, srow, nent
 
 
+def _sampled_rows_entrywise(A, b, p, N, rows, bc):
+    """The sampled rows of the full-size Poisson System (and F on them) against the tensor-product reference of the big mesh itself,
+    entry by entry (|E - R| <= c_id u S, tests/tensor_ref.py): its 1-D tables are (N + p)^2 numbers per axis."""
+    import torch
+    import oracle_api as O
+    import tensor_ref as T
+    o1 = O.OracleIGA(1, 1)
+    o1.axis_uniform(0, p, N)
+    o1.setup()
+    tab = T.AxisTables(o1.axis(0), o1.basis(0))
+    bcs = {(d, s, 0): 1.0 for d in range(3) for s in range(2)} if bc else None
+    ref = T.TensorRef([tab] * 3, T.poisson(3), bcs=bcs)
+    rp, ci, val = A.device_ptrs()
+    rpt = torch.as_tensor(_DevArray(rp, A.nbrows + 1, "<i8"), device="cuda")
+    cit = torch.as_tensor(_DevArray(ci, A.nblocks, "<i4"), device="cuda")
+    vt = torch.as_tensor(_DevArray(val, A.nblocks, "<f8"), device="cuda")
+    rows_t = torch.as_tensor(rows, device="cuda")
+    lo, hi = rpt[rows_t].cpu().numpy(), rpt[rows_t + 1].cpu().numpy()
+    idx = np.concatenate([np.arange(a, z) for a, z in zip(lo, hi)])
+    idx_t = torch.as_tensor(idx, device="cuda")
+    r = np.repeat(rows, hi - lo)
+    c, v = cit[idx_t].cpu().numpy().astype(np.int64), vt[idx_t].cpu().numpy()
+    R, S = ref.entries(r, c)
+    worst = T.compare_entrywise((r, c, v), R, S, T.C_ID, ref, "p=%d N=%d K" % (p, N))
+    Rb, Sb = ref.vector(rows)
+    worst_b = T.compare_entrywise((rows, b.get()[rows]), Rb, Sb, T.C_ID, ref, "p=%d N=%d F" % (p, N))
+    print("p=%d N=%d dirichlet=%s: %d entries, worst %.2f u S (K), %.2f u S (F)" % (p, N, bc, r.size, worst, worst_b))
+    return r.size
+
+
 @pytest.mark.parametrize("p,N", [(3, 256), (2, 128)])
 def test_poisson_full_size_values_vs_scaled_oracle(p, N):
     """Every distinct kind of row of the full-size Poisson System -- with and without the Dirichlet data of demo/Poisson3D.c:37-43 --
-    against the CPU oracle's matrix of a (3p + 3)^3 mesh scaled by the ratio of the element sizes; F likewise (h^3)."""
+    against the CPU oracle's matrix of a (3p + 3)^3 mesh scaled by the ratio of the element sizes; F likewise (h^3).  The same rows, and
+    F on them, entry by entry against the tensor-product reference of the big mesh itself."""
     import petiga_amd as P
     import oracle_api as O
     Ns = 3 * p + 3
@@ -123,6 +154,7 @@ def test_poisson_full_size_values_vs_scaled_oracle(p, N):
             M = (D @ M).tocsr()
         rows, srow, nent = _sampled_rows_vs_scaled_oracle(A, p, N, 1, M, Ns, s)
         assert len(rows) == (4 * p + 1) ** 3 and nent >= len(rows) * (p + 1) ** 3      # (a corner row has (p + 1)^3 entries, an interior one (2p + 1)^3)
+        assert _sampled_rows_entrywise(A, b, p, N, rows, bc) == nent
         if not bc:
             n_s = Ns + p
             sr = srow[:, 0] + n_s * (srow[:, 1] + n_s * srow[:, 2])
