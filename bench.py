@@ -2,8 +2,11 @@
 """bench.py -- element stiffness assemblies per second, 3-D p=3 Poisson on 256^3 elements
 (BASELINE.json metric), one process per GPU.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: nothing else.
   --dump-outputs DIR: after the timed steps, a fixed sample of the last step's A and b goes to DIR/*.npy (dump_outputs).
+  --full: also what the headline figure does not need -- the checksums of A and b (N>1: checked against a single-rank assembly),
+  the HBM traffic of the dominant kernel (N=1: rocprofv3 passes around one-step child runs) and the CPU baseline (N=1).
   N>1: either way works -- `python bench.py --gpus N ...` starts its own N ranks (launch_ranks: children of a process that has
   not touched the GPU) and relays rank 0's line; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
   the ranks are the launcher's.
@@ -412,9 +415,11 @@ def main():
     ap.add_argument("--source", action="store_true", help="poisson only: the form is given as run-time source (IGXSetFormSource), not as the built-in struct")
     ap.add_argument("--body-force", action="store_true", help="elasticity only: the same K with F[a][i] = N_a f_i (IGX_FORM_ELASTICITY_F); the CPU baseline keeps the demo's form")
     ap.add_argument("--two-calls", action="store_true", help="tangent workloads: IFunction and IJacobian as two calls (two passes of the element loop) instead of IGXComputeIFunctionIJacobian")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the N>1 checksum against a single-rank assembly on rank 0")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not spawn the rocprofv3 --pmc passes that measure roofline.traffic (N = 1); replay profiles/traffic.json instead")
+    ap.add_argument("--full", action="store_true",
+                    help="also checksums (N>1: checked against a single-rank assembly), roofline.traffic and the CPU baseline; a plain run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the N>1 checksum against a single-rank assembly on rank 0")
+    ap.add_argument("--no-live-traffic", action="store_true", help="--full: do not spawn the rocprofv3 --pmc passes that measure roofline.traffic (N = 1); replay profiles/traffic.json instead")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write a fixed sample of the last step's A and b (rank 0's rows) to DIR/*.npy in float64")
     args = ap.parse_args()
@@ -549,10 +554,10 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, g, A, b)
 
-    # checksums over the owned rows: partition-independent up to rounding.  N > 1: rank 0 also assembles the whole mesh as a
-    # single rank (it fits next to its share on a 288 GB GPU for the headline) and the sums must agree: a lost or doubled
+    # --full: checksums over the owned rows, partition-independent up to rounding.  N > 1: rank 0 also assembles the whole mesh
+    # as a single rank (it fits next to its share on a 288 GB GPU for the headline) and the sums must agree: a lost or doubled
     # ghost row cannot print a rate.
-    cs = g.checksum(A, b)
+    cs = g.checksum(A, b) if args.full else None
     check = None
     kernel_name, proc_sizes, local_elements = g.kernel_name(), g.sizes()["proc_sizes"], int(g.element_count())
     try:                       # ms by which the upper face of axis 2 was packed before the assembly's last launch finished
@@ -585,7 +590,7 @@ def main():
         scale = [max(float(ref[1]), 1e-300), max(float(ref[1]), 1e-300), max((nrows * float(ref[3])) ** 0.5, 1e-300), max(float(ref[3]), 1e-300)]
         return [abs(float(x) - float(y)) / sc for x, y, sc in zip(cs_n, ref, scale)]
 
-    if world > 1:
+    if world > 1 and args.full:
         dev = "cuda" if backend == "nccl" else "cpu"
         tcs = torch.tensor(cs, dtype=torch.float64, device=dev)
         dist.all_reduce(tcs, op=dist.ReduceOp.SUM)
@@ -645,12 +650,13 @@ def main():
     elems_per_launch = dom_elems / max(dom_launches, 1)
     achieved = flop * elems_per_launch / avg_launch_s / 1e12 if (avg_launch_s > 0 and flop) else None
     executed = dom_flop * elems_per_launch / avg_launch_s / 1e12 if avg_launch_s > 0 else 0.0
-    # HBM bytes per launch of the dominant kernel come from rocprofv3 --pmc passes of this same command
+    # --full: HBM bytes per launch of the dominant kernel come from rocprofv3 --pmc passes of this same command
     # (scripts/profile_round.sh), committed as profiles/traffic.json: they are NOT measured inside this run, so the
     # line names the file; null when the file does not describe this configuration (form, size, degree, ranks, round).
+    # At N = 1 they are then measured in this run unless --no-live-traffic.  A plain run reports null.
     traffic, traffic_source, traffic_raw = None, None, None
     tf = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tf):
+    if args.full and os.path.exists(tf):
         try:
             tj = json.load(open(tf))
             for ent in tj.get("configs", [tj]):
@@ -661,9 +667,10 @@ def main():
                     traffic_source = "profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, round %s; replayed, not measured in this run)" % ent.get("round", tj.get("round"))
         except Exception:
             traffic = None
-    if world == 1 and rank == 0 and not args.no_live_traffic and dom_launches > 0:
-        child = ["--form", args.form, "--size", str(size), "--degree", str(args.degree), "--kernel", str(args.kernel), "--steps", "1", "--warmup", "0",
-                 "--no-cpu-baseline", "--no-live-traffic"] + (["--geometry"] if args.geometry else []) + (["--source"] if args.source else [])
+    if args.full and world == 1 and rank == 0 and not args.no_live_traffic and dom_launches > 0:
+        # the child is a plain run: no passes of its own, no CPU baseline
+        child = ["--form", args.form, "--size", str(size), "--degree", str(args.degree), "--kernel", str(args.kernel), "--steps", "1", "--warmup", "0"] + \
+            (["--geometry"] if args.geometry else []) + (["--source"] if args.source else [])
         lt, note = live_traffic(child, dom_name)
         if lt is not None:
             traffic, traffic_source, traffic_raw = lt["corrected"], note, lt
@@ -712,13 +719,13 @@ def main():
                        "exchange_started_before_assembly_end_ms": overlap_ms, "exchange_early_phases": early_phases,
                        "exchange_link_gbs": round(link[0], 2) if link else None, "exchange_link_source": link[1] if link else None,
                        "exchange_link_probe": ("%.3f ms for %d face message(s) of %s MB per direction" % (link[2], link[3], os.environ.get("IGX_LINK_PROBE_MB", "64"))) if link and link[1] == "measured" else None,
-                       "face_passes": face_passes, "checksum": [float(x) for x in cs], "checksum_check": check},
+                       "face_passes": face_passes, "checksum": [float(x) for x in cs] if cs is not None else None, "checksum_check": check},
             "roofline": roof,
             "device": P.device_info(),
         }
         if roofs:
             line["roofline_per_rank"] = roofs
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(args.form, args.degree, geometry=geometry and args.form != "nsvms")
             line["cpu_baseline"] = cb
             line["speedup_vs_cpu"] = value / max(cb["value"], cb["cores_x_single_core"])

@@ -1,13 +1,14 @@
 #!/usr/bin/env bash
 # N ranks as processes sharing one GPU (gloo test transport): bench.py's whole multi-rank flow -- partition, refresh, assembly, ghost-row
 # reduction, checksum against the single-rank assembly -- for rank counts and workloads beyond what the test suite runs.
-run() { IGX_BENCH_BACKEND=gloo timeout 900 python bench.py "$@" --steps 1 --warmup 1 --no-cpu-baseline 2>gpurun_out/mr.err | python -c "
+ERR="${ERR:-mr.err}"      # stderr of the last case
+run() { IGX_BENCH_BACKEND=gloo timeout 900 python bench.py "$@" --steps 1 --warmup 1 --full --no-cpu-baseline 2>"$ERR" | python -c "
 import json,sys
 l=sys.stdin.readline()
 try:
     d=json.loads(l); c=d['config']; print('OK', '$*', c['partition'], c['kernels'][:40], 'early', c['exchange_early_phases'], 'maxdiff %.1e' % max(c['checksum_check']['rel_diff']))
 except Exception as e:
-    print('FAIL', '$*', repr(e)); print(open('gpurun_out/mr.err').read()[-1500:])"; }
+    print('FAIL', '$*', repr(e)); print(open('$ERR').read()[-1500:])"; }
 if [ "${THIN:-0}" != 1 ]; then
 for n in 3 5 6 7; do run --gpus $n --form poisson --size 48; done
 run --gpus 6 --form cahnhilliard --size 48

@@ -24,7 +24,7 @@ args_of() {
 }
 for t in $TAGS; do
   A=$(args_of $t)
-  python3 bench.py $A --steps 10 --warmup 2 > $OUT/line_$t.json 2> $OUT/line_$t.err
+  python3 bench.py $A --steps 10 --warmup 2 --full > $OUT/line_$t.json 2> $OUT/line_$t.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$t -o kt -- python3 bench.py $A --steps 3 --warmup 1 --no-cpu-baseline --no-live-traffic > $OUT/kt_$t.log 2>&1
   for c in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_${t}_$c -o p -- python3 bench.py $A --steps 1 --warmup 0 --no-cpu-baseline --no-live-traffic > $OUT/pmc_${t}_$c.log 2>&1
@@ -34,7 +34,7 @@ done
 if [ -n "$ONLY_TAGS" ]; then find $OUT -name "*.csv" | wc -l; for t in $TAGS; do tail -c 300 $OUT/line_$t.json; echo; done; exit 0; fi
 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_poisson_LDS -o p -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-live-traffic > $OUT/pmc_poisson_LDS.log 2>&1
 # the metric configuration's form given as run-time source
-python3 bench.py --source --steps 10 --warmup 2 --no-cpu-baseline > $OUT/line_poisson_source.json 2> $OUT/line_poisson_source.err
+python3 bench.py --source --steps 10 --warmup 2 --full --no-cpu-baseline > $OUT/line_poisson_source.json 2> $OUT/line_poisson_source.err
 # secondary timings (one assembly each, current kernels)
 BENCH_COMPACT=1 python3 scripts/bench_configs.py c1 c2 full3 full4 c4g full5 c5r c5g c6 c6b c6m c6p c7 > $OUT/configs.txt 2> $OUT/configs.err
 python3 scripts/bench_rtc.py > $OUT/rtc.txt 2> $OUT/rtc.err

@@ -1,4 +1,4 @@
-"""bench.py --gpus 2 end to end (its own rank launch, transport agreement in exchange.init_comm, ghost refresh, assembly,
+"""bench.py --gpus 2 --full end to end (its own rank launch, transport agreement in exchange.init_comm, ghost refresh, assembly,
 ghost-row reduction, checksum assert against the single-rank assembly, per-rank roofline blocks): two processes sharing the one GPU
 of a GPU test machine with IGX_BENCH_BACKEND=gloo (the host-callback transport; the product transport is RCCL).  The driver's multi-GPU
 run must not be the first execution of this script -- neither as plain `python bench.py --gpus N` (bench.py starts the ranks
@@ -63,7 +63,7 @@ def _check_line(r, form, size, ranks=2, transport="host"):
 @pytest.mark.parametrize("form,size,transport", [("poisson", 64, "rccl"), ("elasticity", 48, "host"), ("cahnhilliard", 64, "host"), ("nsvms", 32, "rccl")])
 def test_bench_two_ranks_checksums(form, size, transport):
     """The way the driver starts it: `python bench.py --gpus 2 ...`, no launcher, WORLD_SIZE unset."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--form", form, "--size", str(size), "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--form", form, "--size", str(size), "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(transport), capture_output=True, text=True, timeout=900)
     _check_line(r, form, size, 2, transport)
 
@@ -74,7 +74,7 @@ def test_bench_four_ranks(ranks, form, size):
     """[1,2,2] as processes sharing the one GPU: the ghost refresh of a nonlinear form (its lists differ in length from the
     reduction's: the exchange buffers of round 3 did not survive that) and the whole N-rank flow of the driver's SCALE run --
     through the library's RCCL branch (comm.hpp kind == 1) on the test double: rccl_ranks == N in the line"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "1", "--warmup", "1", "--form", form, "--size", str(size), "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "1", "--warmup", "1", "--form", form, "--size", str(size), "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env("rccl"), capture_output=True, text=True, timeout=900)
     _check_line(r, form, size, ranks, "rccl")
 
@@ -84,7 +84,7 @@ def test_bench_two_ranks_under_torchrun():
     env = dict(os.environ, IGX_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     port = 29900 + os.getpid() % 90
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--form", "poisson", "--size", "64", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--form", "poisson", "--size", "64", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     _check_line(r, "poisson", 64)
 
