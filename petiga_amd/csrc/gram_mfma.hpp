@@ -2872,6 +2872,9 @@ static int launch_boundary_loads(const Space &s, const SpaceDev &S, const OutDev
 // gram_patch.hpp (round 6): the p = 2 walk of patches of pencils
 static void launch_patches_p2(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch);
 static void launch_state_patches_p2(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, bool first_touch, const void *kernel, const ParamsDev &prm);
+// gram_patch3.hpp (round 8): the p = 3 walk of MX x MY patches of pencils
+template <int MX, int MY>
+static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch);
 // one rank, no axis wrapped inside it, one new node per element on axes 1 and 2 (a patch's nodes are consecutive)
 static bool patch_walk_covers(const Space &s) {
   if (s.proc_sizes[0] * s.proc_sizes[1] * s.proc_sizes[2] != 1) return false;
@@ -2879,6 +2882,15 @@ static bool patch_walk_covers(const Space &s) {
   for (int d = 1; d < 3; ++d)
     for (int e = 0; e + 1 < s.elem_width[d]; ++e) if (s.basis[d].offset[s.elem_start[d] + e + 1] != s.basis[d].offset[s.elem_start[d] + e] + 1) return false;
   return true;
+}
+
+// the p = 3 patch walk's shape (pencils on axes 1, 2) and where it is the automatic choice (IGX_PATCH3=1).  Measured against the pencil
+// walk on cubes of 16^3 to 256^3 elements (System driver, profiles/r08_gram_patch_p3.txt) it was faster at every size, 1.57x at 16^3 and
+// 1.6-1.9x from 24^3 to 256^3; below 16^3 nothing was measured and the pencil walk stays.
+constexpr int PATCH3_MX = 4, PATCH3_MY = 2;
+constexpr long long PATCH3_MIN_ELEMENTS = 16 * 16 * 16;
+static bool patch3_pays(const Space &s) {
+  return (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] >= PATCH3_MIN_ELEMENTS;
 }
 
 static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, bool forced,
@@ -2935,7 +2947,23 @@ static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, h
     done = true;
     return 0;
   }
-  // ... and of a Tangent (IGX_PATCH_STATE=1): 4 x 2 pencils per workgroup, state_patch_p2
+  // (round 8: IGX_PATCH3) p = 3 on the identity geometry, one rank, the sum-factorised Gram phase: the walk of 4 x 2 patches of pencils whose
+  // band rows leave through the whole workgroup (gram_patch3.hpp): 6 colours, 745 instead of 1792 entries per element read-add-written.
+  // It reports itself as a Gram pencil walk: the same element phase, bit-repeatable like it.
+  if (deg == 3 && walk_axis == 0 && !geo && !mod && !fixt && (out.op == OP_MATRIX || out.op == OP_SYSTEM) && s.env.gram_sumfact != 0 && patch_walk_covers(s) &&
+      (s.env.patch3 == 2 || (s.env.patch3 == 1 && patch3_pays(s)))) {
+    if (dom.ev0) (void)hipEventRecord(dom.ev0, stream);
+    launch_patches_p3<PATCH3_MX, PATCH3_MY>(s, S, out, stream, launches, ga.forcing, first_touch);
+    if (dom.ev1) (void)hipEventRecord(dom.ev1, stream);
+    if (pencil_launch_error()) { err = pencil_launch_error(); pencil_launch_error() = nullptr; (void)hipGetLastError(); return IGX_ERR_LIB; }
+    if (hipGetLastError() != hipSuccess) { err = "gram_pencil_patch3 kernel launch failed"; return IGX_ERR_LIB; }
+    dom.name = "gram_pencil<walk=0,p=3,patch>"; dom.launches = launches; dom.elements = (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2];
+    dom.flop_per_element = 2.0 * 2 * 4 * 64 * 10;      // (the element phase of the sum-factorised walk: pencil_mfma_sf on 10 tiles)
+    kname = "gram_pencil(mfma_f64_16x16x4,p=3,walk=0," + std::to_string(PATCH3_MX) + "x" + std::to_string(PATCH3_MY) + " pencils per workgroup,one window)";
+    done = true;
+    return 0;
+  }
+  // p = 2, a Tangent (IGX_PATCH_STATE=1): 4 x 2 pencils per workgroup, state_patch_p2
   if (deg == 2 && walk_axis == 0 && s.env.patch_state && state && !geo && mod->patch_kfn && patch_walk_covers(s)) {
     if (dom.ev0) (void)hipEventRecord(dom.ev0, stream);
     launch_state_patches_p2(s, S, out, stream, launches, first_touch, mod->patch_kfn, mod->prm);

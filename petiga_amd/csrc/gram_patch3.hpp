@@ -1,0 +1,422 @@
+// gram_patch3.hpp -- the p = 3 Gram walk with the band rows combined across all three axes before they reach memory (round 8).
+//
+// The sum-factorised pencil walk (gram_pencil<..., SF = true>, gram_mfma.hpp) is bound by its band-row flush alone: a pencil combines
+// its rows along the walk axis only and read-add-writes 1792 entries per element, 224 bytes at a time, in 16 colours.  Here a
+// workgroup of MX x MY wavefronts walks a PATCH of MX x MY adjacent pencils in step and adds into ONE window in LDS.  A "pair" of an
+// axis is two nodes of the patch that share one of its elements (7 m + 9 of them for m elements); a window BLOCK (r, c) holds the
+// entries (node layer r, pair y, pair x ; node layer c) for all pairs.  Only the upper walk-axis blocks c = r .. r + 3 are kept:
+//   win[16 slots = (c & 3, c - r)][y pair][x pair],
+// the lower half of a band row being read transposed from the blocks of its column layer.  Layer L is complete when every wavefront
+// has added its element L; its runs (row node, 7 column layers) then leave through the whole workgroup -- (7MX+9)(7MY+9) runs of 7
+// entries for MX MY elements: 745 entries per element at 4 x 2 instead of 1792, and 6 colours instead of 16.
+//
+// The element phase is the pencil walk's: pencil_sf_planes once per pencil, then 2 x 4 v_fma_f64 per tile on the staged walk-axis Gram
+// sums.  Bit-repeatable like every walk but gram_patch_p2: an element step is split into ten sub-phases between barriers; in sub-phase
+// k wavefront w adds its tile (k + w) mod 10, so no two wavefronts touch one block at once and every window entry takes its adds in a
+// fixed order.  The F stage and the lifting of the Dirichlet rows are summed in a fixed order too (per-run liftings in LDS, gathered
+// per node).  Every thread owns RUNS runs for the whole walk; their old values are requested a step ahead and consumed behind the
+// barrier that completes the layer.
+//
+// Degree 3, identity geometry, one rank, axis-0 walk, sum-factorised Gram phase; System and Matrix drivers, Dirichlet values on any
+// face, first touch.  Boundary loads: the per-face launch that runs first.
+#pragma once
+#include "gram_patch.hpp"
+
+namespace igx {
+
+template <int MX, int MY> struct Patch3 {
+  static constexpr int W = MX * MY;                                     // pencils (= wavefronts) of a workgroup
+  static constexpr int NX = MX + 3, NY = MY + 3, NODES = NX * NY;       // nodes of a patch on axes 1, 2
+  static constexpr int NXP = 7 * MX + 9, NYP = 7 * MY + 9;              // node pairs that share an element of the patch
+  static constexpr int BLK = NXP * NYP;                                 // doubles per window block (= runs of a layer)
+  static constexpr int SLOTS = 16;                                      // blocks (r, r + d), d = 0..3, keyed by (r + d) & 3 and d
+  static constexpr int RUNS = (BLK + W * 64 - 1) / (W * 64);            // runs per thread
+  static constexpr int SX = MX >= 3 ? 2 : 3, SY = MY >= 3 ? 2 : 3;      // colours per axis: patches SX apart share no node
+  static_assert(MX >= 2 && MY >= 2 && W <= 10, "a patch of at least 2 x 2 pencils, at most one wavefront per tile of the element");
+  static_assert(NODES <= 64 * W, "one thread per F row of the patch");
+};
+
+// LDS behind the walk's tables: the window, the per-run liftings of two layers, the F stage of two layers, the pair tables (ints)
+template <int MX, int MY>
+__host__ __device__ static inline size_t patch3_lds_bytes(int ne_max) {
+  using G = Patch3<MX, MY>;
+  return pencil_lds_bytes(ne_max, false, G::W) + (size_t)(G::SLOTS + 2) * G::BLK * 8 + (size_t)2 * G::W * 16 * 8 +
+         (size_t)(G::NX * 7 + G::NY * 7 + G::NXP + G::NYP + 8) * 4 + 64;
+}
+
+template <bool SYSTEM, int MX, int MY>
+__global__ void __launch_bounds__(MX * MY * 64, 1)
+gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
+  using G = Patch3<MX, MY>;
+  constexpr int P = 3, NB = 4, BW = 7, X = 1, Y = 2, W = G::W, NX = G::NX, NY = G::NY, BLK = G::BLK, NTHR = W * 64;
+  extern __shared__ __attribute__((aligned(16))) double pencil_sm[];
+  const PencilArgs &pa = A.pa;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int seg = blockIdx.x / pa.blocks_per_seg, patch = blockIdx.x - seg * pa.blocks_per_seg;
+  const int tx = patch % A.px_count, ty = patch / A.px_count;
+  const int ppx = A.px_start + tx * A.px_step, ppy = A.py_start + ty * A.py_step;
+  const int ex0 = ppx * MX, ey0 = ppy * MY;
+  const int mxv = min(MX, pa.nelx - ex0), myv = min(MY, pa.nely - ey0);      // elements of the patch inside the mesh
+  const int wi = wave % MX, wj = wave / MX;
+  const bool valid = wi < mxv && wj < myv;
+  const int elx = ex0 + (valid ? wi : 0), ely = ey0 + (valid ? wj : 0);
+  const AxisDev &AW = S.ax[0], &AX = S.ax[1], &AY = S.ax[2];
+  const int ws = pa.w_lo + seg * pa.seg_len, we = min(ws + pa.seg_len, pa.w_hi);
+  const int wh = max(ws - P, pa.w_halo_lo);
+  const int ne = we - wh, nl = ne + P;
+
+  PencilLds T = pencil_lds_carve(pencil_sm, pa.ne_max, false);
+  T.lay0 = AW.off[wh];
+  double *win = reinterpret_cast<double *>(reinterpret_cast<char *>(pencil_sm) + pencil_lds_bytes(pa.ne_max, false, W));
+  double *corr = win + G::SLOTS * BLK;          // [layer & 1][run]: the lifting sum_k K_ik v_k of the run's row over its fixed columns
+  double *Fp = corr + 2 * BLK;                  // [layer & 1][wave][16]: the leaving layer's F sums of each pencil
+  int *XP = reinterpret_cast<int *>(Fp + 2 * W * 16), *YP = XP + NX * 7, *XI = YP + NY * 7, *YI = XI + G::NXP, *cntp = YI + G::NYP;
+  // this wavefront's pencil: its Y-axis rows [a][q][2] (scaled by sqrt(w J)) in LDS, as gram_pencil_body stages them
+  double *vyw = reinterpret_cast<double *>(reinterpret_cast<char *>(pencil_sm) + (pencil_lds_bytes(pa.ne_max, false, W) - (size_t)2 * W * 32 * 8)) + wave * 32;
+  PencilLane L;
+  double sxy = 0;
+  {   // the walk-axis tables of the segment (the Gram sums G_k and F factors of the sum-factorised walk), the window, the pair tables
+    for (int i = tid; i < ne * 32; i += NTHR) {
+      const int e = i >> 5, j = i & 31, ta = j >> 3, tb = (j >> 1) & 3, k = j & 1, eg = wh + e;
+      const double *tw = AW.tab + (size_t)eg * NB * NB * NDER;
+      double g = 0;
+#pragma unroll
+      for (int q = 0; q < NB; ++q) { const double sq = sqrt(AW.w[eg * NB + q] * AW.J[eg]); g += (tw[(q * NB + ta) * NDER + k] * sq) * (tw[(q * NB + tb) * NDER + k] * sq); }
+      T.zt[i] = g;
+    }
+    for (int i = tid; i < ne * 4; i += NTHR) {
+      const int e = i >> 2, a = i & 3, eg = wh + e;
+      double sw = 0;
+#pragma unroll
+      for (int q = 0; q < NB; ++q) { const double sq = sqrt(AW.w[eg * NB + q] * AW.J[eg]); sw += sq * (AW.tab[((size_t)eg * NB * NB + q * NB + a) * NDER] * sq); }
+      T.wq[i] = sw;
+    }
+    for (int i = tid; i < nl; i += NTHR) {
+      const int lay = T.lay0 + i;
+      if (lay < AW.gwidth) {
+        const int rho = AW.rowmap[lay];
+        T.rho[i] = rho; T.cnt[i] = AW.rcnt[rho]; T.pre[i] = AW.prefix[rho];
+        for (int d = 0; d < BW; ++d) T.P[i * 8 + d] = AW.P[lay * BW + d];
+      } else { T.rho[i] = 0; T.cnt[i] = -1; T.pre[i] = 0; }
+    }
+    for (int i = tid; i < G::SLOTS * BLK; i += NTHR) win[i] = 0.0;
+    if (tid < 2) {      // pairs (r, r + d) of an axis that share one of the patch's mv elements k: max(r, c) - 3 <= k <= min(r, c), 0 <= k < mv
+      const int nn = tid == 0 ? NX : NY, mv = tid == 0 ? mxv : myv;
+      int *PT = tid == 0 ? XP : YP, *PI = tid == 0 ? XI : YI;
+      int n = 0;
+      for (int r = 0; r < nn; ++r) for (int d = -3; d <= 3; ++d) {
+        const int c = r + d, hi = r > c ? r : c, lo = r < c ? r : c;
+        const bool ok = c >= 0 && c < nn && max(hi - 3, 0) <= min(lo, mv - 1);
+        PT[r * 7 + d + 3] = ok ? n : -1;
+        if (ok) PI[n++] = r | ((d + 3) << 8);
+      }
+      cntp[tid] = n;
+    }
+    const double *__restrict__ TX = AX.tab + (size_t)elx * (NB * NB * NDER);
+    const double *__restrict__ TY = AY.tab + (size_t)ely * (NB * NB * NDER);
+    const double *__restrict__ WX = AX.w + elx * NB, *__restrict__ WYq = AY.w + ely * NB;
+    const int qx = lane >> 4, ix = lane & 3, iy = (lane >> 2) & 3;
+    const double sx0 = sqrt(WX[qx] * AX.J[elx]);
+    L.u0 = TX[(qx * NB + ix) * NDER + 0] * sx0; L.u1 = TX[(qx * NB + ix) * NDER + 1] * sx0;
+    if (lane < 32) { const int aa = lane >> 3, qq = (lane >> 1) & 3, kk = lane & 1; vyw[lane] = TY[(qq * NB + aa) * NDER + kk] * sqrt(WYq[qq] * AY.J[ely]); }
+    L.vy = vyw + iy * 8;
+    if constexpr (SYSTEM) {      // F lane (fx = lane & 3, fy = (lane >> 2) & 3, walk-axis slot = lane >> 4): forcing * sum_q w N on axes 1, 2
+      const int fx = lane & 3, fy = (lane >> 2) & 3;
+      double sx = 0, sy = 0;
+#pragma unroll
+      for (int q = 0; q < NB; ++q) { sx += WX[q] * TX[(q * NB + fx) * NDER]; sy += WYq[q] * TY[(q * NB + fy) * NDER]; }
+      sxy = valid ? pa.forcing * (sx * sy) * (AX.J[elx] * AY.J[ely]) : 0.0;
+    }
+  }
+  __syncthreads();
+  const int nxp = cntp[0], nyp = cntp[1], nruns = nxp * nyp;
+
+  // ---- the pencil's x-y planes of the Gram block (12 MFMAs), and where this lane's entries go in a window block: tile entry (row a, r ;
+  // column b1, b2) is (y pair (wj + r, wj + b2), x pair (wi + a, wi + b1)) -- the same for all ten tiles
+  d4_t mw, mxy;
+  pencil_sf_planes<NB>(L, mw, mxy);
+  int woff[4];
+  {
+    const int a = lane >> 4, b1 = lane & 3, b2 = (lane >> 2) & 3;
+    const int xp = XP[(wi + a) * 7 + (b1 - a + 3)];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) woff[r] = valid ? YP[(wj + r) * 7 + (b2 - r + 3)] * nxp + xp : 0;
+  }
+
+  // ---- Dirichlet data of the patch (IGAElementBuildFix, src/petigaelem.c:1214-1283: a node is fixed by position, later faces override
+  // earlier ones: axis 0, 1, 2; side 0, 1)
+  bool bany = false, bxlo = false, bxhi = false, bylo = false, byhi = false; int bwlo = -1000, bwhi = -1000;
+  double vwlo = 0, vwhi = 0, vxlo = 0, vxhi = 0, vylo = 0, vyhi = 0;
+  if constexpr (SYSTEM) {
+    bxlo = !AX.periodic && S.bcv[X][0].count > 0 && ex0 + AX.estart == 0;                       vxlo = S.bcv[X][0].value[0];
+    bxhi = !AX.periodic && S.bcv[X][1].count > 0 && ex0 + mxv + AX.estart == AX.esizes;         vxhi = S.bcv[X][1].value[0];
+    bylo = !AY.periodic && S.bcv[Y][0].count > 0 && ey0 + AY.estart == 0;                       vylo = S.bcv[Y][0].value[0];
+    byhi = !AY.periodic && S.bcv[Y][1].count > 0 && ey0 + myv + AY.estart == AY.esizes;         vyhi = S.bcv[Y][1].value[0];
+    if (!AW.periodic && S.bcv[0][0].count > 0 && AW.estart == 0) { bwlo = AW.off[0]; vwlo = S.bcv[0][0].value[0]; }
+    if (!AW.periodic && S.bcv[0][1].count > 0 && AW.estart + AW.nel == AW.esizes) { bwhi = AW.off[AW.nel - 1] + P; vwhi = S.bcv[0][1].value[0]; }
+    bany = bxlo || bxhi || bylo || byhi || bwlo > -1000 || bwhi > -1000;
+  }
+  auto fixed = [&](int xr, int yr, int lay, double &val) -> bool {      // node (layer lay, patch nodes yr, xr)
+    bool f = false;
+    if (lay == bwlo) { f = true; val = vwlo; }
+    if (lay == bwhi) { f = true; val = vwhi; }
+    if (bxlo && xr == 0) { f = true; val = vxlo; }
+    if (bxhi && xr == mxv + P - 1) { f = true; val = vxhi; }
+    if (bylo && yr == 0) { f = true; val = vylo; }
+    if (byhi && yr == myv + P - 1) { f = true; val = vyhi; }
+    return f;
+  };
+  // (the rows the fix-up can reach: a patch on a face of axis 1 or 2, or within p layers of a fixed layer of the walk axis -- patch-uniform)
+  auto bc_layer = [&](int lay) { return bany && (bxlo || bxhi || bylo || byhi || (lay >= bwlo - P && lay <= bwlo + P) || (lay >= bwhi - P && lay <= bwhi + P)); };
+  // elements of the patch's walk that hold a node (the diagonal of a fixed row counts them: each sets K_kk = 1)
+  auto held = [&](int li, int xr, int yr) {
+    return (min(li, ne - 1) - max(li - P, 0) + 1) * (min(xr, mxv - 1) - max(xr - P, 0) + 1) * (min(yr, myv - 1) - max(yr - P, 0) + 1);
+  };
+
+  // ---- this thread's runs u = tid + j NTHR of the band rows, (y pair, x pair) for the whole walk:
+  // pos = RA + RB prefix0(layer) + RC count0(layer) + P0(layer, d); ut = the transposed pair (where the row's lower half is read)
+  long long RA[G::RUNS]; int RB[G::RUNS], RC[G::RUNS], ut[G::RUNS], ucode[G::RUNS];      // ucode: xr | dx + 3 << 5 | yr << 8 | dy + 3 << 13 | first << 16
+  const long long T0 = S.ax[0].tot, T10 = S.ax[1].tot * S.ax[0].tot;
+#pragma unroll
+  for (int j = 0; j < G::RUNS; ++j) {
+    const int u = tid + j * NTHR;
+    RA[j] = 0; RB[j] = 0; RC[j] = 0; ut[j] = 0; ucode[j] = 0;
+    if (u >= nruns) continue;
+    const int yp = u / nxp, xp = u - yp * nxp;
+    const int yr = YI[yp] & 255, dy = (YI[yp] >> 8) - 3, xr = XI[xp] & 255, dx = (XI[xp] >> 8) - 3;
+    const int ixg = AX.off[ex0] + xr, iyg = AY.off[ey0] + yr;
+    const int rhox = AX.rowmap[ixg], rhoy = AY.rowmap[iyg];
+    const long long ps1 = AX.prefix[rhox], ps2 = AY.prefix[rhoy];
+    const int c1 = AX.rcnt[rhox], c2 = AY.rcnt[rhoy], P1 = AX.P[ixg * BW + dx + P], P2 = AY.P[iyg * BW + dy + P];
+    RA[j] = ps2 * T10 + (long long)c2 * (ps1 * T0); RB[j] = c2 * c1; RC[j] = P2 * c1 + P1;
+    ut[j] = YP[(yr + dy) * 7 + (3 - dy)] * nxp + XP[(xr + dx) * 7 + (3 - dx)];
+    // First touch: colours are launched (cx, cy) = (0,0), (1,0), ..., cy-major, and a pair (r, c) of an axis is also held by the patches of
+    // the other elements that share it.  This patch stores -- no read -- when, on both axes, no patch of an earlier colour holds the pair:
+    // when its colour is the lowest among the pair's patches (the first colour of the holders is their lowest cy, then their lowest cx).
+    bool first = false;
+    if (pa.first_touch) {
+      auto axis_first = [](int pp, int s, int m, int e0, int nel, int r, int c) {
+        const int lo = max(e0 + max(r, c) - P, 0), hi = min(e0 + min(r, c), nel - 1);
+        int mn = s;
+        for (int q = lo / m; q <= hi / m; ++q) mn = min(mn, q % s);
+        return pp % s == mn;
+      };
+      first = axis_first(ppx, G::SX, MX, ex0, pa.nelx, xr, xr + dx) && axis_first(ppy, G::SY, MY, ey0, pa.nely, yr, yr + dy);
+    }
+    ucode[j] = xr | ((dx + 3) << 5) | (yr << 8) | ((dy + 3) << 13) | (first ? 1 << 16 : 0);
+  }
+  const int own_lo = (seg == 0 && pa.w_halo_lo == pa.w_lo) ? -1 : AW.off[ws];
+  const int own_hi = (seg == pa.nseg - 1 && !pa.open_hi) ? (1 << 30) : AW.off[we];
+  // the F rows: thread t < NODES is patch node (yr, xr) = (t / NX, t % NX); its F row without the walk-axis part
+  long long frowxy = 0;
+  if (SYSTEM && tid < G::NODES) {
+    const int yr = tid / NX, xr = tid - yr * NX;
+    if (xr <= mxv + P - 1 && yr <= myv + P - 1) frowxy = (long long)S.ax[0].nrow * AX.rowmap[AX.off[ex0] + xr] + (long long)S.ax[0].nrow * S.ax[1].nrow * AY.rowmap[AY.off[ey0] + yr];
+  }
+
+  // the runs of layer li: their seven old values are requested a step ahead (fetch) and consumed when the layer is complete (leave)
+  auto layer_on = [&](int li) { const int lay = T.lay0 + li; return li >= 0 && li < nl && T.cnt[li] > 0 && lay >= own_lo && lay < own_hi; };
+  struct Run { long long base; double o[7]; bool full; };
+  bool ron = false;
+  auto fetch = [&](int li, Run (&rr)[G::RUNS]) {
+    ron = layer_on(li);
+    if (!ron) return;
+    const long long pre = T.pre[li]; const int cnt = T.cnt[li];
+    int p0[7]; bool full = true;
+#pragma unroll
+    for (int d = 0; d < 7; ++d) { p0[d] = T.P[li * 8 + d]; full = full && p0[d] == d; }
+#pragma unroll
+    for (int j = 0; j < G::RUNS; ++j) {
+      Run &r = rr[j];
+      r.full = full;
+      if (tid + j * NTHR >= nruns) continue;
+      r.base = RA[j] + (long long)RB[j] * pre + (long long)RC[j] * cnt;
+      const bool first = (ucode[j] >> 16) & 1;
+      if (full) {      // an interior layer: the run is 56 contiguous bytes
+        const double *p = out.val + r.base;
+        if (first) {
+#pragma unroll
+          for (int d = 0; d < 7; ++d) r.o[d] = 0.0;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { const d2u_t a = *reinterpret_cast<const d2u_t *>(p + 2 * k); r.o[2 * k] = a[0]; r.o[2 * k + 1] = a[1]; }
+          r.o[6] = p[6];
+        }
+      } else {
+#pragma unroll
+        for (int d = 0; d < 7; ++d) r.o[d] = (p0[d] >= 0 && !first) ? out.val[r.base + p0[d]] : 0.0;
+      }
+    }
+  };
+  auto leave = [&](int li, const Run (&rr)[G::RUNS]) {
+    const int c0 = li & 3;
+    const bool bcl = SYSTEM && ron && bc_layer(T.lay0 + li);
+#pragma unroll
+    for (int j = 0; j < G::RUNS; ++j) {
+      const int u = tid + j * NTHR;
+      if (u >= nruns) continue;
+      // upper half: blocks (li, li + d) at the run's pair; lower half: blocks (li - d, li) at the transposed pair.  The blocks of column
+      // layer li are read for the last time here: zeroed for the layer that takes their slots next.
+      double v[7];
+#pragma unroll
+      for (int d = 0; d <= 3; ++d) v[3 + d] = win[(((li + d) & 3) * 4 + d) * BLK + u];
+      win[(c0 * 4) * BLK + u] = 0.0;
+#pragma unroll
+      for (int d = 1; d <= 3; ++d) { double *w = win + (c0 * 4 + d) * BLK + ut[j]; v[3 - d] = *w; *w = 0.0; }
+      if (!ron) continue;
+      const Run &r = rr[j];
+      const int lay = T.lay0 + li;
+      if constexpr (SYSTEM) {      // IGAElementFixSystem (src/petigaelem.c:1377-1387) on the combined run; its row's lifting to the F stage
+        if (bcl) {
+          const int xr = ucode[j] & 31, dx = ((ucode[j] >> 5) & 7) - 3, yr = (ucode[j] >> 8) & 31, dy = ((ucode[j] >> 13) & 7) - 3;
+          double c = 0, rv = 0;
+          const bool rf = fixed(xr, yr, lay, rv);
+#pragma unroll
+          for (int d = 0; d < 7; ++d) {
+            double cv = 0; const bool cf = fixed(xr + dx, yr + dy, lay + d - P, cv);
+            if (cf) c += v[d] * cv;
+            if (rf || cf) v[d] = (d == P && dx == 0 && dy == 0 && rf) ? (double)held(li, xr, yr) : 0.0;
+          }
+          corr[(li & 1) * BLK + u] = c;
+        }
+      }
+      double *p = out.val + r.base;
+      if (r.full) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { d2u_t a; a[0] = r.o[2 * k] + v[2 * k]; a[1] = r.o[2 * k + 1] + v[2 * k + 1]; *reinterpret_cast<d2u_t *>(p + 2 * k) = a; }
+        p[6] = r.o[6] + v[6];
+      } else {
+#pragma unroll
+        for (int d = 0; d < 7; ++d) { const int p0 = T.P[li * 8 + d]; if (p0 >= 0) p[p0] = r.o[d] + v[d]; }
+      }
+    }
+  };
+  // F of layer li: thread t < NODES = patch node (yr, xr): the pencils' sums (Fp) and its runs' liftings (corr), each in a fixed order
+  auto leave_f = [&](int li) {
+    if constexpr (SYSTEM) {
+      if (tid >= G::NODES || !layer_on(li)) return;
+      const int yr = tid / NX, xr = tid - yr * NX;
+      if (xr > mxv + P - 1 || yr > myv + P - 1) return;
+      const int lay = T.lay0 + li;
+      const double *Fl = Fp + (li & 1) * (W * 16);
+      double f = 0;
+      for (int j = max(0, yr - P); j <= min(yr, myv - 1); ++j)
+        for (int i = max(0, xr - P); i <= min(xr, mxv - 1); ++i) f += Fl[(j * MX + i) * 16 + 4 * (yr - j) + (xr - i)];
+      if (bc_layer(lay)) {
+        double fv = 0;
+        if (fixed(xr, yr, lay, fv)) f = fv * (double)held(li, xr, yr);
+        else {
+          const double *cl = corr + (li & 1) * BLK;
+          double c = 0;
+          for (int dy = 0; dy < 7; ++dy) {
+            const int yp = YP[yr * 7 + dy];
+            if (yp < 0) continue;
+            for (int dx = 0; dx < 7; ++dx) { const int xp = XP[xr * 7 + dx]; if (xp >= 0) c += cl[yp * nxp + xp]; }
+          }
+          f -= c;
+        }
+      }
+      // one memory-side add per row and launch (patches of a colour share no node): order-free, and nothing waits for it
+      (void)__hip_atomic_fetch_add(out.vec + (long long)T.rho[li] + frowxy, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  };
+  const int fslot = lane >> 4;
+  double Facc = 0;
+  auto f_stage = [&](int li) {      // the leaving layer's F sums of this pencil (slot 0 of the F lanes), then the slots slide
+    if constexpr (SYSTEM) {
+      if (fslot == 0) Fp[(li & 1) * (W * 16) + wave * 16 + lane] = Facc;
+      const double up = __shfl_down(Facc, 16);
+      Facc = (fslot >= NB - 1) ? 0.0 : up;
+    }
+  };
+
+  Run run[G::RUNS];
+  long long tk0 = 0, tw0 = 0;
+  if (out.clk) { tk0 = __builtin_readcyclecounter(); tw0 = wall_clock64(); }
+  fetch(0, run);
+  for (int ei = 0; ei < ne; ++ei) {
+    const double *g = T.zt + ei * 32;
+    // ten sub-phases: in sub-phase k wavefront w adds tile t = (k + w) mod 10 = (ta, tb), ta <= tb, of its element to block (ei + ta, ei + tb)
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      if (valid) {
+        const int t = k + wave >= 10 ? k + wave - 10 : k + wave;
+        const int ta = (int)((0x3221110000ull >> (4 * t)) & 15), tb = (int)((0x3323213210ull >> (4 * t)) & 15);
+        double *blk = win + (((ei + tb) & 3) * 4 + (tb - ta)) * BLK;
+        const double g0 = g[(ta * 4 + tb) * 2 + 0], g1 = g[(ta * 4 + tb) * 2 + 1];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) (void)__hip_atomic_fetch_add(blk + woff[r], __builtin_fma(g0, mxy[r], g1 * mw[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      if (SYSTEM && k == 0) {      // F_a += f J prod_d sum_q w N: the walk-axis factor was staged with the Gram sums
+        Facc += sxy * T.wq[ei * 4 + fslot];
+        f_stage(ei);
+      }
+      __syncthreads();      // (the last one: every wavefront's element ei is in the window, layer ei is complete, its F sums are staged)
+    }
+    leave(ei, run);
+    fetch(ei + 1, run);
+    __syncthreads();      // the slots of column layer ei are zero again; the liftings of layer ei are staged
+    leave_f(ei);
+  }
+  if (seg == pa.nseg - 1 && !pa.open_hi)      // the last segment owns the layers beyond its last element too
+    for (int li = ne; li < nl; ++li) {
+      f_stage(li);
+      leave(li, run);
+      fetch(li + 1, run);
+      __syncthreads();
+      leave_f(li);
+      __syncthreads();
+    }
+  if (out.clk && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && tid == 0) {
+    // IGX_CLOCK_PROBE: s_memtime against the 100 MHz s_memrealtime over the walk, first and last workgroup of every launch (as gram_pencil_body)
+    atomicAdd(reinterpret_cast<unsigned long long *>(out.clk), (unsigned long long)(__builtin_readcyclecounter() - tk0));
+    atomicAdd(reinterpret_cast<unsigned long long *>(out.clk) + 1, (unsigned long long)(wall_clock64() - tw0));
+    atomicAdd(reinterpret_cast<unsigned long long *>(out.clk) + 2, (unsigned long long)ne);
+  }
+}
+
+#ifndef IGX_RTC
+// the launches of an assembly: SX x SY colours of patches, cy-major (the first-touch rule of the kernel knows the order); pencil_launch_error
+// is set when no segment length fits the LDS
+template <int MX, int MY>
+static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch) {
+  using G = Patch3<MX, MY>;
+  const int nx = s.elem_width[1], ny = s.elem_width[2], nw = s.elem_width[0];
+  const int npx = (nx + MX - 1) / MX, npy = (ny + MY - 1) / MY;
+  const int ncu = pencil_cus();
+  const bool sys = out.op == OP_SYSTEM;
+  for (int cy = 0; cy < G::SY; ++cy) for (int cx = 0; cx < G::SX; ++cx) {
+    PatchArgs A; memset(&A, 0, sizeof(A));
+    A.px_start = cx; A.px_step = G::SX; A.px_count = (npx - cx + G::SX - 1) / G::SX;
+    A.py_start = cy; A.py_step = G::SY; A.py_count = (npy - cy + G::SY - 1) / G::SY;
+    A.npx = npx; A.npy = npy;
+    if (A.px_count <= 0 || A.py_count <= 0) continue;
+    PencilArgs &pa = A.pa;
+    pa.forcing = forcing; pa.first_touch = first_touch ? 1 : 0;
+    pa.nelx = nx; pa.nely = ny; pa.w_lo = 0; pa.w_hi = nw; pa.w_halo_lo = 0; pa.open_hi = 0; pa.wpb = G::W;
+    const long long patches = (long long)A.px_count * A.py_count;
+    // segments: the count with the fewest rounds x (length + halo + set-up), as many resident workgroups per CU as the LDS holds
+    int best = 1; long long bc = -1;
+    for (int n = 1; n <= std::max(1, nw / 2); ++n) {      // (down to two elements per segment)
+      const int len = (nw + n - 1) / n, ns = (nw + len - 1) / len;
+      const size_t lds_n = patch3_lds_bytes<MX, MY>(len + 3);
+      if (lds_n > (size_t)160 * 1024) continue;
+      const long long slots = (long long)ncu * std::max<long long>(1, (long long)(160 * 1024) / (long long)lds_n);
+      const long long cost = ((patches * ns + slots - 1) / slots) * (len + (ns > 1 ? 3 : 0) + 1);
+      if (bc < 0 || cost < bc) { bc = cost; best = n; }
+    }
+    if (s.env.nseg > 0) best = std::min(s.env.nseg, std::max(1, nw / 2));
+    pa.seg_len = (nw + best - 1) / best; pa.nseg = (nw + pa.seg_len - 1) / pa.seg_len;
+    pa.blocks_per_seg = (int)patches; pa.ne_max = pa.seg_len + 3;
+    const size_t lds = patch3_lds_bytes<MX, MY>(pa.ne_max);
+    if (lds > (size_t)160 * 1024) { pencil_launch_error() = "the p = 3 patch walk's tables do not fit the LDS"; return; }
+    auto kern = sys ? gram_pencil_patch3<true, MX, MY> : gram_pencil_patch3<false, MX, MY>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(patches * pa.nseg)), dim3(G::W * 64), lds, stream, S, out, A);
+    launches++;
+  }
+}
+#endif
+
+}  // namespace igx
