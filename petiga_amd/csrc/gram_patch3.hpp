@@ -24,16 +24,14 @@
 
 namespace igx {
 
-template <int MX, int MY> struct Patch3 {
-  static constexpr int W = MX * MY;                                     // pencils (= wavefronts) of a workgroup
-  static constexpr int NX = MX + 3, NY = MY + 3, NODES = NX * NY;       // nodes of a patch on axes 1, 2
-  static constexpr int NXP = 7 * MX + 9, NYP = 7 * MY + 9;              // node pairs that share an element of the patch
-  static constexpr int BLK = NXP * NYP;                                 // doubles per window block (= runs of a layer)
+template <int MX, int MY> struct Patch3 : PatchShape<3, MX, MY> {
+  using G = PatchShape<3, MX, MY>;
+  static constexpr int BLK = G::NXP * G::NYP;                           // doubles per window block (= runs of a layer)
   static constexpr int SLOTS = 16;                                      // blocks (r, r + d), d = 0..3, keyed by (r + d) & 3 and d
-  static constexpr int RUNS = (BLK + W * 64 - 1) / (W * 64);            // runs per thread
-  static constexpr int SX = MX >= 3 ? 2 : 3, SY = MY >= 3 ? 2 : 3;      // colours per axis: patches SX apart share no node
-  static_assert(MX >= 2 && MY >= 2 && W <= 10, "a patch of at least 2 x 2 pencils, at most one wavefront per tile of the element");
-  static_assert(NODES <= 64 * W, "one thread per F row of the patch");
+  static constexpr int RUNS = (BLK + G::W * 64 - 1) / (G::W * 64);      // runs per thread
+  static_assert(G::NXP == 7 * MX + 9 && G::NYP == 7 * MY + 9 && G::SX == (MX >= 3 ? 2 : 3) && G::SY == (MY >= 3 ? 2 : 3), "the patch at p = 3");
+  static_assert(G::W <= 10, "at most one wavefront per tile of the element");
+  static_assert(G::NODES <= 64 * G::W, "one thread per F row of the patch");
 };
 
 // LDS behind the walk's tables: the window, the per-run liftings of two layers, the F stage of two layers, the pair tables (ints)
@@ -41,30 +39,22 @@ template <int MX, int MY>
 __host__ __device__ static inline size_t patch3_lds_bytes(int ne_max) {
   using G = Patch3<MX, MY>;
   return pencil_lds_bytes(ne_max, false, G::W) + (size_t)(G::SLOTS + 2) * G::BLK * 8 + (size_t)2 * G::W * 16 * 8 +
-         (size_t)(G::NX * 7 + G::NY * 7 + G::NXP + G::NYP + 8) * 4 + 64;
+         (size_t)G::PAIR_INTS * 4 + 64;
 }
 
 template <bool SYSTEM, int MX, int MY>
 __global__ void __launch_bounds__(MX * MY * 64, 1)
 gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
   using G = Patch3<MX, MY>;
-  constexpr int P = 3, NB = 4, BW = 7, X = 1, Y = 2, W = G::W, NX = G::NX, NY = G::NY, BLK = G::BLK, NTHR = W * 64;
+  constexpr int P = G::P, NB = 4, BW = G::BW, W = G::W, NX = G::NX, NY = G::NY, BLK = G::BLK, NTHR = W * 64;
   extern __shared__ __attribute__((aligned(16))) double pencil_sm[];
   const PencilArgs &pa = A.pa;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int seg = blockIdx.x / pa.blocks_per_seg, patch = blockIdx.x - seg * pa.blocks_per_seg;
-  const int tx = patch % A.px_count, ty = patch / A.px_count;
-  const int ppx = A.px_start + tx * A.px_step, ppy = A.py_start + ty * A.py_step;
-  const int ex0 = ppx * MX, ey0 = ppy * MY;
-  const int mxv = min(MX, pa.nelx - ex0), myv = min(MY, pa.nely - ey0);      // elements of the patch inside the mesh
-  const int wi = wave % MX, wj = wave / MX;
-  const bool valid = wi < mxv && wj < myv;
-  const int elx = ex0 + (valid ? wi : 0), ely = ey0 + (valid ? wj : 0);
+  const PatchWalk D = patch_decode<G>(S, A, wave);
+  const int seg = D.seg, ex0 = D.ex0, ey0 = D.ey0, mxv = D.mxv, myv = D.myv, wi = D.wi, wj = D.wj, elx = D.elx, ely = D.ely, wh = D.wh, ne = D.ne, nl = D.nl;
+  const bool valid = D.valid;
   const AxisDev &AW = S.ax[0], &AX = S.ax[1], &AY = S.ax[2];
-  const int ws = pa.w_lo + seg * pa.seg_len, we = min(ws + pa.seg_len, pa.w_hi);
-  const int wh = max(ws - P, pa.w_halo_lo);
-  const int ne = we - wh, nl = ne + P;
 
   PencilLds T = pencil_lds_carve(pencil_sm, pa.ne_max, false);
   T.lay0 = AW.off[wh];
@@ -92,27 +82,9 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
       for (int q = 0; q < NB; ++q) { const double sq = sqrt(AW.w[eg * NB + q] * AW.J[eg]); sw += sq * (AW.tab[((size_t)eg * NB * NB + q * NB + a) * NDER] * sq); }
       T.wq[i] = sw;
     }
-    for (int i = tid; i < nl; i += NTHR) {
-      const int lay = T.lay0 + i;
-      if (lay < AW.gwidth) {
-        const int rho = AW.rowmap[lay];
-        T.rho[i] = rho; T.cnt[i] = AW.rcnt[rho]; T.pre[i] = AW.prefix[rho];
-        for (int d = 0; d < BW; ++d) T.P[i * 8 + d] = AW.P[lay * BW + d];
-      } else { T.rho[i] = 0; T.cnt[i] = -1; T.pre[i] = 0; }
-    }
+    patch_stage_layers<BW>(T, AW, nl, tid, NTHR);
     for (int i = tid; i < G::SLOTS * BLK; i += NTHR) win[i] = 0.0;
-    if (tid < 2) {      // pairs (r, r + d) of an axis that share one of the patch's mv elements k: max(r, c) - 3 <= k <= min(r, c), 0 <= k < mv
-      const int nn = tid == 0 ? NX : NY, mv = tid == 0 ? mxv : myv;
-      int *PT = tid == 0 ? XP : YP, *PI = tid == 0 ? XI : YI;
-      int n = 0;
-      for (int r = 0; r < nn; ++r) for (int d = -3; d <= 3; ++d) {
-        const int c = r + d, hi = r > c ? r : c, lo = r < c ? r : c;
-        const bool ok = c >= 0 && c < nn && max(hi - 3, 0) <= min(lo, mv - 1);
-        PT[r * 7 + d + 3] = ok ? n : -1;
-        if (ok) PI[n++] = r | ((d + 3) << 8);
-      }
-      cntp[tid] = n;
-    }
+    patch_pair_tables<G>(XP, YP, XI, YI, cntp, mxv, myv, tid);
     const double *__restrict__ TX = AX.tab + (size_t)elx * (NB * NB * NDER);
     const double *__restrict__ TY = AY.tab + (size_t)ely * (NB * NB * NDER);
     const double *__restrict__ WX = AX.w + elx * NB, *__restrict__ WYq = AY.w + ely * NB;
@@ -144,70 +116,28 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
     for (int r = 0; r < 4; ++r) woff[r] = valid ? YP[(wj + r) * 7 + (b2 - r + 3)] * nxp + xp : 0;
   }
 
-  // ---- Dirichlet data of the patch (IGAElementBuildFix, src/petigaelem.c:1214-1283: a node is fixed by position, later faces override
-  // earlier ones: axis 0, 1, 2; side 0, 1)
-  bool bany = false, bxlo = false, bxhi = false, bylo = false, byhi = false; int bwlo = -1000, bwhi = -1000;
-  double vwlo = 0, vwhi = 0, vxlo = 0, vxhi = 0, vylo = 0, vyhi = 0;
-  if constexpr (SYSTEM) {
-    bxlo = !AX.periodic && S.bcv[X][0].count > 0 && ex0 + AX.estart == 0;                       vxlo = S.bcv[X][0].value[0];
-    bxhi = !AX.periodic && S.bcv[X][1].count > 0 && ex0 + mxv + AX.estart == AX.esizes;         vxhi = S.bcv[X][1].value[0];
-    bylo = !AY.periodic && S.bcv[Y][0].count > 0 && ey0 + AY.estart == 0;                       vylo = S.bcv[Y][0].value[0];
-    byhi = !AY.periodic && S.bcv[Y][1].count > 0 && ey0 + myv + AY.estart == AY.esizes;         vyhi = S.bcv[Y][1].value[0];
-    if (!AW.periodic && S.bcv[0][0].count > 0 && AW.estart == 0) { bwlo = AW.off[0]; vwlo = S.bcv[0][0].value[0]; }
-    if (!AW.periodic && S.bcv[0][1].count > 0 && AW.estart + AW.nel == AW.esizes) { bwhi = AW.off[AW.nel - 1] + P; vwhi = S.bcv[0][1].value[0]; }
-    bany = bxlo || bxhi || bylo || byhi || bwlo > -1000 || bwhi > -1000;
-  }
-  auto fixed = [&](int xr, int yr, int lay, double &val) -> bool {      // node (layer lay, patch nodes yr, xr)
-    bool f = false;
-    if (lay == bwlo) { f = true; val = vwlo; }
-    if (lay == bwhi) { f = true; val = vwhi; }
-    if (bxlo && xr == 0) { f = true; val = vxlo; }
-    if (bxhi && xr == mxv + P - 1) { f = true; val = vxhi; }
-    if (bylo && yr == 0) { f = true; val = vylo; }
-    if (byhi && yr == myv + P - 1) { f = true; val = vyhi; }
-    return f;
-  };
-  // (the rows the fix-up can reach: a patch on a face of axis 1 or 2, or within p layers of a fixed layer of the walk axis -- patch-uniform)
-  auto bc_layer = [&](int lay) { return bany && (bxlo || bxhi || bylo || byhi || (lay >= bwlo - P && lay <= bwlo + P) || (lay >= bwhi - P && lay <= bwhi + P)); };
-  // elements of the patch's walk that hold a node (the diagonal of a fixed row counts them: each sets K_kk = 1)
-  auto held = [&](int li, int xr, int yr) {
-    return (min(li, ne - 1) - max(li - P, 0) + 1) * (min(xr, mxv - 1) - max(xr - P, 0) + 1) * (min(yr, myv - 1) - max(yr - P, 0) + 1);
-  };
+  PatchFix<P> fx;      // the Dirichlet data of the patch
+  if constexpr (SYSTEM) fx.fill(S, D);
 
   // ---- this thread's runs u = tid + j NTHR of the band rows, (y pair, x pair) for the whole walk:
   // pos = RA + RB prefix0(layer) + RC count0(layer) + P0(layer, d); ut = the transposed pair (where the row's lower half is read)
   long long RA[G::RUNS]; int RB[G::RUNS], RC[G::RUNS], ut[G::RUNS], ucode[G::RUNS];      // ucode: xr | dx + 3 << 5 | yr << 8 | dy + 3 << 13 | first << 16
-  const long long T0 = S.ax[0].tot, T10 = S.ax[1].tot * S.ax[0].tot;
 #pragma unroll
   for (int j = 0; j < G::RUNS; ++j) {
     const int u = tid + j * NTHR;
     RA[j] = 0; RB[j] = 0; RC[j] = 0; ut[j] = 0; ucode[j] = 0;
     if (u >= nruns) continue;
     const int yp = u / nxp, xp = u - yp * nxp;
-    const int yr = YI[yp] & 255, dy = (YI[yp] >> 8) - 3, xr = XI[xp] & 255, dx = (XI[xp] >> 8) - 3;
-    const int ixg = AX.off[ex0] + xr, iyg = AY.off[ey0] + yr;
-    const int rhox = AX.rowmap[ixg], rhoy = AY.rowmap[iyg];
-    const long long ps1 = AX.prefix[rhox], ps2 = AY.prefix[rhoy];
-    const int c1 = AX.rcnt[rhox], c2 = AY.rcnt[rhoy], P1 = AX.P[ixg * BW + dx + P], P2 = AY.P[iyg * BW + dy + P];
-    RA[j] = ps2 * T10 + (long long)c2 * (ps1 * T0); RB[j] = c2 * c1; RC[j] = P2 * c1 + P1;
+    int yr, dy, xr, dx;
+    patch_pair<P>(YI[yp], yr, dy); patch_pair<P>(XI[xp], xr, dx);
+    patch_run_address<P>(S, ex0, ey0, xr, dx, yr, dy, RA[j], RB[j], RC[j]);
     ut[j] = YP[(yr + dy) * 7 + (3 - dy)] * nxp + XP[(xr + dx) * 7 + (3 - dx)];
-    // First touch: colours are launched (cx, cy) = (0,0), (1,0), ..., cy-major, and a pair (r, c) of an axis is also held by the patches of
-    // the other elements that share it.  This patch stores -- no read -- when, on both axes, no patch of an earlier colour holds the pair:
-    // when its colour is the lowest among the pair's patches (the first colour of the holders is their lowest cy, then their lowest cx).
     bool first = false;
-    if (pa.first_touch) {
-      auto axis_first = [](int pp, int s, int m, int e0, int nel, int r, int c) {
-        const int lo = max(e0 + max(r, c) - P, 0), hi = min(e0 + min(r, c), nel - 1);
-        int mn = s;
-        for (int q = lo / m; q <= hi / m; ++q) mn = min(mn, q % s);
-        return pp % s == mn;
-      };
-      first = axis_first(ppx, G::SX, MX, ex0, pa.nelx, xr, xr + dx) && axis_first(ppy, G::SY, MY, ey0, pa.nely, yr, yr + dy);
-    }
+    if (pa.first_touch) first = patch_first_touch<G>(A, D, xr, dx, yr, dy);
     ucode[j] = xr | ((dx + 3) << 5) | (yr << 8) | ((dy + 3) << 13) | (first ? 1 << 16 : 0);
   }
-  const int own_lo = (seg == 0 && pa.w_halo_lo == pa.w_lo) ? -1 : AW.off[ws];
-  const int own_hi = (seg == pa.nseg - 1 && !pa.open_hi) ? (1 << 30) : AW.off[we];
+  int own_lo, own_hi;
+  patch_owned_layers(S, A, D, own_lo, own_hi);
   // the F rows: thread t < NODES is patch node (yr, xr) = (t / NX, t % NX); its F row without the walk-axis part
   long long frowxy = 0;
   if (SYSTEM && tid < G::NODES) {
@@ -223,35 +153,20 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
     ron = layer_on(li);
     if (!ron) return;
     const long long pre = T.pre[li]; const int cnt = T.cnt[li];
-    int p0[7]; bool full = true;
-#pragma unroll
-    for (int d = 0; d < 7; ++d) { p0[d] = T.P[li * 8 + d]; full = full && p0[d] == d; }
+    const int *p0 = T.P + li * 8;
+    const bool full = patch_layer_full<BW>(p0);      // (an interior layer: a run is 56 contiguous bytes)
 #pragma unroll
     for (int j = 0; j < G::RUNS; ++j) {
       Run &r = rr[j];
       r.full = full;
       if (tid + j * NTHR >= nruns) continue;
       r.base = RA[j] + (long long)RB[j] * pre + (long long)RC[j] * cnt;
-      const bool first = (ucode[j] >> 16) & 1;
-      if (full) {      // an interior layer: the run is 56 contiguous bytes
-        const double *p = out.val + r.base;
-        if (first) {
-#pragma unroll
-          for (int d = 0; d < 7; ++d) r.o[d] = 0.0;
-        } else {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) { const d2u_t a = *reinterpret_cast<const d2u_t *>(p + 2 * k); r.o[2 * k] = a[0]; r.o[2 * k + 1] = a[1]; }
-          r.o[6] = p[6];
-        }
-      } else {
-#pragma unroll
-        for (int d = 0; d < 7; ++d) r.o[d] = (p0[d] >= 0 && !first) ? out.val[r.base + p0[d]] : 0.0;
-      }
+      patch_run_load<BW>(out.val, r.base, p0, full, (ucode[j] >> 16) & 1, r.o);
     }
   };
   auto leave = [&](int li, const Run (&rr)[G::RUNS]) {
     const int c0 = li & 3;
-    const bool bcl = SYSTEM && ron && bc_layer(T.lay0 + li);
+    const bool bcl = SYSTEM && ron && fx.reaches(T.lay0 + li);
 #pragma unroll
     for (int j = 0; j < G::RUNS; ++j) {
       const int u = tid + j * NTHR;
@@ -271,25 +186,17 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
         if (bcl) {
           const int xr = ucode[j] & 31, dx = ((ucode[j] >> 5) & 7) - 3, yr = (ucode[j] >> 8) & 31, dy = ((ucode[j] >> 13) & 7) - 3;
           double c = 0, rv = 0;
-          const bool rf = fixed(xr, yr, lay, rv);
+          const bool rf = fx.fixed(xr, yr, lay, rv);
 #pragma unroll
           for (int d = 0; d < 7; ++d) {
-            double cv = 0; const bool cf = fixed(xr + dx, yr + dy, lay + d - P, cv);
+            double cv = 0; const bool cf = fx.fixed(xr + dx, yr + dy, lay + d - P, cv);
             if (cf) c += v[d] * cv;
-            if (rf || cf) v[d] = (d == P && dx == 0 && dy == 0 && rf) ? (double)held(li, xr, yr) : 0.0;
+            if (rf || cf) v[d] = (d == P && dx == 0 && dy == 0 && rf) ? (double)fx.held(li, xr, yr, ne) : 0.0;
           }
           corr[(li & 1) * BLK + u] = c;
         }
       }
-      double *p = out.val + r.base;
-      if (r.full) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { d2u_t a; a[0] = r.o[2 * k] + v[2 * k]; a[1] = r.o[2 * k + 1] + v[2 * k + 1]; *reinterpret_cast<d2u_t *>(p + 2 * k) = a; }
-        p[6] = r.o[6] + v[6];
-      } else {
-#pragma unroll
-        for (int d = 0; d < 7; ++d) { const int p0 = T.P[li * 8 + d]; if (p0 >= 0) p[p0] = r.o[d] + v[d]; }
-      }
+      patch_run_add_store<BW>(out.val, r.base, T.P + li * 8, r.full, r.o, v);
     }
   };
   // F of layer li: thread t < NODES = patch node (yr, xr): the pencils' sums (Fp) and its runs' liftings (corr), each in a fixed order
@@ -303,9 +210,9 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
       double f = 0;
       for (int j = max(0, yr - P); j <= min(yr, myv - 1); ++j)
         for (int i = max(0, xr - P); i <= min(xr, mxv - 1); ++i) f += Fl[(j * MX + i) * 16 + 4 * (yr - j) + (xr - i)];
-      if (bc_layer(lay)) {
+      if (fx.reaches(lay)) {
         double fv = 0;
-        if (fixed(xr, yr, lay, fv)) f = fv * (double)held(li, xr, yr);
+        if (fx.fixed(xr, yr, lay, fv)) f = fv * (double)fx.held(li, xr, yr, ne);
         else {
           const double *cl = corr + (li & 1) * BLK;
           double c = 0;
@@ -377,40 +284,17 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
 }
 
 #ifndef IGX_RTC
-// the launches of an assembly: SX x SY colours of patches, cy-major (the first-touch rule of the kernel knows the order); pencil_launch_error
+// the launches of an assembly: SX x SY colours of patches, cy-major (the first-touch rule knows the order); pencil_launch_error
 // is set when no segment length fits the LDS
 template <int MX, int MY>
 static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch) {
   using G = Patch3<MX, MY>;
-  const int nx = s.elem_width[1], ny = s.elem_width[2], nw = s.elem_width[0];
-  const int npx = (nx + MX - 1) / MX, npy = (ny + MY - 1) / MY;
-  const int ncu = pencil_cus();
   const bool sys = out.op == OP_SYSTEM;
   for (int cy = 0; cy < G::SY; ++cy) for (int cx = 0; cx < G::SX; ++cx) {
-    PatchArgs A; memset(&A, 0, sizeof(A));
-    A.px_start = cx; A.px_step = G::SX; A.px_count = (npx - cx + G::SX - 1) / G::SX;
-    A.py_start = cy; A.py_step = G::SY; A.py_count = (npy - cy + G::SY - 1) / G::SY;
-    A.npx = npx; A.npy = npy;
-    if (A.px_count <= 0 || A.py_count <= 0) continue;
-    PencilArgs &pa = A.pa;
-    pa.forcing = forcing; pa.first_touch = first_touch ? 1 : 0;
-    pa.nelx = nx; pa.nely = ny; pa.w_lo = 0; pa.w_hi = nw; pa.w_halo_lo = 0; pa.open_hi = 0; pa.wpb = G::W;
-    const long long patches = (long long)A.px_count * A.py_count;
-    // segments: the count with the fewest rounds x (length + halo + set-up), as many resident workgroups per CU as the LDS holds
-    int best = 1; long long bc = -1;
-    for (int n = 1; n <= std::max(1, nw / 2); ++n) {      // (down to two elements per segment)
-      const int len = (nw + n - 1) / n, ns = (nw + len - 1) / len;
-      const size_t lds_n = patch3_lds_bytes<MX, MY>(len + 3);
-      if (lds_n > (size_t)160 * 1024) continue;
-      const long long slots = (long long)ncu * std::max<long long>(1, (long long)(160 * 1024) / (long long)lds_n);
-      const long long cost = ((patches * ns + slots - 1) / slots) * (len + (ns > 1 ? 3 : 0) + 1);
-      if (bc < 0 || cost < bc) { bc = cost; best = n; }
-    }
-    if (s.env.nseg > 0) best = std::min(s.env.nseg, std::max(1, nw / 2));
-    pa.seg_len = (nw + best - 1) / best; pa.nseg = (nw + pa.seg_len - 1) / pa.seg_len;
-    pa.blocks_per_seg = (int)patches; pa.ne_max = pa.seg_len + 3;
-    const size_t lds = patch3_lds_bytes<MX, MY>(pa.ne_max);
-    if (lds > (size_t)160 * 1024) { pencil_launch_error() = "the p = 3 patch walk's tables do not fit the LDS"; return; }
+    PatchArgs A; size_t lds = 0;
+    if (!patch_colour_args<G>(s, cx, cy, forcing, first_touch, patch3_lds_bytes<MX, MY>, "the p = 3 patch walk's tables do not fit the LDS", A, lds)) { if (pencil_launch_error()) return; continue; }
+    const PencilArgs &pa = A.pa;
+    const long long patches = pa.blocks_per_seg;
     auto kern = sys ? gram_pencil_patch3<true, MX, MY> : gram_pencil_patch3<false, MX, MY>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)(patches * pa.nseg)), dim3(G::W * 64), lds, stream, S, out, A);
