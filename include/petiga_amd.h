@@ -307,6 +307,23 @@ int IGXComputeIJacobian(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXMat J);  
  * measured 3 % slower than the two passes, DESIGN.md 3.1 -- the two drivers run one after the other.  IGXGetKernelName tells. */
 int IGXComputeIFunctionIJacobian(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec F,IGXMat J);
 int IGXComputeFunctionJacobian(IGX iga,IGXVec U,IGXVec F,IGXMat J);
+/* Matrix-free actions (no reference entry point: the product of the driver's matrix with a vector -- what MATSHELL / -snes_mf_operator
+ * ask of an assembly engine once the matrix no longer fits).  Y = A X with A the matrix IGXComputeJacobian / IGXComputeIJacobian
+ * assemble on this rank and, for IGXComputeMatrixAction, the matrix of IGXComputeSystem -- IGXComputeMatrix's K with the matrix
+ * half of IGAElementFixSystem applied, i.e. K itself where no Dirichlet value is set (the operator a linear solve needs).
+ * IGAElementFixJacobian in all three: a fixed column takes no contribution and a fixed row receives X_row once per local element
+ * that holds the node (the element count on the diagonal).  No matrix is allocated and no
+ * index is read: the direction's point values go through mat() in place of a trial function (every mat() is linear in Nb), one
+ * more forward pass per field on the sum-factorised vector kernel (vec_sumfact, ACTION).  Y is zeroed and then assembled like any
+ * vector, with the same row numbering; on several ranks X must hold its ghosts (IGXRefreshGhosts) and IGXReduceGhostRows(iga,NULL,Y)
+ * completes the ghost rows.  Covered: 3-D, nen and nqp <= 4 per axis, identity / polynomial / NURBS geometry with nsd = 3, Dirichlet
+ * values, periodic axes, every built-in or run-time form of order <= 2 without a boundary branch.  Everything else -- a boundary-form
+ * pass, dim != 3, nsd != dim, order-3 or property forms, nen > 4, IGX_VEC_SUMFACT=0, an IGXSetKernel choice other than 0 -- returns
+ * IGX_ERR_SUP with the reason: there is no fallback kernel.  Boundary loads do not enter a matrix and are ignored.  X == Y, a
+ * vector of another IGX or a null vector: IGX_ERR_ARG_WRONG; no form set: IGX_ERR_ARG_WRONGSTATE. */
+int IGXComputeMatrixAction   (IGX iga,IGXVec X,IGXVec Y);                                        /* Y = K X,    K of IGXComputeSystem    */
+int IGXComputeJacobianAction (IGX iga,IGXVec U,IGXVec X,IGXVec Y);                               /* Y = J(U) X, J of IGXComputeJacobian  */
+int IGXComputeIJacobianAction(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec X,IGXVec Y);    /* J of IGXComputeIJacobian             */
 
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
@@ -449,6 +466,7 @@ int IGXChecksum(IGX iga,IGXMat A,IGXVec b,double S[4]);
  * (the Tangent of a scalar struct with the PENCIL_* hooks, below).  gram == 5: block_pencil<MyForm> (System and Matrix driver) of a
  * constant-coefficient multi-field struct.  gram == 6: band_points + band_pt<MyForm> (Matrix / Jacobian / IJacobian of a four-field
  * struct that separates its point coefficients: NCOEF, point_coef, mat_c), without a geometry and on a NURBS map.
+ * gram == 7: the ACTION instantiation of vec_sumfact<MyForm> (IGXCompute*Action of the struct) for the current geometry kind.
  * Returns 0 or IGX_ERR_USER with the compiler's log. */
 int IGXCheckFormSource(IGX iga,int with_matrix,int gram);
 

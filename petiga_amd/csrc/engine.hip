@@ -908,6 +908,26 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
   constexpr int NS = nscalar_of<Form>::v;
   // third-order tabulation, the property array and the point's shape table exist in the general kernel only
   constexpr bool GENERAL = general_only_of<Form>::v;
+  // the matrix-free actions (IGXCompute*Action): vec_sumfact's ACTION instantiation or a refusal that names the reason -- no other kernel forms them
+  if (out.op == OP_MATRIX_ACTION || out.op == OP_JACOBIAN_ACTION || out.op == OP_IJACOBIAN_ACTION) {
+#ifdef IGX_HAVE_VEC_SUMFACT
+    if constexpr (DIM == 3 && !GENERAL && NS == 0 && !has_boundary_of<Form>::v) {
+      if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);
+      if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
+      bool done = false;
+      ParamsDev prm; memset(&prm, 0, sizeof(prm));
+      for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
+      if (int rc = try_vec_sumfact<Form, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
+      return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix action it covers");
+    } else
+#endif
+    {
+      for (int d = 0; d < s.dim; ++d) for (int sd = 0; sd < 2; ++sd) if (s.visit[d][sd]) return fail(IGX_ERR_SUP, "the matrix action does not cover boundary-form passes (IGXSetBoundaryForm): it runs on vec_sumfact alone");
+      if (DIM != 3) return fail(IGX_ERR_SUP, "the matrix action needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)");
+      if (GENERAL) return fail(IGX_ERR_SUP, "the matrix action does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives");
+      return fail(IGX_ERR_SUP, "the matrix action does not cover forms with a boundary branch or functionals");
+    }
+  }
   if (GENERAL && g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a form of order 3 or one that reads the property array runs on the general kernel only");
   if ((Form::NEED & NEED_PROP) && !S.npd) return fail(IGX_ERR_ARG_WRONGSTATE, "No property set");      // src/petigaelem.c:300
   // a geometry of another dimension than the parametric one: tabulated by the general kernel only (no inverse map: src/petigaelem.c:966)
@@ -1306,6 +1326,39 @@ extern "C" int IGXComputeFunction(IGX g, IGXVec U, IGXVec F) { if (!U) return fa
 extern "C" int IGXComputeJacobian(IGX g, IGXVec U, IGXMat J) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_JACOBIAN, J, nullptr, U, nullptr, 0, 0); }
 extern "C" int IGXComputeIFunction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec F) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_IFUNCTION, nullptr, F, U, V, a, t); }
 extern "C" int IGXComputeIJacobian(IGX g, double a, IGXVec V, double t, IGXVec U, IGXMat J) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_IJACOBIAN, J, nullptr, U, V, a, t); }
+// Matrix-free actions: Y = A X with A the matrix IGXComputeSystem (IGXComputeMatrix's K with the fix-up of IGAElementFixSystem) / Jacobian /
+// IJacobian would assemble on this rank, IGAElementFixJacobian included (a fixed column takes nothing, a fixed row receives X_row once per local element that holds the node).  Y is zeroed and
+// assembled like a vector; on several ranks X holds its ghosts and IGXReduceGhostRows(iga, NULL, Y) completes the ghost rows.  The
+// product is formed by vec_sumfact's ACTION instantiation (vec_sumfact.hpp) or refused with IGX_ERR_SUP: there is no other kernel.
+static int compute_action(IGX g, int op, IGXVec U, IGXVec V, IGXVec X, IGXVec Y, double shift, double t) {
+  NEEDIGA(g);
+  if (!X || !Y) return fail(IGX_ERR_ARG_WRONG, "null direction or result vector");
+  if (X == Y) return fail(IGX_ERR_ARG_WRONG, "the direction and the result must be different vectors");
+  if (X->iga != g || Y->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  if ((U && U == Y) || (V && V == Y)) return fail(IGX_ERR_ARG_WRONG, "the result must not be a state vector");
+  if (int rc = ensure_device(g)) return rc;
+  const Space &s = g->s;
+  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  OutDev out; memset(&out, 0, sizeof(out));
+  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
+  out.vec = Y->a.as<double>(); out.X = X->a.as<double>();
+  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
+  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
+  HIPCK(hipMemsetAsync(Y->a.p, 0, Y->a.bytes, g->stream));
+  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
+  const SpaceDev S = make_spacedev(g);
+  g->dom = DomInfo(); g->slab_valid = 0;
+  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
+  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
+  if (rc) return rc;
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
+  return 0;
+}
+extern "C" int IGXComputeMatrixAction(IGX g, IGXVec X, IGXVec Y) { return compute_action(g, OP_MATRIX_ACTION, nullptr, nullptr, X, Y, 0, 0); }
+extern "C" int IGXComputeJacobianAction(IGX g, IGXVec U, IGXVec X, IGXVec Y) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_action(g, OP_JACOBIAN_ACTION, U, nullptr, X, Y, 0, 0); }
+extern "C" int IGXComputeIJacobianAction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec X, IGXVec Y) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_action(g, OP_IJACOBIAN_ACTION, U, V, X, Y, a, t); }
+
 // One pass for the pair a Newton step asks for at the same state (SNESComputeFunction + SNESComputeJacobian; src/petigats.c:23-159,
 // src/petigasnes.c:23-139): the results are those of the two drivers, in one walk where a fused kernel exists, else in two calls.
 extern "C" int IGXComputeIFunctionIJacobian(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec F, IGXMat J) {

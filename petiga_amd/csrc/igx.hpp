@@ -187,7 +187,8 @@ struct SpaceDev {
 
 struct ColorRange { int start[3], step[3], count[3]; };
 
-enum Op { OP_SYSTEM = 0, OP_MATRIX, OP_VECTOR, OP_FUNCTION, OP_JACOBIAN, OP_IFUNCTION, OP_IJACOBIAN, OP_SCALAR };
+enum Op { OP_SYSTEM = 0, OP_MATRIX, OP_VECTOR, OP_FUNCTION, OP_JACOBIAN, OP_IFUNCTION, OP_IJACOBIAN, OP_SCALAR,
+          OP_MATRIX_ACTION, OP_JACOBIAN_ACTION, OP_IJACOBIAN_ACTION };      // Y = A X of the matrix the driver would assemble, matrix-free (vec_sumfact.hpp)
 
 struct OutDev {
   const int64_t *browptr;  // null when no matrix output
@@ -206,7 +207,23 @@ struct OutDev {
   int64_t elem_base;       // OP_SCALAR: index of this launch's first element in the per-element partial sums (vec)
   int vec_mode;            // vec_sumfact as a part of IGAComputeSystem next to a band-row kernel: 1 the whole vector (lifting of the Dirichlet values through
                            // SystemVectorOf<Form>, a fixed row takes its value), 2 the form's vec() alone with the fixed rows left at 0 (block_pencil lifts itself)
+  const double *X;         // OP_*_ACTION: the row-indexed direction (vec is Y), else null
 };
+
+#ifndef IGX_RTC
+// The matrix-free actions (OP_MATRIX_ACTION / OP_JACOBIAN_ACTION / OP_IJACOBIAN_ACTION) run on vec_sumfact (vec_sumfact.hpp, ACTION) or not at all: why not, or null.
+// Boundary loads do not enter a matrix and are ignored.
+inline bool op_is_action(int op) { return op == OP_MATRIX_ACTION || op == OP_JACOBIAN_ACTION || op == OP_IJACOBIAN_ACTION; }
+inline const char *vec_action_refusal(const Space &s, int kernel_choice) {
+  for (int d = 0; d < s.dim; ++d) for (int sd = 0; sd < 2; ++sd) if (s.visit[d][sd]) return "the matrix action does not cover boundary-form passes (IGXSetBoundaryForm): it runs on vec_sumfact alone";
+  if (s.dim != 3) return "the matrix action needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)";
+  if (s.nsd != 0 && s.nsd != 3) return "the matrix action needs a geometry with nsd = dim";
+  for (int d = 0; d < 3; ++d) if (s.basis[d].nen > 4 || s.basis[d].nqp > 4) return "the matrix action needs nen <= 4 and nqp <= 4 on every axis (degree <= 3)";
+  if (s.env.vec_sumfact == 0) return "the matrix action runs on vec_sumfact alone, and IGX_VEC_SUMFACT=0 switches that kernel off";
+  if (kernel_choice != 0) return "the matrix action runs on vec_sumfact alone: IGXSetKernel must leave the choice automatic (0)";
+  return nullptr;
+}
+#endif
 
 constexpr int MAXPARAM = 8;
 struct ParamsDev { double v[MAXPARAM]; };

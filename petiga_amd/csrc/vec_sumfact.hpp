@@ -156,20 +156,28 @@ __device__ __forceinline__ constexpr unsigned vs_kmask_ident(unsigned vmask) {
 // products, no quotient rule) and the kernel needs half the registers
 // the pipelined walk of round 6 (see the kernel): scalar forms without a geometry, where its registers fit four wavefronts per SIMD
 template <class Form, bool GEO> __host__ __device__ constexpr bool vs_pipe() { return !GEO && Form::DOF == 1; }
-template <class Form, bool GEO, int NS = 4>
+template <int N> struct vs_int { static constexpr int value = N; };      // (a derivative order handed to a generic lambda)
+// ACTION: the matrix-free product Y = A X of the matrix the Matrix / Jacobian / IJacobian driver would assemble (OP_*_ACTION): every
+// mat(p, Na, Nb, T) is linear in Nb, so sum_b K_ab X_b = sum_q JW sum_f Phi_f(a, q) sum_j mat(p, e_f, Xf^j)[.][j] with Xf^j = (x^j, grad x^j,
+// hess x^j) the direction's point features -- one more forward pass per field, DOF calls of mat() per test feature, and the way back,
+// the colours and the scatter of the vector drivers.  No matrix is allocated and no index is read.
+template <class Form, bool GEO, int NS = 4, bool ACTION = false>
 __global__ void __launch_bounds__(256, (vs_pipe<Form, GEO>() ? 4 : 2))      // (two waves per SIMD: the geometry variants of NS-VMS and Cahn-Hilliard need 290-350 VGPRs uncapped, one wave per SIMD)
 vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nelem) {
   constexpr int EPW = NS == 3 ? 2 : 1, NL = NS * NS * NS;               // elements per wavefront, lanes per element
   constexpr int DOF = Form::DOF;
-  constexpr unsigned VMASK = vec_test_mask_of<Form>::v;                  // test features vec() reads (bit f)
+  constexpr unsigned VMASK = ACTION ? mat_test_mask_of<Form>::v : vec_test_mask_of<Form>::v;      // test features vec() (ACTION: mat()) reads (bit f)
   constexpr bool SECOND_T = shape_order_of<Form>::v >= 2;                // second-order test features
-  constexpr bool NEEDHU = (Form::NEED & NEED_HU) != 0, NEEDGU = (Form::NEED & (NEED_GU | NEED_HU)) != 0;
+  constexpr unsigned SNEED = ACTION ? mat_need_of<Form>::v : Form::NEED; // what the point callback reads of the state (ACTION: mat() alone)
+  constexpr bool NEEDHU = (SNEED & NEED_HU) != 0, NEEDGU = (SNEED & (NEED_GU | NEED_HU)) != 0;
   constexpr int UORD = NEEDHU ? 2 : (NEEDGU ? 1 : 0);                    // derivative order of the state
+  constexpr int XORD = ACTION ? (SECOND_T ? 2 : 1) : 0;                  // ... of the direction: the trial features mat() reads (Na's layout)
+  constexpr int GORD = UORD > XORD ? UORD : XORD;                        // ... of the geometry map (UORD without ACTION)
   constexpr int NFS = SECOND_T ? 13 : 4;
   // derivatives of the test functions that can carry a coefficient: without a geometry feature tf maps to one of them; with one, the
   // inverse Jacobian mixes the three first derivatives and the rational correction reaches the value
   constexpr unsigned KMASK = GEO ? (SECOND_T ? 0x3FFu : 0xFu) : vs_kmask_ident(VMASK & ((1u << NFS) - 1u));
-  constexpr int NBACK = vs_popc(KMASK) > (SECOND_T ? 9 : 5) ? vs_popc(KMASK) : (SECOND_T ? 9 : 5), NFWD = (UORD == 2 || GEO) ? 10 : 7, NBUF = NBACK > NFWD ? NBACK : NFWD;
+  constexpr int NBACK = vs_popc(KMASK) > (SECOND_T ? 9 : 5) ? vs_popc(KMASK) : (SECOND_T ? 9 : 5), NFWD = (GORD == 2 || GEO) ? 10 : 7, NBUF = NBACK > NFWD ? NBACK : NFWD;
   constexpr int TB = NS * NS * 3;                                        // doubles of one axis' rows [q][a][3], zero padded to NS x NS
   __shared__ double sm_all[4][NBUF * 64 + EPW * 3 * TB];      // Cahn-Hilliard without a geometry: 25 KB per workgroup, two elements per wavefront (a sixth workgroup per CU measured no gain over five: 12.8 ms either way)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -206,7 +214,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   for (int d = 0; d < 3; ++d) { nb[d] = S.ax[d].nen; nq[d] = S.ax[d].nqp; }
   const bool lanenode = i0 < nb[0] && i1 < nb[1] && i2 < nb[2], lanepoint = i0 < nq[0] && i1 < nq[1] && i2 < nq[2];
   // what an element needs from memory, in two steps: its offsets (A), then everything addressed through them (B)
-  struct Pre { int el[3], off[3]; bool live; size_t row; double tab[TPL], U[DOF], V[DOF], Fo[DOF], fx[DOF], wgt, X[3], pt[3], wq[3], Jd[3]; };
+  struct Pre { int el[3], off[3]; bool live; size_t row; double tab[TPL], U[DOF], V[DOF], Fo[DOF], fx[DOF], wgt, X[3], pt[3], wq[3], Jd[3], Xd[ACTION ? DOF : 1]; };
   auto stageA = [&](long long un, Pre &P) {
     const long long w0n = un * EPW, wn = w0n + esub;
     P.live = lane < EPW * NL && wn < nelem;                             // (an odd count leaves the second half of the last wavefront idle)
@@ -232,7 +240,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
 #pragma unroll
     for (int c = 0; c < 3; ++c) P.X[c] = 0.0;
 #pragma unroll
-    for (int f = 0; f < DOF; ++f) { P.U[f] = 0; P.V[f] = 0; P.Fo[f] = 0; P.fx[f] = 0; }
+    for (int f = 0; f < DOF; ++f) { P.U[f] = 0; P.V[f] = 0; P.Fo[f] = 0; P.fx[f] = 0; if constexpr (ACTION) P.Xd[f] = 0; }
     if (P.live && lanenode) {      // this lane's node: control point, state, old F (rowmap in closed form: AxisDev::rwrap)
       const int n0 = P.off[0] + i0, n1 = P.off[1] + i1, n2 = P.off[2] + i2;
       const size_t g = (size_t)n0 + (size_t)S.ax[0].gwidth * ((size_t)n1 + (size_t)S.ax[1].gwidth * (size_t)n2);
@@ -246,6 +254,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
         if (useV) P.V[f] = out.V[P.row * DOF + f];
         if (S.fixtable) P.fx[f] = S.fixtable[P.row * DOF + f];
         if constexpr (PIPE || EF) P.Fo[f] = out.vec[P.row * DOF + f];
+        if constexpr (ACTION) P.Xd[f] = out.X[P.row * DOF + f];
       }
     }
     if constexpr (PIPE) {      // (the geometry variants read these where they use them: no register to spare)
@@ -281,6 +290,11 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   const size_t row = cur.row; double Xw[3] = {cur.X[0] * cur.wgt, cur.X[1] * cur.wgt, cur.X[2] * cur.wgt}; const double wgt = cur.wgt; double Uv[DOF], Vv[DOF], ufix[DOF], Fold[DOF]; bool fixed[DOF];
 #pragma unroll
   for (int f = 0; f < DOF; ++f) { Uv[f] = cur.U[f]; Vv[f] = cur.V[f]; Fold[f] = cur.Fo[f]; ufix[f] = 0; fixed[f] = false; }
+  double Xv[ACTION ? DOF : 1];      // ACTION: the node's values of the direction
+  if constexpr (ACTION) {
+#pragma unroll
+    for (int f = 0; f < DOF; ++f) Xv[f] = cur.Xd[f];
+  }
   if (isnode) {
     if (op != OP_VECTOR || sysvec || sysbody) {
 #pragma unroll
@@ -313,26 +327,26 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   auto k2 = [](int a, int b) { const int lo = a < b ? a : b, hi = a < b ? b : a; return 4 + (lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)); };
   if constexpr (GEO) if (geo || rat) {
     double Dw[10], Dx[3][10];
-    if (UORD == 2) vs_forward<2, NS>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw); else vs_forward<1, NS>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw);
+    if (GORD == 2) vs_forward<2, NS>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw); else vs_forward<1, NS>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw);
     const double W0 = ispoint ? Dw[0] : 1.0;
     iw = 1.0 / W0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) o1[a] = Dw[1 + a] * iw;
-    if (UORD == 2)
+    if (GORD == 2)
 #pragma unroll
       for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) o2[a * 3 + b] = Dw[k2(a, b)] * iw;
     if (geo) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) { if (UORD == 2) vs_forward<2, NS>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); else vs_forward<1, NS>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); }
+      for (int c = 0; c < 3; ++c) { if (GORD == 2) vs_forward<2, NS>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); else vs_forward<1, NS>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); }
       double X1[9], X2[27];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {      // quotient rule on A = sum w X N, W = sum w N (src/petigarat.f90.in + petigamapgeo.f90.in)
         x[c] = Dx[c][0] * iw;
 #pragma unroll
         for (int a = 0; a < 3; ++a) X1[c * 3 + a] = (Dx[c][1 + a] - x[c] * Dw[1 + a]) * iw;
-        if (UORD == 2)
+        if (GORD == 2)
 #pragma unroll
           for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -342,7 +356,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
       detX = det3(X1, 3);
       inv3(X1, 3, detX, E1);
       if (ispoint && !(detX > 0.0)) atomicExch(out.errflag, IGX_ERR_USER);   // src/petigaelem.c:989-993
-      if (UORD == 2) {   // InverseMap order 2 (src/petigamapinv.f90.in:32-45): E2[c][i][j] = -X2[k][a][b] E1[a][i] E1[b][j] E1[c][k]
+      if (GORD == 2) {   // InverseMap order 2 (src/petigamapinv.f90.in:32-45): E2[c][i][j] = -X2[k][a][b] E1[a][i] E1[b][j] E1[c][k]
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           double U9[9], T9[9];
@@ -362,6 +376,48 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
       }
     }
   }
+  // a nodal coefficient -> (value, gradient, Hessian up to order ORD) at this lane's point: the forward contraction, the quotient rule of
+  // rational weights and the inverse map (E1, E2).  The state's fields and, with ACTION, the direction's go through it.
+  auto field_at_point = [&](auto ordc, double coef, double &val, double *g3, double *h9) {
+    constexpr int ORD = decltype(ordc)::value;
+    double D[10];
+    vs_forward<ORD, NS>(coef * wgt, buf, tab0, tab1, tab2, lane, VL, D);
+    val = D[0] * iw;
+    if constexpr (!GEO) {
+      if (ORD >= 1) for (int a = 0; a < 3; ++a) g3[a] = D[1 + a];
+      if (ORD == 2) for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) h9[a * 3 + b] = D[k2(a, b)];
+    } else
+    if (ORD >= 1) {
+      double u1[3], u2[9];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) u1[a] = D[1 + a] * iw - val * o1[a];      // u = A / W, du = (dA - u dW) / W (o1 = dW / W; 0 without weights)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) g3[i] = u1[0] * E1[0 * 3 + i] + u1[1] * E1[1 * 3 + i] + u1[2] * E1[2 * 3 + i];
+      if (ORD == 2) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+          for (int b = 0; b < 3; ++b) {
+            double t = D[k2(a, b)] * iw;
+            if (rat) t -= val * o2[a * 3 + b] + u1[a] * o1[b] + u1[b] * o1[a];
+            u2[a * 3 + b] = t;
+          }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {     // ShapeFunctions summed over a (src/petigamapshf.f90.in:30-58)
+            double sm = 0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+#pragma unroll
+              for (int b = 0; b < 3; ++b) sm += u2[a * 3 + b] * E1[a * 3 + i] * E1[b * 3 + j];
+              sm += u1[a] * E2[a * 9 + i * 3 + j];
+            }
+            h9[i * 3 + j] = sm;
+          }
+      }
+    }
+  };
   double u[DOF], ut[DOF], gu[DOF * 3], hu[DOF * 9];
 #pragma unroll
   for (int f = 0; f < DOF; ++f) {
@@ -370,49 +426,21 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
     for (int i = 0; i < 3; ++i) gu[f * 3 + i] = 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) hu[f * 9 + i] = 0;
-    if ((Form::NEED & (NEED_U | NEED_GU | NEED_HU)) && useU) {
-      double D[10];
-      vs_forward<UORD, NS>((fixed[f] ? ufix[f] : Uv[f]) * wgt, buf, tab0, tab1, tab2, lane, VL, D);
-      u[f] = D[0] * iw;
-      if constexpr (!GEO) {
-        if (UORD >= 1) for (int a = 0; a < 3; ++a) gu[f * 3 + a] = D[1 + a];
-        if (UORD == 2) for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) hu[f * 9 + a * 3 + b] = D[k2(a, b)];
-      } else
-      if (UORD >= 1) {
-        double u1[3], u2[9];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) u1[a] = D[1 + a] * iw - u[f] * o1[a];      // u = A / W, du = (dA - u dW) / W (o1 = dW / W; 0 without weights)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gu[f * 3 + i] = u1[0] * E1[0 * 3 + i] + u1[1] * E1[1 * 3 + i] + u1[2] * E1[2 * 3 + i];
-        if (UORD == 2) {
-#pragma unroll
-          for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-              double t = D[k2(a, b)] * iw;
-              if (rat) t -= u[f] * o2[a * 3 + b] + u1[a] * o1[b] + u1[b] * o1[a];
-              u2[a * 3 + b] = t;
-            }
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {     // ShapeFunctions summed over a (src/petigamapshf.f90.in:30-58)
-              double sm = 0;
-#pragma unroll
-              for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int b = 0; b < 3; ++b) sm += u2[a * 3 + b] * E1[a * 3 + i] * E1[b * 3 + j];
-                sm += u1[a] * E2[a * 9 + i * 3 + j];
-              }
-              hu[f * 9 + i * 3 + j] = sm;
-            }
-        }
-      }
-    }
-    if ((Form::NEED & NEED_UT) && useV) {
+    if ((SNEED & (NEED_U | NEED_GU | NEED_HU)) && useU) field_at_point(vs_int<UORD>(), fixed[f] ? ufix[f] : Uv[f], u[f], gu + f * 3, hu + f * 9);
+    if ((SNEED & NEED_UT) && useV) {
       double D[10];
       vs_forward<0, NS>((fixed[f] ? 0.0 : Vv[f]) * wgt, buf, tab0, tab1, tab2, lane, VL, D);
       ut[f] = D[0] * iw;
+    }
+  }
+  // ACTION: the direction's point features, field by field, behind the state's (a fixed column takes no contribution: gathered as 0)
+  double xv[ACTION ? DOF : 1], gx[ACTION ? DOF * 3 : 1], hx[ACTION && XORD == 2 ? DOF * 9 : 1];
+  if constexpr (ACTION) {
+#pragma unroll
+    for (int f = 0; f < DOF; ++f) {
+      double h9[9];
+      field_at_point(vs_int<XORD>(), fixed[f] ? 0.0 : Xv[f], xv[f], gx + f * 3, h9);
+      if constexpr (XORD == 2) for (int i = 0; i < 9; ++i) hx[f * 9 + i] = h9[i];
     }
   }
   // the next element's loads go out here: its offsets have arrived, and the point stage and the way back lie ahead
@@ -444,7 +472,26 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
     double e[NFS], R[DOF];
 #pragma unroll
     for (int g = 0; g < NFS; ++g) e[g] = (g == tf) ? 1.0 : 0.0;
-    Form::vec(p, e, R);
+    if constexpr (!ACTION) Form::vec(p, e, R);
+    else {      // column j of the blocks against the direction's field j: DOF calls per test feature, not nen x nen
+#pragma unroll
+      for (int i = 0; i < DOF; ++i) R[i] = 0.0;
+#pragma unroll
+      for (int j = 0; j < DOF; ++j) {
+        double Nb[NFS], T[DOF * DOF];
+        Nb[0] = xv[j];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) Nb[1 + a] = gx[j * 3 + a];
+        if constexpr (SECOND_T)
+#pragma unroll
+          for (int a = 0; a < 9; ++a) Nb[4 + a] = hx[j * 9 + a];
+#pragma unroll
+        for (int i = 0; i < DOF * DOF; ++i) T[i] = 0.0;
+        Form::mat(p, e, Nb, T);
+#pragma unroll
+        for (int i = 0; i < DOF; ++i) R[i] += T[i * DOF + j];
+      }
+    }
 #pragma unroll
     for (int f = 0; f < DOF; ++f) {
       const double r = ispoint ? R[f] * JW : 0.0;      // (a padded lane evaluates vec() on zeros: its value may not even be finite)
@@ -498,7 +545,8 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
     double F = SECOND_T ? vs_backward<2, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL) : vs_backward<1, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL);
     F *= wgt;
     if (isnode) {
-      if (fixed[f] && sysvec) F = ufix[f];                       // IGAElementFixSystem: F_e[k] = v
+      if constexpr (ACTION) { if (fixed[f]) F = Xv[f]; }        // IGAElementFixJacobian: a unit diagonal per element, zero row and column beside it
+      else if (fixed[f] && sysvec) F = ufix[f];                  // IGAElementFixSystem: F_e[k] = v
       else if (fixed[f] && sysbody) F = 0.0;                     // (the band-row kernel that follows adds v per element itself)
       else if (fixed[f] && (op == OP_FUNCTION || op == OP_IFUNCTION)) F = Uv[f] - ufix[f];
       if (F != 0.0) { if constexpr (PIPE || EF) out.vec[row * DOF + f] = Fold[f] + F; else out.vec[row * DOF + f] += F; }
@@ -529,12 +577,12 @@ static bool vec_sumfact_covers(const Space &s, const OutDev &out) {
   }
 }
 
-template <class Form>
+template <class Form, bool ACTION = false>
 static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &prm, const OutDev &out, hipStream_t stream, std::string &kname, int &launches, bool &done) {
   done = false;
   if constexpr (nscalar_of<Form>::v > 0 || has_boundary_of<Form>::v) return 0;
   else {
-  if (!vec_sumfact_covers<Form>(s, out)) return 0;
+  if constexpr (!ACTION) { if (!vec_sumfact_covers<Form>(s, out)) return 0; }      // (ACTION: the caller has asked vec_action_refusal)
   launches = 0;
   const int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
   for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
@@ -556,12 +604,12 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
     const bool onepass = true;      // (UNITS = 1 in the kernel)      // (one pass per wavefront: the launch has a wavefront per unit)
     if (three) {
       const unsigned grid = onepass ? (unsigned)((nelem + 7) / 8) : (unsigned)((nelem + 15) / 16);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 3>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 3>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 3, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      else hipLaunchKernelGGL((vec_sumfact<Form, false, 3, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
     } else {
       const unsigned grid = onepass ? (unsigned)((nelem + 3) / 4) : (unsigned)((nelem + 7) / 8);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 4>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 4>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 4, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      else hipLaunchKernelGGL((vec_sumfact<Form, false, 4, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
     }
     launches++;
   }
@@ -569,6 +617,9 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
   {
     bool three = !s.env.no_vec_pairs;
     for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
+    if constexpr (ACTION) kname = three ? "vec_sumfact(matrix action: sum factorisation forward and backward, two elements per wavefront)"
+                                        : "vec_sumfact(matrix action: sum factorisation forward and backward, one wavefront per element)";
+    else
     kname = three ? "vec_sumfact(vector only: sum factorisation forward and backward, two elements per wavefront)"
                   : "vec_sumfact(vector only: sum factorisation forward and backward, one wavefront per element)";
   }
