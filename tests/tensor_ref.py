@@ -50,6 +50,27 @@ def bspline_1d(U, p, k, x, dtype=LD):
     return np.stack(N, axis=-1), np.stack(dN, axis=-1)
 
 
+def bspline_1d_d2(U, p, k, x, dtype=LD):
+    """bspline_1d with the second derivatives: the derivative recurrence applied to the first derivatives of the p functions of
+    degree p - 1 on the same span -> three [nx, p+1]."""
+    N0, N1 = bspline_1d(U, p, k, x, dtype)
+    U = np.asarray(U, dtype=dtype)
+    x = np.asarray(x, dtype=dtype)
+    if p < 2:
+        return N0, N1, np.zeros_like(N0)
+    _, L1 = bspline_1d(U, p - 1, k, x, dtype)               # function j of degree p - 1 on span k has knot index k - p + 1 + j
+    N2 = []
+    for j in range(p + 1):
+        i = k - p + j
+        t = np.zeros_like(x)
+        if j > 0 and U[i + p] != U[i]:
+            t = t + p * L1[:, j - 1] / (U[i + p] - U[i])
+        if j < p and U[i + p + 1] != U[i + 1]:
+            t = t - p * L1[:, j] / (U[i + p + 1] - U[i + 1])
+        N2.append(t)
+    return N0, N1, np.stack(N2, axis=-1)
+
+
 class AxisTables:
     """The assembled 1-D tables of one axis over the elements [e0, e1) (a rank's box), node indices wrapped on a periodic axis.
     axis / basis: the dicts of OracleIGA.axis(i) / .basis(i) -- the doubles (points, weights, Jacobians) the kernels use."""
@@ -302,6 +323,26 @@ class TensorRef:
         out = (cols[:, :, None] * self.dof + np.arange(self.dof)).reshape(len(rows), -1)
         return out, np.repeat(valid, self.dof, axis=1)
 
+    def action(self, X, rows=None):
+        """(R, S) of the rows of the assembled (and fixed-up) matrix times X: R_i = sum_j R_ij X_j and S_i = sum_j S_ij |X_j| over the
+        row's stencil -- the sum of the absolute values of the terms a matrix-free kernel adds (Pabs takes the absolute value inside
+        the point sum).  A fixed row is m X_i, which a kernel that adds X_i once per element rounds: S_i = m |X_i|."""
+        X = np.asarray(X, dtype=np.float64)
+        rows = np.arange(X.size, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
+        cols, valid = self.stencil(rows)
+        rr, cc = np.nonzero(valid)
+        Re, Se = self.entries(rows[rr], cols[rr, cc])
+        Xc = X[cols[rr, cc]]
+        R, S = np.zeros(rows.size, dtype=LD), np.zeros(rows.size, dtype=LD)
+        np.add.at(R, rr, Re * Xc)
+        np.add.at(S, rr, Se * np.abs(Xc))
+        if self.bcs:
+            fx, _ = self.fixed(rows)
+            m = self.multiplicity(rows[fx])
+            R[fx] = m * (LD(1) * X[rows[fx]])
+            S[fx] = m * np.abs(X[rows[fx]])
+        return R, S
+
     def vector(self, rows):
         """(R, S) of the assembled (and fixed-up) right-hand side / residual at the global rows."""
         rows = np.asarray(rows, dtype=np.int64)
@@ -367,17 +408,18 @@ class TensorRef:
         return R, S
 
 
-def compare_entrywise(E, R, S, c, ref=None, what="matrix"):
+def compare_entrywise(E, R, S, c, ref=None, what="matrix", pattern=True):
     """E: (rows, cols, vals) of the engine (or (rows, vals) of a vector); R, S at the same entries.  |E - R| <= c u S entry by entry,
     S = 0 meaning exactly zero.  Returns the worst ratio |E - R| / (u S).  With ref, the pattern is checked too: no duplicate entry,
-    every entry coupled, and every row's whole stencil present."""
+    every entry coupled, and every row's whole stencil present (pattern=False: E is a part of a matrix, ref only names the entries)."""
     if len(E) == 3:
         rows, cols, vals = E
     else:
         (rows, vals), cols = E, None
     rows = np.asarray(rows, dtype=np.int64)
-    if ref is not None and cols is not None:
+    if cols is not None:
         cols = np.asarray(cols, dtype=np.int64)
+    if ref is not None and cols is not None and pattern:
         nmax = int(max(rows.max(initial=0), cols.max(initial=0))) + 1
         key = rows * nmax + cols
         assert np.unique(key).size == key.size, "%s: duplicate entries" % what

@@ -2,7 +2,8 @@
 only the owner's values of X (and U, V) are set, the ghosts arrive through IGXRefreshGhosts; each rank forms its part of Y and
 IGXReduceGhostRows(NULL, Y) completes the rows it owns.  The owned rows of both ranks together equal the single-rank oracle's matrix
 times X: |Y - R| <= tol max(S) with R = A_o X, S = |A_o| |X| (tol 1e-12 for Poisson, 1e-11 for the Tangent), Dirichlet rows
-|Y_i - m_i X_i| <= 1e-12 |m_i X_i|.  Two processes share the GPU over tests/fake_rccl's double of librccl.so, as in
+|Y_i - m_i X_i| <= 1e-12 |m_i X_i|; and row by row |Y_i - R_i| <= C_ID u S_i against the long double references (the TensorRef action for
+Poisson, the point-wise one for Cahn-Hilliard: tests/test_gpu_action_entrywise.py).  Two processes share the GPU over tests/fake_rccl's double of librccl.so, as in
 tests/test_gpu_comm.py; each is started once."""
 import os
 import sys
@@ -117,3 +118,13 @@ def test_two_ranks_match_the_single_rank_oracle_product(name, tmp_path):
     assert fixed.any() == (form == "poisson")
     want = diag[fixed] * X[fixed]
     assert np.all(np.abs(Y[fixed] - want) <= 1e-12 * np.abs(want))
+    # row by row against the long double reference of the single-rank operator: |Y_i - R_i| <= c u S_i
+    import pointwise_ref as PW
+    import tensor_ref as T
+    if form == "poisson":
+        ref = T.reference(orc, 3, T.poisson(3), bcs={(d, s, 0): 1.0 + d for d in range(3) for s in range(2)})
+        Rl, Sl = ref.action(X)
+    else:
+        pw = PW.PointwiseRef(orc)
+        ref, (Rl, Sl) = pw.tref, pw.ch_action(CH, 1e3, U, X)
+    print("row by row: worst %.2f u S (c = %g)" % (PW.compare_rows(Y, Rl, Sl, T.C_ID, ref, name), T.C_ID))
