@@ -13,7 +13,10 @@
 // The element phase is the pencil walk's: pencil_sf_planes once per pencil, then 2 x 4 v_fma_f64 per tile on the staged walk-axis Gram
 // sums.  Bit-repeatable like every walk but gram_patch_p2: an element step is split into ten sub-phases between barriers; in sub-phase
 // k wavefront w adds its tile (k + w) mod 10, so no two wavefronts touch one block at once and every window entry takes its adds in a
-// fixed order.  The F stage and the lifting of the Dirichlet rows are summed in a fixed order too (per-run liftings in LDS, gathered
+// fixed order.  Within a sub-phase a block belongs to one wavefront and an entry to one lane, so the add is a plain LDS read, add and
+// write, not an atomic (round 10: the stamps put nearly half of a step in the sub-phases, each one LDS round trip after another between
+// two barriers; ds_add_f64 was the longest of them, the read of the tile's Gram sums another -- those are read ahead of the sub-phases).
+// The F stage and the lifting of the Dirichlet rows are summed in a fixed order too (per-run liftings in LDS, gathered
 // per node).  Every thread owns RUNS runs for the whole walk; their old values are requested a step ahead and consumed behind the
 // barrier that completes the layer.
 //
@@ -164,7 +167,11 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
       patch_run_load<BW>(out.val, r.base, p0, full, (ucode[j] >> 16) & 1, r.o);
     }
   };
+  long long st[4] = {0, 0, 0, 0}, st_t = 0;      // -DIGX_DEBUG: cycles of [sub-phases | wait for the old values | leave's window and stores, the next loads | closing barrier + F]
+  const bool stamped = kDebug && pa.debug_buf;
+  auto stamp = [&](int k) { if (stamped) { const long long t = __builtin_readcyclecounter(); st[k] += t - st_t; st_t = t; } };
   auto leave = [&](int li, const Run (&rr)[G::RUNS]) {
+    if (stamped) { __builtin_amdgcn_s_waitcnt(0x0F70); stamp(1); }      // (stamped launch only: the wait for the old values, at the top of leave)
     const int c0 = li & 3;
     const bool bcl = SYSTEM && ron && fx.reaches(T.lay0 + li);
 #pragma unroll
@@ -243,7 +250,17 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
   if (out.clk) { tk0 = __builtin_readcyclecounter(); tw0 = wall_clock64(); }
   fetch(0, run);
   for (int ei = 0; ei < ne; ++ei) {
+    if (stamped) st_t = __builtin_readcyclecounter();
     const double *g = T.zt + ei * 32;
+    // this wavefront's Gram sums of the step's ten tiles, read ahead of the sub-phases: one LDS round trip for the ten, not one in each
+    // sub-phase (the table is not written during the walk)
+    double gk[10][2];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const int t = k + wave >= 10 ? k + wave - 10 : k + wave;
+      const int ta = (int)((0x3221110000ull >> (4 * t)) & 15), tb = (int)((0x3323213210ull >> (4 * t)) & 15);
+      gk[k][0] = g[(ta * 4 + tb) * 2 + 0]; gk[k][1] = g[(ta * 4 + tb) * 2 + 1];
+    }
     // ten sub-phases: in sub-phase k wavefront w adds tile t = (k + w) mod 10 = (ta, tb), ta <= tb, of its element to block (ei + ta, ei + tb)
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
@@ -251,9 +268,13 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
         const int t = k + wave >= 10 ? k + wave - 10 : k + wave;
         const int ta = (int)((0x3221110000ull >> (4 * t)) & 15), tb = (int)((0x3323213210ull >> (4 * t)) & 15);
         double *blk = win + (((ei + tb) & 3) * 4 + (tb - ta)) * BLK;
-        const double g0 = g[(ta * 4 + tb) * 2 + 0], g1 = g[(ta * 4 + tb) * 2 + 1];
+        const double g0 = gk[k][0], g1 = gk[k][1];
+        // (a plain read, add and write: no other wavefront touches this block before the barrier, and a lane's four entries are its own)
+        double w[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) (void)__hip_atomic_fetch_add(blk + woff[r], __builtin_fma(g0, mxy[r], g1 * mw[r]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        for (int r = 0; r < 4; ++r) w[r] = blk[woff[r]];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) blk[woff[r]] = w[r] + __builtin_fma(g0, mxy[r], g1 * mw[r]);
       }
       if (SYSTEM && k == 0) {      // F_a += f J prod_d sum_q w N: the walk-axis factor was staged with the Gram sums
         Facc += sxy * T.wq[ei * 4 + fslot];
@@ -261,10 +282,17 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
       }
       __syncthreads();      // (the last one: every wavefront's element ei is in the window, layer ei is complete, its F sums are staged)
     }
+    stamp(0);
     leave(ei, run);
     fetch(ei + 1, run);
+    stamp(2);
     __syncthreads();      // the slots of column layer ei are zero again; the liftings of layer ei are staged
     leave_f(ei);
+    stamp(3);
+  }
+  if (stamped && lane == 0) {      // -DIGX_DEBUG: per wavefront, the four parts of a step summed over the walk, and its elements
+    long long *d = pa.debug_buf + ((size_t)blockIdx.x * W + wave) * 5;
+    d[0] = st[0]; d[1] = st[1]; d[2] = st[2]; d[3] = st[3]; d[4] = ne;
   }
   if (seg == pa.nseg - 1 && !pa.open_hi)      // the last segment owns the layers beyond its last element too
     for (int li = ne; li < nl; ++li) {
@@ -293,11 +321,31 @@ static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &o
   for (int cy = 0; cy < G::SY; ++cy) for (int cx = 0; cx < G::SX; ++cx) {
     PatchArgs A; size_t lds = 0;
     if (!patch_colour_args<G>(s, cx, cy, forcing, first_touch, patch3_lds_bytes<MX, MY>, "the p = 3 patch walk's tables do not fit the LDS", A, lds)) { if (pencil_launch_error()) return; continue; }
-    const PencilArgs &pa = A.pa;
+    PencilArgs &pa = A.pa;
     const long long patches = pa.blocks_per_seg;
     auto kern = sys ? gram_pencil_patch3<true, MX, MY> : gram_pencil_patch3<false, MX, MY>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static int dbg_done = 0, dbg_seen = 0;      // -DIGX_DEBUG, IGX_DEBUG_TIMING=n: the n-th launch of the process is stamped (as launch_patches_p2)
+    const bool dbg_t = kDebug && s.env.debug_timing && !dbg_done && ++dbg_seen >= std::max(1, atoi(getenv("IGX_DEBUG_TIMING") ? getenv("IGX_DEBUG_TIMING") : "1"));
+    const size_t nwg = (size_t)(patches * pa.nseg), dbg_n = nwg * G::W * 5;
+    if (dbg_t) { (void)hipMalloc((void **)&pa.debug_buf, dbg_n * 8); (void)hipMemset(pa.debug_buf, 0, dbg_n * 8); }
     hipLaunchKernelGGL(kern, dim3((unsigned)(patches * pa.nseg)), dim3(G::W * 64), lds, stream, S, out, A);
+    if (dbg_t) {
+      dbg_done = 1;
+      (void)hipStreamSynchronize(stream);
+      std::vector<long long> h(dbg_n);
+      (void)hipMemcpy(h.data(), pa.debug_buf, dbg_n * 8, hipMemcpyDeviceToHost);
+      double sm[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}; long long cnt = 0;
+      for (size_t i = 0; i < nwg * G::W; ++i) {
+        const long long *d = &h[i * 5];
+        if (!d[4]) continue;
+        for (int c = 0; c < 4; ++c) { const double x = (double)d[c] / (double)d[4]; sm[c] += x; mx[c] = std::max(mx[c], x); }
+        cnt++;
+      }
+      if (cnt) fprintf(stderr, "[igx patch3 timing] colour (%d,%d): %zu workgroups, seg_len %d nseg %d; cycles per element step, mean (max) over %lld wavefronts: sub-phases %.0f (%.0f) | wait for the old values %.0f (%.0f) | window, stores, next loads %.0f (%.0f) | closing barrier + F %.0f (%.0f) | step %.0f\n",
+                       cx, cy, nwg, pa.seg_len, pa.nseg, cnt, sm[0] / cnt, mx[0], sm[1] / cnt, mx[1], sm[2] / cnt, mx[2], sm[3] / cnt, mx[3], (sm[0] + sm[1] + sm[2] + sm[3]) / cnt);
+      (void)hipFree(pa.debug_buf); pa.debug_buf = nullptr;
+    }
     launches++;
   }
 }
