@@ -324,6 +324,21 @@ int IGXComputeFunctionJacobian(IGX iga,IGXVec U,IGXVec F,IGXMat J);
 int IGXComputeMatrixAction   (IGX iga,IGXVec X,IGXVec Y);                                        /* Y = K X,    K of IGXComputeSystem    */
 int IGXComputeJacobianAction (IGX iga,IGXVec U,IGXVec X,IGXVec Y);                               /* Y = J(U) X, J of IGXComputeJacobian  */
 int IGXComputeIJacobianAction(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec X,IGXVec Y);    /* J of IGXComputeIJacobian             */
+/* Matrix-free diagonals (what MATOP_GET_DIAGONAL asks of a shell matrix: Jacobi, Chebyshev/Jacobi smoothing, diagonal scaling).
+ * D = diag A with A exactly the operator the matching action applies, IGAElementFixJacobian included: a fixed dof holds the number
+ * of local elements at its node, and a free field on a node whose other fields are fixed keeps its own entry.  Every mat() is
+ * linear in Na and in Nb, and for a form that reads N and grad N only the diagonal factorises over the axes like the action: mat()
+ * on the columns of the point's 4 x 4 geometry chain, folded into ten slots, goes back through the 1-D product rows (N^2, N N', N'^2)
+ * (vec_sumfact, DIAGONAL) -- no matrix, no index, no probing vectors.  D is zeroed and then assembled like any
+ * vector, with the same row numbering, bit-repeatable; on several ranks U and V must hold their ghosts and
+ * IGXReduceGhostRows(iga,NULL,D) completes the ghost rows.  Covered: what the actions cover, for forms and run-time structs whose
+ * shape features are of first order.  Second-order shape features (Cahn-Hilliard), a boundary-form pass, dim != 3, nsd != dim,
+ * order-3 or property forms, nen > 4, IGX_VEC_SUMFACT=0, an IGXSetKernel choice other than 0 return IGX_ERR_SUP with the reason:
+ * there is no fallback kernel.  D == U or V, a vector of another IGX or a null vector: IGX_ERR_ARG_WRONG; no form set:
+ * IGX_ERR_ARG_WRONGSTATE.  The dof x dof point-block diagonal is not formed. */
+int IGXComputeMatrixDiagonal   (IGX iga,IGXVec D);                                               /* diag of the matrix of IGXComputeSystem   */
+int IGXComputeJacobianDiagonal (IGX iga,IGXVec U,IGXVec D);                                      /* diag of IGXComputeJacobian's J(U)        */
+int IGXComputeIJacobianDiagonal(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec D);           /* diag of IGXComputeIJacobian's J          */
 
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
@@ -467,6 +482,7 @@ int IGXChecksum(IGX iga,IGXMat A,IGXVec b,double S[4]);
  * constant-coefficient multi-field struct.  gram == 6: band_points + band_pt<MyForm> (Matrix / Jacobian / IJacobian of a four-field
  * struct that separates its point coefficients: NCOEF, point_coef, mat_c), without a geometry and on a NURBS map.
  * gram == 7: the ACTION instantiation of vec_sumfact<MyForm> (IGXCompute*Action of the struct) for the current geometry kind.
+ * gram == 8: its DIAGONAL instantiation (IGXCompute*Diagonal of the struct; first-order shape features) likewise.
  * Returns 0 or IGX_ERR_USER with the compiler's log. */
 int IGXCheckFormSource(IGX iga,int with_matrix,int gram);
 

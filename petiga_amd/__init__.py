@@ -96,6 +96,8 @@ def lib(build_if_needed=False):
         "IGXComputeIFunctionIJacobian": [V, C.c_double, V, C.c_double, V, V, V], "IGXComputeFunctionJacobian": [V, V, V, V],
         "IGXComputeMatrixAction": [V, V, V], "IGXComputeJacobianAction": [V, V, V, V],
         "IGXComputeIJacobianAction": [V, C.c_double, V, C.c_double, V, V, V],
+        "IGXComputeMatrixDiagonal": [V, V], "IGXComputeJacobianDiagonal": [V, V, V],
+        "IGXComputeIJacobianDiagonal": [V, C.c_double, V, C.c_double, V, V],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -429,6 +431,10 @@ class IGX:
     def compute_matrix_action(self, X, Y): _ck(lib().IGXComputeMatrixAction(self.h, X.h, Y.h))
     def compute_jacobian_action(self, U, X, Y): _ck(lib().IGXComputeJacobianAction(self.h, U.h, X.h, Y.h))
     def compute_ijacobian_action(self, a, V, t, U, X, Y): _ck(lib().IGXComputeIJacobianAction(self.h, a, V.h, t, U.h, X.h, Y.h))
+    # matrix-free diagonals: D = diag A of the operator the matching action applies (a fixed dof holds its element count)
+    def compute_matrix_diagonal(self, D): _ck(lib().IGXComputeMatrixDiagonal(self.h, D.h))
+    def compute_jacobian_diagonal(self, U, D): _ck(lib().IGXComputeJacobianDiagonal(self.h, U.h, D.h))
+    def compute_ijacobian_diagonal(self, a, V, t, U, D): _ck(lib().IGXComputeIJacobianDiagonal(self.h, a, V.h, t, U.h, D.h))
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))
     def synchronize(self): _ck(lib().IGXSynchronize(self.h))
@@ -520,7 +526,7 @@ class IGX:
 
     def check_form_source(self, with_matrix=True, gram=False):
         """Compile-only check of the run-time form against the kernels the drivers would launch for the current degrees (no GPU needed)."""
-        # gram: False / True = the struct declares MAT_PAIR_MASK; 2, 3, 4 = the pencil walk / the vector kernel / state_pencil instead; 7 = the vector kernel's ACTION instantiation (compute_*_action)
+        # gram: False / True = the struct declares MAT_PAIR_MASK; 2, 3, 4 = the pencil walk / the vector kernel / state_pencil instead; 7 = the vector kernel's ACTION instantiation (compute_*_action); 8 = its DIAGONAL instantiation (compute_*_diagonal)
         _ck(lib().IGXCheckFormSource(self.h, 1 if with_matrix else 0, int(gram)))
 
     def comm_overlap_ms(self):

@@ -928,6 +928,24 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
       return fail(IGX_ERR_SUP, "the matrix action does not cover forms with a boundary branch or functionals");
     }
   }
+  // the matrix-free diagonals (IGXCompute*Diagonal): vec_sumfact's DIAGONAL instantiation or a refusal, under the actions' conditions and first-order shape features
+  if (op_is_diagonal(out.op)) {
+    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
+    if (GENERAL) return fail(IGX_ERR_SUP, VEC_DIAGONAL_GENERAL);
+    if (NS != 0 || has_boundary_of<Form>::v) return fail(IGX_ERR_SUP, "the matrix diagonal does not cover forms with a boundary branch or functionals");
+    if (shape_order_of<Form>::v >= 2) return fail(IGX_ERR_SUP, VEC_DIAGONAL_SECOND);
+#ifdef IGX_HAVE_VEC_SUMFACT
+    if constexpr (DIM == 3 && !GENERAL && NS == 0 && !has_boundary_of<Form>::v && shape_order_of<Form>::v < 2) {
+      if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
+      bool done = false;
+      ParamsDev prm; memset(&prm, 0, sizeof(prm));
+      for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
+      if (int rc = try_vec_sumfact<Form, false, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
+      return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix diagonal it covers");
+    }
+#endif
+    return fail(IGX_ERR_SUP, "the matrix diagonal needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)");
+  }
   if (GENERAL && g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a form of order 3 or one that reads the property array runs on the general kernel only");
   if ((Form::NEED & NEED_PROP) && !S.npd) return fail(IGX_ERR_ARG_WRONGSTATE, "No property set");      // src/petigaelem.c:300
   // a geometry of another dimension than the parametric one: tabulated by the general kernel only (no inverse map: src/petigaelem.c:966)
@@ -1358,6 +1376,37 @@ static int compute_action(IGX g, int op, IGXVec U, IGXVec V, IGXVec X, IGXVec Y,
 extern "C" int IGXComputeMatrixAction(IGX g, IGXVec X, IGXVec Y) { return compute_action(g, OP_MATRIX_ACTION, nullptr, nullptr, X, Y, 0, 0); }
 extern "C" int IGXComputeJacobianAction(IGX g, IGXVec U, IGXVec X, IGXVec Y) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_action(g, OP_JACOBIAN_ACTION, U, nullptr, X, Y, 0, 0); }
 extern "C" int IGXComputeIJacobianAction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec X, IGXVec Y) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_action(g, OP_IJACOBIAN_ACTION, U, V, X, Y, a, t); }
+
+// Matrix-free diagonals: D = diag A of the matrix the matching action applies (IGAElementFixJacobian included: a fixed dof holds the
+// number of local elements at its node), formed by vec_sumfact's DIAGONAL instantiation (vec_sumfact.hpp) or refused with IGX_ERR_SUP.
+// D is zeroed and assembled like a vector; on several ranks U and V hold their ghosts and IGXReduceGhostRows(iga, NULL, D) completes the ghost rows.
+static int compute_diagonal(IGX g, int op, IGXVec U, IGXVec V, IGXVec D, double shift, double t) {
+  NEEDIGA(g);
+  if (!D) return fail(IGX_ERR_ARG_WRONG, "null result vector");
+  if (D->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  if ((U && U == D) || (V && V == D)) return fail(IGX_ERR_ARG_WRONG, "the result must not be a state vector");
+  if (int rc = ensure_device(g)) return rc;
+  const Space &s = g->s;
+  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  OutDev out; memset(&out, 0, sizeof(out));
+  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
+  out.vec = D->a.as<double>();
+  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
+  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
+  HIPCK(hipMemsetAsync(D->a.p, 0, D->a.bytes, g->stream));
+  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
+  const SpaceDev S = make_spacedev(g);
+  g->dom = DomInfo(); g->slab_valid = 0;
+  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
+  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
+  if (rc) return rc;
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
+  return 0;
+}
+extern "C" int IGXComputeMatrixDiagonal(IGX g, IGXVec D) { return compute_diagonal(g, OP_MATRIX_DIAGONAL, nullptr, nullptr, D, 0, 0); }
+extern "C" int IGXComputeJacobianDiagonal(IGX g, IGXVec U, IGXVec D) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_diagonal(g, OP_JACOBIAN_DIAGONAL, U, nullptr, D, 0, 0); }
+extern "C" int IGXComputeIJacobianDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec D) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_diagonal(g, OP_IJACOBIAN_DIAGONAL, U, V, D, a, t); }
 
 // One pass for the pair a Newton step asks for at the same state (SNESComputeFunction + SNESComputeJacobian; src/petigats.c:23-159,
 // src/petigasnes.c:23-139): the results are those of the two drivers, in one walk where a fused kernel exists, else in two calls.

@@ -188,7 +188,8 @@ struct SpaceDev {
 struct ColorRange { int start[3], step[3], count[3]; };
 
 enum Op { OP_SYSTEM = 0, OP_MATRIX, OP_VECTOR, OP_FUNCTION, OP_JACOBIAN, OP_IFUNCTION, OP_IJACOBIAN, OP_SCALAR,
-          OP_MATRIX_ACTION, OP_JACOBIAN_ACTION, OP_IJACOBIAN_ACTION };      // Y = A X of the matrix the driver would assemble, matrix-free (vec_sumfact.hpp)
+          OP_MATRIX_ACTION, OP_JACOBIAN_ACTION, OP_IJACOBIAN_ACTION,        // Y = A X of the matrix the driver would assemble, matrix-free (vec_sumfact.hpp)
+          OP_MATRIX_DIAGONAL, OP_JACOBIAN_DIAGONAL, OP_IJACOBIAN_DIAGONAL };  // D = diag A of the same matrix, matrix-free (vec_sumfact.hpp, DIAGONAL; vec is D)
 
 struct OutDev {
   const int64_t *browptr;  // null when no matrix output
@@ -223,6 +224,15 @@ inline const char *vec_action_refusal(const Space &s, int kernel_choice) {
   if (kernel_choice != 0) return "the matrix action runs on vec_sumfact alone: IGXSetKernel must leave the choice automatic (0)";
   return nullptr;
 }
+// The matrix-free diagonals (OP_*_DIAGONAL) run where the actions run (vec_sumfact.hpp, DIAGONAL), first-order shape features only:
+// the same checks, asked through vec_action_refusal, under the diagonal's name.
+inline bool op_is_diagonal(int op) { return op == OP_MATRIX_DIAGONAL || op == OP_JACOBIAN_DIAGONAL || op == OP_IJACOBIAN_DIAGONAL; }
+inline std::string vec_diagonal_refusal(const Space &s, int kernel_choice) {
+  const char *why = vec_action_refusal(s, kernel_choice);
+  return why ? std::string("the matrix diagonal runs where the matrix action runs, and ") + why : std::string();
+}
+constexpr const char *VEC_DIAGONAL_SECOND = "the matrix diagonal does not cover forms with second-order shape features (Cahn-Hilliard's Laplacian): six product rows per axis and 55 coefficient slots per point are another kernel";
+constexpr const char *VEC_DIAGONAL_GENERAL = "the matrix diagonal does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives";
 #endif
 
 constexpr int MAXPARAM = 8;

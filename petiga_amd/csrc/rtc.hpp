@@ -83,7 +83,7 @@ struct RtcForm {
   hipModule_t module = nullptr; hipFunction_t func = nullptr;
   std::map<int, std::shared_ptr<RtcFeature>> feature;   // key: TA | NW << 4 | DOFI << 8 | HASM << 12
   std::map<int, std::shared_ptr<RtcFeature>> pencil;    // form_pencil instantiations; key: SYSTEM | P << 1 | IDENT << 4 | RAT << 5
-  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | two elements per wavefront << 1 | ACTION << 2
+  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | two elements per wavefront << 1 | ACTION << 2 | DIAGONAL << 3
   std::map<int, std::shared_ptr<RtcFeature>> state;     // state_pencil instantiations; key: P (+ 10 + rational on a mapped geometry, + 100 packed tiles)
   std::map<int, std::shared_ptr<RtcFeature>> block;     // block_pencil instantiations; key: SYSTEM
   std::map<int, std::shared_ptr<RtcFeature>> band;      // band_points + band_pt instantiations; key: GEO | RAT << 1 | degree << 2
@@ -463,20 +463,21 @@ static bool rtc_vecsf_eligible(const Space &s, const RtcForm &F, const OutDev &o
   return true;
 }
 // action: the ACTION instantiation (the matrix-free product of IGXCompute*Action); the caller has asked vec_action_refusal
-static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done, bool compile_only = false, bool action = false) {
+// diagonal: the DIAGONAL instantiation (IGXCompute*Diagonal), likewise; a struct of SHAPE_ORDER <= 1
+static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done, bool compile_only = false, bool action = false, bool diagonal = false) {
   done = false;
   const Space &s = g->s;
-  if (!compile_only && !action && !rtc_vecsf_eligible(s, F, out)) return 0;
+  if (!compile_only && !action && !diagonal && !rtc_vecsf_eligible(s, F, out)) return 0;
   const bool geo = s.nsd > 0 || s.rational;
   bool three = !s.env.no_vec_pairs;      // p <= 2: two elements per wavefront
   for (int d = 0; d < 3; ++d) three = three && s.axis[d].p >= 1 && s.axis[d].p <= 2 && (compile_only || (s.basis[d].nen <= 3 && s.basis[d].nqp <= 3));
-  const int key = (geo ? 1 : 0) | (three ? 2 : 0) | (action ? 4 : 0);
+  const int key = (geo ? 1 : 0) | (three ? 2 : 0) | (action ? 4 : 0) | (diagonal ? 8 : 0);
   std::shared_ptr<RtcFeature> K;
   auto it = F.vecsf.find(key);
   if (it != F.vecsf.end() && (it->second->module || compile_only)) K = it->second;
   else {
     K.reset(new RtcFeature());
-    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + (three ? "3" : "4") + (action ? ", true>" : ">");
+    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + (three ? "3" : "4") + (diagonal ? ", false, true>" : (action ? ", true>" : ">"));
     const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, long long);\n";
     if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, false, true)) return rc;
     if (!compile_only) {
@@ -510,7 +511,7 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
     launches++;
   }
   g->last_launches = launches;
-  g->last_kernel = std::string("vec_sumfact<") + F.name + (action ? ">(hiprtc,matrix action: sum factorisation" : ">(hiprtc,vector only: sum factorisation") + " forward and backward, " + (three ? "two elements per wavefront)" : "one wavefront per element)");
+  g->last_kernel = std::string("vec_sumfact<") + F.name + (diagonal ? ">(hiprtc,matrix diagonal: sum factorisation forward, product rows backward, " : (action ? ">(hiprtc,matrix action: sum factorisation forward and backward, " : ">(hiprtc,vector only: sum factorisation forward and backward, ")) + (three ? "two elements per wavefront)" : "one wavefront per element)");
   done = true;
   return 0;
 }
@@ -702,6 +703,14 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
   return rc;
 }
 
+// what of the struct itself keeps it off the DIAGONAL instantiation (meta: rtc.hpp:79), or null
+static const char *rtc_diagonal_refusal(const RtcForm &F) {
+  if (F.meta[1] >= 3 || ((unsigned)F.meta[2] & (NEED_PROP | NEED_D3U | NEED_MAPX))) return VEC_DIAGONAL_GENERAL;
+  if (F.meta[7]) return "the matrix diagonal does not cover forms with a boundary branch";
+  if (F.meta[4] >= 2) return VEC_DIAGONAL_SECOND;
+  return nullptr;
+}
+
 static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
   Space &s = g->s;
   g->rtc_note.clear();
@@ -722,6 +731,13 @@ static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
     bool done = false;
     if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, true)) return rc;
     return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix action it covers");
+  }
+  if (op_is_diagonal(out.op)) {    // the matrix-free diagonals: vec_sumfact's DIAGONAL instantiation of the struct or a refusal, as for the built-in forms
+    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
+    if (const char *why = rtc_diagonal_refusal(F)) return fail(IGX_ERR_SUP, why);
+    bool done = false;
+    if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, false, true)) return rc;
+    return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix diagonal it covers");
   }
   // a struct of ORDER 3, or one that reads the property array / the point's shape table / third derivatives of the state: the general kernel (as launch_generic)
   if (F.meta[1] >= 3 || ((unsigned)F.meta[2] & (NEED_PROP | NEED_D3U | NEED_MAPX)) || (s.nsd && s.nsd != s.dim)) {      // (... or a geometry with nsd != dim)
@@ -966,6 +982,12 @@ extern "C" int IGXCheckFormSource(IGX g, int with_matrix, int gram) {
     if (s.dim != 3) return fail(IGX_ERR_SUP, "the matrix action needs dim 3");
     bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
     return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, true);
+  }
+  if (gram == 8) {           // ... and its DIAGONAL instantiation (IGXCompute*Diagonal of the struct): compile only
+    if (s.dim != 3) return fail(IGX_ERR_SUP, "the matrix diagonal needs dim 3");
+    if (g->rtc->func) { if (const char *why = rtc_diagonal_refusal(*g->rtc)) return fail(IGX_ERR_SUP, why); }      // (the struct's constants are read from the loaded module; without a GPU the kernel's static_assert names the cause)
+    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
+    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, false, true);
   }
   if (gram == 3) {           // the sum-factorised vector kernel (vec_sumfact) of the struct, with and without a geometry: compile only
     if (s.dim != 3) return fail(IGX_ERR_SUP, "the sum-factorised vector kernel needs dim 3");

@@ -161,14 +161,23 @@ template <int N> struct vs_int { static constexpr int value = N; };      // (a d
 // mat(p, Na, Nb, T) is linear in Nb, so sum_b K_ab X_b = sum_q JW sum_f Phi_f(a, q) sum_j mat(p, e_f, Xf^j)[.][j] with Xf^j = (x^j, grad x^j,
 // hess x^j) the direction's point features -- one more forward pass per field, DOF calls of mat() per test feature, and the way back,
 // the colours and the scatter of the vector drivers.  No matrix is allocated and no index is read.
-template <class Form, bool GEO, int NS = 4, bool ACTION = false>
+// DIAGONAL: the diagonal D_a^i = K_aa^ii of the same matrix (OP_*_DIAGONAL), first-order shape features only.  mat() is linear in Na
+// as well, and R_a's features are w_a M(q) (N_a, d0 N_a, d1 N_a, d2 N_a) with M the point's 4 x 4 geometry chain (1 / W, E1 / W and the
+// rational correction; the identity without a geometry), so mat() on the columns of M gives B_kl = JW (M^T C M)_kl directly: at most
+// 4 x 4 calls per point.  D_k N_a D_l N_a factorises per axis into N^2, N N' or N'^2 and the per-axis product commutes: B folds
+// into ten slots indexed like the ten derivatives, and the way back is vs_backward<2> on the product rows {N^2, N N', N'^2} in
+// place of {N, N', N''}, once per field, times w_a^2.  No direction, no pass for one.
+template <class Form, bool GEO, int NS = 4, bool ACTION = false, bool DIAGONAL = false>
 __global__ void __launch_bounds__(256, (vs_pipe<Form, GEO>() ? 4 : 2))      // (two waves per SIMD: the geometry variants of NS-VMS and Cahn-Hilliard need 290-350 VGPRs uncapped, one wave per SIMD)
 vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nelem) {
   constexpr int EPW = NS == 3 ? 2 : 1, NL = NS * NS * NS;               // elements per wavefront, lanes per element
   constexpr int DOF = Form::DOF;
-  constexpr unsigned VMASK = ACTION ? mat_test_mask_of<Form>::v : vec_test_mask_of<Form>::v;      // test features vec() (ACTION: mat()) reads (bit f)
+  static_assert(!(ACTION && DIAGONAL), "one of the two");
+  static_assert(!DIAGONAL || shape_order_of<Form>::v < 2, "the matrix diagonal does not cover forms with second-order shape features: its ten product slots hold N and grad N only");
+  constexpr bool MATOP = ACTION || DIAGONAL;                             // mat() at the points, not vec()
+  constexpr unsigned VMASK = MATOP ? mat_test_mask_of<Form>::v : vec_test_mask_of<Form>::v;      // test features vec() (MATOP: mat()) reads (bit f)
   constexpr bool SECOND_T = shape_order_of<Form>::v >= 2;                // second-order test features
-  constexpr unsigned SNEED = ACTION ? mat_need_of<Form>::v : Form::NEED; // what the point callback reads of the state (ACTION: mat() alone)
+  constexpr unsigned SNEED = MATOP ? mat_need_of<Form>::v : Form::NEED;  // what the point callback reads of the state (MATOP: mat() alone)
   constexpr bool NEEDHU = (SNEED & NEED_HU) != 0, NEEDGU = (SNEED & (NEED_GU | NEED_HU)) != 0;
   constexpr int UORD = NEEDHU ? 2 : (NEEDGU ? 1 : 0);                    // derivative order of the state
   constexpr int XORD = ACTION ? (SECOND_T ? 2 : 1) : 0;                  // ... of the direction: the trial features mat() reads (Na's layout)
@@ -176,10 +185,12 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   constexpr int NFS = SECOND_T ? 13 : 4;
   // derivatives of the test functions that can carry a coefficient: without a geometry feature tf maps to one of them; with one, the
   // inverse Jacobian mixes the three first derivatives and the rational correction reaches the value
-  constexpr unsigned KMASK = GEO ? (SECOND_T ? 0x3FFu : 0xFu) : vs_kmask_ident(VMASK & ((1u << NFS) - 1u));
-  constexpr int NBACK = vs_popc(KMASK) > (SECOND_T ? 9 : 5) ? vs_popc(KMASK) : (SECOND_T ? 9 : 5), NFWD = (GORD == 2 || GEO) ? 10 : 7, NBUF = NBACK > NFWD ? NBACK : NFWD;
+  constexpr unsigned KMASK = DIAGONAL ? 0x3FFu : (GEO ? (SECOND_T ? 0x3FFu : 0xFu) : vs_kmask_ident(VMASK & ((1u << NFS) - 1u)));      // (DIAGONAL: the ten product slots)
+  constexpr bool BACK2 = SECOND_T || DIAGONAL;                           // the way back runs to order 2
+  constexpr int NBACK = vs_popc(KMASK) > (BACK2 ? 9 : 5) ? vs_popc(KMASK) : (BACK2 ? 9 : 5), NFWD = (GORD == 2 || GEO) ? 10 : 7, NBUF = NBACK > NFWD ? NBACK : NFWD;
   constexpr int TB = NS * NS * 3;                                        // doubles of one axis' rows [q][a][3], zero padded to NS x NS
-  __shared__ double sm_all[4][NBUF * 64 + EPW * 3 * TB];      // Cahn-Hilliard without a geometry: 25 KB per workgroup, two elements per wavefront (a sixth workgroup per CU measured no gain over five: 12.8 ms either way)
+  constexpr int NTAB = DIAGONAL ? 2 : 1;                                 // DIAGONAL: the product rows [q][a][3] = (N^2, N N', N'^2) behind the rows
+  __shared__ double sm_all[4][NBUF * 64 + NTAB * EPW * 3 * TB];      // Cahn-Hilliard without a geometry: 25 KB per workgroup, two elements per wavefront (a sixth workgroup per CU measured no gain over five: 12.8 ms either way)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int esub = (EPW == 2 && lane >= NL) ? 1 : 0;                    // which of the wavefront's elements this lane works on
   // Round 6 (PIPE: scalar forms without a geometry): every global load of the unit -- the 1-D rows, the node's state and old F, the
@@ -283,6 +294,15 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   VS_SYNC();      // (the previous element's readers of the rows are done)
 #pragma unroll
   for (int k = 0; k < TPL; ++k) if (lane < TB) buf[NBUF * 64 + k * TB + lane] = cur.tab[k];
+  if constexpr (DIAGONAL) {      // the product rows, once per element and axis: entry (q, a, v) from (N, N') of (q, a)
+    VS_SYNC();
+    const int j0 = lane < TB ? lane - lane % 3 : 0, v = lane % 3;
+#pragma unroll
+    for (int k = 0; k < TPL; ++k) {
+      const double n0 = buf[NBUF * 64 + k * TB + j0], n1 = buf[NBUF * 64 + k * TB + j0 + 1];
+      if (lane < TB) buf[NBUF * 64 + (TPL + k) * TB + lane] = (v == 0 ? n0 : n1) * (v == 2 ? n1 : n0);
+    }
+  }
   if (PIPE && more) stageA(unext, nxt);
   // Dirichlet flags (IGAElementBuildFix / FixValues, src/petigaelem.c:1214-1358)
   const bool isnode = live && lanenode;
@@ -466,6 +486,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   for (int f = 0; f < DOF; ++f)
 #pragma unroll
     for (int k = 0; k < 10; ++k) Cq[f][k] = 0.0;
+  if constexpr (!DIAGONAL)      // (its point stage follows the loop)
 #pragma unroll
   for (int tf = 0; tf < NFS; ++tf) {
     if (!((VMASK >> tf) & 1u)) continue;
@@ -518,9 +539,37 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
       }
     }
   }
+  if constexpr (DIAGONAL) {
+    // column k of M (the header's comment): the physical features (value, gradient) of a function whose parametric ones are e_k
+    auto mcol = [&](int k, double (&c)[4]) {
+      if constexpr (!GEO) { for (int f = 0; f < 4; ++f) c[f] = (f == k) ? 1.0 : 0.0; }
+      else {
+        c[0] = k == 0 ? iw : 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) c[1 + i] = k == 0 ? -(E1[0 * 3 + i] * o1[0] + E1[1 * 3 + i] * o1[1] + E1[2 * 3 + i] * o1[2]) * iw : E1[(k - 1) * 3 + i] * iw;
+      }
+    };
+    // columns of M with an entry mat() reads on the test side: without a geometry e_k itself; with one the gradient rows fill every column
+    constexpr unsigned TK = GEO ? ((VMASK & 0xEu) ? 0xFu : 0x1u) : (VMASK & 0xFu);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!((TK >> k) & 1u)) continue;
+      double Na[4]; mcol(k, Na);
+#pragma unroll
+      for (int l = 0; l < 4; ++l) {
+        double Nb[4], T[DOF * DOF]; mcol(l, Nb);
+#pragma unroll
+        for (int i = 0; i < DOF * DOF; ++i) T[i] = 0.0;
+        Form::mat(p, Na, Nb, T);
+        const int slot = (k == 0 || l == 0) ? k + l : k2(k - 1, l - 1);      // B_kl and B_lk share a slot
+#pragma unroll
+        for (int f = 0; f < DOF; ++f) Cq[f][slot] += ispoint ? T[f * DOF + f] * JW : 0.0;
+      }
+    }
+  }
   // rational test functions: R_a = w_a N_a / W, d_b R_a = (w_a / W) (d_b N_a - N_a W_b / W), d_b d_c R_a = (w_a / W) (d_b d_c N_a -
   // d_b N_a o_c - d_c N_a o_b - N_a (W_bc / W - 2 o_b o_c)) (src/petigarat.f90.in, order 2): the coefficients of the polynomial basis
-  if (rat) {
+  if (!DIAGONAL && rat) {      // (DIAGONAL: M holds the correction)
 #pragma unroll
     for (int f = 0; f < DOF; ++f) {
       double c0 = Cq[f][0] - (Cq[f][1] * o1[0] + Cq[f][2] * o1[1] + Cq[f][3] * o1[2]);
@@ -542,10 +591,13 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   // ---- backward, IGAElementFixFunction (src/petigaelem.c:1449-1461), IGAElementAssembleVec
 #pragma unroll
   for (int f = 0; f < DOF; ++f) {
-    double F = SECOND_T ? vs_backward<2, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL) : vs_backward<1, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL);
+    double F;
+    if constexpr (DIAGONAL) F = vs_backward<2, KMASK, NS>(Cq[f], buf, tab0 + EPW * 3 * TB, tab1 + EPW * 3 * TB, tab2 + EPW * 3 * TB, lane, VL) * wgt;      // (the product rows; w_a^2 with the line below)
+    else F = SECOND_T ? vs_backward<2, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL) : vs_backward<1, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL);
     F *= wgt;
     if (isnode) {
       if constexpr (ACTION) { if (fixed[f]) F = Xv[f]; }        // IGAElementFixJacobian: a unit diagonal per element, zero row and column beside it
+      else if constexpr (DIAGONAL) { if (fixed[f]) F = 1.0; }   // ... and that unit diagonal itself: the element count once assembled
       else if (fixed[f] && sysvec) F = ufix[f];                  // IGAElementFixSystem: F_e[k] = v
       else if (fixed[f] && sysbody) F = 0.0;                     // (the band-row kernel that follows adds v per element itself)
       else if (fixed[f] && (op == OP_FUNCTION || op == OP_IFUNCTION)) F = Uv[f] - ufix[f];
@@ -577,12 +629,12 @@ static bool vec_sumfact_covers(const Space &s, const OutDev &out) {
   }
 }
 
-template <class Form, bool ACTION = false>
+template <class Form, bool ACTION = false, bool DIAGONAL = false>
 static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &prm, const OutDev &out, hipStream_t stream, std::string &kname, int &launches, bool &done) {
   done = false;
   if constexpr (nscalar_of<Form>::v > 0 || has_boundary_of<Form>::v) return 0;
   else {
-  if constexpr (!ACTION) { if (!vec_sumfact_covers<Form>(s, out)) return 0; }      // (ACTION: the caller has asked vec_action_refusal)
+  if constexpr (!ACTION && !DIAGONAL) { if (!vec_sumfact_covers<Form>(s, out)) return 0; }      // (ACTION, DIAGONAL: the caller has asked vec_action_refusal)
   launches = 0;
   const int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
   for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
@@ -604,12 +656,12 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
     const bool onepass = true;      // (UNITS = 1 in the kernel)      // (one pass per wavefront: the launch has a wavefront per unit)
     if (three) {
       const unsigned grid = onepass ? (unsigned)((nelem + 7) / 8) : (unsigned)((nelem + 15) / 16);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 3, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 3, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 3, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      else hipLaunchKernelGGL((vec_sumfact<Form, false, 3, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
     } else {
       const unsigned grid = onepass ? (unsigned)((nelem + 3) / 4) : (unsigned)((nelem + 7) / 8);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 4, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 4, ACTION>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 4, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      else hipLaunchKernelGGL((vec_sumfact<Form, false, 4, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
     }
     launches++;
   }
@@ -617,7 +669,9 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
   {
     bool three = !s.env.no_vec_pairs;
     for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
-    if constexpr (ACTION) kname = three ? "vec_sumfact(matrix action: sum factorisation forward and backward, two elements per wavefront)"
+    if constexpr (DIAGONAL) kname = three ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, two elements per wavefront)"
+                                          : "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, one wavefront per element)";
+    else if constexpr (ACTION) kname = three ? "vec_sumfact(matrix action: sum factorisation forward and backward, two elements per wavefront)"
                                         : "vec_sumfact(matrix action: sum factorisation forward and backward, one wavefront per element)";
     else
     kname = three ? "vec_sumfact(vector only: sum factorisation forward and backward, two elements per wavefront)"
