@@ -316,9 +316,10 @@ int IGXComputeFunctionJacobian(IGX iga,IGXVec U,IGXVec F,IGXMat J);
  * index is read: the direction's point values go through mat() in place of a trial function (every mat() is linear in Nb), one
  * more forward pass per field on the sum-factorised vector kernel (vec_sumfact, ACTION).  Y is zeroed and then assembled like any
  * vector, with the same row numbering; on several ranks X must hold its ghosts (IGXRefreshGhosts) and IGXReduceGhostRows(iga,NULL,Y)
- * completes the ghost rows.  Covered: 3-D, nen and nqp <= 4 per axis, identity / polynomial / NURBS geometry with nsd = 3, Dirichlet
+ * completes the ghost rows.  Covered: 3-D, nen and nqp <= 8 per axis (degree <= 7; up to 4 one wavefront works on an element, up
+ * to 6 and up to 8 one workgroup of 256 / 512 threads), identity / polynomial / NURBS geometry with nsd = 3, Dirichlet
  * values, periodic axes, every built-in or run-time form of order <= 2 without a boundary branch.  Everything else -- a boundary-form
- * pass, dim != 3, nsd != dim, order-3 or property forms, nen > 4, IGX_VEC_SUMFACT=0, an IGXSetKernel choice other than 0 -- returns
+ * pass, dim != 3, nsd != dim, order-3 or property forms, nen or nqp > 8, IGX_VEC_SUMFACT=0, an IGXSetKernel choice other than 0 -- returns
  * IGX_ERR_SUP with the reason: there is no fallback kernel.  Boundary loads do not enter a matrix and are ignored.  X == Y, a
  * vector of another IGX or a null vector: IGX_ERR_ARG_WRONG; no form set: IGX_ERR_ARG_WRONGSTATE. */
 int IGXComputeMatrixAction   (IGX iga,IGXVec X,IGXVec Y);                                        /* Y = K X,    K of IGXComputeSystem    */
@@ -333,7 +334,7 @@ int IGXComputeIJacobianAction(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec
  * vector, with the same row numbering, bit-repeatable; on several ranks U and V must hold their ghosts and
  * IGXReduceGhostRows(iga,NULL,D) completes the ghost rows.  Covered: what the actions cover, for forms and run-time structs whose
  * shape features are of first order.  Second-order shape features (Cahn-Hilliard), a boundary-form pass, dim != 3, nsd != dim,
- * order-3 or property forms, nen > 4, IGX_VEC_SUMFACT=0, an IGXSetKernel choice other than 0 return IGX_ERR_SUP with the reason:
+ * order-3 or property forms, nen or nqp > 8, IGX_VEC_SUMFACT=0, an IGXSetKernel choice other than 0 return IGX_ERR_SUP with the reason:
  * there is no fallback kernel.  D == U or V, a vector of another IGX or a null vector: IGX_ERR_ARG_WRONG; no form set:
  * IGX_ERR_ARG_WRONGSTATE.  The dof x dof point-block diagonal is not formed. */
 int IGXComputeMatrixDiagonal   (IGX iga,IGXVec D);                                               /* diag of the matrix of IGXComputeSystem   */
@@ -482,7 +483,9 @@ int IGXChecksum(IGX iga,IGXMat A,IGXVec b,double S[4]);
  * constant-coefficient multi-field struct.  gram == 6: band_points + band_pt<MyForm> (Matrix / Jacobian / IJacobian of a four-field
  * struct that separates its point coefficients: NCOEF, point_coef, mat_c), without a geometry and on a NURBS map.
  * gram == 7: the ACTION instantiation of vec_sumfact<MyForm> (IGXCompute*Action of the struct) for the current geometry kind.
- * gram == 8: its DIAGONAL instantiation (IGXCompute*Diagonal of the struct; first-order shape features) likewise.
+ * gram == 8: its DIAGONAL instantiation (IGXCompute*Diagonal of the struct; first-order shape features) likewise.  Both compile the
+ * layout the driver would launch for the degrees and quadrature sizes set so far (one wavefront per element up to nen, nqp = 4, one
+ * workgroup per element with 6 x 6 x 6 or 8 x 8 x 8 lanes above) and return IGX_ERR_SUP with the driver's reason where it would refuse.
  * Returns 0 or IGX_ERR_USER with the compiler's log. */
 int IGXCheckFormSource(IGX iga,int with_matrix,int gram);
 

@@ -215,11 +215,22 @@ struct OutDev {
 // The matrix-free actions (OP_MATRIX_ACTION / OP_JACOBIAN_ACTION / OP_IJACOBIAN_ACTION) run on vec_sumfact (vec_sumfact.hpp, ACTION) or not at all: why not, or null.
 // Boundary loads do not enter a matrix and are ignored.
 inline bool op_is_action(int op) { return op == OP_MATRIX_ACTION || op == OP_JACOBIAN_ACTION || op == OP_IJACOBIAN_ACTION; }
+// basis functions and points of axis d: the basis' once the space is set up, before that what the axes and rules set so far will give (src/petigabasis.c:103)
+inline void vec_axis_sizes(const Space &s, int d, int &nen, int &nqp) {
+  if (s.setup) { nen = s.basis[d].nen; nqp = s.basis[d].nqp; }
+  else { nen = s.axis[d].p + 1; nqp = s.rule_nqp[d] > 0 ? s.rule_nqp[d] : s.axis[d].p + 1; }
+}
+// the largest of them over the three axes: up to 4 a wavefront holds an element (3: two), up to 6 and up to 8 a workgroup does
+inline int vec_lanes_per_axis(const Space &s) {
+  int m = 0;
+  for (int d = 0; d < 3; ++d) { int nen, nqp; vec_axis_sizes(s, d, nen, nqp); m = nen > m ? nen : m; m = nqp > m ? nqp : m; }
+  return m;
+}
 inline const char *vec_action_refusal(const Space &s, int kernel_choice) {
   for (int d = 0; d < s.dim; ++d) for (int sd = 0; sd < 2; ++sd) if (s.visit[d][sd]) return "the matrix action does not cover boundary-form passes (IGXSetBoundaryForm): it runs on vec_sumfact alone";
   if (s.dim != 3) return "the matrix action needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)";
   if (s.nsd != 0 && s.nsd != 3) return "the matrix action needs a geometry with nsd = dim";
-  for (int d = 0; d < 3; ++d) if (s.basis[d].nen > 4 || s.basis[d].nqp > 4) return "the matrix action needs nen <= 4 and nqp <= 4 on every axis (degree <= 3)";
+  if (vec_lanes_per_axis(s) > 8) return "the matrix action needs nen <= 8 and nqp <= 8 on every axis (degree <= 7)";
   if (s.env.vec_sumfact == 0) return "the matrix action runs on vec_sumfact alone, and IGX_VEC_SUMFACT=0 switches that kernel off";
   if (kernel_choice != 0) return "the matrix action runs on vec_sumfact alone: IGXSetKernel must leave the choice automatic (0)";
   return nullptr;

@@ -83,7 +83,7 @@ struct RtcForm {
   hipModule_t module = nullptr; hipFunction_t func = nullptr;
   std::map<int, std::shared_ptr<RtcFeature>> feature;   // key: TA | NW << 4 | DOFI << 8 | HASM << 12
   std::map<int, std::shared_ptr<RtcFeature>> pencil;    // form_pencil instantiations; key: SYSTEM | P << 1 | IDENT << 4 | RAT << 5
-  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | two elements per wavefront << 1 | ACTION << 2 | DIAGONAL << 3
+  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | two elements per wavefront << 1 | ACTION << 2 | DIAGONAL << 3 | one workgroup per element with 6 (8) lanes per axis << 4 (5)
   std::map<int, std::shared_ptr<RtcFeature>> state;     // state_pencil instantiations; key: P (+ 10 + rational on a mapped geometry, + 100 packed tiles)
   std::map<int, std::shared_ptr<RtcFeature>> block;     // block_pencil instantiations; key: SYSTEM
   std::map<int, std::shared_ptr<RtcFeature>> band;      // band_points + band_pt instantiations; key: GEO | RAT << 1 | degree << 2
@@ -471,13 +471,16 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   const bool geo = s.nsd > 0 || s.rational;
   bool three = !s.env.no_vec_pairs;      // p <= 2: two elements per wavefront
   for (int d = 0; d < 3; ++d) three = three && s.axis[d].p >= 1 && s.axis[d].p <= 2 && (compile_only || (s.basis[d].nen <= 3 && s.basis[d].nqp <= 3));
-  const int key = (geo ? 1 : 0) | (three ? 2 : 0) | (action ? 4 : 0) | (diagonal ? 8 : 0);
+  const int ns = (action || diagonal) ? vec_lanes_per_axis(s) : 4;      // above 4: one workgroup per element, 6 or 8 lanes per axis (the vector-only drivers stay below)
+  const int wg = ns > 6 ? 8 : (ns > 4 ? 6 : 0);
+  if (wg) three = false;
+  const int key = (geo ? 1 : 0) | (three ? 2 : 0) | (action ? 4 : 0) | (diagonal ? 8 : 0) | (wg == 6 ? 16 : 0) | (wg == 8 ? 32 : 0);
   std::shared_ptr<RtcFeature> K;
   auto it = F.vecsf.find(key);
   if (it != F.vecsf.end() && (it->second->module || compile_only)) K = it->second;
   else {
     K.reset(new RtcFeature());
-    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + (three ? "3" : "4") + (diagonal ? ", false, true>" : (action ? ", true>" : ">"));
+    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + (wg == 8 ? "8" : (wg == 6 ? "6" : (three ? "3" : "4"))) + (diagonal ? ", false, true>" : (action ? ", true>" : ">"));
     const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, long long);\n";
     if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, false, true)) return rc;
     if (!compile_only) {
@@ -506,12 +509,12 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
     args.cr = cr; args.nelem = (long long)cr.count[0] * cr.count[1] * cr.count[2];
     size_t asz = sizeof(args);
     void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    const unsigned want = (unsigned)((args.nelem + (three ? 7 : 3)) / (three ? 8 : 4));      // (a wavefront walks a sequence of elements: vec_sumfact.hpp, round 6)
-    HIPCK(hipModuleLaunchKernel(K->func[0], want, 1, 1, 256, 1, 1, 0, g->stream, nullptr, cfg));
+    const unsigned want = wg ? (unsigned)args.nelem : (unsigned)((args.nelem + (three ? 7 : 3)) / (three ? 8 : 4));      // (a wavefront walks a sequence of elements: vec_sumfact.hpp, round 6)
+    HIPCK(hipModuleLaunchKernel(K->func[0], want, 1, 1, wg == 8 ? 512 : 256, 1, 1, 0, g->stream, nullptr, cfg));
     launches++;
   }
   g->last_launches = launches;
-  g->last_kernel = std::string("vec_sumfact<") + F.name + (diagonal ? ">(hiprtc,matrix diagonal: sum factorisation forward, product rows backward, " : (action ? ">(hiprtc,matrix action: sum factorisation forward and backward, " : ">(hiprtc,vector only: sum factorisation forward and backward, ")) + (three ? "two elements per wavefront)" : "one wavefront per element)");
+  g->last_kernel = std::string("vec_sumfact<") + F.name + (diagonal ? ">(hiprtc,matrix diagonal: sum factorisation forward, product rows backward, " : (action ? ">(hiprtc,matrix action: sum factorisation forward and backward, " : ">(hiprtc,vector only: sum factorisation forward and backward, ")) + (wg == 8 ? "one workgroup per element, 8 x 8 x 8 lanes)" : (wg == 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : (three ? "two elements per wavefront)" : "one wavefront per element)")));
   done = true;
   return 0;
 }
@@ -980,12 +983,14 @@ extern "C" int IGXCheckFormSource(IGX g, int with_matrix, int gram) {
   }
   if (gram == 7) {           // ... and its ACTION instantiation (IGXCompute*Action of the struct): compile only
     if (s.dim != 3) return fail(IGX_ERR_SUP, "the matrix action needs dim 3");
+    if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);      // (where the driver would refuse)
     bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
     return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, true);
   }
   if (gram == 8) {           // ... and its DIAGONAL instantiation (IGXCompute*Diagonal of the struct): compile only
     if (s.dim != 3) return fail(IGX_ERR_SUP, "the matrix diagonal needs dim 3");
     if (g->rtc->func) { if (const char *why = rtc_diagonal_refusal(*g->rtc)) return fail(IGX_ERR_SUP, why); }      // (the struct's constants are read from the loaded module; without a GPU the kernel's static_assert names the cause)
+    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
     bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
     return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, false, true);
   }

@@ -15,7 +15,8 @@
 // One wavefront per element (4 x 4 x 4 lanes = nodes = points), two elements per wavefront when no axis has more than three basis
 // functions or points (p <= 2: 2 x 27 of the 64 lanes), no matrix cores (there is no
 // dense contraction left: the work per element drops from ~nen * nqp * features to ~(nen + nqp) * (p+1) * components), coloured
-// scatter (conflict-free, fixed order: bitwise repeatable).  dim 3, nen <= 4 and nqp <= 4 per axis; first-order test features on
+// scatter (conflict-free, fixed order: bitwise repeatable).  dim 3, nen <= 4 and nqp <= 4 per axis (the matrix-free ACTION and DIAGONAL
+// instantiations: up to 8, one workgroup per element above 4 -- vs_layout below); first-order test features on
 // any geometry, second-order test features (Cahn-Hilliard's Laplacian) likewise (round 4); no boundary loads, no boundary
 // passes -- everything else stays on the feature kernel.
 #pragma once
@@ -32,111 +33,121 @@ __device__ __forceinline__ constexpr int vs_m(int v0, int v1) { return v0 == 0 ?
 __device__ __forceinline__ constexpr int vs_mv0(int m) { return (m == 1 || m == 4) ? 1 : (m == 3 ? 2 : 0); }
 __device__ __forceinline__ constexpr int vs_mv1(int m) { return (m == 2 || m == 4) ? 1 : (m == 5 ? 2 : 0); }
 
-#define VS_SYNC() do { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); } while (0)
+// the barrier between the stages of a contraction: of the wavefront where a wavefront holds the element (NS <= 4), of the workgroup
+// (WG) where a workgroup does (NS = 6, 8).  Every thread of the workgroup reaches every one of them.
+template <bool WG> __device__ __forceinline__ void vs_sync() {
+  if constexpr (WG) __syncthreads();
+  else { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+}
+#define VS_SYNC() vs_sync<WG>()
+// the loops over the contracted index: unrolled in full up to NS = 4, by half above (8 steps in full keep up to 80 LDS loads of the way
+// back in flight: Elasticity's and NS-VMS' actions spilled 16-146 registers at NS = 6, 8 under the 256 two wavefronts per SIMD leave)
+#define VS_UNROLL(NS) ((NS) <= 4 ? (NS) : (NS) / 2)      // (UNR in the helpers)
 
-// forward: D[k] = sum_a coef_a D_k N_a(q) at this lane's point; ORD = highest derivative order wanted.  buf: 10 x 64 doubles of this
-// wave; tab[d]: [q][a][3] (value, first, second derivative), zero padded to NS x NS.
+// forward: D[k] = sum_a coef_a D_k N_a(q) at this lane's point; ORD = highest derivative order wanted.  buf: 10 x BS doubles of this
+// wave (WG: of this workgroup; BS >= NS^3 is the stride between the buffers); tab[d]: [q][a][3] (value, first, second derivative),
+// zero padded to NS x NS.
 // NS: lanes per axis -- 4: one element per wavefront; 3 (nen, nqp <= 3 on every axis): two elements per wavefront, lanes 0..26 and
 // 27..53.  L: this lane's (i0, i1, i2) and the first lane of its element.
 struct VsLane { int i0, i1, i2, base; };
-template <int ORD, int NS>
+template <int ORD, int NS, int BS = 64, bool WG = false>
 __device__ __forceinline__ void vs_forward(double coef, double *buf, const double *tab0, const double *tab1, const double *tab2, int lane, const VsLane &L, double (&D)[10]) {
   const int i0 = L.i0, i1 = L.i1, i2 = L.i2;
-  constexpr int S1 = NS, S2 = NS * NS;
-  double *in = buf + L.base, *T1 = buf + 64 + L.base, *T2 = buf + 4 * 64 + L.base;
+  constexpr int S1 = NS, S2 = NS * NS, UNR = VS_UNROLL(NS);
+  double *in = buf + L.base, *T1 = buf + BS + L.base, *T2 = buf + 4 * BS + L.base;
   lane -= L.base;
   VS_SYNC();
   in[lane] = coef;
   VS_SYNC();
   {   // axis 0: lane (q0, a1, a2)
     double t[3] = {0, 0, 0};
-#pragma unroll
+#pragma unroll UNR
     for (int a0 = 0; a0 < NS; ++a0) {
       const double c = in[a0 + S1 * i1 + S2 * i2];
 #pragma unroll
       for (int v = 0; v <= ORD; ++v) t[v] += c * tab0[(i0 * NS + a0) * 3 + v];
     }
 #pragma unroll
-    for (int v = 0; v <= ORD; ++v) T1[v * 64 + lane] = t[v];
+    for (int v = 0; v <= ORD; ++v) T1[v * BS + lane] = t[v];
   }
   VS_SYNC();
   {   // axis 1: lane (q0, q1, a2)
     double t[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
+#pragma unroll UNR
     for (int a1 = 0; a1 < NS; ++a1) {
 #pragma unroll
       for (int m = 0; m < 6; ++m) {
         if (vs_mv0(m) + vs_mv1(m) > ORD) continue;
-        t[m] += T1[vs_mv0(m) * 64 + i0 + S1 * a1 + S2 * i2] * tab1[(i1 * NS + a1) * 3 + vs_mv1(m)];
+        t[m] += T1[vs_mv0(m) * BS + i0 + S1 * a1 + S2 * i2] * tab1[(i1 * NS + a1) * 3 + vs_mv1(m)];
       }
     }
 #pragma unroll
-    for (int m = 0; m < 6; ++m) if (vs_mv0(m) + vs_mv1(m) <= ORD) T2[m * 64 + lane] = t[m];
+    for (int m = 0; m < 6; ++m) if (vs_mv0(m) + vs_mv1(m) <= ORD) T2[m * BS + lane] = t[m];
   }
   VS_SYNC();
 #pragma unroll
   for (int k = 0; k < 10; ++k) D[k] = 0.0;
-#pragma unroll
+#pragma unroll UNR
   for (int a2 = 0; a2 < NS; ++a2) {
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
       if (vs_v0(k) + vs_v1(k) + vs_v2(k) > ORD) continue;
-      D[k] += T2[vs_m(vs_v0(k), vs_v1(k)) * 64 + i0 + S1 * i1 + S2 * a2] * tab2[(i2 * NS + a2) * 3 + vs_v2(k)];
+      D[k] += T2[vs_m(vs_v0(k), vs_v1(k)) * BS + i0 + S1 * i1 + S2 * a2] * tab2[(i2 * NS + a2) * 3 + vs_v2(k)];
     }
   }
 }
 
-// backward: F_a = sum_q sum_k C_k(q) D_k N_a(q) at this lane's node; buf: 16 x 64 doubles of this wave
+// backward: F_a = sum_q sum_k C_k(q) D_k N_a(q) at this lane's node; buf: max(popc(KMASK), 9) x BS doubles of this wave (workgroup)
 // KMASK: the derivatives k whose coefficient can be non-zero (the others are neither stored nor summed); Cb holds them back to back
 __device__ __forceinline__ constexpr int vs_popc(unsigned m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
 __device__ __forceinline__ constexpr int vs_kc(unsigned kmask, int k) { return vs_popc(kmask & ((1u << k) - 1u)); }
-template <int ORD, unsigned KMASK, int NS>
+template <int ORD, unsigned KMASK, int NS, int BS = 64, bool WG = false>
 __device__ __forceinline__ double vs_backward(const double (&C)[10], double *buf, const double *tab0, const double *tab1, const double *tab2, int lane, const VsLane &L) {
   const int i0 = L.i0, i1 = L.i1, i2 = L.i2;
-  constexpr int T1s = NS, T2s = NS * NS;
+  constexpr int T1s = NS, T2s = NS * NS, UNR = VS_UNROLL(NS);
   // (round 6: S2 takes the place of Cb -- every lane holds its sums in registers until all have read Cb -- and S1 sits behind S2:
   //  max(popc, 9) buffers instead of popc + 6; with the forward stage's 10 that is 30 KB per workgroup, five workgroups per CU instead of four)
   constexpr int NS2 = ORD >= 2 ? 6 : 3;
-  double *Cb = buf + L.base, *S2 = buf + L.base, *S1 = buf + NS2 * 64 + L.base;
+  double *Cb = buf + L.base, *S2 = buf + L.base, *S1 = buf + NS2 * BS + L.base;
   lane -= L.base;
   VS_SYNC();
 #pragma unroll
-  for (int k = 0; k < 10; ++k) if (((KMASK >> k) & 1u) && vs_v0(k) + vs_v1(k) + vs_v2(k) <= ORD) Cb[vs_kc(KMASK, k) * 64 + lane] = C[k];
+  for (int k = 0; k < 10; ++k) if (((KMASK >> k) & 1u) && vs_v0(k) + vs_v1(k) + vs_v2(k) <= ORD) Cb[vs_kc(KMASK, k) * BS + lane] = C[k];
   VS_SYNC();
   {   // axis 2: lane (q0, q1, a2)
     double t[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
+#pragma unroll UNR
     for (int q2 = 0; q2 < NS; ++q2) {
 #pragma unroll
       for (int k = 0; k < 10; ++k) {
         if (!((KMASK >> k) & 1u) || vs_v0(k) + vs_v1(k) + vs_v2(k) > ORD) continue;
-        t[vs_m(vs_v0(k), vs_v1(k))] += Cb[vs_kc(KMASK, k) * 64 + i0 + T1s * i1 + T2s * q2] * tab2[(q2 * NS + i2) * 3 + vs_v2(k)];
+        t[vs_m(vs_v0(k), vs_v1(k))] += Cb[vs_kc(KMASK, k) * BS + i0 + T1s * i1 + T2s * q2] * tab2[(q2 * NS + i2) * 3 + vs_v2(k)];
       }
     }
     VS_SYNC();      // (every lane has read Cb)
 #pragma unroll
-    for (int m = 0; m < 6; ++m) if (vs_mv0(m) + vs_mv1(m) <= ORD) S2[m * 64 + lane] = t[m];
+    for (int m = 0; m < 6; ++m) if (vs_mv0(m) + vs_mv1(m) <= ORD) S2[m * BS + lane] = t[m];
   }
   VS_SYNC();
   {   // axis 1: lane (q0, a1, a2)
     double t[3] = {0, 0, 0};
-#pragma unroll
+#pragma unroll UNR
     for (int q1 = 0; q1 < NS; ++q1) {
 #pragma unroll
       for (int m = 0; m < 6; ++m) {
         if (vs_mv0(m) + vs_mv1(m) > ORD) continue;
-        t[vs_mv0(m)] += S2[m * 64 + i0 + T1s * q1 + T2s * i2] * tab1[(q1 * NS + i1) * 3 + vs_mv1(m)];
+        t[vs_mv0(m)] += S2[m * BS + i0 + T1s * q1 + T2s * i2] * tab1[(q1 * NS + i1) * 3 + vs_mv1(m)];
       }
     }
 #pragma unroll
-    for (int v = 0; v <= ORD; ++v) S1[v * 64 + lane] = t[v];
+    for (int v = 0; v <= ORD; ++v) S1[v * BS + lane] = t[v];
   }
   VS_SYNC();
   double f = 0;
-#pragma unroll
+#pragma unroll UNR
   for (int q0 = 0; q0 < NS; ++q0) {
 #pragma unroll
-    for (int v = 0; v <= ORD; ++v) f += S1[v * 64 + q0 + T1s * i1 + T2s * i2] * tab0[(q0 * NS + i0) * 3 + v];
+    for (int v = 0; v <= ORD; ++v) f += S1[v * BS + q0 + T1s * i1 + T2s * i2] * tab0[(q0 * NS + i0) * 3 + v];
   }
   return f;
 }
@@ -167,11 +178,24 @@ template <int N> struct vs_int { static constexpr int value = N; };      // (a d
 // 4 x 4 calls per point.  D_k N_a D_l N_a factorises per axis into N^2, N N' or N'^2 and the per-axis product commutes: B folds
 // into ten slots indexed like the ten derivatives, and the way back is vs_backward<2> on the product rows {N^2, N N', N'^2} in
 // place of {N, N', N''}, once per field, times w_a^2.  No direction, no pass for one.
+// NS = 6, 8 (ACTION and DIAGONAL; nen or nqp above 4 on some axis): one workgroup per element -- 256 threads (216 of them lanes of the
+// 6 x 6 x 6 nodes = points, the 40 others idle: they load zeros, store nothing and reach every barrier) or 512 threads (8 x 8 x 8), thread t
+// = (i0, i1, i2) with i0 fastest; the same helpers with the workgroup's barrier and a stride of 256 / 512 doubles between the buffers; no
+// pairing of elements and no early loads (PIPE, EF).  Not covered: the vector-only drivers above four (they stay on the feature
+// kernel), nen or nqp above 8, the diagonal of second-order shape features (refused by name).
+template <int NS> struct vs_layout {
+  static constexpr bool WG = NS > 4;                                     // one workgroup, not one wavefront, per element
+  static constexpr int BS = NS <= 4 ? 64 : (NS <= 6 ? 256 : 512);        // doubles between two buffers = threads of an element's unit
+  static constexpr int THREADS = WG ? BS : 256, NWAVE = WG ? 1 : 4;      // threads per workgroup, units per workgroup
+};
 template <class Form, bool GEO, int NS = 4, bool ACTION = false, bool DIAGONAL = false>
-__global__ void __launch_bounds__(256, (vs_pipe<Form, GEO>() ? 4 : 2))      // (two waves per SIMD: the geometry variants of NS-VMS and Cahn-Hilliard need 290-350 VGPRs uncapped, one wave per SIMD)
+__global__ void __launch_bounds__(vs_layout<NS>::THREADS, ((!vs_layout<NS>::WG && vs_pipe<Form, GEO>()) ? 4 : 2))      // (two waves per SIMD: the geometry variants of NS-VMS and Cahn-Hilliard need 290-350 VGPRs uncapped, one wave per SIMD)
 vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nelem) {
   constexpr int EPW = NS == 3 ? 2 : 1, NL = NS * NS * NS;               // elements per wavefront, lanes per element
   constexpr int DOF = Form::DOF;
+  constexpr bool WG = vs_layout<NS>::WG;
+  constexpr int BS = vs_layout<NS>::BS, NWAVE = vs_layout<NS>::NWAVE;
+  static_assert(NS == 3 || NS == 4 || ((NS == 6 || NS == 8) && (ACTION || DIAGONAL)), "lanes per axis: 3 or 4 per wavefront, 6 or 8 per workgroup (ACTION, DIAGONAL)");
   static_assert(!(ACTION && DIAGONAL), "one of the two");
   static_assert(!DIAGONAL || shape_order_of<Form>::v < 2, "the matrix diagonal does not cover forms with second-order shape features: its ten product slots hold N and grad N only");
   constexpr bool MATOP = ACTION || DIAGONAL;                             // mat() at the points, not vec()
@@ -190,8 +214,8 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   constexpr int NBACK = vs_popc(KMASK) > (BACK2 ? 9 : 5) ? vs_popc(KMASK) : (BACK2 ? 9 : 5), NFWD = (GORD == 2 || GEO) ? 10 : 7, NBUF = NBACK > NFWD ? NBACK : NFWD;
   constexpr int TB = NS * NS * 3;                                        // doubles of one axis' rows [q][a][3], zero padded to NS x NS
   constexpr int NTAB = DIAGONAL ? 2 : 1;                                 // DIAGONAL: the product rows [q][a][3] = (N^2, N N', N'^2) behind the rows
-  __shared__ double sm_all[4][NBUF * 64 + NTAB * EPW * 3 * TB];      // Cahn-Hilliard without a geometry: 25 KB per workgroup, two elements per wavefront (a sixth workgroup per CU measured no gain over five: 12.8 ms either way)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ double sm_all[NWAVE][NBUF * BS + NTAB * EPW * 3 * TB];      // Cahn-Hilliard without a geometry: 25 KB per workgroup, two elements per wavefront (a sixth workgroup per CU measured no gain over five: 12.8 ms either way)
+  const int lane = WG ? (int)threadIdx.x : (int)(threadIdx.x & 63), wave = WG ? 0 : (int)(threadIdx.x >> 6);
   const int esub = (EPW == 2 && lane >= NL) ? 1 : 0;                    // which of the wavefront's elements this lane works on
   // Round 6 (PIPE: scalar forms without a geometry): every global load of the unit -- the 1-D rows, the node's state and old F, the
   // point's weights -- leaves at its start, behind closed forms for the element's offset and the row map.  A wavefront's life was a
@@ -199,13 +223,13 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   // behind a wavefront fence the compiler does not move loads across) around 2-3 us of arithmetic: 9.3 us with four wavefronts per
   // SIMD to hide it, 7.7 us now.  (The colour makes the early read of F safe: no other element of the launch touches these rows.)
   // Off for the geometry variants: they are at their 256 registers already.
-  constexpr bool PIPE = vs_pipe<Form, GEO>();
-  constexpr bool EF = GEO && Form::DOF == 1;      // ... scalar forms on a geometry: old F and the product of the point's weights (three registers) leave early too
+  constexpr bool PIPE = !WG && vs_pipe<Form, GEO>();
+  constexpr bool EF = !WG && GEO && Form::DOF == 1;      // ... scalar forms on a geometry: old F and the product of the point's weights (three registers) leave early too
   constexpr int TPL = EPW * 3;                                           // table entries per lane: lane j < TB holds entry j of each (element, axis) block
-  const long long nunits = (nelem + EPW - 1) / EPW, ustride = (long long)gridDim.x * 4;
-  long long unit = (long long)blockIdx.x * 4 + wave;
-  if (unit >= nunits) return;
-  double *buf = sm_all[wave], *tab0 = buf + NBUF * 64 + esub * 3 * TB, *tab1 = tab0 + TB, *tab2 = tab1 + TB;
+  const long long nunits = (nelem + EPW - 1) / EPW, ustride = (long long)gridDim.x * NWAVE;
+  long long unit = (long long)blockIdx.x * NWAVE + wave;
+  if (unit >= nunits) return;      // (WG: the whole workgroup leaves, ahead of every barrier)
+  double *buf = sm_all[wave], *tab0 = buf + NBUF * BS + esub * 3 * TB, *tab1 = tab0 + TB, *tab2 = tab1 + TB;
   auto element_at = [&](long long ww, long long wfirst, int (&e3)[3]) {
     long long b = ww < nelem ? ww : wfirst;
     const int t0 = (int)(b % cr.count[0]); b /= cr.count[0];
@@ -213,7 +237,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
     e3[0] = cr.start[0] + t0 * cr.step[0]; e3[1] = cr.start[1] + t1 * cr.step[1]; e3[2] = cr.start[2] + (int)b * cr.step[2];
   };
   const int ll = lane < EPW * NL ? lane - esub * NL : 0;                 // (the lanes beyond the last element idle on lane 0's indices)
-  const int i0 = NS == 4 ? (ll & 3) : ll % 3, i1 = NS == 4 ? ((ll >> 2) & 3) : (ll / 3) % 3, i2 = NS == 4 ? (ll >> 4) : ll / 9;
+  const int i0 = NS == 4 ? (ll & 3) : ll % NS, i1 = NS == 4 ? ((ll >> 2) & 3) : (ll / NS) % NS, i2 = NS == 4 ? (ll >> 4) : ll / (NS * NS);
   const VsLane VL = {i0, i1, i2, esub * NL};
   const int il[3] = {i0, i1, i2};
   const int op = out.op;
@@ -293,14 +317,14 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   int el[3] = {cur.el[0], cur.el[1], cur.el[2]};
   VS_SYNC();      // (the previous element's readers of the rows are done)
 #pragma unroll
-  for (int k = 0; k < TPL; ++k) if (lane < TB) buf[NBUF * 64 + k * TB + lane] = cur.tab[k];
+  for (int k = 0; k < TPL; ++k) if (lane < TB) buf[NBUF * BS + k * TB + lane] = cur.tab[k];
   if constexpr (DIAGONAL) {      // the product rows, once per element and axis: entry (q, a, v) from (N, N') of (q, a)
     VS_SYNC();
     const int j0 = lane < TB ? lane - lane % 3 : 0, v = lane % 3;
 #pragma unroll
     for (int k = 0; k < TPL; ++k) {
-      const double n0 = buf[NBUF * 64 + k * TB + j0], n1 = buf[NBUF * 64 + k * TB + j0 + 1];
-      if (lane < TB) buf[NBUF * 64 + (TPL + k) * TB + lane] = (v == 0 ? n0 : n1) * (v == 2 ? n1 : n0);
+      const double n0 = buf[NBUF * BS + k * TB + j0], n1 = buf[NBUF * BS + k * TB + j0 + 1];
+      if (lane < TB) buf[NBUF * BS + (TPL + k) * TB + lane] = (v == 0 ? n0 : n1) * (v == 2 ? n1 : n0);
     }
   }
   if (PIPE && more) stageA(unext, nxt);
@@ -347,7 +371,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   auto k2 = [](int a, int b) { const int lo = a < b ? a : b, hi = a < b ? b : a; return 4 + (lo == 0 ? hi : (lo == 1 ? 2 + hi : 5)); };
   if constexpr (GEO) if (geo || rat) {
     double Dw[10], Dx[3][10];
-    if (GORD == 2) vs_forward<2, NS>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw); else vs_forward<1, NS>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw);
+    if (GORD == 2) vs_forward<2, NS, BS, WG>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw); else vs_forward<1, NS, BS, WG>(wgt, buf, tab0, tab1, tab2, lane, VL, Dw);
     const double W0 = ispoint ? Dw[0] : 1.0;
     iw = 1.0 / W0;
 #pragma unroll
@@ -359,7 +383,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
         for (int b = 0; b < 3; ++b) o2[a * 3 + b] = Dw[k2(a, b)] * iw;
     if (geo) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) { if (GORD == 2) vs_forward<2, NS>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); else vs_forward<1, NS>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); }
+      for (int c = 0; c < 3; ++c) { if (GORD == 2) vs_forward<2, NS, BS, WG>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); else vs_forward<1, NS, BS, WG>(Xw[c], buf, tab0, tab1, tab2, lane, VL, Dx[c]); }
       double X1[9], X2[27];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {      // quotient rule on A = sum w X N, W = sum w N (src/petigarat.f90.in + petigamapgeo.f90.in)
@@ -401,7 +425,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   auto field_at_point = [&](auto ordc, double coef, double &val, double *g3, double *h9) {
     constexpr int ORD = decltype(ordc)::value;
     double D[10];
-    vs_forward<ORD, NS>(coef * wgt, buf, tab0, tab1, tab2, lane, VL, D);
+    vs_forward<ORD, NS, BS, WG>(coef * wgt, buf, tab0, tab1, tab2, lane, VL, D);
     val = D[0] * iw;
     if constexpr (!GEO) {
       if (ORD >= 1) for (int a = 0; a < 3; ++a) g3[a] = D[1 + a];
@@ -449,7 +473,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
     if ((SNEED & (NEED_U | NEED_GU | NEED_HU)) && useU) field_at_point(vs_int<UORD>(), fixed[f] ? ufix[f] : Uv[f], u[f], gu + f * 3, hu + f * 9);
     if ((SNEED & NEED_UT) && useV) {
       double D[10];
-      vs_forward<0, NS>((fixed[f] ? 0.0 : Vv[f]) * wgt, buf, tab0, tab1, tab2, lane, VL, D);
+      vs_forward<0, NS, BS, WG>((fixed[f] ? 0.0 : Vv[f]) * wgt, buf, tab0, tab1, tab2, lane, VL, D);
       ut[f] = D[0] * iw;
     }
   }
@@ -592,8 +616,8 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
 #pragma unroll
   for (int f = 0; f < DOF; ++f) {
     double F;
-    if constexpr (DIAGONAL) F = vs_backward<2, KMASK, NS>(Cq[f], buf, tab0 + EPW * 3 * TB, tab1 + EPW * 3 * TB, tab2 + EPW * 3 * TB, lane, VL) * wgt;      // (the product rows; w_a^2 with the line below)
-    else F = SECOND_T ? vs_backward<2, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL) : vs_backward<1, KMASK, NS>(Cq[f], buf, tab0, tab1, tab2, lane, VL);
+    if constexpr (DIAGONAL) F = vs_backward<2, KMASK, NS, BS, WG>(Cq[f], buf, tab0 + EPW * 3 * TB, tab1 + EPW * 3 * TB, tab2 + EPW * 3 * TB, lane, VL) * wgt;      // (the product rows; w_a^2 with the line below)
+    else F = SECOND_T ? vs_backward<2, KMASK, NS, BS, WG>(Cq[f], buf, tab0, tab1, tab2, lane, VL) : vs_backward<1, KMASK, NS, BS, WG>(Cq[f], buf, tab0, tab1, tab2, lane, VL);
     F *= wgt;
     if (isnode) {
       if constexpr (ACTION) { if (fixed[f]) F = Xv[f]; }        // IGAElementFixJacobian: a unit diagonal per element, zero row and column beside it
@@ -610,6 +634,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   }      // the wavefront's next element
 }
 #undef VS_SYNC
+#undef VS_UNROLL
 
 #ifndef IGX_RTC
 // dim 3, at most 4 basis functions and 4 points per axis; vector-only drivers; no boundary loads (Function / IFunction subtract
@@ -653,6 +678,21 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
     bool three = !s.env.no_vec_pairs;
     for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
     const bool g1 = s.nsd > 0 || s.rational;
+    if constexpr (ACTION || DIAGONAL) {      // more than four basis functions or points on an axis: one workgroup per element, 6 or 8 lanes per axis
+      const int ns = vec_lanes_per_axis(s);
+      if (ns > 4) {
+        const unsigned grid = (unsigned)nelem;
+        if (ns <= 6) {
+          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 6, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
+          else hipLaunchKernelGGL((vec_sumfact<Form, false, 6, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
+        } else {
+          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 8, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
+          else hipLaunchKernelGGL((vec_sumfact<Form, false, 8, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
+        }
+        launches++;
+        continue;
+      }
+    }
     const bool onepass = true;      // (UNITS = 1 in the kernel)      // (one pass per wavefront: the launch has a wavefront per unit)
     if (three) {
       const unsigned grid = onepass ? (unsigned)((nelem + 7) / 8) : (unsigned)((nelem + 15) / 16);
@@ -669,6 +709,11 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
   {
     bool three = !s.env.no_vec_pairs;
     for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
+    const int ns = vec_lanes_per_axis(s);
+    if ((ACTION || DIAGONAL) && ns > 4)
+      kname = std::string(DIAGONAL ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, " : "vec_sumfact(matrix action: sum factorisation forward and backward, ")
+            + (ns <= 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : "one workgroup per element, 8 x 8 x 8 lanes)");
+    else
     if constexpr (DIAGONAL) kname = three ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, two elements per wavefront)"
                                           : "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, one wavefront per element)";
     else if constexpr (ACTION) kname = three ? "vec_sumfact(matrix action: sum factorisation forward and backward, two elements per wavefront)"
