@@ -336,10 +336,31 @@ int IGXComputeIJacobianAction(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec
  * shape features are of first order.  Second-order shape features (Cahn-Hilliard), a boundary-form pass, dim != 3, nsd != dim,
  * order-3 or property forms, nen or nqp > 8, IGX_VEC_SUMFACT=0, an IGXSetKernel choice other than 0 return IGX_ERR_SUP with the reason:
  * there is no fallback kernel.  D == U or V, a vector of another IGX or a null vector: IGX_ERR_ARG_WRONG; no form set:
- * IGX_ERR_ARG_WRONGSTATE.  The dof x dof point-block diagonal is not formed. */
+ * IGX_ERR_ARG_WRONGSTATE.  The dof x dof point-block diagonal: IGXCompute*BlockDiagonal below. */
 int IGXComputeMatrixDiagonal   (IGX iga,IGXVec D);                                               /* diag of the matrix of IGXComputeSystem   */
 int IGXComputeJacobianDiagonal (IGX iga,IGXVec U,IGXVec D);                                      /* diag of IGXComputeJacobian's J(U)        */
 int IGXComputeIJacobianDiagonal(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec D);           /* diag of IGXComputeIJacobian's J          */
+/* Matrix-free point-block diagonals (what PCPBJACOBI / MatInvertBlockDiagonal ask of a shell matrix): the dof x dof blocks
+ * A_(a,i),(a,j) of every node a, A exactly the operator of the matching action and diagonal, IGAElementFixJacobian included: an
+ * entry (i,j), i != j, with either field fixed at the node is exactly 0, a fixed (i,i) holds the number of local elements at the
+ * node, a free field beside fixed ones keeps its own entries.  The container is nb = dof ordinary IGXVecs of this IGX, one per
+ * block column: B[j][node*dof + i] = A_(node,i),(node,j) -- row numbering, IGXReduceGhostRows(iga,NULL,B[j]), IGXRefreshGhosts, the
+ * copies and the index lists work on each column unchanged.  The point stage keeps the whole dof x dof tile mat() returns where the
+ * diagonal keeps its diagonal, block row by block row, and every field pair goes back through the same product rows (vec_sumfact,
+ * DIAGONAL + BLOCK).  The columns are zeroed and assembled in the fixed colour order, bit-repeatable; on several
+ * ranks U and V must hold their ghosts and one IGXReduceGhostRows per column completes the owned rows.  Coverage and refusals are
+ * the diagonals' (IGX_ERR_SUP with the diagonal's reason under the block diagonal's name); dof <= 8.  nb != dof, a null or repeated
+ * entry of B, an entry of another IGX or one that is U or V: IGX_ERR_ARG_WRONG; no form set: IGX_ERR_ARG_WRONGSTATE.
+ * IGXBlockDiagonalInvert replaces every local block by its inverse (Gauss-Jordan with partial pivoting, one thread per node; on
+ * several ranks reduce and refresh each column first so that every local row holds its complete block).  A block with a zero or
+ * non-finite pivot becomes the zero block and is counted in *nsingular, which synchronises the stream; NULL skips the count and
+ * the synchronisation.  IGXBlockDiagonalApply: Y_node = B_node X_node for every local row; X == Y or X, Y among B:
+ * IGX_ERR_ARG_WRONG. */
+int IGXComputeMatrixBlockDiagonal   (IGX iga,int nb,IGXVec *B);
+int IGXComputeJacobianBlockDiagonal (IGX iga,IGXVec U,int nb,IGXVec *B);
+int IGXComputeIJacobianBlockDiagonal(IGX iga,double a,IGXVec V,double t,IGXVec U,int nb,IGXVec *B);
+int IGXBlockDiagonalInvert(IGX iga,int nb,IGXVec *B,int64_t *nsingular /* may be NULL */);
+int IGXBlockDiagonalApply (IGX iga,int nb,IGXVec *B,IGXVec X,IGXVec Y);   /* Y_node = B_node X_node */
 
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
@@ -486,6 +507,7 @@ int IGXChecksum(IGX iga,IGXMat A,IGXVec b,double S[4]);
  * gram == 8: its DIAGONAL instantiation (IGXCompute*Diagonal of the struct; first-order shape features) likewise.  Both compile the
  * layout the driver would launch for the degrees and quadrature sizes set so far (one wavefront per element up to nen, nqp = 4, one
  * workgroup per element with 6 x 6 x 6 or 8 x 8 x 8 lanes above) and return IGX_ERR_SUP with the driver's reason where it would refuse.
+ * gram == 9: DIAGONAL with BLOCK (IGXCompute*BlockDiagonal of the struct), the same way.
  * Returns 0 or IGX_ERR_USER with the compiler's log. */
 int IGXCheckFormSource(IGX iga,int with_matrix,int gram);
 

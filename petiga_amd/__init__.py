@@ -98,6 +98,9 @@ def lib(build_if_needed=False):
         "IGXComputeIJacobianAction": [V, C.c_double, V, C.c_double, V, V, V],
         "IGXComputeMatrixDiagonal": [V, V], "IGXComputeJacobianDiagonal": [V, V, V],
         "IGXComputeIJacobianDiagonal": [V, C.c_double, V, C.c_double, V, V],
+        "IGXComputeMatrixBlockDiagonal": [V, C.c_int, C.POINTER(V)], "IGXComputeJacobianBlockDiagonal": [V, V, C.c_int, C.POINTER(V)],
+        "IGXComputeIJacobianBlockDiagonal": [V, C.c_double, V, C.c_double, V, C.c_int, C.POINTER(V)],
+        "IGXBlockDiagonalInvert": [V, C.c_int, C.POINTER(V), C.POINTER(C.c_int64)], "IGXBlockDiagonalApply": [V, C.c_int, C.POINTER(V), V, V],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -435,6 +438,18 @@ class IGX:
     def compute_matrix_diagonal(self, D): _ck(lib().IGXComputeMatrixDiagonal(self.h, D.h))
     def compute_jacobian_diagonal(self, U, D): _ck(lib().IGXComputeJacobianDiagonal(self.h, U.h, D.h))
     def compute_ijacobian_diagonal(self, a, V, t, U, D): _ck(lib().IGXComputeIJacobianDiagonal(self.h, a, V.h, t, U.h, D.h))
+    # matrix-free point-block diagonals: B is a list of dof Vecs, B[j][node * dof + i] = A_(node,i),(node,j) of the same operator
+    @staticmethod
+    def _cols(B): return len(B), (C.c_void_p * max(len(B), 1))(*[b.h.value for b in B])
+    def compute_matrix_block_diagonal(self, B): _ck(lib().IGXComputeMatrixBlockDiagonal(self.h, *self._cols(B)))
+    def compute_jacobian_block_diagonal(self, U, B): _ck(lib().IGXComputeJacobianBlockDiagonal(self.h, U.h, *self._cols(B)))
+    def compute_ijacobian_block_diagonal(self, a, V, t, U, B): _ck(lib().IGXComputeIJacobianBlockDiagonal(self.h, a, V.h, t, U.h, *self._cols(B)))
+    def block_diagonal_invert(self, B, count=True):
+        """B <- the inverse of every block, in place; returns the number of singular blocks (zeroed), or None with count=False (no synchronisation)"""
+        n = C.c_int64(0)
+        _ck(lib().IGXBlockDiagonalInvert(self.h, *self._cols(B), C.byref(n) if count else None))
+        return int(n.value) if count else None
+    def block_diagonal_apply(self, B, X, Y): _ck(lib().IGXBlockDiagonalApply(self.h, *self._cols(B), X.h, Y.h))
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))
     def synchronize(self): _ck(lib().IGXSynchronize(self.h))
@@ -526,7 +541,7 @@ class IGX:
 
     def check_form_source(self, with_matrix=True, gram=False):
         """Compile-only check of the run-time form against the kernels the drivers would launch for the current degrees (no GPU needed)."""
-        # gram: False / True = the struct declares MAT_PAIR_MASK; 2, 3, 4 = the pencil walk / the vector kernel / state_pencil instead; 7 = the vector kernel's ACTION instantiation (compute_*_action); 8 = its DIAGONAL instantiation (compute_*_diagonal)
+        # gram: False / True = the struct declares MAT_PAIR_MASK; 2, 3, 4 = the pencil walk / the vector kernel / state_pencil instead; 7 = the vector kernel's ACTION instantiation (compute_*_action); 8 = its DIAGONAL instantiation (compute_*_diagonal); 9 = DIAGONAL with BLOCK (compute_*_block_diagonal)
         _ck(lib().IGXCheckFormSource(self.h, 1 if with_matrix else 0, int(gram)))
 
     def comm_overlap_ms(self):

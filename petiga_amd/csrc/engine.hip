@@ -18,6 +18,7 @@
 #define IGX_HAVE_VEC_SUMFACT 1
 #endif
 #ifndef IGX_TU_DISPATCH
+#include "block_diag.hpp"
 #include "gram_mfma.hpp"
 #include "gram_patch.hpp"
 #include "gram_patch3.hpp"
@@ -88,6 +89,7 @@ struct _p_IGX {
   std::function<void()> zero_matrix;   // MatZeroEntries of the running IGXCompute*, called by the kernel path that needs it
   std::function<void()> slab_done;     // set during an assembly with a communicator: marks "upper face of axis 2 assembled" on the engine stream
   DevBuf partials, dbgbuf, clkbuf;   // IGXComputeScalar: per-element partial sums + reduction stages
+  DevBuf nsingular;                  // IGXBlockDiagonalInvert: the count of singular blocks
   DomInfo dom;
   int64_t nbrows = 0, nblocks = 0;
   std::shared_ptr<IgxComm> comm;   // transport of the ghost-row exchange (comm.hpp)
@@ -928,23 +930,27 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
       return fail(IGX_ERR_SUP, "the matrix action does not cover forms with a boundary branch or functionals");
     }
   }
-  // the matrix-free diagonals (IGXCompute*Diagonal): vec_sumfact's DIAGONAL instantiation or a refusal, under the actions' conditions and first-order shape features
-  if (op_is_diagonal(out.op)) {
-    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
-    if (GENERAL) return fail(IGX_ERR_SUP, VEC_DIAGONAL_GENERAL);
-    if (NS != 0 || has_boundary_of<Form>::v) return fail(IGX_ERR_SUP, "the matrix diagonal does not cover forms with a boundary branch or functionals");
-    if (shape_order_of<Form>::v >= 2) return fail(IGX_ERR_SUP, VEC_DIAGONAL_SECOND);
+  // the matrix-free diagonals (IGXCompute*Diagonal) and point-block diagonals (IGXCompute*BlockDiagonal): vec_sumfact's DIAGONAL instantiation
+  // (with BLOCK) or a refusal, under the actions' conditions and first-order shape features; the block diagonal gives the diagonal's reasons under its own name
+  if (op_is_diagonal(out.op) || op_is_block_diagonal(out.op)) {
+    const bool blk = op_is_block_diagonal(out.op);
+    auto refuse = [&](const std::string &why) { return fail(IGX_ERR_SUP, blk ? vec_block_diagonal_reason(why) : why); };
+    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return refuse(why); }
+    if (GENERAL) return refuse(VEC_DIAGONAL_GENERAL);
+    if (NS != 0 || has_boundary_of<Form>::v) return refuse(VEC_DIAGONAL_BOUNDARY);
+    if (shape_order_of<Form>::v >= 2) return refuse(VEC_DIAGONAL_SECOND);
 #ifdef IGX_HAVE_VEC_SUMFACT
     if constexpr (DIM == 3 && !GENERAL && NS == 0 && !has_boundary_of<Form>::v && shape_order_of<Form>::v < 2) {
       if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
       bool done = false;
       ParamsDev prm; memset(&prm, 0, sizeof(prm));
       for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
-      if (int rc = try_vec_sumfact<Form, false, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
-      return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix diagonal it covers");
+      if (int rc = blk ? try_vec_sumfact<Form, false, true, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)
+                       : try_vec_sumfact<Form, false, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
+      return done ? 0 : fail(IGX_ERR_PLIB, blk ? "vec_sumfact did not take a matrix block diagonal it covers" : "vec_sumfact did not take a matrix diagonal it covers");
     }
 #endif
-    return fail(IGX_ERR_SUP, "the matrix diagonal needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)");
+    return refuse("the matrix diagonal needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)");
   }
   if (GENERAL && g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a form of order 3 or one that reads the property array runs on the general kernel only");
   if ((Form::NEED & NEED_PROP) && !S.npd) return fail(IGX_ERR_ARG_WRONGSTATE, "No property set");      // src/petigaelem.c:300
@@ -1407,6 +1413,88 @@ static int compute_diagonal(IGX g, int op, IGXVec U, IGXVec V, IGXVec D, double 
 extern "C" int IGXComputeMatrixDiagonal(IGX g, IGXVec D) { return compute_diagonal(g, OP_MATRIX_DIAGONAL, nullptr, nullptr, D, 0, 0); }
 extern "C" int IGXComputeJacobianDiagonal(IGX g, IGXVec U, IGXVec D) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_diagonal(g, OP_JACOBIAN_DIAGONAL, U, nullptr, D, 0, 0); }
 extern "C" int IGXComputeIJacobianDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec D) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_diagonal(g, OP_IJACOBIAN_DIAGONAL, U, V, D, a, t); }
+
+// Matrix-free point-block diagonals: the dof x dof blocks A_(a,i),(a,j) of every node a of the same operator (what PCPBJACOBI /
+// MatInvertBlockDiagonal ask of a shell matrix), in dof ordinary vectors, one per block column: B[j][node * dof + i] = A_(node,i),(node,j).
+// vec_sumfact's DIAGONAL + BLOCK instantiation (vec_sumfact.hpp) or a refusal with IGX_ERR_SUP; the columns are zeroed and assembled like
+// vectors, and one IGXReduceGhostRows(iga, NULL, B[j]) per column completes the owned rows on several ranks.
+static int check_block_columns(IGX g, int nb, IGXVec *B) {
+  if (nb != g->s.dof) return fail(IGX_ERR_ARG_WRONG, "the block diagonal has dof columns: nb must equal dof");
+  if (nb < 1 || nb > MAXBC) return fail(IGX_ERR_ARG_WRONG, "the block diagonal needs dof <= 8");
+  if (!B) return fail(IGX_ERR_ARG_WRONG, "null array of block columns");
+  for (int j = 0; j < nb; ++j) {
+    if (!B[j]) return fail(IGX_ERR_ARG_WRONG, "null block column");
+    if (B[j]->iga != g) return fail(IGX_ERR_ARG_WRONG, "block column created by another IGX");
+    for (int k = 0; k < j; ++k) if (B[k] == B[j]) return fail(IGX_ERR_ARG_WRONG, "the same vector given for two block columns");
+  }
+  return 0;
+}
+static int compute_block_diagonal(IGX g, int op, IGXVec U, IGXVec V, int nb, IGXVec *B, double shift, double t) {
+  NEEDIGA(g);
+  if (int rc = check_block_columns(g, nb, B)) return rc;
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  for (int j = 0; j < nb; ++j) if ((U && U == B[j]) || (V && V == B[j])) return fail(IGX_ERR_ARG_WRONG, "a block column must not be a state vector");
+  if (int rc = ensure_device(g)) return rc;
+  const Space &s = g->s;
+  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  OutDev out; memset(&out, 0, sizeof(out));
+  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
+  for (int j = 0; j < nb; ++j) out.bcol[j] = B[j]->a.as<double>();
+  out.vec = out.bcol[0];
+  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
+  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
+  for (int j = 0; j < nb; ++j) HIPCK(hipMemsetAsync(B[j]->a.p, 0, B[j]->a.bytes, g->stream));
+  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
+  const SpaceDev S = make_spacedev(g);
+  g->dom = DomInfo(); g->slab_valid = 0;
+  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
+  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
+  if (rc) return rc;
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
+  return 0;
+}
+extern "C" int IGXComputeMatrixBlockDiagonal(IGX g, int nb, IGXVec *B) { return compute_block_diagonal(g, OP_MATRIX_BLOCK_DIAGONAL, nullptr, nullptr, nb, B, 0, 0); }
+extern "C" int IGXComputeJacobianBlockDiagonal(IGX g, IGXVec U, int nb, IGXVec *B) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_block_diagonal(g, OP_JACOBIAN_BLOCK_DIAGONAL, U, nullptr, nb, B, 0, 0); }
+extern "C" int IGXComputeIJacobianBlockDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, int nb, IGXVec *B) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_block_diagonal(g, OP_IJACOBIAN_BLOCK_DIAGONAL, U, V, nb, B, a, t); }
+
+// The blocks as a preconditioner (block_diag.hpp): B <- B^-1 block by block in place (every local row; on several ranks after the
+// reduction and a refresh of each column), and Y_node = B_node X_node.  nsingular: the number of blocks with a zero or non-finite pivot,
+// which become zero blocks; reading it synchronises the stream, NULL skips both.
+static int block_diagonal_run(IGX g, int nb, IGXVec *B, IGXVec X, IGXVec Y, int64_t *nsingular, bool invert) {
+  NEEDIGA(g);
+  if (int rc = check_block_columns(g, nb, B)) return rc;
+  if (!invert) {
+    if (!X || !Y) return fail(IGX_ERR_ARG_WRONG, "null vector");
+    if (X->iga != g || Y->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+    if (X == Y) return fail(IGX_ERR_ARG_WRONG, "X and Y must differ");
+    for (int j = 0; j < nb; ++j) if (X == B[j] || Y == B[j]) return fail(IGX_ERR_ARG_WRONG, "X and Y must not be block columns");
+  }
+  if (int rc = ensure_device(g)) return rc;
+  BlockCols cols; memset(&cols, 0, sizeof(cols));
+  for (int j = 0; j < nb; ++j) cols.col[j] = B[j]->a.as<double>();
+  unsigned long long *cnt = nullptr;
+  if (invert && nsingular) {
+    if (!g->nsingular.p && g->nsingular.alloc(sizeof(unsigned long long))) return fail(IGX_ERR_MEM, "device allocation failed");
+    cnt = g->nsingular.as<unsigned long long>();
+    HIPCK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long), g->stream));
+  }
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[0], g->stream)); HIPCK(hipEventRecord(g->ev[1], g->stream)); }
+  g->slab_valid = 0;
+  block_diag_launch(nb, invert, cols, invert ? nullptr : X->a.as<double>(), invert ? nullptr : Y->a.as<double>(), (long long)g->nbrows, cnt, g->stream);
+  if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "block diagonal kernel launch failed");
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
+  g->last_launches = 1;
+  g->last_kernel = invert ? "block_diag_invert(Gauss-Jordan with partial pivoting, one thread per node)" : "block_diag_apply(one thread per node)";
+  if (cnt) {
+    unsigned long long h = 0;
+    HIPCK(hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, g->stream));
+    HIPCK(hipStreamSynchronize(g->stream));
+    *nsingular = (int64_t)h;
+  }
+  return 0;
+}
+extern "C" int IGXBlockDiagonalInvert(IGX g, int nb, IGXVec *B, int64_t *nsingular) { return block_diagonal_run(g, nb, B, nullptr, nullptr, nsingular, true); }
+extern "C" int IGXBlockDiagonalApply(IGX g, int nb, IGXVec *B, IGXVec X, IGXVec Y) { return block_diagonal_run(g, nb, B, X, Y, nullptr, false); }
 
 // One pass for the pair a Newton step asks for at the same state (SNESComputeFunction + SNESComputeJacobian; src/petigats.c:23-159,
 // src/petigasnes.c:23-139): the results are those of the two drivers, in one walk where a fused kernel exists, else in two calls.

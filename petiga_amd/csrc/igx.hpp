@@ -189,7 +189,8 @@ struct ColorRange { int start[3], step[3], count[3]; };
 
 enum Op { OP_SYSTEM = 0, OP_MATRIX, OP_VECTOR, OP_FUNCTION, OP_JACOBIAN, OP_IFUNCTION, OP_IJACOBIAN, OP_SCALAR,
           OP_MATRIX_ACTION, OP_JACOBIAN_ACTION, OP_IJACOBIAN_ACTION,        // Y = A X of the matrix the driver would assemble, matrix-free (vec_sumfact.hpp)
-          OP_MATRIX_DIAGONAL, OP_JACOBIAN_DIAGONAL, OP_IJACOBIAN_DIAGONAL };  // D = diag A of the same matrix, matrix-free (vec_sumfact.hpp, DIAGONAL; vec is D)
+          OP_MATRIX_DIAGONAL, OP_JACOBIAN_DIAGONAL, OP_IJACOBIAN_DIAGONAL,    // D = diag A of the same matrix, matrix-free (vec_sumfact.hpp, DIAGONAL; vec is D)
+          OP_MATRIX_BLOCK_DIAGONAL, OP_JACOBIAN_BLOCK_DIAGONAL, OP_IJACOBIAN_BLOCK_DIAGONAL };      // its dof x dof point blocks (DIAGONAL, BLOCK; bcol are the columns)
 
 struct OutDev {
   const int64_t *browptr;  // null when no matrix output
@@ -209,6 +210,7 @@ struct OutDev {
   int vec_mode;            // vec_sumfact as a part of IGAComputeSystem next to a band-row kernel: 1 the whole vector (lifting of the Dirichlet values through
                            // SystemVectorOf<Form>, a fixed row takes its value), 2 the form's vec() alone with the fixed rows left at 0 (block_pencil lifts itself)
   const double *X;         // OP_*_ACTION: the row-indexed direction (vec is Y), else null
+  double *bcol[MAXBC];     // OP_*_BLOCK_DIAGONAL: the dof block columns, bcol[j][node * dof + i] = A_(node,i),(node,j) (vec is bcol[0]), else null
 };
 
 #ifndef IGX_RTC
@@ -244,6 +246,14 @@ inline std::string vec_diagonal_refusal(const Space &s, int kernel_choice) {
 }
 constexpr const char *VEC_DIAGONAL_SECOND = "the matrix diagonal does not cover forms with second-order shape features (Cahn-Hilliard's Laplacian): six product rows per axis and 55 coefficient slots per point are another kernel";
 constexpr const char *VEC_DIAGONAL_GENERAL = "the matrix diagonal does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives";
+constexpr const char *VEC_DIAGONAL_BOUNDARY = "the matrix diagonal does not cover forms with a boundary branch or functionals";
+// The point-block diagonals (OP_*_BLOCK_DIAGONAL) run where the diagonals run (vec_sumfact.hpp, DIAGONAL + BLOCK): the diagonal's checks and
+// reasons, asked through the functions and constants above, under the block diagonal's name.
+inline bool op_is_block_diagonal(int op) { return op == OP_MATRIX_BLOCK_DIAGONAL || op == OP_JACOBIAN_BLOCK_DIAGONAL || op == OP_IJACOBIAN_BLOCK_DIAGONAL; }
+inline std::string vec_block_diagonal_reason(const std::string &diagonal_reason) {
+  return diagonal_reason.empty() ? diagonal_reason : std::string("the matrix block diagonal runs where the matrix diagonal runs, and ") + diagonal_reason;
+}
+inline std::string vec_block_diagonal_refusal(const Space &s, int kernel_choice) { return vec_block_diagonal_reason(vec_diagonal_refusal(s, kernel_choice)); }
 #endif
 
 constexpr int MAXPARAM = 8;

@@ -83,7 +83,7 @@ struct RtcForm {
   hipModule_t module = nullptr; hipFunction_t func = nullptr;
   std::map<int, std::shared_ptr<RtcFeature>> feature;   // key: TA | NW << 4 | DOFI << 8 | HASM << 12
   std::map<int, std::shared_ptr<RtcFeature>> pencil;    // form_pencil instantiations; key: SYSTEM | P << 1 | IDENT << 4 | RAT << 5
-  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | two elements per wavefront << 1 | ACTION << 2 | DIAGONAL << 3 | one workgroup per element with 6 (8) lanes per axis << 4 (5)
+  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | two elements per wavefront << 1 | ACTION << 2 | DIAGONAL << 3 | 6 lanes << 4 | 8 lanes << 5 | BLOCK << 6 | one workgroup per element with 6 (8) lanes per axis << 4 (5)
   std::map<int, std::shared_ptr<RtcFeature>> state;     // state_pencil instantiations; key: P (+ 10 + rational on a mapped geometry, + 100 packed tiles)
   std::map<int, std::shared_ptr<RtcFeature>> block;     // block_pencil instantiations; key: SYSTEM
   std::map<int, std::shared_ptr<RtcFeature>> band;      // band_points + band_pt instantiations; key: GEO | RAT << 1 | degree << 2
@@ -464,8 +464,10 @@ static bool rtc_vecsf_eligible(const Space &s, const RtcForm &F, const OutDev &o
 }
 // action: the ACTION instantiation (the matrix-free product of IGXCompute*Action); the caller has asked vec_action_refusal
 // diagonal: the DIAGONAL instantiation (IGXCompute*Diagonal), likewise; a struct of SHAPE_ORDER <= 1
-static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done, bool compile_only = false, bool action = false, bool diagonal = false) {
+// block: DIAGONAL with BLOCK (IGXCompute*BlockDiagonal): the dof x dof point blocks into out.bcol
+static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done, bool compile_only = false, bool action = false, bool diagonal = false, bool block = false) {
   done = false;
+  if (block) diagonal = true;
   const Space &s = g->s;
   if (!compile_only && !action && !diagonal && !rtc_vecsf_eligible(s, F, out)) return 0;
   const bool geo = s.nsd > 0 || s.rational;
@@ -474,13 +476,13 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   const int ns = (action || diagonal) ? vec_lanes_per_axis(s) : 4;      // above 4: one workgroup per element, 6 or 8 lanes per axis (the vector-only drivers stay below)
   const int wg = ns > 6 ? 8 : (ns > 4 ? 6 : 0);
   if (wg) three = false;
-  const int key = (geo ? 1 : 0) | (three ? 2 : 0) | (action ? 4 : 0) | (diagonal ? 8 : 0) | (wg == 6 ? 16 : 0) | (wg == 8 ? 32 : 0);
+  const int key = (geo ? 1 : 0) | (three ? 2 : 0) | (action ? 4 : 0) | (diagonal ? 8 : 0) | (wg == 6 ? 16 : 0) | (wg == 8 ? 32 : 0) | (block ? 64 : 0);
   std::shared_ptr<RtcFeature> K;
   auto it = F.vecsf.find(key);
   if (it != F.vecsf.end() && (it->second->module || compile_only)) K = it->second;
   else {
     K.reset(new RtcFeature());
-    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + (wg == 8 ? "8" : (wg == 6 ? "6" : (three ? "3" : "4"))) + (diagonal ? ", false, true>" : (action ? ", true>" : ">"));
+    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + (wg == 8 ? "8" : (wg == 6 ? "6" : (three ? "3" : "4"))) + (block ? ", false, true, true>" : (diagonal ? ", false, true>" : (action ? ", true>" : ">")));
     const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, long long);\n";
     if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, false, true)) return rc;
     if (!compile_only) {
@@ -514,7 +516,7 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
     launches++;
   }
   g->last_launches = launches;
-  g->last_kernel = std::string("vec_sumfact<") + F.name + (diagonal ? ">(hiprtc,matrix diagonal: sum factorisation forward, product rows backward, " : (action ? ">(hiprtc,matrix action: sum factorisation forward and backward, " : ">(hiprtc,vector only: sum factorisation forward and backward, ")) + (wg == 8 ? "one workgroup per element, 8 x 8 x 8 lanes)" : (wg == 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : (three ? "two elements per wavefront)" : "one wavefront per element)")));
+  g->last_kernel = std::string("vec_sumfact<") + F.name + (block ? ">(hiprtc,matrix block diagonal: sum factorisation forward, product rows backward per field pair, " : diagonal ? ">(hiprtc,matrix diagonal: sum factorisation forward, product rows backward, " : (action ? ">(hiprtc,matrix action: sum factorisation forward and backward, " : ">(hiprtc,vector only: sum factorisation forward and backward, ")) + (wg == 8 ? "one workgroup per element, 8 x 8 x 8 lanes)" : (wg == 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : (three ? "two elements per wavefront)" : "one wavefront per element)")));
   done = true;
   return 0;
 }
@@ -741,6 +743,14 @@ static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
     bool done = false;
     if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, false, true)) return rc;
     return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix diagonal it covers");
+  }
+  if (op_is_block_diagonal(out.op)) {    // the point-block diagonals: the DIAGONAL + BLOCK instantiation or the diagonal's refusal under the block diagonal's name
+    { const std::string why = vec_block_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
+    if (const char *why = rtc_diagonal_refusal(F)) return fail(IGX_ERR_SUP, vec_block_diagonal_reason(why));
+    if (s.dof != F.meta[0]) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
+    bool done = false;
+    if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, false, true, true)) return rc;
+    return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix block diagonal it covers");
   }
   // a struct of ORDER 3, or one that reads the property array / the point's shape table / third derivatives of the state: the general kernel (as launch_generic)
   if (F.meta[1] >= 3 || ((unsigned)F.meta[2] & (NEED_PROP | NEED_D3U | NEED_MAPX)) || (s.nsd && s.nsd != s.dim)) {      // (... or a geometry with nsd != dim)
@@ -993,6 +1003,12 @@ extern "C" int IGXCheckFormSource(IGX g, int with_matrix, int gram) {
     { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
     bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
     return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, false, true);
+  }
+  if (gram == 9) {           // ... and DIAGONAL with BLOCK (IGXCompute*BlockDiagonal of the struct) for the layout the driver would launch: compile only
+    { const std::string why = vec_block_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
+    if (g->rtc->func) { if (const char *why = rtc_diagonal_refusal(*g->rtc)) return fail(IGX_ERR_SUP, vec_block_diagonal_reason(why)); }
+    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
+    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, false, true, true);
   }
   if (gram == 3) {           // the sum-factorised vector kernel (vec_sumfact) of the struct, with and without a geometry: compile only
     if (s.dim != 3) return fail(IGX_ERR_SUP, "the sum-factorised vector kernel needs dim 3");

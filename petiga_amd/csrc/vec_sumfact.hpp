@@ -188,7 +188,12 @@ template <int NS> struct vs_layout {
   static constexpr int BS = NS <= 4 ? 64 : (NS <= 6 ? 256 : 512);        // doubles between two buffers = threads of an element's unit
   static constexpr int THREADS = WG ? BS : 256, NWAVE = WG ? 1 : 4;      // threads per workgroup, units per workgroup
 };
-template <class Form, bool GEO, int NS = 4, bool ACTION = false, bool DIAGONAL = false>
+// BLOCK (with DIAGONAL): the dof x dof point-block diagonal B_a^ij = K_aa^ij of the same matrix (OP_*_BLOCK_DIAGONAL), column j into
+// out.bcol[j].  D_k N_a D_l N_a is symmetric in (k, l) for every field pair, so every (i, j) folds into the same ten slots; the tile
+// mat() returns holds them all.  Block row by block row: for a test field i the point stage keeps row i of every tile (DOF x 10
+// coefficients, as many as DIAGONAL holds -- all DOF^2 x 10 would be 320 registers for NS-VMS) and DOF ways back follow; the compiler
+// drops the rows of a call that are not kept.  An entry beside a fixed dof is 0, a fixed (i, i) the unit diagonal (IGAElementFixJacobian).
+template <class Form, bool GEO, int NS = 4, bool ACTION = false, bool DIAGONAL = false, bool BLOCK = false>
 __global__ void __launch_bounds__(vs_layout<NS>::THREADS, ((!vs_layout<NS>::WG && vs_pipe<Form, GEO>()) ? 4 : 2))      // (two waves per SIMD: the geometry variants of NS-VMS and Cahn-Hilliard need 290-350 VGPRs uncapped, one wave per SIMD)
 vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nelem) {
   constexpr int EPW = NS == 3 ? 2 : 1, NL = NS * NS * NS;               // elements per wavefront, lanes per element
@@ -197,6 +202,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   constexpr int BS = vs_layout<NS>::BS, NWAVE = vs_layout<NS>::NWAVE;
   static_assert(NS == 3 || NS == 4 || ((NS == 6 || NS == 8) && (ACTION || DIAGONAL)), "lanes per axis: 3 or 4 per wavefront, 6 or 8 per workgroup (ACTION, DIAGONAL)");
   static_assert(!(ACTION && DIAGONAL), "one of the two");
+  static_assert(!BLOCK || DIAGONAL, "the point-block diagonal is a variant of DIAGONAL");
   static_assert(!DIAGONAL || shape_order_of<Form>::v < 2, "the matrix diagonal does not cover forms with second-order shape features: its ten product slots hold N and grad N only");
   constexpr bool MATOP = ACTION || DIAGONAL;                             // mat() at the points, not vec()
   constexpr unsigned VMASK = MATOP ? mat_test_mask_of<Form>::v : vec_test_mask_of<Form>::v;      // test features vec() (MATOP: mat()) reads (bit f)
@@ -575,6 +581,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
     };
     // columns of M with an entry mat() reads on the test side: without a geometry e_k itself; with one the gradient rows fill every column
     constexpr unsigned TK = GEO ? ((VMASK & 0xEu) ? 0xFu : 0x1u) : (VMASK & 0xFu);
+    if constexpr (!BLOCK) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (!((TK >> k) & 1u)) continue;
@@ -588,6 +595,41 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
         const int slot = (k == 0 || l == 0) ? k + l : k2(k - 1, l - 1);      // B_kl and B_lk share a slot
 #pragma unroll
         for (int f = 0; f < DOF; ++f) Cq[f][slot] += ispoint ? T[f * DOF + f] * JW : 0.0;
+      }
+    }
+    } else {
+      // ---- BLOCK, block row by block row: the point stage for the test field f keeps row f of every tile (Cq[g]: the trial field g),
+      // then one way back per trial field
+#pragma unroll
+      for (int f = 0; f < DOF; ++f) {
+#pragma unroll
+        for (int g = 0; g < DOF; ++g)
+#pragma unroll
+          for (int k = 0; k < 10; ++k) Cq[g][k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (!((TK >> k) & 1u)) continue;
+          double Na[4]; mcol(k, Na);
+#pragma unroll
+          for (int l = 0; l < 4; ++l) {
+            double Nb[4], T[DOF * DOF]; mcol(l, Nb);
+#pragma unroll
+            for (int i = 0; i < DOF * DOF; ++i) T[i] = 0.0;
+            Form::mat(p, Na, Nb, T);
+            const int slot = (k == 0 || l == 0) ? k + l : k2(k - 1, l - 1);      // B^{fg}_kl and B^{fg}_lk share a slot, for every field pair
+#pragma unroll
+            for (int g = 0; g < DOF; ++g) Cq[g][slot] += ispoint ? T[f * DOF + g] * JW : 0.0;
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < DOF; ++g) {
+          double F = vs_backward<2, KMASK, NS, BS, WG>(Cq[g], buf, tab0 + EPW * 3 * TB, tab1 + EPW * 3 * TB, tab2 + EPW * 3 * TB, lane, VL) * wgt;      // (the product rows; w_a^2 with the line below)
+          F *= wgt;
+          if (isnode) {
+            if (fixed[f] || fixed[g]) F = (f == g) ? 1.0 : 0.0;      // IGAElementFixJacobian: the unit diagonal, a zero row and column beside it
+            if (F != 0.0) { double *col = out.bcol[g]; if constexpr (PIPE || EF) col[row * DOF + f] = Fold[f] + F; else col[row * DOF + f] += F; }      // (PIPE, EF: DOF = 1, bcol[0] is vec)
+          }
+        }
       }
     }
   }
@@ -613,6 +655,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
     }
   }
   // ---- backward, IGAElementFixFunction (src/petigaelem.c:1449-1461), IGAElementAssembleVec
+  if constexpr (!BLOCK)      // (its ways back follow its point stages above)
 #pragma unroll
   for (int f = 0; f < DOF; ++f) {
     double F;
@@ -654,7 +697,7 @@ static bool vec_sumfact_covers(const Space &s, const OutDev &out) {
   }
 }
 
-template <class Form, bool ACTION = false, bool DIAGONAL = false>
+template <class Form, bool ACTION = false, bool DIAGONAL = false, bool BLOCK = false>
 static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &prm, const OutDev &out, hipStream_t stream, std::string &kname, int &launches, bool &done) {
   done = false;
   if constexpr (nscalar_of<Form>::v > 0 || has_boundary_of<Form>::v) return 0;
@@ -683,11 +726,11 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
       if (ns > 4) {
         const unsigned grid = (unsigned)nelem;
         if (ns <= 6) {
-          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 6, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
-          else hipLaunchKernelGGL((vec_sumfact<Form, false, 6, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
+          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 6, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
+          else hipLaunchKernelGGL((vec_sumfact<Form, false, 6, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
         } else {
-          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 8, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
-          else hipLaunchKernelGGL((vec_sumfact<Form, false, 8, ACTION, DIAGONAL>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
+          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 8, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
+          else hipLaunchKernelGGL((vec_sumfact<Form, false, 8, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
         }
         launches++;
         continue;
@@ -696,12 +739,12 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
     const bool onepass = true;      // (UNITS = 1 in the kernel)      // (one pass per wavefront: the launch has a wavefront per unit)
     if (three) {
       const unsigned grid = onepass ? (unsigned)((nelem + 7) / 8) : (unsigned)((nelem + 15) / 16);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 3, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 3, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 3, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      else hipLaunchKernelGGL((vec_sumfact<Form, false, 3, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
     } else {
       const unsigned grid = onepass ? (unsigned)((nelem + 3) / 4) : (unsigned)((nelem + 7) / 8);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 4, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 4, ACTION, DIAGONAL>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 4, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
+      else hipLaunchKernelGGL((vec_sumfact<Form, false, 4, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
     }
     launches++;
   }
@@ -711,10 +754,12 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
     for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
     const int ns = vec_lanes_per_axis(s);
     if ((ACTION || DIAGONAL) && ns > 4)
-      kname = std::string(DIAGONAL ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, " : "vec_sumfact(matrix action: sum factorisation forward and backward, ")
+      kname = std::string(BLOCK ? "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, " : DIAGONAL ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, " : "vec_sumfact(matrix action: sum factorisation forward and backward, ")
             + (ns <= 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : "one workgroup per element, 8 x 8 x 8 lanes)");
     else
-    if constexpr (DIAGONAL) kname = three ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, two elements per wavefront)"
+    if constexpr (BLOCK) kname = three ? "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, two elements per wavefront)"
+                                       : "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, one wavefront per element)";
+    else if constexpr (DIAGONAL) kname = three ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, two elements per wavefront)"
                                           : "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, one wavefront per element)";
     else if constexpr (ACTION) kname = three ? "vec_sumfact(matrix action: sum factorisation forward and backward, two elements per wavefront)"
                                         : "vec_sumfact(matrix action: sum factorisation forward and backward, one wavefront per element)";
