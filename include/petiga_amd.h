@@ -361,6 +361,35 @@ int IGXComputeJacobianBlockDiagonal (IGX iga,IGXVec U,int nb,IGXVec *B);
 int IGXComputeIJacobianBlockDiagonal(IGX iga,double a,IGXVec V,double t,IGXVec U,int nb,IGXVec *B);
 int IGXBlockDiagonalInvert(IGX iga,int nb,IGXVec *B,int64_t *nsingular /* may be NULL */);
 int IGXBlockDiagonalApply (IGX iga,int nb,IGXVec *B,IGXVec X,IGXVec Y);   /* Y_node = B_node X_node */
+/* Fast diagonalisation (Sangalli and Tani, SIAM J. Sci. Comput. 38, 2016): a preconditioner for the matrix-free operators whose quality
+ * depends on neither the mesh nor the degree.  On the parametric tensor-product space the operator
+ *   A0 = alpha M2 x M1 x M0 + beta[0] M2 x M1 x K0 + beta[1] M2 x K1 x M0 + beta[2] K2 x M1 x M0
+ * (M_d, K_d the 1-D mass and stiffness matrices of axis d) is diagonal in the basis U2 x U1 x U0 of the 1-D generalised eigenvectors
+ * K_d U_d = M_d U_d Lambda_d, U_d^T M_d U_d = I: A0^-1 R = (U2 x U1 x U0) [ (U2^T x U1^T x U0^T) R ./ (alpha + sum_d beta[d] lambda_d) ].
+ * IT IGNORES THE GEOMETRY AND THE RATIONAL WEIGHTS: without a geometry it is the exact inverse of IGXComputeMatrixAction's operator for
+ * Poisson (alpha = 0, beta = 1) and Mass (alpha = 1, beta = 0), field by field; on a mapped geometry a spectrally equivalent preconditioner.
+ * IGXFastDiagSetUp runs after IGXSetUp and is host work only (no HIP call): M_d and K_d come from the axis' own tables (IGXGetBasis: offset,
+ * detJac, weight, value[..][0], value[..][1]; a periodic axis wraps), so the inverse is exact for the rule set; any degree, continuity,
+ * knot vector and rule size.  The fixed dofs are a union of faces (IGXSetBoundaryValue; never on a periodic axis), so the free dofs of a
+ * field are a product of index ranges: per axis and per combination "first / last function fixed" some field uses, those functions are
+ * dropped and the eigenproblem is solved by the library's own solver (Cholesky of M_d, cyclic Jacobi); fields with the same combination
+ * share the result.  A mode with |alpha + sum_d beta[d] lambda_d| <= 1e-12 max|denominator| (the maximum over all fields) has its reciprocal
+ * set to 0, a pseudo-inverse (the constant of pure-Neumann Poisson); *nzeroed (may be NULL) counts them over all fields.  alpha < 0, a
+ * beta[d] < 0 and alpha = beta = 0: IGX_ERR_ARG_OUTOFRANGE.  The state belongs to the IGX: a second call replaces it, IGXSetUp drops it,
+ * IGXDestroy frees it.
+ * IGXFastDiagApply: per field f, Z[free dofs of f] = A0,f^-1 R[free dofs of f] and Z[fixed] = R[fixed] / count, the correctly rounded
+ * quotient, count the number of elements at the node (the diagonal IGXComputeMatrixAction and IGXComputeMatrixDiagonal put there).  Fields
+ * are independent (the vector Laplacian part of Elasticity, a multi-field Mass).  Z may be R.  Six contractions along the axes of the
+ * vector on v_mfma_f64_16x16x4_f64 (fast_diag.hpp), no atomics, bit-repeatable; the device copies of the tables and two
+ * work vectors of the local vector's size are made at the first call.  IGXSetTiming / IGXGetLastTiming / IGXGetKernelName cover it.
+ * IGXFastDiagGetAxis hands back the eigen-system field `field` uses on `axis`: the index of its first free function, the number m of free
+ * functions, Lambda ascending and U column-major m x m (either array may be NULL).
+ * IGX_ERR_SUP with a reason that names fast diagonalisation: dim != 3, more than one rank on an axis (the transforms are global along an
+ * axis), a fix table (IGXSetFixTable), dof > 8.  IGXFastDiagApply before IGXFastDiagSetUp: IGX_ERR_ORDER; after the set of Dirichlet
+ * faces changed since IGXFastDiagSetUp: IGX_ERR_ARG_WRONGSTATE; null, foreign or wrong-sized vectors: IGX_ERR_ARG_WRONG. */
+int IGXFastDiagSetUp (IGX iga,double alpha,const double beta[3],int *nzeroed);
+int IGXFastDiagApply (IGX iga,IGXVec R,IGXVec Z);              /* Z = P R; Z may be R */
+int IGXFastDiagGetAxis(IGX iga,int axis,int field,int *first,int *m,double lambda[],double U[]);
 
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the

@@ -101,6 +101,8 @@ def lib(build_if_needed=False):
         "IGXComputeMatrixBlockDiagonal": [V, C.c_int, C.POINTER(V)], "IGXComputeJacobianBlockDiagonal": [V, V, C.c_int, C.POINTER(V)],
         "IGXComputeIJacobianBlockDiagonal": [V, C.c_double, V, C.c_double, V, C.c_int, C.POINTER(V)],
         "IGXBlockDiagonalInvert": [V, C.c_int, C.POINTER(V), C.POINTER(C.c_int64)], "IGXBlockDiagonalApply": [V, C.c_int, C.POINTER(V), V, V],
+        "IGXFastDiagSetUp": [V, C.c_double, _dp, _ip], "IGXFastDiagApply": [V, V, V],
+        "IGXFastDiagGetAxis": [V, C.c_int, C.c_int, _ip, _ip, _dp, _dp],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -450,6 +452,20 @@ class IGX:
         _ck(lib().IGXBlockDiagonalInvert(self.h, *self._cols(B), C.byref(n) if count else None))
         return int(n.value) if count else None
     def block_diagonal_apply(self, B, X, Y): _ck(lib().IGXBlockDiagonalApply(self.h, *self._cols(B), X.h, Y.h))
+    # fast diagonalisation: the exact inverse of alpha M + sum_d beta_d K_d on the parametric space, field by field (ignores the geometry)
+    def fast_diag_setup(self, alpha, beta):
+        """host work only; returns the number of modes whose reciprocal denominator was set to 0 (a pseudo-inverse)"""
+        nz = C.c_int(0)
+        _ck(lib().IGXFastDiagSetUp(self.h, float(alpha), (C.c_double * 3)(*[float(b) for b in beta]), C.byref(nz)))
+        return int(nz.value)
+    def fast_diag_apply(self, R, Z): _ck(lib().IGXFastDiagApply(self.h, R.h, Z.h))
+    def fast_diag_get_axis(self, axis, field=0):
+        """(first free function, m, Lambda [m] ascending, U [m, m] with U[:, k] eigenvector k) of the eigen-system `field` uses on `axis`"""
+        first, m = C.c_int(0), C.c_int(0)
+        _ck(lib().IGXFastDiagGetAxis(self.h, axis, field, C.byref(first), C.byref(m), None, None))
+        lam, U = np.zeros(m.value), np.zeros(m.value * m.value)
+        _ck(lib().IGXFastDiagGetAxis(self.h, axis, field, None, None, lam.ctypes.data_as(_dp), U.ctypes.data_as(_dp)))
+        return int(first.value), int(m.value), lam, U.reshape(m.value, m.value).T.copy()
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))
     def synchronize(self): _ck(lib().IGXSynchronize(self.h))

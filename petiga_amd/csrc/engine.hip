@@ -19,6 +19,7 @@
 #endif
 #ifndef IGX_TU_DISPATCH
 #include "block_diag.hpp"
+#include "fast_diag.hpp"
 #include "gram_mfma.hpp"
 #include "gram_patch.hpp"
 #include "gram_patch3.hpp"
@@ -73,6 +74,13 @@ struct AxisBufs { DevBuf tab, w, J, pt, off, rowmap, rcnt, P, rcol, prefix, bnd;
 
 struct IgxComm;
 struct RtcForm;
+// IGXFastDiagSetUp's host result and the device copies IGXFastDiagApply makes of it at its first call
+struct FastDiagState {
+  FastDiag h;
+  bool on_device = false;
+  DevBuf tf[3][4], tb[3][4], s[3][4], count[3];     // [axis][combo]: forward table T[j][i] = U[j - first][i], backward T[i][j], beta lambda; [axis]: elements per function
+  DevBuf work[2];                                   // two ping-pong buffers of the local vector's size
+};
 struct _p_IGX {
   Space s;
   bool on_device = false;
@@ -101,6 +109,7 @@ struct _p_IGX {
   std::function<void(int)> face_done;  // marks "upper face of axis 1 / 0 assembled" (gram_mfma.hpp)
   std::shared_ptr<RtcForm> rtc; std::string rtc_source, rtc_name;   // run-time compiled user form (rtc.hpp)
   std::shared_ptr<RtcForm> rtc_scalar;                              // ... and the last user functional (IGXComputeScalarSource)
+  std::shared_ptr<FastDiagState> fd;                                // fast diagonalisation (IGXFastDiagSetUp; fast_diag.hpp)
 };
 
 struct _p_IGXMat {
@@ -175,7 +184,7 @@ extern "C" int IGXAxisSetKnots(IGX g, int i, int m, const double U[]) { AXISCK(g
 static int apply_geometry(IGX g);
 static int apply_property(IGX g);
 extern "C" int IGXSetUp(IGX g) {
-  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false;
+  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; g->fd.reset();
   if (rc) return fail(rc, e);
   if (int rp = apply_property(g)) return rp;
   return apply_geometry(g);   // a control net given by IGXRead / an earlier IGXSetGeometry survives re-partitioning
@@ -1495,6 +1504,113 @@ static int block_diagonal_run(IGX g, int nb, IGXVec *B, IGXVec X, IGXVec Y, int6
 }
 extern "C" int IGXBlockDiagonalInvert(IGX g, int nb, IGXVec *B, int64_t *nsingular) { return block_diagonal_run(g, nb, B, nullptr, nullptr, nsingular, true); }
 extern "C" int IGXBlockDiagonalApply(IGX g, int nb, IGXVec *B, IGXVec X, IGXVec Y) { return block_diagonal_run(g, nb, B, X, Y, nullptr, false); }
+
+// Fast diagonalisation (Sangalli & Tani 2016): Z = P R with P the exact inverse of alpha M + sum_d beta_d K_d on the parametric tensor-product
+// space, field by field over each field's free dofs, and R / count in the fixed rows.  IGXFastDiagSetUp is host work (host.cpp: the 1-D
+// matrices from the space's tables and their generalised eigenpairs); IGXFastDiagApply uploads the tables at its first call and runs six
+// contractions of fast_diag.hpp over two work vectors: axes 0, 1, 2 forward (the last one scales by the reciprocal denominators), then 2, 1, 0
+// backward (the last one writes the fixed rows).
+static const char *fast_diag_refusal(IGX g) {
+  const Space &s = g->s;
+  if (s.dim != 3) return "fast diagonalisation needs dim = 3 (three 1-D eigen-systems and six contractions)";
+  for (int d = 0; d < 3; ++d) if (s.proc_sizes[d] != 1) return "fast diagonalisation needs one rank on every axis: its transforms are global along an axis";
+  if (g->fixtable.p) return "fast diagonalisation does not cover a fix table (IGXSetFixTable): its fixed dofs are not a union of faces";
+  if (s.dof > MAXBC) return "fast diagonalisation needs dof <= 8";
+  return nullptr;
+}
+extern "C" int IGXFastDiagSetUp(IGX g, double alpha, const double beta[3], int *nzeroed) {
+  NEEDIGA(g);
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXFastDiagSetUp()");
+  if (const char *why = fast_diag_refusal(g)) return fail(IGX_ERR_SUP, why);
+  if (!beta) return fail(IGX_ERR_ARG_WRONG, "null beta");
+  if (!(alpha >= 0) || !(beta[0] >= 0) || !(beta[1] >= 0) || !(beta[2] >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "fast diagonalisation needs alpha >= 0 and beta >= 0");
+  if (alpha == 0 && beta[0] == 0 && beta[1] == 0 && beta[2] == 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "fast diagonalisation needs alpha or some beta positive");
+  std::shared_ptr<FastDiagState> st(new FastDiagState());
+  std::string e;
+  if (int rc = fast_diag_setup(g->s, alpha, beta, st->h, e)) return fail(rc, e);
+  g->fd = st;
+  if (nzeroed) *nzeroed = st->h.nzeroed;
+  return 0;
+}
+extern "C" int IGXFastDiagGetAxis(IGX g, int axis, int field, int *first, int *m, double lambda[], double U[]) {
+  AXISCK(g, axis);
+  if (!g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() first");
+  if (field < 0 || field >= g->fd->h.dof) return fail(IGX_ERR_ARG_OUTOFRANGE, "Expecting 0<=field<dof");
+  const FastDiagEig &E = g->fd->h.eig[axis][g->fd->h.combo(axis, field)];
+  if (first) *first = E.first; if (m) *m = E.m;
+  if (lambda) std::copy(E.lambda.begin(), E.lambda.end(), lambda);
+  if (U) std::copy(E.U.begin(), E.U.end(), U);
+  return 0;
+}
+static int fast_diag_upload(IGX g) {
+  FastDiagState &st = *g->fd; const FastDiag &h = st.h;
+  for (int d = 0; d < 3; ++d) {
+    const int n = h.n[d];
+    for (int c = 0; c < 4; ++c) {
+      const FastDiagEig &E = h.eig[d][c];
+      if (!E.used) continue;
+      std::vector<double> tf((size_t)n * n, 0.0), tb((size_t)n * n, 0.0), sv(n, 0.0);
+      for (int i = 0; i < E.m; ++i) for (int k = 0; k < E.m; ++k) {      // node first + i, mode k
+        const double u = E.U[(size_t)i + (size_t)E.m * k];
+        tf[(size_t)(E.first + i) * n + k] = u; tb[(size_t)k * n + E.first + i] = u;
+      }
+      for (int k = 0; k < E.m; ++k) sv[k] = E.s[k];
+      if (st.tf[d][c].upload(tf) || st.tb[d][c].upload(tb) || st.s[d][c].upload(sv)) return fail(IGX_ERR_MEM, "device allocation of the fast-diagonalisation tables failed");
+    }
+    if (st.count[d].upload(h.count[d])) return fail(IGX_ERR_MEM, "device allocation of the fast-diagonalisation tables failed");
+  }
+  const size_t bytes = (size_t)g->nbrows * g->s.dof * sizeof(double);
+  for (int k = 0; k < 2; ++k) if (st.work[k].alloc(bytes)) return fail(IGX_ERR_MEM, "device allocation of the fast-diagonalisation work vectors failed");
+  st.on_device = true;
+  return 0;
+}
+extern "C" int IGXFastDiagApply(IGX g, IGXVec R, IGXVec Z) {
+  NEEDIGA(g);
+  if (!g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() before IGXFastDiagApply()");
+  if (const char *why = fast_diag_refusal(g)) return fail(IGX_ERR_SUP, why);
+  FastDiagState &st = *g->fd; const FastDiag &h = st.h;
+  {
+    bool now[3][2][MAXFD];
+    fast_diag_fixed_faces(g->s, now);
+    if (memcmp(now, h.fixed, sizeof(now)) != 0) return fail(IGX_ERR_ARG_WRONGSTATE, "the set of Dirichlet faces changed since IGXFastDiagSetUp(): call IGXFastDiagSetUp() again");
+  }
+  if (!R || !Z) return fail(IGX_ERR_ARG_WRONG, "null vector");
+  if (R->iga != g || Z->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if (int rc = ensure_device(g)) return rc;
+  const long long n0 = h.n[0], n1 = h.n[1], n2 = h.n[2], dof = h.dof;
+  if (R->n != n0 * n1 * n2 * dof || Z->n != R->n || g->nbrows != n0 * n1 * n2) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  if (!st.on_device) if (int rc = fast_diag_upload(g)) return rc;
+  bool uniform = true;      // every field has the tables of field 0: the fields are columns like any others
+  for (int d = 0; d < 3; ++d) for (int f = 1; f < dof; ++f) if (h.combo(d, f) != h.combo(d, 0)) uniform = false;
+  FdArgs a; memset(&a, 0, sizeof(a));
+  a.dof = (int)dof; a.nsel = uniform ? 1 : (int)dof;
+  a.n0 = (int)n0; a.n1 = (int)n1; a.n2 = (int)n2; a.alpha = h.alpha; a.thresh = h.thresh; a.R = R->a.as<double>();
+  for (int d = 0; d < 3; ++d) {
+    a.count[d] = st.count[d].as<double>();
+    for (int f = 0; f < dof; ++f) { a.s[d][f] = st.s[d][h.combo(d, f)].as<double>(); a.lo[d][f] = h.fixed[d][0][f]; a.hi[d][f] = h.fixed[d][1][f]; }
+  }
+  const long long inner[3] = {dof, n0 * dof, n0 * n1 * dof}, outer[3] = {n1 * n2, n2, 1};
+  double *w0 = st.work[0].as<double>(), *w1 = st.work[1].as<double>();
+  struct Step { int axis; bool back; int mode; const double *in; double *out; };
+  const Step steps[6] = {{0, false, FD_PLAIN, R->a.as<double>(), w0}, {1, false, FD_PLAIN, w0, w1}, {2, false, FD_SCALE, w1, w0},
+                         {2, true, FD_PLAIN, w0, w1}, {1, true, FD_PLAIN, w1, w0}, {0, true, FD_FINAL, w0, Z->a.as<double>()}};
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[0], g->stream)); HIPCK(hipEventRecord(g->ev[1], g->stream)); }
+  g->slab_valid = 0;
+  for (const Step &sp : steps) {
+    const int d = sp.axis;
+    a.in = sp.in; a.out = sp.out; a.mode = sp.mode; a.n = h.n[d]; a.inner = inner[d]; a.outer = outer[d];
+    for (int f = 0; f < dof; ++f) a.T[f] = (sp.back ? st.tb : st.tf)[d][h.combo(d, f)].as<double>();
+    if (fast_diag_launch(a, g->stream)) return fail(IGX_ERR_SUP, "fast diagonalisation: the vector is too large for one launch grid");
+    if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "fast diagonalisation kernel launch failed");
+  }
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
+  g->last_launches = 6;
+  char name[160];
+  snprintf(name, sizeof(name), "fast_diag(mfma_f64_16x16x4, 6 contractions, row tiles %d/%d/%d, %s)", fd_row_tiles(h.n[0]), fd_row_tiles(h.n[1]), fd_row_tiles(h.n[2]),
+           uniform ? "fields share their tables" : "tables per field");
+  g->last_kernel = name;
+  return 0;
+}
 
 // One pass for the pair a Newton step asks for at the same state (SNESComputeFunction + SNESComputeJacobian; src/petigats.c:23-159,
 // src/petigasnes.c:23-139): the results are those of the two drivers, in one walk where a fused kernel exists, else in two calls.

@@ -271,6 +271,179 @@ int basis_init(Basis1D &b, const Axis &ax, const Rule1D &rule, int nqp, std::str
   return 0;
 }
 
+// ------------------------------------------------------------------ fast diagonalisation: the host half (IGXFastDiagSetUp)
+// On a tensor-product space the parametric operator alpha M2 x M1 x M0 + beta0 M2 x M1 x K0 + beta1 M2 x K1 x M0 + beta2 K2 x M1 x M0 is
+// diagonal in the basis U2 x U1 x U0 of the 1-D generalised eigenvectors K_d U_d = M_d U_d Lambda_d, U_d^T M_d U_d = I (Sangalli & Tani,
+// SIAM J. Sci. Comput. 38 (2016)).  M_d and K_d come from the tables the element kernels read (offset, detJac, weight, value[..][0 and 1]),
+// so the inverse is exact for the rule the user set.  The eigen-solver is this file's: Cholesky of M and the reduction L^-1 K L^-T in
+// long double, cyclic Jacobi on the reduced matrix, U = L^-T Q in long double.  Sizes are one axis' function count.
+void fast_diag_fixed_faces(const Space &s, bool fixed[3][2][MAXFD]) {
+  for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) for (int f = 0; f < MAXFD; ++f) {
+    fixed[d][sd][f] = false;
+    if (d >= s.dim || s.axis[d].periodic) continue;      // (IGAElementBuildFix skips periodic axes, src/petigaelem.c:1214)
+    const BC &bc = s.value[d][sd];
+    for (int k = 0; k < bc.count; ++k) if (bc.field[k] == f && f < s.dof) fixed[d][sd][f] = true;
+  }
+}
+
+namespace {
+// eigenpairs of the symmetric C [m][m] (destroyed): cyclic Jacobi, eigenvalues ascending in lam, eigenvector k in row k of Qt
+void jacobi_eigen(int m, std::vector<double> &C, std::vector<double> &lam, std::vector<double> &Qt) {
+  Qt.assign((size_t)m * m, 0.0);
+  for (int i = 0; i < m; ++i) Qt[(size_t)i * m + i] = 1.0;
+  double norm2 = 0;
+  for (size_t i = 0; i < (size_t)m * m; ++i) norm2 += C[i] * C[i];
+  const double small2 = norm2 * 1e-40, skip = std::sqrt(norm2) * 1e-24;
+  for (int sweep = 0; sweep < 100; ++sweep) {
+    double off2 = 0;
+    for (int p = 0; p < m; ++p) for (int q = p + 1; q < m; ++q) off2 += C[(size_t)p * m + q] * C[(size_t)p * m + q];
+    if (off2 <= small2) break;
+    for (int p = 0; p < m - 1; ++p) {
+      double *rp = &C[(size_t)p * m], *vp = &Qt[(size_t)p * m];
+      for (int q = p + 1; q < m; ++q) {
+        double *rq = &C[(size_t)q * m], *vq = &Qt[(size_t)q * m];
+        const double apq = rp[q];
+        if (std::fabs(apq) <= skip) { rp[q] = 0.0; rq[p] = 0.0; continue; }
+        const double app = rp[p], aqq = rq[q];
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < m; ++k) { const double a = rp[k], b = rq[k]; rp[k] = c * a - sn * b; rq[k] = sn * a + c * b; }
+        rp[p] = app - t * apq; rq[q] = aqq + t * apq; rp[q] = 0.0; rq[p] = 0.0;
+        for (int k = 0; k < m; ++k) { if (k == p || k == q) continue; C[(size_t)k * m + p] = rp[k]; C[(size_t)k * m + q] = rq[k]; }
+        for (int k = 0; k < m; ++k) { const double a = vp[k], b = vq[k]; vp[k] = c * a - sn * b; vq[k] = sn * a + c * b; }
+      }
+    }
+  }
+  std::vector<int> order(m);
+  for (int i = 0; i < m; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return C[(size_t)a * m + a] < C[(size_t)b * m + b]; });
+  lam.resize(m);
+  std::vector<double> Q2((size_t)m * m);
+  for (int k = 0; k < m; ++k) { lam[k] = C[(size_t)order[k] * m + order[k]]; std::copy(&Qt[(size_t)order[k] * m], &Qt[(size_t)order[k] * m] + m, &Q2[(size_t)k * m]); }
+  Qt.swap(Q2);
+}
+
+// K U = M U Lambda, U^T M U = I for the symmetric positive definite M and symmetric K, both [m][m]
+int generalised_eigen(int m, const std::vector<double> &M, const std::vector<double> &K, FastDiagEig &out, std::string &err) {
+  typedef long double ld;
+  out.lambda.clear(); out.U.clear();
+  if (m <= 0) return 0;
+  std::vector<ld> L((size_t)m * m, 0.0L), X((size_t)m * m);
+  for (int j = 0; j < m; ++j) {      // M = L L^T
+    ld dg = M[(size_t)j * m + j];
+    for (int k = 0; k < j; ++k) dg -= L[(size_t)j * m + k] * L[(size_t)j * m + k];
+    if (!(dg > 0)) { err = "fast diagonalisation: the 1-D mass matrix of an axis is not positive definite"; return IGX_ERR_PLIB; }
+    const ld ljj = sqrtl(dg);
+    L[(size_t)j * m + j] = ljj;
+    for (int i = j + 1; i < m; ++i) {
+      ld v = M[(size_t)i * m + j];
+      for (int k = 0; k < j; ++k) v -= L[(size_t)i * m + k] * L[(size_t)j * m + k];
+      L[(size_t)i * m + j] = v / ljj;
+    }
+  }
+  // X = L^-1 K (rows by forward substitution), then C = X L^-T, i.e. C^T = L^-1 X^T: the same substitution on X^T
+  auto forward = [&](std::vector<ld> &B) {      // B <- L^-1 B, B [m][m] row-major
+    for (int i = 0; i < m; ++i) {
+      ld *bi = &B[(size_t)i * m];
+      for (int k = 0; k < i; ++k) { const ld l = L[(size_t)i * m + k]; if (l == 0) continue; const ld *bk = &B[(size_t)k * m]; for (int c = 0; c < m; ++c) bi[c] -= l * bk[c]; }
+      const ld inv = 1.0L / L[(size_t)i * m + i];
+      for (int c = 0; c < m; ++c) bi[c] *= inv;
+    }
+  };
+  for (size_t i = 0; i < (size_t)m * m; ++i) X[i] = K[i];
+  forward(X);
+  for (int i = 0; i < m; ++i) for (int j = i + 1; j < m; ++j) std::swap(X[(size_t)i * m + j], X[(size_t)j * m + i]);
+  forward(X);
+  std::vector<double> C((size_t)m * m), Qt;
+  for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) C[(size_t)i * m + j] = (double)((X[(size_t)i * m + j] + X[(size_t)j * m + i]) / 2);
+  jacobi_eigen(m, C, out.lambda, Qt);
+  out.U.assign((size_t)m * m, 0.0);
+  std::vector<ld> y(m);
+  for (int k = 0; k < m; ++k) {      // L^T u = q_k by back substitution
+    for (int i = m - 1; i >= 0; --i) {
+      ld v = Qt[(size_t)k * m + i];
+      for (int j = i + 1; j < m; ++j) v -= L[(size_t)j * m + i] * y[j];
+      y[i] = v / L[(size_t)i * m + i];
+    }
+    for (int i = 0; i < m; ++i) out.U[(size_t)i + (size_t)m * k] = (double)y[i];
+  }
+  return 0;
+}
+}  // namespace
+
+int fast_diag_setup(const Space &s, double alpha, const double beta[3], FastDiag &fd, std::string &err) {
+  fd = FastDiag();
+  fd.alpha = alpha; fd.dof = s.dof;
+  for (int d = 0; d < 3; ++d) fd.beta[d] = beta[d];
+  fast_diag_fixed_faces(s, fd.fixed);
+  std::vector<double> Mfull[3], Kfull[3];
+  for (int d = 0; d < 3; ++d) {
+    const Basis1D &b = s.basis[d];
+    const int n = s.axis[d].nnp, per = s.axis[d].periodic;
+    if (s.lay[d].nrow != n) { err = "fast diagonalisation: the row box of an axis is not its function range"; return IGX_ERR_PLIB; }
+    fd.n[d] = n;
+    std::vector<double> &M = Mfull[d], &K = Kfull[d];
+    M.assign((size_t)n * n, 0.0); K.assign((size_t)n * n, 0.0); fd.count[d].assign(n, 0.0);
+    for (int e = 0; e < b.nel; ++e) {
+      auto fn = [&](int a) { const int i = b.offset[e] + a; return per ? ((i % n) + n) % n : i; };
+      for (int a = 0; a < b.nen; ++a) fd.count[d][fn(a)] += 1.0;
+      for (int q = 0; q < b.nqp; ++q) {
+        const double wj = b.weight[(size_t)e * b.nqp + q] * b.detJac[e];
+        const double *v = &b.value[((size_t)e * b.nqp + q) * b.nen * 5];
+        for (int a = 0; a < b.nen; ++a) for (int c = 0; c < b.nen; ++c) {
+          M[(size_t)fn(a) * n + fn(c)] += wj * v[a * 5] * v[c * 5];
+          K[(size_t)fn(a) * n + fn(c)] += wj * v[a * 5 + 1] * v[c * 5 + 1];
+        }
+      }
+    }
+    for (int f = 0; f < s.dof; ++f) {
+      FastDiagEig &E = fd.eig[d][fd.combo(d, f)];
+      if (E.used) continue;
+      E.used = true;
+      E.first = fd.fixed[d][0][f] ? 1 : 0;
+      E.m = std::max(0, n - E.first - (fd.fixed[d][1][f] ? 1 : 0));
+      // an axis with the tables and the combination of an earlier one (a cube): its eigenpairs
+      bool reused = false;
+      for (int d2 = 0; d2 < d && !reused; ++d2) {
+        const FastDiagEig &E2 = fd.eig[d2][fd.combo(d, f)];
+        if (E2.used && fd.n[d2] == n && Mfull[d2] == M && Kfull[d2] == K) { E.lambda = E2.lambda; E.U = E2.U; reused = true; }
+      }
+      if (reused) continue;
+      const int m = E.m;
+      std::vector<double> Ms((size_t)m * m), Ks((size_t)m * m);
+      for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) { Ms[(size_t)i * m + j] = M[(size_t)(E.first + i) * n + E.first + j]; Ks[(size_t)i * m + j] = K[(size_t)(E.first + i) * n + E.first + j]; }
+      if (int rc = generalised_eigen(m, Ms, Ks, E, err)) return rc;
+    }
+  }
+  // the denominators ((alpha + s0) + s1) + s2 with the rounded products s_d = beta_d lambda_d: sums alone, in this order here and on the
+  // device, so the modes zeroed there are the modes counted here
+  double dmax = 0;
+  for (int d = 0; d < 3; ++d) for (int c = 0; c < 4; ++c) {
+    FastDiagEig &E = fd.eig[d][c];
+    E.s.resize(E.lambda.size());
+    for (size_t i = 0; i < E.lambda.size(); ++i) E.s[i] = beta[d] * E.lambda[i];
+  }
+  for (int f = 0; f < s.dof; ++f) {
+    double v = alpha;
+    for (int d = 0; d < 3; ++d) { double mx = 0; for (double x : fd.eig[d][fd.combo(d, f)].s) mx = std::max(mx, std::fabs(x)); v += mx; }
+    dmax = std::max(dmax, v);
+  }
+  fd.thresh = 1e-12 * dmax;
+  fd.nzeroed = 0;
+  for (int f = 0; f < s.dof; ++f) {
+    const FastDiagEig &E0 = fd.eig[0][fd.combo(0, f)], &E1 = fd.eig[1][fd.combo(1, f)], &E2 = fd.eig[2][fd.combo(2, f)];
+    for (int k = 0; k < E2.m; ++k) for (int j = 0; j < E1.m; ++j) {
+      const double sjk[2] = {E1.s[j], E2.s[k]};
+      for (int i = 0; i < E0.m; ++i) {
+        const double den = ((alpha + E0.s[i]) + sjk[0]) + sjk[1];
+        if (std::fabs(den) <= fd.thresh) fd.nzeroed++;
+      }
+    }
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------ processor grid (src/petigapart.c:11-168)
 // The search below follows the reference step for step (initial guesses from the real-valued optimum,
 // three descending sweeps, cube tie-breaks) because the resulting grid is part of the bit-exact contract.

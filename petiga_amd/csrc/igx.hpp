@@ -146,6 +146,31 @@ int  space_setup(Space &s, std::string &err);          // IGASetUp stages 1+3 (s
 int  space_layout(Space &s, std::string &err);         // AxisLayout for the three axes
 int  exchange_supported(const Space &s, std::string &err);   // 0, or IGX_ERR_SUP when a periodic ghost layer would wrap onto its own rank
 
+// Fast diagonalisation (IGXFastDiagSetUp, host.cpp; the contractions: fast_diag.hpp).  Per axis and per combination "first / last function
+// fixed" (combo = lo + 2 * hi) that some field uses: the generalised eigenpairs K U = M U Lambda, U^T M U = I, of the axis' 1-D stiffness and
+// mass matrices over its free functions.
+constexpr int MAXFD = 8;         // fields (= MAXBC)
+struct FastDiagEig {
+  bool used = false;             // some field uses the combination
+  int first = 0, m = 0;          // the free functions are first .. first + m - 1
+  std::vector<double> lambda;    // [m] ascending
+  std::vector<double> s;         // [m] beta_axis * lambda, rounded: the axis' share of a mode's denominator
+  std::vector<double> U;         // [m][m] column-major: U[i + m * k] = component i of eigenvector k
+};
+struct FastDiag {
+  double alpha = 0, beta[3] = {0, 0, 0};
+  int n[3] = {1, 1, 1};                        // functions per axis (the vector's row box: one rank)
+  int dof = 0;
+  bool fixed[3][2][MAXFD];                     // [axis][side][field]: the face is a Dirichlet face of the field (never on a periodic axis)
+  FastDiagEig eig[3][4];                       // [axis][combo]
+  std::vector<double> count[3];                // [n]: elements that hold the function (their product over the axes: the fixed rows' diagonal)
+  double thresh = 0;                           // modes with |alpha + sum beta lambda| <= thresh are zeroed
+  int nzeroed = 0;
+  int combo(int d, int f) const { return (fixed[d][0][f] ? 1 : 0) + (fixed[d][1][f] ? 2 : 0); }
+};
+void fast_diag_fixed_faces(const Space &s, bool fixed[3][2][MAXFD]);      // the Dirichlet faces as the element kernels read them
+int  fast_diag_setup(const Space &s, double alpha, const double beta[3], FastDiag &fd, std::string &err);
+
 #endif   // !IGX_RTC
 
 // ------------------------------------------------------------------ device descriptors (POD, passed by value)
