@@ -276,7 +276,8 @@ int basis_init(Basis1D &b, const Axis &ax, const Rule1D &rule, int nqp, std::str
 // diagonal in the basis U2 x U1 x U0 of the 1-D generalised eigenvectors K_d U_d = M_d U_d Lambda_d, U_d^T M_d U_d = I (Sangalli & Tani,
 // SIAM J. Sci. Comput. 38 (2016)).  M_d and K_d come from the tables the element kernels read (offset, detJac, weight, value[..][0 and 1]),
 // so the inverse is exact for the rule the user set.  The eigen-solver is this file's: Cholesky of M and the reduction L^-1 K L^-T in
-// long double, cyclic Jacobi on the reduced matrix, U = L^-T Q in long double.  Sizes are one axis' function count.
+// long double, cyclic Jacobi on the reduced matrix in double, a refinement of its eigenpairs in long double (refine_eigen), U = L^-T Q in
+// long double.  Sizes are one axis' function count.
 void fast_diag_fixed_faces(const Space &s, bool fixed[3][2][MAXFD]) {
   for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) for (int f = 0; f < MAXFD; ++f) {
     fixed[d][sd][f] = false;
@@ -324,6 +325,66 @@ void jacobi_eigen(int m, std::vector<double> &C, std::vector<double> &lam, std::
   Qt.swap(Q2);
 }
 
+// Refinement of the eigenpairs of the symmetric C [m][m] in long double (Ogita & Aishima, Japan J. Indust. Appl. Math. 35 (2018)):
+// Q holds the approximate eigenvector k in its row k, lam the eigenvalues, ascending.  The double-precision rotations above leave
+// Q Q^T - I and the off-diagonal of Q C Q^T at some 4e-16 m; one step Q <- (I + E^T) Q with
+//   R = I - Q Q^T,  S = Q C Q^T,  lam_k = S_kk / (1 - R_kk),  E_kl = (S_kl + lam_l R_kl) / (lam_l - lam_k),  E_kk = R_kk / 2
+// squares both errors.  Inside a cluster of eigenvalues (a periodic axis has exact pairs; |lam_l - lam_k| <= delta = 2 (|S - diag S| +
+// |lam|max |R|), what the present pairs cannot resolve) the quotient is meaningless and any orthonormal basis of the invariant subspace
+// serves: there E_kl = R_kl / 2, which restores orthonormality alone.  Steps repeat until max|E| <= 1e-9
+// (the next step's correction would be below the long-double rounding of the products), three at the most.
+void refine_eigen(int m, const std::vector<long double> &C, std::vector<double> &lam, std::vector<long double> &Q) {
+  typedef long double ld;
+  const size_t mm = (size_t)m * m;
+  std::vector<ld> W(mm), S(mm), R(mm), E(mm), l(m);
+  std::vector<double> Ed(mm), Qd(mm), D(mm);
+  for (int step = 0; step < 3; ++step) {
+    std::fill(W.begin(), W.end(), 0.0L);
+    for (int k = 0; k < m; ++k)      // W = Q C
+      for (int i = 0; i < m; ++i) { const ld q = Q[(size_t)k * m + i]; const ld *c = &C[(size_t)i * m]; ld *w = &W[(size_t)k * m]; for (int j = 0; j < m; ++j) w[j] += q * c[j]; }
+    for (int k = 0; k < m; ++k) for (int h = k; h < m; ++h) {
+      const ld *qk = &Q[(size_t)k * m], *qh = &Q[(size_t)h * m], *wk = &W[(size_t)k * m];
+      ld s = 0, g = 0;
+      for (int j = 0; j < m; ++j) { s += wk[j] * qh[j]; g += qk[j] * qh[j]; }
+      S[(size_t)k * m + h] = S[(size_t)h * m + k] = s;
+      R[(size_t)k * m + h] = R[(size_t)h * m + k] = (k == h ? 1.0L : 0.0L) - g;
+    }
+    for (int k = 0; k < m; ++k) l[k] = S[(size_t)k * m + k] / (1.0L - R[(size_t)k * m + k]);
+    ld s2 = 0, r2 = 0, lmax = 0, emax = 0;
+    for (int k = 0; k < m; ++k) {
+      lmax = std::max(lmax, fabsl(l[k]));
+      for (int h = 0; h < m; ++h) { r2 += R[(size_t)k * m + h] * R[(size_t)k * m + h]; if (h != k) s2 += S[(size_t)k * m + h] * S[(size_t)k * m + h]; }
+    }
+    // a cluster: a gap the present eigenvalues cannot tell from 0 (the paper's delta, Frobenius for spectral norms), or below double's reach
+    const ld delta = std::max(2 * (sqrtl(s2) + lmax * sqrtl(r2)), 1e-14L * lmax);
+    for (int k = 0; k < m; ++k) for (int h = 0; h < m; ++h) {
+      const ld r = R[(size_t)k * m + h];
+      ld e = r / 2;
+      if (k != h) {
+        const ld num = S[(size_t)k * m + h] + l[h] * r, gap = l[h] - l[k];
+        if (fabsl(gap) > delta && fabsl(num) <= 1e-3L * fabsl(gap)) e = num / gap;
+      }
+      E[(size_t)k * m + h] = e;
+      emax = std::max(emax, fabsl(e));
+    }
+    // row h of Q += sum_k E_kh (row k of Q): the correction is at most 1e-3 of Q, so double products leave it exact to 1e-19 of Q
+    for (size_t i = 0; i < mm; ++i) { Ed[i] = (double)E[i]; Qd[i] = (double)Q[i]; }
+    std::fill(D.begin(), D.end(), 0.0);
+    for (int h = 0; h < m; ++h) {
+      double *dh = &D[(size_t)h * m];
+      for (int k = 0; k < m; ++k) { const double e = Ed[(size_t)k * m + h]; const double *qk = &Qd[(size_t)k * m]; for (int i = 0; i < m; ++i) dh[i] += e * qk[i]; }
+    }
+    for (size_t i = 0; i < mm; ++i) Q[i] += D[i];
+    if (emax <= 1e-9L) break;
+  }
+  // the Rayleigh quotients of the step before the last correction are exact to second order in it; a cluster may have changed its order
+  std::vector<int> order(m);
+  for (int i = 0; i < m; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return l[a] < l[b]; });
+  W = Q;
+  for (int k = 0; k < m; ++k) { lam[k] = (double)l[order[k]]; std::copy(&W[(size_t)order[k] * m], &W[(size_t)order[k] * m] + m, &Q[(size_t)k * m]); }
+}
+
 // K U = M U Lambda, U^T M U = I for the symmetric positive definite M and symmetric K, both [m][m]
 int generalised_eigen(int m, const std::vector<double> &M, const std::vector<double> &K, FastDiagEig &out, std::string &err) {
   typedef long double ld;
@@ -356,13 +417,16 @@ int generalised_eigen(int m, const std::vector<double> &M, const std::vector<dou
   for (int i = 0; i < m; ++i) for (int j = i + 1; j < m; ++j) std::swap(X[(size_t)i * m + j], X[(size_t)j * m + i]);
   forward(X);
   std::vector<double> C((size_t)m * m), Qt;
-  for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) C[(size_t)i * m + j] = (double)((X[(size_t)i * m + j] + X[(size_t)j * m + i]) / 2);
+  for (int i = 0; i < m; ++i) for (int j = i; j < m; ++j) X[(size_t)i * m + j] = X[(size_t)j * m + i] = (X[(size_t)i * m + j] + X[(size_t)j * m + i]) / 2;
+  for (size_t i = 0; i < (size_t)m * m; ++i) C[i] = (double)X[i];
   jacobi_eigen(m, C, out.lambda, Qt);
+  std::vector<ld> Q(Qt.begin(), Qt.end());
+  refine_eigen(m, X, out.lambda, Q);
   out.U.assign((size_t)m * m, 0.0);
   std::vector<ld> y(m);
   for (int k = 0; k < m; ++k) {      // L^T u = q_k by back substitution
     for (int i = m - 1; i >= 0; --i) {
-      ld v = Qt[(size_t)k * m + i];
+      ld v = Q[(size_t)k * m + i];
       for (int j = i + 1; j < m; ++j) v -= L[(size_t)j * m + i] * y[j];
       y[i] = v / L[(size_t)i * m + i];
     }

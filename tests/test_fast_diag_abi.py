@@ -81,6 +81,13 @@ AXES = {
     "p2 nqp = p + 2": (2, _uniform(2, 9), False, 4),
     "p7 with 6 elements": (7, _uniform(7, 6), False, None),
     "p3 uniform, 17 elements": (3, _uniform(3, 17), False, None),
+    # axis lengths of real runs: m = 72 and 150 (the row-tile ladder of the device half), 260 (two row blocks; the benchmark's 256^3 at
+    # p = 3 has 259), the ill-conditioned p = 7 at that length, and the exact eigenvalue pairs of a periodic axis
+    "p2 uniform, 70 elements": (2, _uniform(2, 70), False, None),
+    "p3 uniform, 147 elements": (3, _uniform(3, 147), False, None),
+    "p2 uniform, 258 elements": (2, _uniform(2, 258), False, None),
+    "p7 uniform, 250 elements": (7, _uniform(7, 250), False, None),
+    "p2 periodic, 300 elements": (2, _uniform(2, 300, periodic=True), True, None),
 }
 OBSERVED = {}
 

@@ -88,6 +88,12 @@ POISSON = {
     "p2 (70,3,3), faces on axis 0, m = 70": (2, [70, 3, 3], [(0, 0), (0, 1)], None, None),
     "p3 non-uniform with a C0 knot": (3, [5, 4, 3], [(0, 0), (0, 1), (2, 1)], [[0, 0, 0, 0, 0.25, 0.5, 0.5, 0.5, 0.7, 1, 1, 1, 1], None, None], None),
     "p2 (5,4,3), nqp = 4 on axis 1": (2, [5, 4, 3], [(0, 0), (1, 1), (2, 1)], None, [None, 4, None]),
+    # the axis lengths of real runs (260 functions: two row blocks; the benchmark's 256^3 at p = 3 has 259), quasi-1-D and quasi-2-D so
+    # that spsolve stays fast: here the host eigen-solver's accuracy at m = 258 decides
+    "p2 (258,2,2), six faces, m = 258 on axis 0": (2, [258, 2, 2], ALL6, None, None),
+    "p2 (2,258,2), six faces, m = 258 on axis 1": (2, [2, 258, 2], ALL6, None, None),
+    "p2 (2,2,258), six faces, m = 258 on axis 2": (2, [2, 2, 258], ALL6, None, None),
+    "p3 (97,45,2), six faces, m = 98 and 46": (3, [97, 45, 2], ALL6, None, None),
 }
 
 
