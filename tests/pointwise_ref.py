@@ -12,7 +12,8 @@ The bound S is the same sums with every factor replaced by its absolute value, e
 state's abs-sum (e^u -> e^u (1 + uabs)): S bounds any order of summation, it is not fitted to an implementation.  The comparison is
 that of tensor_ref.py: |E - R| <= c u S, with c = C_ID on the identity geometry and C_MAP on an affine map
 (test_pointwise_reference.py calibrates both on the CPU oracle).  3-D, one field; identity geometry or an affine map x = A g + b
-(constant NURBS weights included: the rational basis is then the B-spline basis).
+(constant NURBS weights included: the rational basis is then the B-spline basis); curved_ref.py is the same reference on a general
+NURBS map, where the Jacobian, the map's second derivatives and W vary from point to point.
 
 Dirichlet semantics are TensorRef's (fixed / multiplicity, the last face wins): the state takes the boundary value at a fixed node, the
 direction X and the rate V take 0 there; a fixed Function row is m (U - v), a fixed action row m X (S = m |X|: a kernel that adds X
@@ -180,7 +181,7 @@ class PointwiseRef:
     # -- Cahn-Hilliard (orc_form_ch_residual / orc_form_ch_tangent), identity geometry
     def _ch(self, ctx, Uf):
         """The coefficients at the points and the absolute sums their bounds need.  ctx: (theta, alpha, cbar, L0, lambda, tau)."""
-        assert not self.mapped, "Cahn-Hilliard: identity geometry only (the map's Hessian is zero only in exact arithmetic)"
+        assert not self.mapped, "Cahn-Hilliard: identity geometry only here; curved_ref.CurvedRef has it on a mapped geometry, the map's Hessian included"
         theta, alpha, _, L0, lam, _ = ctx
         scale = LD(L0) * LD(L0) / LD(lam) if L0 > 0 else 3 * LD(alpha)
         h = LD(0.5) / LD(theta)

@@ -6,7 +6,8 @@ set is a Cartesian product and every quadrature term factorises.  So is the sum 
 summing the same products -- sum-factorised phases, MFMA accumulation trees, LDS adds -- stays within a small multiple of u*S of the
 exact value (u = 2^-53).  This module evaluates, at arbitrary global (row, col) pairs, the exact value R of the discrete operation (the
 1-D tables in long double, from the points, weights and Jacobians the kernels use) and the bound S, and compares a matrix with them
-entry by entry: |E - R| <= c * u * S, with S = 0 meaning exactly zero.
+entry by entry: |E - R| <= c * u * S, with S = 0 meaning exactly zero.  On a curved map no term factorises: curved_ref.py evaluates
+the same forms at the quadrature points of a general NURBS geometry.
 
 Indices are the engine's global natural numbering: node * dof + field, node = i0 + n0 * (i1 + n1 * i2) (axis 0 fastest).
 """
