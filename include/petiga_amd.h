@@ -391,6 +391,49 @@ int IGXFastDiagSetUp (IGX iga,double alpha,const double beta[3],int *nzeroed);
 int IGXFastDiagApply (IGX iga,IGXVec R,IGXVec Z);              /* Z = P R; Z may be R */
 int IGXFastDiagGetAxis(IGX iga,int axis,int field,int *first,int *m,double lambda[],double U[]);
 
+/* Vector algebra on IGXVec, for a caller without PETSc's Vec: what a Krylov iteration needs besides the operators above.  Every call is
+ * enqueued on the engine's stream; the vectors of one call must belong to the same IGX (a null or foreign vector: IGX_ERR_ARG_WRONG).
+ * Sweeps of 16-byte accesses with a scalar tail over a capped grid (krylov.hpp).  IGXVecAXPBY with b = 0 gives y = a x whatever y held.
+ * IGXVecPointwiseDivide gives the correctly rounded quotients.  IGXVecDot and IGXVecNorm2 sum over the rows this rank OWNS (IGXChecksum's
+ * rule; on one rank every row) and hand the number back, so they synchronise the stream; on several ranks the caller adds the parts, as
+ * for IGXComputeScalar (for the norm: the squares).  The sums use no atomics: each workgroup adds its lanes in a fixed tree and stores one
+ * partial, the partials are added in index order by a one-workgroup kernel: bitwise repeatable. */
+int IGXVecSet  (IGXVec y,double value);
+int IGXVecCopy (IGXVec x,IGXVec y);                       /* y = x */
+int IGXVecScale(IGXVec y,double a);
+int IGXVecAXPBY(IGXVec y,double a,IGXVec x,double b);     /* y = a x + b y */
+int IGXVecPointwiseDivide(IGXVec z,IGXVec x,IGXVec d);    /* z = x ./ d, z may be x */
+int IGXVecDot  (IGXVec x,IGXVec y,double *s);             /* over the rows this rank owns; synchronises */
+int IGXVecNorm2(IGXVec x,double *s);
+
+/* The Krylov loop on the matrix-free operators, resident on the device: A x = b with A the action `op` names at the state (a, V, t, U)
+ * -- IGXComputeMatrixAction, IGXComputeJacobianAction (U) or IGXComputeIJacobianAction (a, V, t, U), through the same entry the call
+ * itself takes -- by preconditioned CG or right-preconditioned BiCGStab, from the initial guess x holds on entry.  It is the native loop
+ * of a caller without PETSc, not a KSP adapter.  The preconditioner: none; IGX_PC_JACOBI, the matching IGXCompute*Diagonal formed by the
+ * solve at the same state; IGX_PC_PBJACOBI, the matching IGXCompute*BlockDiagonal formed and inverted by the solve (IGXBlockDiagonalInvert's
+ * kernel); IGX_PC_FASTDIAG, the state of the caller's IGXFastDiagSetUp (alpha and beta are a modelling choice; without it: IGX_ERR_ORDER).
+ * Stop test, on the recurrence residual: |r|_2 <= max(rtol |b|_2, atol), once per iteration (BiCGStab has no half-step exit).  A solve
+ * that does not converge RETURNS 0: info->reason says why -- IGX_DIVERGED_ITS after maxit iterations, IGX_DIVERGED_BREAKDOWN for a zero or
+ * non-finite denominator (CG: also p.Ap <= 0), IGX_DIVERGED_NAN for a NaN norm; b = 0 gives x = 0, 0 iterations, IGX_CONVERGED_ATOL.  x on
+ * return is the iterate whose norm was tested; history (NULL, or maxit + 1 doubles) receives |r_k|_2, k = 0 .. iterations.
+ * The vectors never leave the device: the sweeps between two operator calls are fused, each emits the partial sums the next one needs,
+ * alpha, beta and omega are formed on the device from those slabs (krylov.hpp), and the host reads one small record per
+ * iteration for the stop test.  Work vectors (4 for CG, 8 for BiCGStab, plus the diagonal or the dof block columns) are allocated at the
+ * first solve and kept with the IGX while the method and the preconditioner need the same set; IGXSetUp drops them, IGXDestroy frees them.
+ * Bitwise repeatable.  IGXSetTiming / IGXGetLastTiming cover the whole solve (total time, the operators' and preconditioners' own kernel
+ * time, launches); IGXGetKernelName gives "krylov(<method>, pc=<..>, <the action's kernel name>, <k> iterations)".
+ * IGX_ERR_SUP with a reason that names the Krylov solve: more than one rank on an axis (the library has no sum across ranks), and
+ * whatever the action, the diagonal, the block diagonal or fast diagonalisation refuse, with their reason.  x == b, null or foreign
+ * vectors, U / V missing where op needs them, x a state vector: IGX_ERR_ARG_WRONG; maxit < 0, a negative tolerance, an unknown method,
+ * operator or preconditioner: IGX_ERR_ARG_OUTOFRANGE; before IGXSetUp: IGX_ERR_ORDER; no form set: IGX_ERR_ARG_WRONGSTATE. */
+typedef enum { IGX_SOLVE_CG = 0, IGX_SOLVE_BICGSTAB = 1 } IGXSolveMethod;
+typedef enum { IGX_OP_MATRIX = 0, IGX_OP_JACOBIAN = 1, IGX_OP_IJACOBIAN = 2 } IGXSolveOperator;
+typedef enum { IGX_PC_NONE = 0, IGX_PC_JACOBI = 1, IGX_PC_PBJACOBI = 2, IGX_PC_FASTDIAG = 3 } IGXSolvePC;
+typedef enum { IGX_CONVERGED_RTOL = 1, IGX_CONVERGED_ATOL = 2, IGX_DIVERGED_ITS = -1, IGX_DIVERGED_BREAKDOWN = -2, IGX_DIVERGED_NAN = -3 } IGXSolveReason;
+typedef struct { int method, op, pc; double a, t; IGXVec V, U; double rtol, atol; int maxit; } IGXSolveSpec;
+typedef struct { int iterations, reason; double rnorm0, rnorm, bnorm; } IGXSolveInfo;
+int IGXSolve(IGX iga,const IGXSolveSpec *spec,IGXVec b,IGXVec x,IGXSolveInfo *info,double *history /* NULL or [maxit+1]: |r_k|_2 */);
+
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
  * ranks, and U must hold the ghost rows' values).  The point callbacks are the ones the reference's tests use:

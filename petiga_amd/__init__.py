@@ -38,6 +38,21 @@ class IGXTables(C.Structure):
                 ("property", C.c_int), ("propertyA", _dp)]
 
 
+class IGXSolveSpec(C.Structure):
+    _fields_ = [("method", C.c_int), ("op", C.c_int), ("pc", C.c_int), ("a", C.c_double), ("t", C.c_double), ("V", C.c_void_p), ("U", C.c_void_p),
+                ("rtol", C.c_double), ("atol", C.c_double), ("maxit", C.c_int)]
+
+
+class IGXSolveInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("reason", C.c_int), ("rnorm0", C.c_double), ("rnorm", C.c_double), ("bnorm", C.c_double)]
+
+
+SOLVE_METHODS = dict(cg=0, bicgstab=1)
+SOLVE_OPERATORS = dict(matrix=0, jacobian=1, ijacobian=2)
+SOLVE_PCS = dict(none=0, jacobi=1, pbjacobi=2, fastdiag=3)
+SOLVE_REASONS = {1: "converged_rtol", 2: "converged_atol", -1: "diverged_its", -2: "diverged_breakdown", -3: "diverged_nan"}
+
+
 # IGXTransportFn (include/petiga_amd.h): the host-callback transport of the ghost-row exchange
 TRANSPORT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, _ip, C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
 
@@ -103,6 +118,9 @@ def lib(build_if_needed=False):
         "IGXBlockDiagonalInvert": [V, C.c_int, C.POINTER(V), C.POINTER(C.c_int64)], "IGXBlockDiagonalApply": [V, C.c_int, C.POINTER(V), V, V],
         "IGXFastDiagSetUp": [V, C.c_double, _dp, _ip], "IGXFastDiagApply": [V, V, V],
         "IGXFastDiagGetAxis": [V, C.c_int, C.c_int, _ip, _ip, _dp, _dp],
+        "IGXVecSet": [V, C.c_double], "IGXVecCopy": [V, V], "IGXVecScale": [V, C.c_double], "IGXVecAXPBY": [V, C.c_double, V, C.c_double],
+        "IGXVecPointwiseDivide": [V, V, V], "IGXVecDot": [V, V, _dp], "IGXVecNorm2": [V, _dp],
+        "IGXSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -170,6 +188,24 @@ class Vec:
         p = C.c_void_p()
         _ck(lib().IGXVecGetDeviceArray(self.h, C.byref(p)))
         return p.value
+
+    # vector algebra on the device (enqueued on the engine's stream; dot and norm hand a number back and so synchronise)
+    def fill(self, value): _ck(lib().IGXVecSet(self.h, float(value))); return self
+    def copy_from(self, x): _ck(lib().IGXVecCopy(x.h, self.h)); return self
+    def scale(self, a): _ck(lib().IGXVecScale(self.h, float(a))); return self
+    def axpby(self, a, x, b=1.0): _ck(lib().IGXVecAXPBY(self.h, float(a), x.h, float(b))); return self      # self = a x + b self
+    def pointwise_divide(self, x, d): _ck(lib().IGXVecPointwiseDivide(self.h, x.h, d.h)); return self      # self = x ./ d
+
+    def dot(self, y):
+        """over the rows this rank owns; on several ranks the caller adds the parts"""
+        s = C.c_double(0)
+        _ck(lib().IGXVecDot(self.h, y.h, C.byref(s)))
+        return s.value
+
+    def norm(self):
+        s = C.c_double(0)
+        _ck(lib().IGXVecNorm2(self.h, C.byref(s)))
+        return s.value
 
     def indices(self, numbering=0, owned_only=False):
         """Global index of every entry (natural or PETSc numbering), -1 for not-owned rows when owned_only."""
@@ -466,6 +502,22 @@ class IGX:
         lam, U = np.zeros(m.value), np.zeros(m.value * m.value)
         _ck(lib().IGXFastDiagGetAxis(self.h, axis, field, None, None, lam.ctypes.data_as(_dp), U.ctypes.data_as(_dp)))
         return int(first.value), int(m.value), lam, U.reshape(m.value, m.value).T.copy()
+
+    def solve(self, b, x, method="cg", op="matrix", pc="none", rtol=1e-10, atol=0.0, maxit=1000, a=0.0, t=0.0, V=None, U=None, history=False):
+        """IGXSolve: A x = b on the device with A the action `op` names at the state (a, V, t, U), from the guess x holds.  Returns a dict of
+        the info fields (iterations, reason, reason_name, rnorm0, rnorm, bnorm) and, with history=True, |r_k| for k = 0 .. iterations."""
+        code = lambda table, v: table[v] if isinstance(v, str) else int(v)
+        spec = IGXSolveSpec(code(SOLVE_METHODS, method), code(SOLVE_OPERATORS, op), code(SOLVE_PCS, pc), float(a), float(t),
+                            V.h if V is not None else None, U.h if U is not None else None, float(rtol), float(atol), int(maxit))
+        info = IGXSolveInfo()
+        hist = np.zeros(max(int(maxit), 0) + 1) if history else None
+        _ck(lib().IGXSolve(self.h, C.byref(spec), b.h if b is not None else None, x.h if x is not None else None, C.byref(info),
+                           hist.ctypes.data_as(_dp) if history else None))
+        out = dict(iterations=info.iterations, reason=info.reason, reason_name=SOLVE_REASONS.get(info.reason, str(info.reason)),
+                   rnorm0=info.rnorm0, rnorm=info.rnorm, bnorm=info.bnorm)
+        if history:
+            out["history"] = hist[:info.iterations + 1].copy()
+        return out
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))
     def synchronize(self): _ck(lib().IGXSynchronize(self.h))

@@ -74,6 +74,7 @@ struct AxisBufs { DevBuf tab, w, J, pt, off, rowmap, rcnt, P, rcol, prefix, bnd;
 
 struct IgxComm;
 struct RtcForm;
+struct KrylovState;
 // IGXFastDiagSetUp's host result and the device copies IGXFastDiagApply makes of it at its first call
 struct FastDiagState {
   FastDiag h;
@@ -110,6 +111,8 @@ struct _p_IGX {
   std::shared_ptr<RtcForm> rtc; std::string rtc_source, rtc_name;   // run-time compiled user form (rtc.hpp)
   std::shared_ptr<RtcForm> rtc_scalar;                              // ... and the last user functional (IGXComputeScalarSource)
   std::shared_ptr<FastDiagState> fd;                                // fast diagonalisation (IGXFastDiagSetUp; fast_diag.hpp)
+  DevBuf krscal;                                                    // IGXVecDot / IGXSolve: the slabs of partial sums, the record and the device scalars (krylov.hpp)
+  std::shared_ptr<KrylovState> krylov;                              // IGXSolve's work vectors and preconditioner storage, kept between solves
 };
 
 struct _p_IGXMat {
@@ -118,6 +121,14 @@ struct _p_IGXMat {
   DevBuf coo_i, coo_j;     // coordinate lists kept on the device for the hand-back (IGXMatGetCOODevice), or empty
 };
 struct _p_IGXVec { IGX iga; int64_t n; DevBuf a; };
+// IGXSolve keeps its vectors with the IGX (krylov.hpp; IGXSetUp drops them, IGXDestroy frees them)
+struct KrylovState {
+  int method = -1, pc = -1, dof = 0; int64_t n = 0;
+  std::vector<std::unique_ptr<_p_IGXVec>> work, pcv;     // r z p Ap (CG), r rhat p v s t y z (BiCGStab); the diagonal or the dof block columns
+  std::string name;                                      // the last solve's kernel name: while it is the last kernel IGXGetLastTiming reports the solve's own figures
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~KrylovState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
 
 #ifndef IGX_TU_DISPATCH
 extern "C" const char *IGXGetLastError(void) { return g_err.c_str(); }
@@ -184,7 +195,7 @@ extern "C" int IGXAxisSetKnots(IGX g, int i, int m, const double U[]) { AXISCK(g
 static int apply_geometry(IGX g);
 static int apply_property(IGX g);
 extern "C" int IGXSetUp(IGX g) {
-  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; g->fd.reset();
+  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; g->fd.reset(); g->krylov.reset();
   if (rc) return fail(rc, e);
   if (int rp = apply_property(g)) return rp;
   return apply_geometry(g);   // a control net given by IGXRead / an earlier IGXSetGeometry survives re-partitioning
@@ -571,7 +582,7 @@ extern "C" int IGXSetTiming(IGX g, int flag) {
 }
 extern "C" int IGXGetLastTiming(IGX g, double *total_ms, double *kernel_ms, int *launches) {
   NEEDIGA(g);
-  if (g->timing && g->ev[0]) {
+  if (g->timing && g->ev[0] && !(g->krylov && g->krylov->name == g->last_kernel)) {      // (after IGXSolve: the figures the solve stored)
     HIPCK(hipEventSynchronize(g->ev[3]));
     float a = 0, b = 0;
     HIPCK(hipEventElapsedTime(&a, g->ev[0], g->ev[3]));
@@ -1750,4 +1761,284 @@ extern "C" int IGXGetClockProbe(IGX g, double *shader_mhz, int64_t *elements) {
 #include "coo.hpp"
 #include "fileio.hpp"
 #include "rtc.hpp"
+
+// ------------------------------------------------------------------ vector algebra on IGXVec and the Krylov loop (krylov.hpp)
+// (the last thing in the unit: every kernel above is compiled as it was before these existed)
+#include "krylov.hpp"
+// Everything is enqueued on the engine's stream; IGXVecDot / IGXVecNorm2 read their result back and so synchronise.  The sums run over the
+// rows this rank owns (a prefix of the row box on every axis, as in IGXChecksum): on several ranks the caller adds the parts.
+static int kr_scalars(IGX g) {
+  if (g->krscal.p) return 0;
+  if (g->krscal.alloc(KR_SCAL_DOUBLES * sizeof(double))) return fail(IGX_ERR_MEM, "device allocation of the partial-sum slabs failed");
+  HIPCK(hipMemset(g->krscal.p, 0, g->krscal.bytes));
+  return 0;
+}
+static double *kr_slab(IGX g, int k) { return g->krscal.as<double>() + (size_t)k * KR_G; }
+static double *kr_rec(IGX g) { return g->krscal.as<double>() + (size_t)KR_NSLAB * KR_G; }
+static int kr_vec_args(IGXVec a, IGXVec b = nullptr, IGXVec c = nullptr, bool three = false, bool two = false) {
+  if (!a || ((two || three) && !b) || (three && !c)) return fail(IGX_ERR_ARG_WRONG, "null vector");
+  if ((b && b->iga != a->iga) || (c && c->iga != a->iga)) return fail(IGX_ERR_ARG_WRONG, "vectors created by different IGX");
+  if ((b && b->n != a->n) || (c && c->n != a->n)) return fail(IGX_ERR_ARG_WRONG, "vectors of different sizes");
+  return 0;
+}
+#define KR_LAUNCH(kernel, grid, block, g, ...) do { hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (g)->stream, __VA_ARGS__); if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, #kernel ": kernel launch failed"); } while (0)
+extern "C" int IGXVecSet(IGXVec y, double value) {
+  if (int rc = kr_vec_args(y)) return rc;
+  y->iga->slab_valid = 0;
+  KR_LAUNCH(kr_set, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), value, (long long)y->n);
+  return 0;
+}
+extern "C" int IGXVecCopy(IGXVec x, IGXVec y) {
+  if (int rc = kr_vec_args(x, y, nullptr, false, true)) return rc;
+  y->iga->slab_valid = 0;
+  if (x != y) HIPCK(hipMemcpyAsync(y->a.p, x->a.p, x->a.bytes, hipMemcpyDeviceToDevice, y->iga->stream));
+  return 0;
+}
+extern "C" int IGXVecScale(IGXVec y, double a) {
+  if (int rc = kr_vec_args(y)) return rc;
+  y->iga->slab_valid = 0;
+  KR_LAUNCH(kr_scale, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), a, (long long)y->n);
+  return 0;
+}
+extern "C" int IGXVecAXPBY(IGXVec y, double a, IGXVec x, double b) {
+  if (int rc = kr_vec_args(y, x, nullptr, false, true)) return rc;
+  y->iga->slab_valid = 0;
+  KR_LAUNCH(kr_axpby, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), a, x->a.as<double>(), b, (long long)y->n);
+  return 0;
+}
+extern "C" int IGXVecPointwiseDivide(IGXVec z, IGXVec x, IGXVec d) {
+  if (int rc = kr_vec_args(z, x, d, true)) return rc;
+  z->iga->slab_valid = 0;
+  KR_LAUNCH(kr_pdiv, kr_grid(z->n), KR_T, z->iga, z->a.as<double>(), x->a.as<double>(), d->a.as<double>(), (long long)z->n);
+  return 0;
+}
+extern "C" int IGXVecDot(IGXVec x, IGXVec y, double *s) {
+  if (int rc = kr_vec_args(x, y, nullptr, false, true)) return rc;
+  if (!s) return fail(IGX_ERR_ARG_WRONG, "null result");
+  IGX g = x->iga;
+  if (int rc = kr_scalars(g)) return rc;
+  const Space &sp = g->s;
+  int nown[3]; bool all = true;
+  for (int d = 0; d < 3; ++d) {
+    const AxisLayout &L = sp.lay[d]; nown[d] = 0;
+    for (int r = 0; r < L.nrow; ++r) if (L.owned[r]) { if (nown[d] != r) return fail(IGX_ERR_PLIB, "owned rows are not a prefix of the row box"); nown[d]++; }
+    if (nown[d] != L.nrow) all = false;
+  }
+  double *slab = kr_slab(g, KS_USER), *rec = kr_rec(g);
+  if (all) KR_LAUNCH(kr_dot, KR_G, KR_T, g, x->a.as<double>(), y->a.as<double>(), (long long)x->n, slab);
+  else KR_LAUNCH(kr_dot_owned, KR_G, KR_T, g, x->a.as<double>(), y->a.as<double>(), nown[0], nown[1], nown[2], sp.lay[0].nrow, sp.lay[1].nrow, sp.dof, slab);
+  KrSlabs sl; memset(&sl, 0, sizeof(sl)); sl.s[0] = slab; sl.m = 1;
+  KR_LAUNCH(kr_record, 1, 64, g, sl, rec);
+  HIPCK(hipMemcpyAsync(s, rec, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIPCK(hipStreamSynchronize(g->stream));
+  return 0;
+}
+extern "C" int IGXVecNorm2(IGXVec x, double *s) {
+  if (int rc = IGXVecDot(x, x, s)) return rc;
+  *s = std::sqrt(*s);
+  return 0;
+}
+
+// IGXSolve.  The operator is the action driver's internal entry (compute_action) at the state of the specification, the preconditioners
+// are the diagonal drivers' (compute_diagonal, compute_block_diagonal, block_diagonal_run) and IGXFastDiagApply: whatever they refuse the
+// solve refuses, with their reason under its own name.  The loops and their kernels: krylov.hpp.
+static const char *kr_solve_refusal(IGX g) {
+  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return "the Krylov solve needs one rank on every axis: the library has no sum across ranks (IGXVecDot gives each rank's part)";
+  return nullptr;
+}
+static int kr_refused(int rc) { return rc == IGX_ERR_SUP ? fail(rc, "the Krylov solve runs where its operator and its preconditioner run, and " + std::string(g_err)) : rc; }
+static bool kr_bad_host(double d) { return !(std::fabs(d) > 0.0) || !std::isfinite(d); }
+extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSolveInfo *info, double *history) {
+  NEEDIGA(g);
+  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null solve specification");
+  if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown method");
+  if (sp->op < IGX_OP_MATRIX || sp->op > IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown operator");
+  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown preconditioner");
+  if (sp->maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: maxit must not be negative");
+  if (!(sp->rtol >= 0) || !(sp->atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: the tolerances must not be negative");
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXSolve()");
+  if (const char *why = kr_solve_refusal(g)) return fail(IGX_ERR_SUP, why);
+  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  if (!b || !x) return fail(IGX_ERR_ARG_WRONG, "null right-hand side or solution vector");
+  if (b->iga != g || x->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if (x == b) return fail(IGX_ERR_ARG_WRONG, "the solution and the right-hand side must be different vectors");
+  IGXVec U = sp->op == IGX_OP_MATRIX ? nullptr : sp->U, V = sp->op == IGX_OP_IJACOBIAN ? sp->V : nullptr;
+  if (sp->op != IGX_OP_MATRIX && !U) return fail(IGX_ERR_ARG_WRONG, "null state vector");
+  if (sp->op == IGX_OP_IJACOBIAN && !V) return fail(IGX_ERR_ARG_WRONG, "null state vector");
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  if ((U && U == x) || (V && V == x)) return fail(IGX_ERR_ARG_WRONG, "the solution must not be a state vector");
+  if (sp->pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() before IGXSolve() with IGX_PC_FASTDIAG");
+  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string("the Krylov solve runs where its operator and its preconditioner run, and ") + why);
+  if (int rc = ensure_device(g)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  if (b->n != n || x->n != n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  if (int rc = kr_scalars(g)) return rc;
+  const bool cg = sp->method == IGX_SOLVE_CG;
+  const int dof = g->s.dof, pc = sp->pc;
+  const double shift = sp->op == IGX_OP_IJACOBIAN ? sp->a : 0.0, t = sp->op == IGX_OP_IJACOBIAN ? sp->t : 0.0;
+  // work vectors: kept while the method and the preconditioner need the same set
+  if (!g->krylov || g->krylov->method != sp->method || g->krylov->pc != pc || g->krylov->dof != dof || g->krylov->n != n) {
+    g->krylov.reset();
+    std::shared_ptr<KrylovState> st(new KrylovState());
+    auto add = [&](std::vector<std::unique_ptr<_p_IGXVec>> &to) {
+      std::unique_ptr<_p_IGXVec> v(new _p_IGXVec()); v->iga = g; v->n = n;
+      if (v->a.alloc((size_t)n * sizeof(double)) || hipMemset(v->a.p, 0, v->a.bytes) != hipSuccess) return 1;
+      to.push_back(std::move(v)); return 0;
+    };
+    for (int k = 0; k < (cg ? 4 : 8); ++k) if (add(st->work)) return fail(IGX_ERR_MEM, "device allocation of the Krylov work vectors failed");
+    for (int k = 0; k < (pc == IGX_PC_JACOBI ? 1 : pc == IGX_PC_PBJACOBI ? dof : 0); ++k) if (add(st->pcv)) return fail(IGX_ERR_MEM, "device allocation of the preconditioner's vectors failed");
+    st->method = sp->method; st->pc = pc; st->dof = dof; st->n = n;
+    g->krylov = st;
+  }
+  KrylovState &st = *g->krylov;
+  const bool timing = g->timing;
+  if (timing) { for (auto &e : st.ev) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(st.ev[0], g->stream)); }
+  int launches = 0; double op_ms = 0; std::string opname;
+  auto account = [&](int own) -> int {      // after a driver's entry (own = 0: its launches and, timed, its kernel time) or own launches of this loop
+    if (own) { launches += own; return 0; }
+    launches += g->last_launches;
+    if (timing) { float ms = 0; HIPCK(hipEventSynchronize(g->ev[2])); HIPCK(hipEventElapsedTime(&ms, g->ev[1], g->ev[2])); op_ms += ms; }
+    return 0;
+  };
+  const int actop = sp->op == IGX_OP_MATRIX ? OP_MATRIX_ACTION : sp->op == IGX_OP_JACOBIAN ? OP_JACOBIAN_ACTION : OP_IJACOBIAN_ACTION;
+  auto A = [&](IGXVec in, IGXVec out) -> int {
+    if (int rc = compute_action(g, actop, U, V, in, out, shift, t)) return kr_refused(rc);
+    if (opname.empty()) opname = g->last_kernel;
+    return account(0);
+  };
+  std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
+  if (pc == IGX_PC_JACOBI) {
+    const int dop = sp->op == IGX_OP_MATRIX ? OP_MATRIX_DIAGONAL : sp->op == IGX_OP_JACOBIAN ? OP_JACOBIAN_DIAGONAL : OP_IJACOBIAN_DIAGONAL;
+    if (int rc = compute_diagonal(g, dop, U, V, cols[0], shift, t)) return kr_refused(rc);
+    if (int rc = account(0)) return rc;
+  } else if (pc == IGX_PC_PBJACOBI) {
+    const int bop = sp->op == IGX_OP_MATRIX ? OP_MATRIX_BLOCK_DIAGONAL : sp->op == IGX_OP_JACOBIAN ? OP_JACOBIAN_BLOCK_DIAGONAL : OP_IJACOBIAN_BLOCK_DIAGONAL;
+    if (int rc = compute_block_diagonal(g, bop, U, V, dof, cols.data(), shift, t)) return kr_refused(rc);
+    if (int rc = account(0)) return rc;
+    if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return kr_refused(rc);
+    if (int rc = account(0)) return rc;
+  }
+  // out = M^-1 in (IGX_PC_NONE: the caller aliases the two)
+  auto M = [&](IGXVec in, IGXVec out) -> int {
+    if (pc == IGX_PC_NONE) return 0;
+    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); return account(1); }
+    if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return kr_refused(rc);
+    return account(0);
+  };
+  double rec[KR_NREC];
+  double *drec = kr_rec(g), *dsc = drec + KR_NREC;
+  auto read_record = [&](int m) -> int { HIPCK(hipMemcpyAsync(rec, drec, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->stream)); HIPCK(hipStreamSynchronize(g->stream)); return 0; };
+  auto record = [&](std::initializer_list<int> slabs) -> int {
+    KrSlabs sl; memset(&sl, 0, sizeof(sl));
+    for (int k : slabs) sl.s[sl.m++] = kr_slab(g, k);
+    KR_LAUNCH(kr_record, 1, 64, g, sl, drec);
+    if (int rc = account(1)) return rc;
+    return read_record(sl.m);
+  };
+  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
+  double *xd = x->a.as<double>(); const double *bd = b->a.as<double>();
+  g->slab_valid = 0;
+  int its = 0, reason = 0;
+  double bnorm = 0, rnorm = 0, rnorm0 = 0, thr = 0;
+  // r = b - A x with |r| and |b|, shared by both methods: the product goes to work vector 3 (Ap / v), r is work vector 0
+  if (int rc = A(x, st.work[3].get())) return rc;
+  KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), bd, D(3), n, kr_slab(g, KS_RR), kr_slab(g, KS_BB));
+  account(1);
+  auto stop = [&]() {      // the test of the recurrence residual, 0 to go on
+    if (std::isnan(rnorm)) return (int)IGX_DIVERGED_NAN;
+    if (rnorm <= thr) return (int)(rnorm <= sp->rtol * bnorm ? IGX_CONVERGED_RTOL : IGX_CONVERGED_ATOL);
+    if (its >= sp->maxit) return (int)IGX_DIVERGED_ITS;
+    return 0;
+  };
+  auto start = [&]() -> bool {      // after the first record (rec[0] = r.r, rec[1] = b.b): true when the loop has something to do
+    bnorm = std::sqrt(rec[1]); rnorm0 = rnorm = std::sqrt(rec[0]); thr = std::max(sp->rtol * bnorm, sp->atol);
+    if (history) history[0] = rnorm;
+    if (std::isnan(bnorm)) { reason = IGX_DIVERGED_NAN; return false; }
+    if (bnorm == 0.0) { reason = IGX_CONVERGED_ATOL; return false; }
+    return true;
+  };
+  if (cg) {
+    IGXVec r = st.work[0].get(), z = pc == IGX_PC_NONE ? r : st.work[1].get(), p = st.work[2].get(), Ap = st.work[3].get();
+    int cur = 0;      // KS_A + cur holds the newest r.z, KS_A + 1 - cur the one before; KS_C holds p.Ap
+    auto precondition = [&](int slab) -> int {
+      if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, z->a.as<double>(), r->a.as<double>(), cols[0]->a.as<double>(), n, kr_slab(g, slab)); return account(1); }
+      if (int rc = M(r, z)) return rc;
+      KR_LAUNCH(kr_dot, KR_G, KR_T, g, r->a.as<double>(), z->a.as<double>(), n, kr_slab(g, slab));
+      return account(1);
+    };
+    if (int rc = precondition(KS_A)) return rc;
+    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
+    double rz = rec[2];
+    if (start()) {
+      HIPCK(hipMemcpyAsync(p->a.p, z->a.p, z->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+      while (!(reason = stop())) {
+        if (kr_bad_host(rz)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
+        if (its > 0) { KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, p->a.as<double>(), z->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_A + 1 - cur)); account(1); }
+        if (int rc = A(p, Ap)) return rc;
+        KR_LAUNCH(kr_dot, KR_G, KR_T, g, p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C));
+        KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C), kr_slab(g, KS_A + cur), kr_slab(g, KS_RR));
+        account(2);
+        cur ^= 1;
+        if (int rc = precondition(KS_A + cur)) return rc;
+        if (int rc = record({KS_RR, KS_C, KS_A + cur})) return rc;
+        if (!(rec[1] > 0.0) || !std::isfinite(rec[1])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // p.Ap <= 0: the update kernel left x and r alone
+        ++its; rnorm = std::sqrt(rec[0]); rz = rec[2];
+        if (history) history[its] = rnorm;
+      }
+    }
+  } else {
+    IGXVec r = st.work[0].get(), rhat = st.work[1].get(), p = st.work[2].get(), v = st.work[3].get(), s = st.work[4].get(), tv = st.work[5].get();
+    IGXVec y = pc == IGX_PC_NONE ? p : st.work[6].get(), z = pc == IGX_PC_NONE ? s : st.work[7].get();
+    int cur = 0;      // KS_A + cur holds rho' = rhat.r of the iteration at hand; KS_C rhat.v, KS_D t.s, KS_E t.t
+    static const double one3[3] = {1.0, 1.0, 1.0};
+    HIPCK(hipMemcpyAsync(rhat->a.p, r->a.p, r->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+    KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), r->a.as<double>(), n, kr_slab(g, KS_A));
+    account(1);
+    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
+    double rho_next = rec[2], omega = 1.0;
+    if (start()) {
+      HIPCK(hipMemsetAsync(v->a.p, 0, v->a.bytes, g->stream));
+      HIPCK(hipMemsetAsync(p->a.p, 0, p->a.bytes, g->stream));
+      HIPCK(hipMemcpyAsync(dsc, one3, sizeof(one3), hipMemcpyHostToDevice, g->stream));
+      while (!(reason = stop())) {
+        if (kr_bad_host(rho_next) || kr_bad_host(omega)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
+        KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), dsc);
+        account(1);
+        if (int rc = M(p, y)) return rc;
+        if (int rc = A(y, v)) return rc;
+        KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_C));
+        KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_C));
+        account(2);
+        if (int rc = M(s, z)) return rc;
+        if (int rc = A(z, tv)) return rc;
+        KR_LAUNCH(kr_dot2, KR_G, KR_T, g, tv->a.as<double>(), s->a.as<double>(), n, kr_slab(g, KS_D), kr_slab(g, KS_E));
+        KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(), n,
+                  kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_RR), kr_slab(g, KS_A + 1 - cur));
+        KR_LAUNCH(kr_bicg_record, 1, 64, g, kr_slab(g, KS_RR), kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_A + 1 - cur), drec, dsc);
+        account(3);
+        if (int rc = read_record(7)) return rc;
+        cur ^= 1;
+        if (kr_bad_host(rec[1]) || kr_bad_host(rec[2])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // rhat.v or t.t: the update kernel left x and r alone
+        ++its; rnorm = std::sqrt(rec[0]); rho_next = rec[4]; omega = rec[6];
+        if (history) history[its] = rnorm;
+      }
+    }
+  }
+  if (reason == IGX_CONVERGED_ATOL && bnorm == 0.0) {      // b = 0: the solution is 0
+    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, xd, 0.0, n);
+    account(1);
+    rnorm0 = rnorm = 0.0; if (history) history[0] = 0.0;
+    HIPCK(hipStreamSynchronize(g->stream));
+  }
+  static const char *const methods[2] = {"cg", "bicgstab"}, *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
+  st.name = std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)";
+  g->last_kernel = st.name; g->last_launches = launches;
+  if (timing) {
+    float ms = 0;
+    HIPCK(hipEventRecord(st.ev[1], g->stream)); HIPCK(hipEventSynchronize(st.ev[1])); HIPCK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
+    g->last_total_ms = ms; g->last_kernel_ms = op_ms;
+  }
+  if (info) { info->iterations = its; info->reason = reason; info->rnorm0 = rnorm0; info->rnorm = rnorm; info->bnorm = bnorm; }
+  return 0;
+}
 #endif   // !IGX_TU_DISPATCH
