@@ -2,6 +2,8 @@
 krylov.hpp: preconditioned CG -- the loop of pcg() in tests/fast_diag_ref.py with an initial guess, atol, a history and the outcomes -- and
 right-preconditioned BiCGStab in the order DESIGN.md 3.12 states (one test of |r| per iteration, no half-step exit).  `dot` is the inner product the loop uses: np.dot, or another summation
 order to see what rounding alone moves.  Both return (x, info) with info = dict(iterations, reason, rnorm0, rnorm, bnorm, history)."""
+import math
+
 import numpy as np
 
 from fast_diag_ref import pcg      # noqa: F401  (the loop cg() restates; tests/test_krylov_abi.py holds the two against each other)
@@ -27,6 +29,33 @@ def _info(its, reason, hist, bnorm):
     return dict(iterations=its, reason=reason, rnorm0=hist[0], rnorm=hist[-1], bnorm=bnorm, history=np.array(hist))
 
 
+U_ROUND = 2.0 ** -53
+
+
+def exact_dot(x, y):
+    """the correctly rounded value of sum x_i y_i and sum |x_i y_i|: every product as rounded value + rounding error (Veltkamp / Dekker)"""
+    def split(a):
+        c = 134217729.0 * a
+        hi = c - (c - a)
+        return hi, a - hi
+    p = x * y
+    xh, xl = split(x)
+    yh, yl = split(y)
+    e = ((xh * yh - p) + xh * yl + xl * yh) + xl * yl
+    return math.fsum(np.concatenate([p, e])), math.fsum(np.abs(p))
+
+
+def gamma(n):
+    """gamma_n = n u / (1 - n u): the bound of a sum of n terms in any order"""
+    return n * U_ROUND / (1.0 - n * U_ROUND)
+
+
+def norm_bound(n, root):
+    """|s - sqrt(exact)| of a computed 2-norm of length n: gamma_n on the sum of squares through the square root, one rounding for the
+    library's sqrt and one for the reference's (the bound of tests/test_gpu_vec_algebra.py)"""
+    return (gamma(n) / 2 + gamma(n) ** 2 + 2 * U_ROUND) * root
+
+
 def dot_reversed(a, b):
     """the same products added from the far end, one by one in chunks: another summation order than np.dot's"""
     return float(np.sum((a * b)[::-1].reshape(-1)))
@@ -36,6 +65,47 @@ def dot_pairwise_chunks(a, b, chunk=37):
     """partial sums over chunks of 37 added in order: the shape of a slab reduction"""
     q = a * b
     return float(sum(float(np.sum(q[i:i + chunk])) for i in range(0, q.size, chunk)))
+
+
+ORDERS = (("np.dot", np.dot), ("from the far end", dot_reversed), ("chunks", dot_pairwise_chunks))
+
+
+def count_window(counts):
+    """(lo, hi, m) of a loop's iteration counts in several summation orders: rounding alone moves the count between lo and hi, so another
+    order is held to [lo - m, hi + m] with m = max(1, hi - lo)"""
+    lo, hi = min(counts), max(counts)
+    return lo, hi, max(1, hi - lo)
+
+
+def head_deviation(hist, ref, first=1, last=5):
+    """the largest relative deviation of entries first .. last of a history from the reference's (over the entries both have)"""
+    m = min(len(hist), len(ref), last + 1)
+    if m <= first:
+        return 0.0
+    h, r = np.asarray(hist[first:m]), np.asarray(ref[first:m])
+    return float((np.abs(h - r) / np.abs(r)).max())
+
+
+def corner_dofs(nodes, dof=1):
+    """the dofs of the eight corner nodes of a box of nodes[0] x nodes[1] x nodes[2] nodes, axis 0 fastest, dof entries per node"""
+    n0, n1, n2 = nodes
+    at = [i + n0 * (j + n1 * k) for k in (0, n2 - 1) for j in (0, n1 - 1) for i in (0, n0 - 1)]
+    return np.array([a * dof + f for a in at for f in range(dof)])
+
+
+ALL6 = [(d, s) for d in range(3) for s in range(2)]
+# the problems of tests/test_gpu_krylov_lengths.py that tests/test_krylov_abi.py also runs on the oracle's matrix:
+# n -> (form, dof, p, N, Dirichlet values (axis, side, field, value)); identity geometry
+SMALL_LENGTHS = {
+    175: ("poisson", 1, 2, (5, 3, 3), [(d, s, 0, 0.0) for d, s in ALL6]),
+    1025: ("poisson", 1, 2, (3, 3, 39), [(d, s, 0, 0.0) for d, s in ALL6]),
+    1029: ("elasticity", 3, 2, (5, 5, 5), [(0, 0, 0, 0.0), (0, 0, 1, 0.0), (0, 0, 2, 0.0), (0, 1, 0, 0.0)]),
+}
+
+
+def x_true(n):
+    """the fixed random solution of the length: b is the operator's action on it"""
+    return np.random.default_rng(n).standard_normal(n)
 
 
 def cg(op, prec, b, x0=None, rtol=1e-10, atol=0.0, maxit=None, dot=np.dot):

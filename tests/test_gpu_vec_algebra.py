@@ -16,9 +16,12 @@ import math
 import numpy as np
 import pytest
 
+from krylov_ref import U_ROUND
+from krylov_ref import exact_dot as _exact_dot
+from krylov_ref import gamma as _gamma
+
 pytestmark = pytest.mark.gpu
 
-U_ROUND = 2.0 ** -53
 # name -> (dof, p, N)
 LENGTHS = {"8": (1, 1, (1, 1, 1)), "45": (1, 1, (2, 2, 4)), "135": (3, 2, (1, 1, 3)), "592704": (8, 2, (40, 40, 40))}
 
@@ -44,23 +47,6 @@ def _data(name):
     for a in (x, y, d):
         a.setflags(write=False)
     return x, y, d
-
-
-def _exact_dot(x, y):
-    """the correctly rounded value of sum x_i y_i and sum |x_i y_i|: every product as rounded value + rounding error (Veltkamp / Dekker)"""
-    def split(a):
-        c = 134217729.0 * a
-        hi = c - (c - a)
-        return hi, a - hi
-    p = x * y
-    xh, xl = split(x)
-    yh, yl = split(y)
-    e = ((xh * yh - p) + xh * yl + xl * yh) + xl * yl
-    return math.fsum(np.concatenate([p, e])), math.fsum(np.abs(p))
-
-
-def _gamma(n):
-    return n * U_ROUND / (1.0 - n * U_ROUND)
 
 
 @pytest.mark.parametrize("name", sorted(LENGTHS, key=int))

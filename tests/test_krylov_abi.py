@@ -1,7 +1,8 @@
 """The vector algebra on IGXVec and IGXSolve in the C ABI (include/petiga_amd.h) and its Python view: the eight calls are declared, exported and
 bound with the header's argument counts; the two structs have the header's layout; the refusals that are decided before any HIP call, each
 by code and word; and the two reference loops of tests/krylov_ref.py against scipy's sparse direct solve on a small SPD and a small
-nonsymmetric matrix built here (and cg() against pcg(), bit for bit)."""
+nonsymmetric matrix built here (and cg() against pcg(), bit for bit); and, on the oracle's matrices, what tests/test_gpu_krylov_lengths.py
+leans on: the count rule between the summation orders and the two corner-supported outcomes."""
 import ctypes as C
 import os
 import re
@@ -221,3 +222,69 @@ def test_summation_order_moves_the_cg_count_by_one_at_the_most(p, N):
         counts = [K.cg(lambda v: A @ v, prec, b, rtol=1e-10, dot=dot)[1]["iterations"] for dot in (np.dot, K.dot_reversed, K.dot_pairwise_chunks)]
         print("p = %d %s, pc %s: iterations %s" % (p, N, label, counts))
         assert max(counts) - min(counts) <= 1
+
+
+# ---- the references of tests/test_gpu_krylov_lengths.py, on the oracle's matrices
+def _length_problem(n):
+    """(A, {pc: M^-1}) of a problem of krylov_ref.SMALL_LENGTHS from the oracle's matrix, with numpy's preconditioners"""
+    import oracle_api as O
+    from common import make_pair
+    from fast_diag_ref import FastDiagRef, axis_matrices, fixed_faces
+    form, dof, p, N, bcs = K.SMALL_LENGTHS[n]
+    orc, _ = make_pair(3, dof, p, list(N), engine=False)
+    for bc in bcs:
+        orc.set_boundary_value(*bc)
+    if form == "poisson":
+        A = orc.compute_system("orc_form_poisson")[0].scipy().tocsr()
+    else:
+        from test_gpu_matrix_action import EL
+        A = orc.compute_system("orc_form_elasticity", O.ElasticityCtx(*EL))[0].scipy().tocsr()
+    assert A.shape[0] == n
+    D = A.diagonal()
+    precs = {"none": lambda v: v.copy(), "jacobi": lambda v: v / D}
+    if n == 1025:
+        fd = FastDiagRef([axis_matrices(orc.axis(d)["U"], orc.axis(d)["p"]) for d in range(3)], 1, fixed_faces(1, [bc[:3] for bc in bcs]), 0.0, [1.0, 1.0, 1.0])
+        precs["fastdiag"] = fd.apply
+    if dof > 1:
+        dense = A.toarray().reshape(n // dof, dof, n // dof, dof)
+        inv = np.linalg.inv(np.stack([dense[i, :, i, :] for i in range(n // dof)]))
+        precs["pbjacobi"] = lambda v: np.einsum("nij,nj->ni", inv, v.reshape(-1, dof)).reshape(-1)
+    return A, precs
+
+
+@pytest.mark.parametrize("n", sorted(K.SMALL_LENGTHS))
+def test_count_rule_holds_between_the_host_orders(n):
+    """The device count is held to [lo - m, hi + m], m = max(1, hi - lo), over the host loop in three summation orders: here each order is
+    held to the window of the other two, on b = A x_true as the GPU cases form it."""
+    A, precs = _length_problem(n)
+    b = A @ K.x_true(n)
+    for pc in sorted(precs):
+        counts = []
+        for _, dot in K.ORDERS:
+            x, info = K.cg(lambda v: A @ v, precs[pc], b, rtol=1e-10, maxit=600, dot=dot)
+            assert info["reason"] == K.CONVERGED_RTOL
+            assert np.abs(x - K.x_true(n)).max() <= 1e-7 * np.abs(K.x_true(n)).max()
+            counts.append(info["iterations"])
+        print("n = %d, pc %s: iterations %s" % (n, pc, counts))
+        for i, k in enumerate(counts):
+            lo, hi, m = K.count_window(counts[:i] + counts[i + 1:])
+            assert lo - m <= k <= hi + m, (pc, counts)
+
+
+def test_corner_supported_outcomes_of_the_host_loops():
+    """b on the eight corner dofs of the all-Dirichlet box (a corner node lies in one element: its row and column are the identity's, so
+    A b = b exactly): CG without a preconditioner is exact after one step; BiCGStab from x0 = c b has s = 0, t = 0, t.t = 0 and breaks down
+    at iteration 0 with x untouched."""
+    n = 175
+    A, precs = _length_problem(n)
+    form, dof, p, N, _ = K.SMALL_LENGTHS[n]
+    b = np.zeros(n)
+    b[K.corner_dofs([N[d] + p for d in range(3)])] = np.random.default_rng(8).standard_normal(8)
+    assert np.count_nonzero(b) == 8 and np.array_equal(A @ b, b)
+    op = lambda v: A @ v
+    for _, dot in K.ORDERS:
+        x, info = K.cg(op, precs["none"], b, rtol=1e-10, dot=dot)
+        assert info["reason"] == K.CONVERGED_RTOL and info["iterations"] == 1 and info["rnorm"] == 0.0 and np.array_equal(x, b)
+        x0 = 0.375 * b
+        x, info = K.bicgstab(op, precs["none"], b, x0=x0, rtol=1e-9, dot=dot)
+        assert info["reason"] == K.DIVERGED_BREAKDOWN and info["iterations"] == 0 and info["history"].size == 1 and np.array_equal(x, x0)
