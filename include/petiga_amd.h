@@ -434,6 +434,61 @@ typedef struct { int method, op, pc; double a, t; IGXVec V, U; double rtol, atol
 typedef struct { int iterations, reason; double rnorm0, rnorm, bnorm; } IGXSolveInfo;
 int IGXSolve(IGX iga,const IGXSolveSpec *spec,IGXVec b,IGXVec x,IGXSolveInfo *info,double *history /* NULL or [maxit+1]: |r_k|_2 */);
 
+/* The Newton loop on the matrix-free operators, resident on the device: G(x) = 0 from the guess x holds on entry, for the nonlinear forms
+ * (Bratu, Cahn-Hilliard, NS-VMS, Bratu as IFunction).  op = IGX_OP_JACOBIAN: G(U) = IGXComputeFunction(U), dG/dU the Jacobian at U.
+ * op = IGX_OP_IJACOBIAN: G(U) = IGXComputeIFunction(a, a U + W, t, U), dG/dU = IGXComputeIJacobian(a, a U + W, t, U) -- with a = 1/dt and
+ * W = -U_n/dt one call is a backward-Euler step, with other constants a generalized-alpha stage.  The residual goes through the entry
+ * IGXComputeFunction / IGXComputeIFunction take, the linear solve is IGXSolve (method, pc, lin_atol, lin_maxit are its; its rtol is eta).
+ * It is the native loop of a caller without PETSc, not a SNES adapter.  |.| is the 2-norm.
+ * Start.  F = G(x), f = |F|, history[0] = f.  In this order: f is NaN: IGX_NEWTON_DIVERGED_FNORM_NAN; f <= atol:
+ *   IGX_NEWTON_CONVERGED_FNORM_ABS with 0 iterations and x untouched bit for bit; maxit == 0: IGX_NEWTON_DIVERGED_MAX_IT.
+ * Iteration k, the linear solve.  eta = lin_rtol under IGX_FORCING_CONSTANT.  Under IGX_FORCING_EW2 (Eisenstat-Walker, choice 2):
+ *   eta_0 = lin_rtol, eta_k = 0.9 (f_k / f_{k-1})^2; if 0.9 eta_{k-1}^2 > 0.1, eta_k is not below that value; eta_k is at most 0.9.
+ *   d = 0 (IGXVecSet's kernel); IGXSolve on J(x) d = F with rtol = eta, atol = lin_atol, maxit = lin_maxit at the state U = x and, for
+ *   IGX_OP_IJACOBIAN, V = a x + W.  IGX_DIVERGED_BREAKDOWN or IGX_DIVERGED_NAN of that solve: IGX_NEWTON_DIVERGED_LINEAR_SOLVE, x stays the
+ *   current iterate.  IGX_DIVERGED_ITS is an inexact step and is used as it is.
+ * Iteration k, the line search.  lambda = 1.  Trial: x_t = x - lambda d, F_t = G(x_t), f_t = |F_t|.  IGX_LINESEARCH_BASIC accepts the first
+ *   trial unless f_t is NaN: that gives IGX_NEWTON_DIVERGED_FNORM_NAN with x restored to the last accepted iterate bit for bit.
+ *   IGX_LINESEARCH_BT accepts when f_t <= (1 - 1e-4 lambda) f (a non-finite f_t is not accepted); otherwise lambda /= 2, at most
+ *   max_backtracks times; when the halvings are exhausted: IGX_NEWTON_DIVERGED_LINE_SEARCH with x restored bit for bit.
+ * After an accepted trial.  snorm = lambda |d|, xnorm = |x|; the accepted F_t is the next F (no second evaluation); ++iterations,
+ *   history[k+1] = f.  In this order: f is NaN: IGX_NEWTON_DIVERGED_FNORM_NAN; f <= atol: IGX_NEWTON_CONVERGED_FNORM_ABS; f <= rtol fnorm0:
+ *   IGX_NEWTON_CONVERGED_FNORM_RELATIVE; snorm <= stol xnorm: IGX_NEWTON_CONVERGED_SNORM_RELATIVE; iterations >= maxit:
+ *   IGX_NEWTON_DIVERGED_MAX_IT.
+ * A solve that does not converge RETURNS 0: info->reason says why.  A call that returns an error code (a refusal passed on by the residual
+ * or by IGXSolve in the middle of the loop) leaves x the last accepted iterate too.  info: linear_iterations is the sum over the inner solves (linear_its,
+ * NULL or maxit ints, receives each), last_linear_reason the last one's IGXSolveReason, backtracks the halvings over the whole call,
+ * function_evaluations every G formed: 1 + iterations + backtracks, and one more where the call ends on a trial that was not accepted.
+ * Between two operator calls a trial is one sweep (newton.hpp): it saves the accepted iterate, forms x - lambda d in place
+ * and V = a x + W (the rounded product plus W, never contracted) and emits the partial sums of d.d and x.x; the host reads one record of
+ * three sums per function evaluation.  No atomics: bitwise repeatable.  Work vectors (F, F_t, d, the saved iterate, V) are kept with the
+ * IGX like IGXSolve's; IGXSetUp drops them, IGXDestroy frees them.  IGXSetTiming / IGXGetLastTiming cover the whole call (total time, the
+ * operators' kernel time summed over residuals and inner solves, launches); IGXGetKernelName gives
+ * "newton(<basic|bt>, <the last inner solve's krylov(...) name>, <k> iterations)".
+ * Refusals, decided before the first HIP call as in IGXSolve.  IGX_ERR_ARG_WRONG: a null spec or x, a foreign or wrong-sized vector, W
+ * missing or W == x for IGX_OP_IJACOBIAN.  IGX_ERR_ARG_OUTOFRANGE: op == IGX_OP_MATRIX, an unknown op, method, pc, linesearch or forcing, a
+ * negative or NaN tolerance, a negative maxit, lin_maxit or max_backtracks.  IGX_ERR_ORDER: before IGXSetUp; IGX_PC_FASTDIAG without
+ * IGXFastDiagSetUp.  IGX_ERR_ARG_WRONGSTATE: no form set.  IGX_ERR_SUP with a reason that names the Newton solve: more than one rank on an
+ * axis; whatever IGXSolve, the action or the vector driver refuse is passed on with their reason. */
+typedef enum { IGX_NEWTON_CONVERGED_FNORM_ABS = 2, IGX_NEWTON_CONVERGED_FNORM_RELATIVE = 3, IGX_NEWTON_CONVERGED_SNORM_RELATIVE = 4,
+               IGX_NEWTON_DIVERGED_LINEAR_SOLVE = -3, IGX_NEWTON_DIVERGED_FNORM_NAN = -4,
+               IGX_NEWTON_DIVERGED_MAX_IT = -5, IGX_NEWTON_DIVERGED_LINE_SEARCH = -6 } IGXNewtonReason;   /* SNESConvergedReason's numbers */
+typedef enum { IGX_LINESEARCH_BASIC = 0, IGX_LINESEARCH_BT = 1 } IGXNewtonLineSearch;
+typedef enum { IGX_FORCING_CONSTANT = 0, IGX_FORCING_EW2 = 1 } IGXNewtonForcing;
+typedef struct {
+  int op;                       /* IGX_OP_JACOBIAN or IGX_OP_IJACOBIAN (IGX_OP_MATRIX: IGX_ERR_ARG_OUTOFRANGE) */
+  double a, t; IGXVec W;        /* IJACOBIAN only: G(U) = IFunction(a, a U + W, t, U); dG/dU is IJacobian(a, a U + W, t, U) */
+  int method, pc;               /* of the inner IGXSolve */
+  double lin_rtol, lin_atol; int lin_maxit;
+  int forcing;
+  double rtol, atol, stol; int maxit;
+  int linesearch, max_backtracks;
+} IGXNewtonSpec;
+typedef struct { int iterations, reason, linear_iterations, function_evaluations, backtracks, last_linear_reason;
+                 double fnorm0, fnorm, snorm, xnorm; } IGXNewtonInfo;
+int IGXSolveNonlinear(IGX iga,const IGXNewtonSpec *spec,IGXVec x,IGXNewtonInfo *info,
+                      double *history /* NULL or [maxit+1]: |F_k|_2 */,int *linear_its /* NULL or [maxit] */);
+
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
  * ranks, and U must hold the ghost rows' values).  The point callbacks are the ones the reference's tests use:

@@ -47,10 +47,25 @@ class IGXSolveInfo(C.Structure):
     _fields_ = [("iterations", C.c_int), ("reason", C.c_int), ("rnorm0", C.c_double), ("rnorm", C.c_double), ("bnorm", C.c_double)]
 
 
+class IGXNewtonSpec(C.Structure):
+    _fields_ = [("op", C.c_int), ("a", C.c_double), ("t", C.c_double), ("W", C.c_void_p), ("method", C.c_int), ("pc", C.c_int),
+                ("lin_rtol", C.c_double), ("lin_atol", C.c_double), ("lin_maxit", C.c_int), ("forcing", C.c_int),
+                ("rtol", C.c_double), ("atol", C.c_double), ("stol", C.c_double), ("maxit", C.c_int), ("linesearch", C.c_int), ("max_backtracks", C.c_int)]
+
+
+class IGXNewtonInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("reason", C.c_int), ("linear_iterations", C.c_int), ("function_evaluations", C.c_int), ("backtracks", C.c_int),
+                ("last_linear_reason", C.c_int), ("fnorm0", C.c_double), ("fnorm", C.c_double), ("snorm", C.c_double), ("xnorm", C.c_double)]
+
+
 SOLVE_METHODS = dict(cg=0, bicgstab=1)
 SOLVE_OPERATORS = dict(matrix=0, jacobian=1, ijacobian=2)
 SOLVE_PCS = dict(none=0, jacobi=1, pbjacobi=2, fastdiag=3)
 SOLVE_REASONS = {1: "converged_rtol", 2: "converged_atol", -1: "diverged_its", -2: "diverged_breakdown", -3: "diverged_nan"}
+NEWTON_LINESEARCHES = dict(basic=0, bt=1)
+NEWTON_FORCINGS = dict(constant=0, ew2=1)
+NEWTON_REASONS = {2: "converged_fnorm_abs", 3: "converged_fnorm_relative", 4: "converged_snorm_relative", -3: "diverged_linear_solve", -4: "diverged_fnorm_nan",
+                  -5: "diverged_max_it", -6: "diverged_line_search", 0: "iterating"}
 
 
 # IGXTransportFn (include/petiga_amd.h): the host-callback transport of the ghost-row exchange
@@ -121,6 +136,7 @@ def lib(build_if_needed=False):
         "IGXVecSet": [V, C.c_double], "IGXVecCopy": [V, V], "IGXVecScale": [V, C.c_double], "IGXVecAXPBY": [V, C.c_double, V, C.c_double],
         "IGXVecPointwiseDivide": [V, V, V], "IGXVecDot": [V, V, _dp], "IGXVecNorm2": [V, _dp],
         "IGXSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
+        "IGXSolveNonlinear": [V, C.POINTER(IGXNewtonSpec), V, C.POINTER(IGXNewtonInfo), _dp, _ip],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -517,6 +533,25 @@ class IGX:
                    rnorm0=info.rnorm0, rnorm=info.rnorm, bnorm=info.bnorm)
         if history:
             out["history"] = hist[:info.iterations + 1].copy()
+        return out
+
+    def solve_nonlinear(self, x, op="jacobian", W=None, a=0.0, t=0.0, method="bicgstab", pc="none", lin_rtol=1e-5, lin_atol=0.0, lin_maxit=1000,
+                        forcing="constant", rtol=1e-8, atol=0.0, stol=0.0, maxit=50, linesearch="basic", max_backtracks=10):
+        """IGXSolveNonlinear: Newton's method on G(x) = 0 on the device from the guess x holds, G the residual `op` names -- "jacobian":
+        compute_function(x); "ijacobian": compute_ifunction(a, a x + W, t, x) -- with solve() as the linear solve.  Returns a dict of the
+        info fields (iterations, reason, reason_name, linear_iterations, function_evaluations, backtracks, last_linear_reason, fnorm0, fnorm,
+        snorm, xnorm), history (|F_k| for k = 0 .. iterations) and linear_its (the inner iterations of each step)."""
+        code = lambda table, v: table[v] if isinstance(v, str) else int(v)
+        spec = IGXNewtonSpec(code(SOLVE_OPERATORS, op), float(a), float(t), W.h if W is not None else None, code(SOLVE_METHODS, method), code(SOLVE_PCS, pc),
+                             float(lin_rtol), float(lin_atol), int(lin_maxit), code(NEWTON_FORCINGS, forcing), float(rtol), float(atol), float(stol), int(maxit),
+                             code(NEWTON_LINESEARCHES, linesearch), int(max_backtracks))
+        info = IGXNewtonInfo()
+        hist, lin = np.zeros(max(int(maxit), 0) + 1), np.full(max(int(maxit), 1), -1, dtype=np.int32)
+        _ck(lib().IGXSolveNonlinear(self.h, C.byref(spec), x.h if x is not None else None, C.byref(info), hist.ctypes.data_as(_dp), lin.ctypes.data_as(_ip)))
+        out = {k: getattr(info, k) for k, _ in IGXNewtonInfo._fields_}
+        out["reason_name"] = NEWTON_REASONS.get(info.reason, str(info.reason))
+        out["history"] = hist[:info.iterations + 1].copy()
+        out["linear_its"] = lin[lin >= 0].astype(int)      # one per inner solve: a step that ends the call in its line search or its solve has one too
         return out
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))

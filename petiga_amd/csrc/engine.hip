@@ -75,6 +75,7 @@ struct AxisBufs { DevBuf tab, w, J, pt, off, rowmap, rcnt, P, rcol, prefix, bnd;
 struct IgxComm;
 struct RtcForm;
 struct KrylovState;
+struct NewtonState;
 // IGXFastDiagSetUp's host result and the device copies IGXFastDiagApply makes of it at its first call
 struct FastDiagState {
   FastDiag h;
@@ -113,6 +114,7 @@ struct _p_IGX {
   std::shared_ptr<FastDiagState> fd;                                // fast diagonalisation (IGXFastDiagSetUp; fast_diag.hpp)
   DevBuf krscal;                                                    // IGXVecDot / IGXSolve: the slabs of partial sums, the record and the device scalars (krylov.hpp)
   std::shared_ptr<KrylovState> krylov;                              // IGXSolve's work vectors and preconditioner storage, kept between solves
+  std::shared_ptr<NewtonState> newton;                              // IGXSolveNonlinear's work vectors, kept between solves
 };
 
 struct _p_IGXMat {
@@ -128,6 +130,14 @@ struct KrylovState {
   std::string name;                                      // the last solve's kernel name: while it is the last kernel IGXGetLastTiming reports the solve's own figures
   hipEvent_t ev[2] = {nullptr, nullptr};
   ~KrylovState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+// ... and so does IGXSolveNonlinear (newton.hpp)
+struct NewtonState {
+  int64_t n = 0; bool has_v = false;
+  std::vector<std::unique_ptr<_p_IGXVec>> work;          // F F_t d xs, and V for an IFunction
+  std::string name;                                      // the last solve's kernel name (IGXGetLastTiming, as for KrylovState)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~NewtonState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 #ifndef IGX_TU_DISPATCH
@@ -195,7 +205,7 @@ extern "C" int IGXAxisSetKnots(IGX g, int i, int m, const double U[]) { AXISCK(g
 static int apply_geometry(IGX g);
 static int apply_property(IGX g);
 extern "C" int IGXSetUp(IGX g) {
-  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; g->fd.reset(); g->krylov.reset();
+  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; g->fd.reset(); g->krylov.reset(); g->newton.reset();
   if (rc) return fail(rc, e);
   if (int rp = apply_property(g)) return rp;
   return apply_geometry(g);   // a control net given by IGXRead / an earlier IGXSetGeometry survives re-partitioning
@@ -582,7 +592,7 @@ extern "C" int IGXSetTiming(IGX g, int flag) {
 }
 extern "C" int IGXGetLastTiming(IGX g, double *total_ms, double *kernel_ms, int *launches) {
   NEEDIGA(g);
-  if (g->timing && g->ev[0] && !(g->krylov && g->krylov->name == g->last_kernel)) {      // (after IGXSolve: the figures the solve stored)
+  if (g->timing && g->ev[0] && !(g->krylov && g->krylov->name == g->last_kernel) && !(g->newton && g->newton->name == g->last_kernel)) {      // (after IGXSolve / IGXSolveNonlinear: the figures the solve stored)
     HIPCK(hipEventSynchronize(g->ev[3]));
     float a = 0, b = 0;
     HIPCK(hipEventElapsedTime(&a, g->ev[0], g->ev[3]));
@@ -2039,6 +2049,144 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
     g->last_total_ms = ms; g->last_kernel_ms = op_ms;
   }
   if (info) { info->iterations = its; info->reason = reason; info->rnorm0 = rnorm0; info->rnorm = rnorm; info->bnorm = bnorm; }
+  return 0;
+}
+
+// ------------------------------------------------------------------ the Newton loop (newton.hpp)
+#include "newton.hpp"
+// IGXSolveNonlinear.  The residual is the vector driver's internal entry (compute: what IGXComputeFunction / IGXComputeIFunction call), the
+// linear solve is IGXSolve itself: whatever they refuse the Newton solve refuses, with their reason under its own name.  The loop is the
+// one the header states; between two operator calls a trial is one sweep of newton.hpp.
+static int nw_refused(int rc) { return rc == IGX_ERR_SUP ? fail(rc, "the Newton solve runs where its residual and its linear solve run, and " + std::string(g_err)) : rc; }
+extern "C" int IGXSolveNonlinear(IGX g, const IGXNewtonSpec *sp, IGXVec x, IGXNewtonInfo *info, double *history, int *linear_its) {
+  NEEDIGA(g);
+  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null Newton specification");
+  if (sp->op == IGX_OP_MATRIX) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: a linear operator has no Newton loop (IGX_OP_MATRIX: call IGXSolve)");
+  if (sp->op != IGX_OP_JACOBIAN && sp->op != IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown operator");
+  if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown method");
+  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown preconditioner");
+  if (sp->linesearch != IGX_LINESEARCH_BASIC && sp->linesearch != IGX_LINESEARCH_BT) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown line search");
+  if (sp->forcing != IGX_FORCING_CONSTANT && sp->forcing != IGX_FORCING_EW2) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown forcing");
+  if (!(sp->lin_rtol >= 0) || !(sp->lin_atol >= 0) || !(sp->rtol >= 0) || !(sp->atol >= 0) || !(sp->stol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: the tolerances must not be negative");
+  if (sp->maxit < 0 || sp->lin_maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: maxit and lin_maxit must not be negative");
+  if (sp->max_backtracks < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: max_backtracks must not be negative");
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXSolveNonlinear()");
+  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, "the Newton solve needs one rank on every axis: its norms and its linear solve have no sum across ranks");
+  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  if (sp->pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() before IGXSolveNonlinear() with IGX_PC_FASTDIAG");
+  const bool ifun = sp->op == IGX_OP_IJACOBIAN;
+  IGXVec W = ifun ? sp->W : nullptr;
+  if (ifun && !W) return fail(IGX_ERR_ARG_WRONG, "IGXSolveNonlinear: IGX_OP_IJACOBIAN needs the vector W of V = a U + W");
+  if (!x) return fail(IGX_ERR_ARG_WRONG, "null solution vector");
+  if (x->iga != g || (W && W->iga != g)) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if (W == x) return fail(IGX_ERR_ARG_WRONG, "W and the solution must be different vectors");
+  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string("the Newton solve runs where its residual and its linear solve run, and ") + why);
+  if (int rc = ensure_device(g)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  if (x->n != n || (W && W->n != n)) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  if (int rc = kr_scalars(g)) return rc;
+  if (!g->newton || g->newton->n != n || g->newton->has_v != ifun) {
+    g->newton.reset();
+    std::shared_ptr<NewtonState> ns(new NewtonState());
+    for (int k = 0; k < (ifun ? 5 : 4); ++k) {
+      std::unique_ptr<_p_IGXVec> v(new _p_IGXVec()); v->iga = g; v->n = n;
+      if (v->a.alloc((size_t)n * sizeof(double)) || hipMemset(v->a.p, 0, v->a.bytes) != hipSuccess) return fail(IGX_ERR_MEM, "device allocation of the Newton work vectors failed");
+      ns->work.push_back(std::move(v));
+    }
+    ns->n = n; ns->has_v = ifun;
+    g->newton = ns;
+  }
+  NewtonState &st = *g->newton;
+  IGXVec F = st.work[0].get(), Ft = st.work[1].get(), d = st.work[2].get(), xs = st.work[3].get(), V = ifun ? st.work[4].get() : nullptr;
+  const bool timing = g->timing, bt = sp->linesearch == IGX_LINESEARCH_BT;
+  if (timing) { for (auto &e : st.ev) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(st.ev[0], g->stream)); }
+  int launches = 0; double op_ms = 0; std::string linname = "no linear solve";
+  double *xd = x->a.as<double>(), *Vd = V ? V->a.as<double>() : nullptr; const double *Wd = W ? W->a.as<double>() : nullptr;
+  const double shift = ifun ? sp->a : 0.0, t = ifun ? sp->t : 0.0;
+  double *drec = kr_rec(g), rec[3] = {0, 0, 0};
+  int evals = 0;
+  // F_out = G(x) with the state V as the last sweep left it; rec = (F.F, d.d, x.x), the last two only after a trial sweep
+  auto residual = [&](IGXVec out, int m) -> int {
+    if (int rc = compute(g, ifun ? OP_IFUNCTION : OP_FUNCTION, nullptr, out, x, V, shift, t)) return nw_refused(rc);
+    launches += g->last_launches;
+    if (timing) { float ms = 0; HIPCK(hipEventSynchronize(g->ev[2])); HIPCK(hipEventElapsedTime(&ms, g->ev[1], g->ev[2])); op_ms += ms; }
+    KR_LAUNCH(kr_dot, KR_G, KR_T, g, out->a.as<double>(), out->a.as<double>(), n, kr_slab(g, KS_RR));
+    KrSlabs sl; memset(&sl, 0, sizeof(sl)); sl.s[0] = kr_slab(g, KS_RR); sl.s[1] = kr_slab(g, KS_A); sl.s[2] = kr_slab(g, KS_B); sl.m = m;
+    KR_LAUNCH(kr_record, 1, 64, g, sl, drec);
+    launches += 2; ++evals;
+    HIPCK(hipMemcpyAsync(rec, drec, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->stream)); HIPCK(hipStreamSynchronize(g->stream));
+    return 0;
+  };
+  g->slab_valid = 0;
+  int its = 0, reason = 0, lin_total = 0, backtracks = 0, last_lin = 0;
+  double fnorm0 = 0, f = 0, snorm = 0, xnorm = 0, eta = sp->lin_rtol, fprev = 0;
+  if (ifun) { KR_LAUNCH(nw_state, kr_grid(n), KR_T, g, Vd, xd, Wd, shift, n); ++launches; }
+  if (int rc = residual(F, 1)) return rc;
+  fnorm0 = f = std::sqrt(rec[0]);
+  if (history) history[0] = f;
+  if (std::isnan(f)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN;
+  else if (f <= sp->atol) reason = IGX_NEWTON_CONVERGED_FNORM_ABS;
+  else if (sp->maxit == 0) reason = IGX_NEWTON_DIVERGED_MAX_IT;
+  while (!reason) {
+    // the linear solve J(x) d = F from d = 0, to eta
+    if (sp->forcing == IGX_FORCING_EW2 && its > 0) {
+      const double q = f / fprev, floor_ = 0.9 * (eta * eta);
+      double e = 0.9 * (q * q);
+      if (floor_ > 0.1 && e < floor_) e = floor_;
+      eta = e > 0.9 ? 0.9 : e;
+    }
+    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, d->a.as<double>(), 0.0, n); ++launches;
+    IGXSolveSpec ls; memset(&ls, 0, sizeof(ls));
+    ls.method = sp->method; ls.op = sp->op; ls.pc = sp->pc; ls.a = shift; ls.t = t; ls.V = V; ls.U = x; ls.rtol = eta; ls.atol = sp->lin_atol; ls.maxit = sp->lin_maxit;
+    IGXSolveInfo li; memset(&li, 0, sizeof(li));
+    if (int rc = IGXSolve(g, &ls, F, d, &li, nullptr)) return nw_refused(rc);
+    launches += g->last_launches; if (timing) op_ms += g->last_kernel_ms;
+    linname = g->krylov->name;
+    lin_total += li.iterations; last_lin = li.reason;
+    if (linear_its) linear_its[its] = li.iterations;
+    if (li.reason == IGX_DIVERGED_BREAKDOWN || li.reason == IGX_DIVERGED_NAN) { reason = IGX_NEWTON_DIVERGED_LINEAR_SOLVE; break; }
+    // the line search: one sweep and one residual per trial
+    double lambda = 1.0; int halvings = 0; bool accepted = false;
+    KR_LAUNCH(nw_first_trial, KR_G, KR_T, g, xd, xs->a.as<double>(), d->a.as<double>(), Vd, Wd, shift, n, kr_slab(g, KS_A), kr_slab(g, KS_B)); ++launches;
+    for (;;) {
+      if (int rc = residual(Ft, 3)) {      // x holds a trial that was never judged: hand back the last accepted iterate with the driver's error
+        (void)hipMemcpyAsync(x->a.p, xs->a.p, x->a.bytes, hipMemcpyDeviceToDevice, g->stream); (void)hipStreamSynchronize(g->stream);
+        return rc;
+      }
+      const double ft = std::sqrt(rec[0]);
+      if (!bt) { if (std::isnan(ft)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN; else accepted = true; }
+      else if (std::isfinite(ft) && ft <= (1.0 - 1e-4 * lambda) * f) accepted = true;
+      else if (halvings == sp->max_backtracks) reason = IGX_NEWTON_DIVERGED_LINE_SEARCH;
+      if (accepted) { fprev = f; f = ft; break; }
+      if (reason) break;
+      lambda *= 0.5; ++halvings; ++backtracks;
+      KR_LAUNCH(nw_back_trial, KR_G, KR_T, g, xd, xs->a.as<double>(), d->a.as<double>(), Vd, Wd, shift, lambda, n, kr_slab(g, KS_A), kr_slab(g, KS_B)); ++launches;
+    }
+    if (!accepted) {      // x is the last accepted iterate again, bit for bit
+      HIPCK(hipMemcpyAsync(x->a.p, xs->a.p, x->a.bytes, hipMemcpyDeviceToDevice, g->stream)); HIPCK(hipStreamSynchronize(g->stream));
+      break;
+    }
+    snorm = lambda * std::sqrt(rec[1]); xnorm = std::sqrt(rec[2]);
+    std::swap(F, Ft);
+    ++its;
+    if (history) history[its] = f;
+    if (std::isnan(f)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN;
+    else if (f <= sp->atol) reason = IGX_NEWTON_CONVERGED_FNORM_ABS;
+    else if (f <= sp->rtol * fnorm0) reason = IGX_NEWTON_CONVERGED_FNORM_RELATIVE;
+    else if (snorm <= sp->stol * xnorm) reason = IGX_NEWTON_CONVERGED_SNORM_RELATIVE;
+    else if (its >= sp->maxit) reason = IGX_NEWTON_DIVERGED_MAX_IT;
+  }
+  st.name = std::string("newton(") + (bt ? "bt" : "basic") + ", " + linname + ", " + std::to_string(its) + " iterations)";
+  g->last_kernel = st.name; g->last_launches = launches;
+  if (timing) {
+    float ms = 0;
+    HIPCK(hipEventRecord(st.ev[1], g->stream)); HIPCK(hipEventSynchronize(st.ev[1])); HIPCK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
+    g->last_total_ms = ms; g->last_kernel_ms = op_ms;
+  }
+  if (info) {
+    info->iterations = its; info->reason = reason; info->linear_iterations = lin_total; info->function_evaluations = evals; info->backtracks = backtracks;
+    info->last_linear_reason = last_lin; info->fnorm0 = fnorm0; info->fnorm = f; info->snorm = snorm; info->xnorm = xnorm;
+  }
   return 0;
 }
 #endif   // !IGX_TU_DISPATCH

@@ -1,6 +1,6 @@
 // krylov.hpp -- vector algebra on IGXVec (IGXVecSet ... IGXVecNorm2) and the device-resident Krylov loop (IGXSolve: CG and right-preconditioned
 // BiCGStab over IGXCompute*Action and the diagonal / point-block / fast-diagonalisation preconditioners).  Included by the main unit only,
-// after the drivers it calls.
+// after the drivers it calls.  The sweep macros (KR_PAIRS ... KR_C2) live between kr_sweep_begin.hpp and kr_sweep_end.hpp, here and in newton.hpp.
 // Sweeps: KR_T threads per workgroup, a grid-stride loop over a grid capped at KR_G workgroups, 16-byte accesses (every IGXVec starts at its
 // allocation, so the pairs are aligned) and a scalar tail of n & 1 entries in thread 0 of workgroup 0.
 // Reductions: a kernel that emits a sum always runs KR_G workgroups; each adds its lanes in a fixed tree (wavefront shuffles, then LDS in wave
@@ -38,10 +38,7 @@ __device__ inline double kr_block_sum(double v, double *red) {
   __syncthreads();
   return s;
 }
-#define KR_PAIRS(i) for (long long i = (long long)blockIdx.x * KR_T + threadIdx.x, st_ = (long long)gridDim.x * KR_T, n2_ = n >> 1; i < n2_; i += st_)
-#define KR_TAIL ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0)
-#define KR_V2(p) reinterpret_cast<kr_d2 *>(p)
-#define KR_C2(p) reinterpret_cast<const kr_d2 *>(p)
+#include "kr_sweep_begin.hpp"
 
 // ------------------------------------------------------------------ vector algebra
 __global__ void __launch_bounds__(KR_T) kr_set(double *y, double v, long long n) {
@@ -202,10 +199,7 @@ __global__ void __launch_bounds__(64) kr_bicg_record(const double *slab_rr, cons
   sc[0] = rho1; sc[1] = alpha; sc[2] = omega;
 }
 
-#undef KR_PAIRS
-#undef KR_TAIL
-#undef KR_V2
-#undef KR_C2
+#include "kr_sweep_end.hpp"
 
 // workgroups of a sweep that emits no sum: one pass of pairs, KR_G at the most
 inline unsigned kr_grid(long long n) { const long long w = ((n >> 1) + KR_T - 1) / KR_T; return (unsigned)(w < 1 ? 1 : (w > KR_G ? KR_G : w)); }
