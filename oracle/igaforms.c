@@ -213,6 +213,13 @@ int orc_form_nitsche(OrcPoint *p,double *K,double *F,void *ctx)
   return 0;
 }
 
+/* orc_form_nitsche's face terms alone (nothing inside): an error on a face cannot hide under interior terms of the same size */
+int orc_form_nitsche_face(OrcPoint *p,double *K,double *F,void *ctx)
+{
+  if (!p->atboundary) return 0;   /* the caller zeroes K and F before every point */
+  return orc_form_nitsche(p,K,F,ctx);
+}
+
 /* src/petigacomp.c:102-120 (ErrorSqr) specialised to test/IGAErrNorm.c's Exact; ctx = int* order.
  * U == all-zero vector reproduces "norm of the exact solution" (vecU NULL in the reference). */
 int orc_scalar_errnorm(OrcPoint *p,const double *U,int n,double *S,void *ctx)
@@ -239,6 +246,17 @@ int orc_scalar_volume(OrcPoint *p,const double *U,int n,double *S,void *ctx)
 {
   (void)U; (void)n; (void)ctx;
   if (p->atboundary) S[1] = 1.0; else S[0] = 1.0;
+  return 0;
+}
+
+/* S[0] = int x . n dS over the visited faces, S[1] the volume: the divergence theorem gives S[0] = dim S[1] over all faces */
+int orc_scalar_flux(OrcPoint *p,const double *U,int n,double *S,void *ctx)
+{
+  double x[3]={0,0,0}; int i;
+  (void)U; (void)n; (void)ctx;
+  orc_point_geommap(p,x);
+  if (p->atboundary) for (i=0;i<p->dim;i++) S[0] += x[i]*p->normal[i];
+  else S[1] = 1.0;
   return 0;
 }
 

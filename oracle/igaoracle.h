@@ -178,6 +178,7 @@ int orc_form_l2proj_x2 (OrcPoint*,double*,double*,void*);  /* test/IGAFixTable.c
 int orc_form_poisson_f (OrcPoint*,double*,double*,void*);  /* test/IGAFixTable.c System2 */
 int orc_form_boundary_integral(OrcPoint*,double*,double*,void*);  /* demo/BoundaryIntegral.c System */
 int orc_form_nitsche(OrcPoint*,double*,double*,void*);            /* demo/NitscheMethod.c System; ctx = int* degree */
+int orc_form_nitsche_face(OrcPoint*,double*,double*,void*);       /* orc_form_nitsche's face terms alone */
 int orc_form_errnorm   (OrcPoint*,double*,double*,void*);  /* test/IGAErrNorm.c System (dof=4) */
 int orc_form_elasticity(OrcPoint*,double*,double*,void*);  /* demo/Elasticity3D.c System */
 int orc_form_der3      (OrcPoint*,double*,double*,void*);  /* third derivatives p->shape[3] (test/IGAGeometryMap.c:179,221); ctx: double[3] = {k3, f3, u3} */
@@ -197,6 +198,7 @@ int orc_form_bratu_ijacobian(OrcPoint*,double,const double*,double,const double*
 int orc_scalar_errnorm  (OrcPoint*,const double*,int,double*,void*); /* ctx = int* order; test/IGAErrNorm.c Exact */
 int orc_scalar_x2err    (OrcPoint*,const double*,int,double*,void*); /* test/IGAFixTable.c Exact, L2 */
 int orc_scalar_volume   (OrcPoint*,const double*,int,double*,void*); /* test/IGAGeometryMap.c Scalar */
+int orc_scalar_flux     (OrcPoint*,const double*,int,double*,void*); /* S[0] = int x . n dS on the visited faces, S[1] = volume */
 
 /* field interpolation at a point: src/petigaval.F90:182-251 */
 void orc_point_value(const OrcPoint*,const double*U,double*u);

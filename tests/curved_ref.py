@@ -239,6 +239,7 @@ class CurvedRef:
         det = sum(Jv[0, i] * cof[i, 0] for i in range(3))
         Ev = cof / det
         self.x, self.detv = np.array([c.v for c in x]), det
+        self.xq, self.J = x, J                                 # (as Q: face_ref.py forms the normal of a face from the columns of J)
         if self.wrong in ("point", "element"):                 # the metric (J^-1, det J, the map's Hessian) of another point
             nq = self.nqp[0]
             if self.wrong == "point":

@@ -12,8 +12,9 @@ TOL = 1e-12
 
 
 def _rel(a, b):
+    """The worst error of a component relative to that component's own magnitude (not to the largest of them)."""
     a, b = np.asarray(a), np.asarray(b)
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+    return (np.abs(a - b) / np.maximum(np.abs(b), 1e-300)).max()
 
 
 @pytest.mark.parametrize("dim", [1, 2, 3])
