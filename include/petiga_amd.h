@@ -489,6 +489,79 @@ typedef struct { int iterations, reason, linear_iterations, function_evaluations
 int IGXSolveNonlinear(IGX iga,const IGXNewtonSpec *spec,IGXVec x,IGXNewtonInfo *info,
                       double *history /* NULL or [maxit+1]: |F_k|_2 */,int *linear_its /* NULL or [maxit] */);
 
+/* The generalized-alpha time loop on the Newton solve, resident on the device: F(t, U, dU/dt) = 0, first order in time, for the forms with an
+ * IFunction (Cahn-Hilliard, NS-VMS, Bratu as IFunction), from U = U_n and V = V_n = dU/dt at t0.  The scheme is (alpha_m, alpha_f, gamma):
+ * the radius parametrisation of the reference's demos is alpha_m = (3 - rho) / (2 (1 + rho)), alpha_f = 1 / (1 + rho), gamma = 1/2 + alpha_m -
+ * alpha_f (demo/CahnHilliard3D.c:281-287, demo/NavierStokesVMS.c:397-401: rho = 0.5); (1, 1, 1) is backward Euler.  It is the native loop of
+ * a caller without PETSc, not a TS adapter.  fl(.) is one rounding to double; no product is contracted with a sum.
+ * State.  t = t0, h = dt, steps = 0; U0, V0 the accepted state (copies of U and V); with resume = 0 no U_{n-1} is held.
+ *   max_steps == 0: IGX_TS_CONVERGED_STEPS, and t0 == max_time: IGX_TS_CONVERGED_TIME, both with nothing launched and U, V untouched.
+ * Step n -> n+1 begins with rejections = 0 (the limit max_rejections is per step) and tries attempts until one is accepted:
+ * Attempt.  p = h (the proposed step).  If max_time - t <= (1 + 1e-9) h the attempt is shortened to end at max_time: h = max_time - t
+ *   (exempt from dt_min).  That is t + h > max_time, and also a step that would end within 1e-9 h before max_time: the remainder it would
+ *   leave is the rounding of t, and a step of that size divides rounding noise by h in V1.
+ *   Stage (one sweep, ts_stage).  On the host a = alpha_m / (alpha_f gamma h) and c0 = 1 - alpha_m / gamma.
+ *     W_i = fl(fl(c0 V0_i) - fl(a U0_i)), x_i = U0_i (the stage guess).
+ *   Solve.  IGXSolveNonlinear with the caller's newton spec, op = IGX_OP_IJACOBIAN, that a, t = t_n + alpha_f h, W, on x.  The stage unknown
+ *     is x = U_{n+alpha_f}; V = a x + W is then V_{n+alpha_m} (an identity: with U_{n+af} = U0 + af (U1 - U0), V1 = (U1 - U0) / (gamma h) +
+ *     (1 - 1/gamma) V0 and V_{n+am} = V0 + am (V1 - V0) one gets V_{n+am} = a (x - U0) + (1 - am/gamma) V0).
+ *   A negative IGXNewtonReason is a failed attempt (logged with wlte = -1).  adapt == 0: IGX_TS_DIVERGED_NONLINEAR_SOLVE.  Otherwise
+ *     ++rejections, h = h / 4; rejections > max_rejections or h < dt_min: IGX_TS_DIVERGED_NONLINEAR_SOLVE; else the next attempt.
+ *   Update (one sweep, ts_update) into two trial vectors, with c1 = 1 / alpha_f, c2 = 1 / (gamma h), c3 = 1 - 1 / gamma from the host:
+ *     U1_i = fl(U0_i + fl(c1 fl(x_i - U0_i))),  V1_i = fl(fl(c2 fl(U1_i - U0_i)) + fl(c3 V0_i)),
+ *     and the partial sums of U1 . U1.  An estimate exists when adapt != 0 and a U_{n-1} is held (not on the first step of a fresh start).
+ *     Then, with r = 1 + h_{n-1} / h and d1 = r, d2 = r - 1, d3 = r (r - 1) from the host, the same sweep forms the second-order
+ *     backward-difference estimate on unequal steps, e_i = fl(fl(fl(U1_i / d1) - fl(U0_i / d2)) + fl(Uprev_i / d3)) (correctly rounded
+ *     quotients), and emits the partial sums of q_i^2, q_i = fl(e_i / fl(adapt_atol + fl(adapt_rtol max(|U1_i|, |fl(U1_i + e_i)|)))).
+ *     The host reads ONE record of the two sums; unorm = sqrt(U1 . U1), wlte = sqrt(sum / n), n the vector's length.  No estimate: wlte = -1.
+ *   unorm or wlte is NaN: IGX_TS_DIVERGED_NAN (logged, not accepted).
+ *   No estimate: the attempt is accepted and the next step proposes p again (growth starts from the second step: start small).
+ *   With an estimate: fac = min(10, max(0.1, 0.9 / sqrt(wlte))), 10 for wlte == 0.  wlte <= 1 accepts, and the next step proposes
+ *     min(dt_max, max(dt_min, fac h)) -- or p again where the attempt was shortened.  Otherwise ++rejections, h = fac h;
+ *     rejections > max_rejections or h < dt_min: IGX_TS_DIVERGED_STEP_REJECTED; else the next attempt.
+ * Acceptance.  Uprev <- U0 <- U1 and V0 <- V1 by pointer among the work vectors, h_{n-1} = h; t += h (t = max_time exactly where the
+ *   attempt was shortened); ++steps; dt_last = h; h = the next proposal.  t == max_time: IGX_TS_CONVERGED_TIME; else steps == max_steps:
+ *   IGX_TS_CONVERGED_STEPS.
+ * Return.  U and V receive the last accepted state, once (a failed or rejected attempt never touches it: a call that diverges hands back
+ *   the last accepted state bit for bit, with every step accepted before it).  A call that does not converge RETURNS 0: info->reason says
+ *   why.  info: steps, rejections and attempts over the whole call, the sums of the Newton solves' iterations, linear iterations and function
+ *   evaluations, t, dt_last (the last accepted h, 0 for none), dt_next (the h the next step would propose: pass it as dt to continue),
+ *   unorm = |U|_2 of the last accepted step (0 for none).  log (NULL, or nlog records) receives one record per ATTEMPT: t the time the
+ *   attempt starts from, dt its h, wlte, accepted, and the Newton solve's iterations, reason and linear iterations; attempts past nlog
+ *   are counted in info->attempts but not logged.
+ * resume = 1 continues the previous call: its U_{n-1} and h_{n-1} are kept with the IGX, so the estimate is available at once; t0 and dt
+ *   are still the caller's (pass info->t and info->dt_next).  Six steps in one call and three plus three with resume give the same bits.
+ *   IGX_ERR_ORDER when the IGX holds none: no earlier call that accepted a step, after IGXSetUp, or a vector length that differs.
+ * What the stepper does not do.  It does not form V_0: the caller gives it.  It does not change form parameters (the dt in NS-VMS's tau
+ * stays what the caller set).  U must hold the Dirichlet values on entry: the residual pins the stage value, and with alpha_f < 1 a wrong
+ * boundary value in U_n is extrapolated into U_{n+1} (PETSc's TSALPHA behaves the same way).  dt_min limits reductions only: the caller's
+ * dt and the shortened last step are taken as they are.  Second-order-in-time forms are out of scope.
+ * Work vectors (W, x, three rotating U and two rotating V) are kept with the IGX like the Newton solve's; IGXSetUp drops them, IGXDestroy
+ * frees them.  No atomics: bitwise repeatable (timestep.hpp).  IGXSetTiming / IGXGetLastTiming cover the whole call (total
+ * time, the operators' kernel time summed over the Newton solves, launches); IGXGetKernelName gives
+ * "timestep(am=.., af=.., g=.., <the last newton(...) name>, <k> steps, <r> rejections)".
+ * Refusals, decided before the first HIP call as in IGXSolveNonlinear.  IGX_ERR_ARG_WRONG: a null spec, U or V, a foreign or wrong-sized
+ * vector, U == V.  IGX_ERR_ARG_OUTOFRANGE with a message that names IGXTimeStep and the member: newton.op != IGX_OP_IJACOBIAN; alpha_m,
+ * alpha_f or gamma not finite or <= 0; dt <= 0 or NaN; max_time < t0 (or NaN); a negative max_steps or max_rejections; a negative or NaN
+ * adapt_rtol, adapt_atol, dt_min or dt_max; dt_max < dt_min; adapt with both tolerances 0; and what IGXSolveNonlinear refuses in newton.
+ * IGX_ERR_ORDER: before IGXSetUp; resume without a kept state; IGX_PC_FASTDIAG without IGXFastDiagSetUp.  IGX_ERR_ARG_WRONGSTATE: no form
+ * set.  IGX_ERR_SUP with a reason that names the time stepper: more than one rank on an axis; whatever IGXSolveNonlinear refuses in the
+ * loop is passed on with its reason under the stepper's name, and U, V hold the last accepted state (the entry state where no step was
+ * accepted before it). */
+typedef enum { IGX_TS_CONVERGED_TIME = 1, IGX_TS_CONVERGED_STEPS = 2,
+               IGX_TS_DIVERGED_NONLINEAR_SOLVE = -1, IGX_TS_DIVERGED_STEP_REJECTED = -2, IGX_TS_DIVERGED_NAN = -3 } IGXTimeStepReason;
+typedef struct {
+  double alpha_m, alpha_f, gamma;      /* the scheme */
+  double t0, dt, max_time; int max_steps;
+  int adapt; double adapt_rtol, adapt_atol, dt_min, dt_max; int max_rejections;   /* per step */
+  int resume;                          /* 0: a fresh start; 1: continue the previous call (its U_{n-1} and h_{n-1} are kept with the IGX) */
+  IGXNewtonSpec newton;                /* op must be IGX_OP_IJACOBIAN; its a, t and W are the stepper's and are ignored */
+} IGXTimeStepSpec;
+typedef struct { double t, dt, wlte; int accepted, newton_iterations, newton_reason, linear_iterations; } IGXTimeStepLog;   /* one per ATTEMPT */
+typedef struct { int steps, reason, rejections, attempts, newton_iterations, linear_iterations, function_evaluations;
+                 double t, dt_last, dt_next, unorm; } IGXTimeStepInfo;
+int IGXTimeStep(IGX iga,const IGXTimeStepSpec *spec,IGXVec U,IGXVec V,IGXTimeStepInfo *info,IGXTimeStepLog *log,int nlog);
+
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
  * ranks, and U must hold the ghost rows' values).  The point callbacks are the ones the reference's tests use:

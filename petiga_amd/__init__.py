@@ -58,6 +58,22 @@ class IGXNewtonInfo(C.Structure):
                 ("last_linear_reason", C.c_int), ("fnorm0", C.c_double), ("fnorm", C.c_double), ("snorm", C.c_double), ("xnorm", C.c_double)]
 
 
+class IGXTimeStepSpec(C.Structure):
+    _fields_ = [("alpha_m", C.c_double), ("alpha_f", C.c_double), ("gamma", C.c_double), ("t0", C.c_double), ("dt", C.c_double), ("max_time", C.c_double),
+                ("max_steps", C.c_int), ("adapt", C.c_int), ("adapt_rtol", C.c_double), ("adapt_atol", C.c_double), ("dt_min", C.c_double), ("dt_max", C.c_double),
+                ("max_rejections", C.c_int), ("resume", C.c_int), ("newton", IGXNewtonSpec)]
+
+
+class IGXTimeStepLog(C.Structure):
+    _fields_ = [("t", C.c_double), ("dt", C.c_double), ("wlte", C.c_double), ("accepted", C.c_int), ("newton_iterations", C.c_int), ("newton_reason", C.c_int),
+                ("linear_iterations", C.c_int)]
+
+
+class IGXTimeStepInfo(C.Structure):
+    _fields_ = [("steps", C.c_int), ("reason", C.c_int), ("rejections", C.c_int), ("attempts", C.c_int), ("newton_iterations", C.c_int), ("linear_iterations", C.c_int),
+                ("function_evaluations", C.c_int), ("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("unorm", C.c_double)]
+
+
 SOLVE_METHODS = dict(cg=0, bicgstab=1)
 SOLVE_OPERATORS = dict(matrix=0, jacobian=1, ijacobian=2)
 SOLVE_PCS = dict(none=0, jacobi=1, pbjacobi=2, fastdiag=3)
@@ -66,6 +82,25 @@ NEWTON_LINESEARCHES = dict(basic=0, bt=1)
 NEWTON_FORCINGS = dict(constant=0, ew2=1)
 NEWTON_REASONS = {2: "converged_fnorm_abs", 3: "converged_fnorm_relative", 4: "converged_snorm_relative", -3: "diverged_linear_solve", -4: "diverged_fnorm_nan",
                   -5: "diverged_max_it", -6: "diverged_line_search", 0: "iterating"}
+TS_REASONS = {1: "converged_time", 2: "converged_steps", -1: "diverged_nonlinear_solve", -2: "diverged_step_rejected", -3: "diverged_nan", 0: "iterating"}
+TS_LOG_DTYPE = np.dtype([("t", "f8"), ("dt", "f8"), ("wlte", "f8"), ("accepted", "i4"), ("newton_iterations", "i4"), ("newton_reason", "i4"), ("linear_iterations", "i4")])
+
+
+def alpha_scheme(rho_inf=None, scheme=None, alpha=None):
+    """(alpha_m, alpha_f, gamma) of IGXTimeStep: from the spectral radius at infinity (the parametrisation TSALPHA's radius option sets),
+    scheme="backward_euler" = (1, 1, 1), or the three numbers passed through.  With nothing given: rho_inf = 0.5, the reference demos' choice."""
+    if sum(v is not None for v in (rho_inf, scheme, alpha)) > 1:
+        raise ValueError("give one of rho_inf, scheme and alpha")
+    if alpha is not None:
+        am, af, g = (float(v) for v in alpha)
+        return am, af, g
+    if scheme is not None:
+        if scheme != "backward_euler":
+            raise ValueError("unknown scheme %r" % (scheme,))
+        return 1.0, 1.0, 1.0
+    rho = 0.5 if rho_inf is None else float(rho_inf)
+    am, af = (3.0 - rho) / (2.0 * (1.0 + rho)), 1.0 / (1.0 + rho)
+    return am, af, 0.5 + am - af
 
 
 # IGXTransportFn (include/petiga_amd.h): the host-callback transport of the ghost-row exchange
@@ -137,6 +172,7 @@ def lib(build_if_needed=False):
         "IGXVecPointwiseDivide": [V, V, V], "IGXVecDot": [V, V, _dp], "IGXVecNorm2": [V, _dp],
         "IGXSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
         "IGXSolveNonlinear": [V, C.POINTER(IGXNewtonSpec), V, C.POINTER(IGXNewtonInfo), _dp, _ip],
+        "IGXTimeStep": [V, C.POINTER(IGXTimeStepSpec), V, V, C.POINTER(IGXTimeStepInfo), C.POINTER(IGXTimeStepLog), C.c_int],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -552,6 +588,32 @@ class IGX:
         out["reason_name"] = NEWTON_REASONS.get(info.reason, str(info.reason))
         out["history"] = hist[:info.iterations + 1].copy()
         out["linear_its"] = lin[lin >= 0].astype(int)      # one per inner solve: a step that ends the call in its line search or its solve has one too
+        return out
+
+    def time_step(self, U, V, dt, max_time=float("inf"), max_steps=1, rho_inf=None, scheme=None, alpha=None, t0=0.0, adapt=False, adapt_rtol=1e-3, adapt_atol=1e-3,
+                  dt_min=0.0, dt_max=float("inf"), max_rejections=10, resume=False, nlog=None, method="bicgstab", pc="none", lin_rtol=1e-5, lin_atol=0.0,
+                  lin_maxit=1000, forcing="constant", rtol=1e-8, atol=0.0, stol=0.0, maxit=50, linesearch="basic", max_backtracks=10):
+        """IGXTimeStep: generalized-alpha steps on the device from U = U_n, V = dU/dt at t0, each stage one solve_nonlinear(op="ijacobian") with
+        the Newton keywords given here.  The scheme: rho_inf (default 0.5), scheme="backward_euler" or alpha=(alpha_m, alpha_f, gamma).  U and V
+        hold the last accepted state on return.  Returns a dict of the info fields (steps, reason, reason_name, rejections, attempts,
+        newton_iterations, linear_iterations, function_evaluations, t, dt_last, dt_next, unorm) and log, a structured array with one record
+        per attempt (t, dt, wlte, accepted, newton_iterations, newton_reason, linear_iterations)."""
+        code = lambda table, v: table[v] if isinstance(v, str) else int(v)
+        am, af, g = alpha_scheme(rho_inf, scheme, alpha)
+        newton = IGXNewtonSpec(SOLVE_OPERATORS["ijacobian"], 0.0, 0.0, None, code(SOLVE_METHODS, method), code(SOLVE_PCS, pc), float(lin_rtol), float(lin_atol),
+                               int(lin_maxit), code(NEWTON_FORCINGS, forcing), float(rtol), float(atol), float(stol), int(maxit),
+                               code(NEWTON_LINESEARCHES, linesearch), int(max_backtracks))
+        spec = IGXTimeStepSpec(am, af, g, float(t0), float(dt), float(max_time), int(max_steps), int(bool(adapt)), float(adapt_rtol), float(adapt_atol),
+                               float(dt_min), float(dt_max), int(max_rejections), int(bool(resume)), newton)
+        if nlog is None:
+            nlog = max(int(max_steps), 0) * (max(int(max_rejections), 0) + 1 if adapt else 1)
+        nlog = min(max(int(nlog), 1), 1 << 16)
+        log = (IGXTimeStepLog * nlog)()
+        info = IGXTimeStepInfo()
+        _ck(lib().IGXTimeStep(self.h, C.byref(spec), U.h if U is not None else None, V.h if V is not None else None, C.byref(info), log, nlog))
+        out = {k: getattr(info, k) for k, _ in IGXTimeStepInfo._fields_}
+        out["reason_name"] = TS_REASONS.get(info.reason, str(info.reason))
+        out["log"] = np.frombuffer(log, dtype=TS_LOG_DTYPE, count=min(info.attempts, nlog)).copy()
         return out
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))

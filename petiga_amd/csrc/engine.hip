@@ -76,6 +76,7 @@ struct IgxComm;
 struct RtcForm;
 struct KrylovState;
 struct NewtonState;
+struct TimeStepState;
 // IGXFastDiagSetUp's host result and the device copies IGXFastDiagApply makes of it at its first call
 struct FastDiagState {
   FastDiag h;
@@ -115,6 +116,7 @@ struct _p_IGX {
   DevBuf krscal;                                                    // IGXVecDot / IGXSolve: the slabs of partial sums, the record and the device scalars (krylov.hpp)
   std::shared_ptr<KrylovState> krylov;                              // IGXSolve's work vectors and preconditioner storage, kept between solves
   std::shared_ptr<NewtonState> newton;                              // IGXSolveNonlinear's work vectors, kept between solves
+  std::shared_ptr<TimeStepState> timestep;                          // IGXTimeStep's work vectors, U_{n-1} and h_{n-1}, kept between calls
 };
 
 struct _p_IGXMat {
@@ -138,6 +140,16 @@ struct NewtonState {
   std::string name;                                      // the last solve's kernel name (IGXGetLastTiming, as for KrylovState)
   hipEvent_t ev[2] = {nullptr, nullptr};
   ~NewtonState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+// ... and IGXTimeStep (timestep.hpp), with what resume = 1 continues from
+struct TimeStepState {
+  int64_t n = 0;
+  std::vector<std::unique_ptr<_p_IGXVec>> work;          // W x, three rotating U (U0 U1 Uprev), two rotating V (V0 V1)
+  int u0 = 2, u1 = 3, uprev = 4, v0 = 5, v1 = 6;         // where the rotation stands
+  bool have_prev = false; double hprev = 0;              // U_{n-1} = work[uprev] and h_{n-1} of the last accepted step
+  std::string name;                                      // the last call's kernel name (IGXGetLastTiming, as for KrylovState)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~TimeStepState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 #ifndef IGX_TU_DISPATCH
@@ -205,7 +217,7 @@ extern "C" int IGXAxisSetKnots(IGX g, int i, int m, const double U[]) { AXISCK(g
 static int apply_geometry(IGX g);
 static int apply_property(IGX g);
 extern "C" int IGXSetUp(IGX g) {
-  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; g->fd.reset(); g->krylov.reset(); g->newton.reset();
+  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; g->fd.reset(); g->krylov.reset(); g->newton.reset(); g->timestep.reset();
   if (rc) return fail(rc, e);
   if (int rp = apply_property(g)) return rp;
   return apply_geometry(g);   // a control net given by IGXRead / an earlier IGXSetGeometry survives re-partitioning
@@ -592,7 +604,8 @@ extern "C" int IGXSetTiming(IGX g, int flag) {
 }
 extern "C" int IGXGetLastTiming(IGX g, double *total_ms, double *kernel_ms, int *launches) {
   NEEDIGA(g);
-  if (g->timing && g->ev[0] && !(g->krylov && g->krylov->name == g->last_kernel) && !(g->newton && g->newton->name == g->last_kernel)) {      // (after IGXSolve / IGXSolveNonlinear: the figures the solve stored)
+  if (g->timing && g->ev[0] && !(g->krylov && g->krylov->name == g->last_kernel) && !(g->newton && g->newton->name == g->last_kernel) &&
+      !(g->timestep && g->timestep->name == g->last_kernel)) {      // (after IGXSolve / IGXSolveNonlinear / IGXTimeStep: the figures the call stored)
     HIPCK(hipEventSynchronize(g->ev[3]));
     float a = 0, b = 0;
     HIPCK(hipEventElapsedTime(&a, g->ev[0], g->ev[3]));
@@ -2058,9 +2071,8 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
 // linear solve is IGXSolve itself: whatever they refuse the Newton solve refuses, with their reason under its own name.  The loop is the
 // one the header states; between two operator calls a trial is one sweep of newton.hpp.
 static int nw_refused(int rc) { return rc == IGX_ERR_SUP ? fail(rc, "the Newton solve runs where its residual and its linear solve run, and " + std::string(g_err)) : rc; }
-extern "C" int IGXSolveNonlinear(IGX g, const IGXNewtonSpec *sp, IGXVec x, IGXNewtonInfo *info, double *history, int *linear_its) {
-  NEEDIGA(g);
-  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null Newton specification");
+// what the specification alone decides (IGXTimeStep asks the same of the spec it passes on)
+static int nw_spec_refusal(const IGXNewtonSpec *sp) {
   if (sp->op == IGX_OP_MATRIX) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: a linear operator has no Newton loop (IGX_OP_MATRIX: call IGXSolve)");
   if (sp->op != IGX_OP_JACOBIAN && sp->op != IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown operator");
   if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown method");
@@ -2070,6 +2082,12 @@ extern "C" int IGXSolveNonlinear(IGX g, const IGXNewtonSpec *sp, IGXVec x, IGXNe
   if (!(sp->lin_rtol >= 0) || !(sp->lin_atol >= 0) || !(sp->rtol >= 0) || !(sp->atol >= 0) || !(sp->stol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: the tolerances must not be negative");
   if (sp->maxit < 0 || sp->lin_maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: maxit and lin_maxit must not be negative");
   if (sp->max_backtracks < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: max_backtracks must not be negative");
+  return 0;
+}
+extern "C" int IGXSolveNonlinear(IGX g, const IGXNewtonSpec *sp, IGXVec x, IGXNewtonInfo *info, double *history, int *linear_its) {
+  NEEDIGA(g);
+  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null Newton specification");
+  if (int rc = nw_spec_refusal(sp)) return rc;
   if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXSolveNonlinear()");
   for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, "the Newton solve needs one rank on every axis: its norms and its linear solve have no sum across ranks");
   if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
@@ -2187,6 +2205,153 @@ extern "C" int IGXSolveNonlinear(IGX g, const IGXNewtonSpec *sp, IGXVec x, IGXNe
     info->iterations = its; info->reason = reason; info->linear_iterations = lin_total; info->function_evaluations = evals; info->backtracks = backtracks;
     info->last_linear_reason = last_lin; info->fnorm0 = fnorm0; info->fnorm = f; info->snorm = snorm; info->xnorm = xnorm;
   }
+  return 0;
+}
+// ------------------------------------------------------------------ the generalized-alpha time loop (timestep.hpp)
+#include "timestep.hpp"
+// IGXTimeStep.  Every stage is IGXSolveNonlinear itself: whatever it refuses the stepper refuses, with its reason under the stepper's name.
+// The loop is the one the header states; around a Newton solve an attempt is the two sweeps of timestep.hpp and one record of two sums.
+static int ts_refused(int rc) { return fail(rc, "IGXTimeStep: the time stepper takes its stages with IGXSolveNonlinear, and " + std::string(g_err)); }
+extern "C" int IGXTimeStep(IGX g, const IGXTimeStepSpec *sp, IGXVec U, IGXVec V, IGXTimeStepInfo *info, IGXTimeStepLog *log, int nlog) {
+  NEEDIGA(g);
+  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null time-step specification");
+  if (sp->newton.op != IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: newton.op must be IGX_OP_IJACOBIAN (the stepper is first order in time on an IFunction)");
+  if (!(sp->alpha_m > 0) || !std::isfinite(sp->alpha_m)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: alpha_m must be positive and finite");
+  if (!(sp->alpha_f > 0) || !std::isfinite(sp->alpha_f)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: alpha_f must be positive and finite");
+  if (!(sp->gamma > 0) || !std::isfinite(sp->gamma)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: gamma must be positive and finite");
+  if (!(sp->dt > 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt must be positive");
+  if (!(sp->max_time >= sp->t0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_time must not be below t0");
+  if (sp->max_steps < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_steps must not be negative");
+  if (sp->max_rejections < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_rejections must not be negative");
+  if (!(sp->adapt_rtol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt_rtol must not be negative");
+  if (!(sp->adapt_atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt_atol must not be negative");
+  if (!(sp->dt_min >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_min must not be negative");
+  if (!(sp->dt_max >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_max must not be negative");
+  if (sp->dt_max < sp->dt_min) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_max must not be below dt_min");
+  if (sp->adapt && sp->adapt_rtol == 0 && sp->adapt_atol == 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt needs a positive adapt_rtol or adapt_atol");
+  if (int rc = nw_spec_refusal(&sp->newton)) return fail(rc, "IGXTimeStep: newton: " + std::string(g_err));
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXTimeStep()");
+  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, "the time stepper needs one rank on every axis: its norms and its Newton solve have no sum across ranks");
+  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  if (sp->newton.pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() before IGXTimeStep() with IGX_PC_FASTDIAG");
+  if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "IGXTimeStep: null U or V");
+  if (U->iga != g || V->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if (U == V) return fail(IGX_ERR_ARG_WRONG, "IGXTimeStep: U and V must be different vectors");
+  if (U->n != V->n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  if (sp->resume && !(g->timestep && g->timestep->have_prev && g->timestep->n == U->n)) return fail(IGX_ERR_ORDER, "IGXTimeStep: resume = 1 without a previous call on vectors of this length whose U_{n-1} the IGX still holds");
+  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string("the time stepper runs where its Newton solve runs, and ") + why);
+  if (int rc = ensure_device(g)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  if (U->n != n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  IGXTimeStepInfo out; memset(&out, 0, sizeof(out));
+  out.t = sp->t0; out.dt_next = sp->dt;
+  if (sp->max_steps == 0 || sp->t0 == sp->max_time) {      // nothing to do, nothing launched
+    out.reason = sp->max_steps == 0 ? IGX_TS_CONVERGED_STEPS : IGX_TS_CONVERGED_TIME;
+    if (info) *info = out;
+    return 0;
+  }
+  if (int rc = kr_scalars(g)) return rc;
+  if (!g->timestep || g->timestep->n != n) {
+    g->timestep.reset();
+    std::shared_ptr<TimeStepState> ts(new TimeStepState());
+    for (int k = 0; k < 7; ++k) {
+      std::unique_ptr<_p_IGXVec> v(new _p_IGXVec()); v->iga = g; v->n = n;
+      if (v->a.alloc((size_t)n * sizeof(double)) || hipMemset(v->a.p, 0, v->a.bytes) != hipSuccess) return fail(IGX_ERR_MEM, "device allocation of the time stepper's work vectors failed");
+      ts->work.push_back(std::move(v));
+    }
+    ts->n = n;
+    g->timestep = ts;
+  }
+  TimeStepState &st = *g->timestep;
+  if (!sp->resume) st.have_prev = false;
+  IGXVec W = st.work[0].get(), x = st.work[1].get();
+  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
+  const bool timing = g->timing;
+  if (timing) { for (auto &e : st.ev) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(st.ev[0], g->stream)); }
+  int launches = 0; double op_ms = 0; std::string nwname = "no newton solve";
+  HIPCK(hipMemcpyAsync(D(st.u0), U->a.p, U->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+  HIPCK(hipMemcpyAsync(D(st.v0), V->a.p, V->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+  const double am = sp->alpha_m, af = sp->alpha_f, gm = sp->gamma;
+  double t = sp->t0, h = sp->dt;
+  double *drec = kr_rec(g), rec[2] = {0, 0};
+  int reason = 0, rc_out = 0;
+  while (!reason) {
+    int rejections = 0;
+    for (;;) {      // the attempts of one step
+      const double p = h;
+      const double left = sp->max_time - t;
+      const bool shortened = left <= (1.0 + 1e-9) * h;      // ... or a remainder of rounding size would be left over
+      if (shortened) h = left;
+      const double a = am / (af * gm * h), c0 = 1.0 - am / gm;
+      KR_LAUNCH(ts_stage, kr_grid(n), KR_T, g, D(0), D(1), D(st.u0), D(st.v0), c0, a, n); ++launches;
+      IGXNewtonSpec ns = sp->newton; ns.op = IGX_OP_IJACOBIAN; ns.a = a; ns.t = t + af * h; ns.W = W;
+      IGXNewtonInfo ni; memset(&ni, 0, sizeof(ni));
+      if (int rc = IGXSolveNonlinear(g, &ns, x, &ni, nullptr, nullptr)) { rc_out = ts_refused(rc); break; }
+      launches += g->last_launches; if (timing) op_ms += g->last_kernel_ms;
+      nwname = g->newton->name;
+      out.newton_iterations += ni.iterations; out.linear_iterations += ni.linear_iterations; out.function_evaluations += ni.function_evaluations;
+      IGXTimeStepLog *lg = log && out.attempts < nlog ? log + out.attempts : nullptr;
+      ++out.attempts;
+      if (lg) { lg->t = t; lg->dt = h; lg->wlte = -1.0; lg->accepted = 0; lg->newton_iterations = ni.iterations; lg->newton_reason = ni.reason; lg->linear_iterations = ni.linear_iterations; }
+      if (ni.reason < 0) {      // a failed attempt
+        if (!sp->adapt) { reason = IGX_TS_DIVERGED_NONLINEAR_SOLVE; break; }
+        ++rejections; ++out.rejections; h = h / 4;
+        if (rejections > sp->max_rejections || h < sp->dt_min) { reason = IGX_TS_DIVERGED_NONLINEAR_SOLVE; break; }
+        continue;
+      }
+      const bool estimate = sp->adapt && st.have_prev;
+      TsUpdate k; memset(&k, 0, sizeof(k));
+      k.c1 = 1.0 / af; k.c2 = 1.0 / (gm * h); k.c3 = 1.0 - 1.0 / gm; k.atol = sp->adapt_atol; k.rtol = sp->adapt_rtol;
+      if (estimate) { const double r = 1.0 + st.hprev / h; k.d1 = r; k.d2 = r - 1.0; k.d3 = r * (r - 1.0); }
+      if (estimate) KR_LAUNCH(ts_update<true>, KR_G, KR_T, g, D(st.u1), D(st.v1), D(1), D(st.u0), D(st.v0), D(st.uprev), k, n, kr_slab(g, KS_A), kr_slab(g, KS_B));
+      else KR_LAUNCH(ts_update<false>, KR_G, KR_T, g, D(st.u1), D(st.v1), D(1), D(st.u0), D(st.v0), (const double *)nullptr, k, n, kr_slab(g, KS_A), kr_slab(g, KS_B));
+      KrSlabs sl; memset(&sl, 0, sizeof(sl)); sl.s[0] = kr_slab(g, KS_A); sl.s[1] = kr_slab(g, KS_B); sl.m = 2;
+      KR_LAUNCH(kr_record, 1, 64, g, sl, drec);
+      launches += 2;
+      HIPCK(hipMemcpyAsync(rec, drec, 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream)); HIPCK(hipStreamSynchronize(g->stream));
+      const double unorm = std::sqrt(rec[0]), wlte = estimate ? std::sqrt(rec[1] / (double)n) : -1.0;
+      if (lg) lg->wlte = wlte;
+      if (std::isnan(unorm) || std::isnan(wlte)) { reason = IGX_TS_DIVERGED_NAN; break; }
+      double next = p;
+      if (estimate) {
+        const double fac = wlte == 0.0 ? 10.0 : std::min(10.0, std::max(0.1, 0.9 / std::sqrt(wlte)));
+        if (!(wlte <= 1.0)) {      // rejected by the estimate
+          ++rejections; ++out.rejections; h = fac * h;
+          if (rejections > sp->max_rejections || h < sp->dt_min) { reason = IGX_TS_DIVERGED_STEP_REJECTED; break; }
+          continue;
+        }
+        if (!shortened) next = std::min(sp->dt_max, std::max(sp->dt_min, fac * h));
+      }
+      // accepted: Uprev <- U0 <- U1, V0 <- V1 by pointer
+      if (lg) lg->accepted = 1;
+      { const int old = st.uprev; st.uprev = st.u0; st.u0 = st.u1; st.u1 = old; std::swap(st.v0, st.v1); }
+      st.have_prev = true; st.hprev = h;
+      t = shortened ? sp->max_time : t + h;
+      ++out.steps; out.dt_last = h; out.unorm = unorm;
+      h = next;
+      if (t == sp->max_time) reason = IGX_TS_CONVERGED_TIME;
+      else if (out.steps == sp->max_steps) reason = IGX_TS_CONVERGED_STEPS;
+      break;
+    }
+    if (rc_out) break;
+  }
+  // the caller's U and V are written once, here: the last accepted state
+  if (out.steps > 0) {
+    (void)hipMemcpyAsync(U->a.p, D(st.u0), U->a.bytes, hipMemcpyDeviceToDevice, g->stream);
+    (void)hipMemcpyAsync(V->a.p, D(st.v0), V->a.bytes, hipMemcpyDeviceToDevice, g->stream);
+  }
+  if (rc_out) { (void)hipStreamSynchronize(g->stream); return rc_out; }
+  HIPCK(hipStreamSynchronize(g->stream));
+  char scheme[96]; snprintf(scheme, sizeof(scheme), "timestep(am=%g, af=%g, g=%g, ", am, af, gm);
+  st.name = std::string(scheme) + nwname + ", " + std::to_string(out.steps) + " steps, " + std::to_string(out.rejections) + " rejections)";
+  g->last_kernel = st.name; g->last_launches = launches;
+  if (timing) {
+    float ms = 0;
+    HIPCK(hipEventRecord(st.ev[1], g->stream)); HIPCK(hipEventSynchronize(st.ev[1])); HIPCK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
+    g->last_total_ms = ms; g->last_kernel_ms = op_ms;
+  }
+  out.reason = reason; out.t = t; out.dt_next = h;
+  if (info) *info = out;
   return 0;
 }
 #endif   // !IGX_TU_DISPATCH
