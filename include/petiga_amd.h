@@ -562,6 +562,45 @@ typedef struct { int steps, reason, rejections, attempts, newton_iterations, lin
                  double t, dt_last, dt_next, unorm; } IGXTimeStepInfo;
 int IGXTimeStep(IGX iga,const IGXTimeStepSpec *spec,IGXVec U,IGXVec V,IGXTimeStepInfo *info,IGXTimeStepLog *log,int nlog);
 
+/* Evaluation of a discrete field at arbitrary points, on the device (IGAProbe, src/petigaprobe.c; known-answer test test/IGAProbe.c): what
+ * the field an IGXVec holds -- the result of IGXSolve, IGXSolveNonlinear, IGXTimeStep -- is at a point, where coefficients are not values.
+ * IGXProbeCreate copies npts parametric points u [npts][dim] to the device and locates them there once, one launch for all points: per
+ *   axis the span of IGA_FindSpan, U[k] <= u < U[k+1] by binary search in the knot vector; the upper end of the axis belongs to the last
+ *   non-empty span, so at an interior knot the evaluation is from the right, and a knot of multiplicity > 1 never yields an empty span.
+ *   order (0..3) is the highest derivative a later call may ask for (IGAProbeSetOrder).  The probe belongs to the IGX under IGXVec's
+ *   lifetime rules (destroy it before the IGX); after another IGXSetUp it is stale and every call on it returns IGX_ERR_ORDER.  npts = 0 is
+ *   legal, launches nothing and touches no device.
+ * IGXProbeEvaluate: out [npts][dof][dim^der], entry [pt][c][i..] the derivative der (0..order) of field c, the full tensors in the layout of
+ *   IGA_GetGrad / Hess / Der3 (src/petigaprobe.c:456-462).  Derivatives are with respect to the physical coordinates when a geometry with
+ *   nsd = dim is set (rationalise -> geometry map -> inverse map -> shape functions, src/petigaprobe.c:346-423), parametric otherwise (no
+ *   geometry, or nsd != dim as in the reference); rational weights enter whenever they are set.  One launch on the engine's stream, one
+ *   point per lane over a grid capped at 2048 workgroups of 64 lanes (131072 points per turn of its grid-stride loop); the 1-D rows of
+ *   values and derivatives up to the third are computed on the device at the point, the quotient rule and the chain through the map act
+ *   once per point on the partial sums (probe.hpp).  The sum over basis functions runs in an order that depends on the
+ *   point alone and no atomics are used: a point's result is bit-identical wherever it stands in the list, whatever the other points are,
+ *   and from run to run.  The call copies the result back and synchronises.  IGXSetTiming / IGXGetLastTiming give the total time and the
+ *   kernel's own time; IGXGetKernelName gives "probe(<dim>d, p=<..>, order=<der>, <identity|polynomial|rational>, <npts> points)".
+ * IGXProbeGeomMap: x [npts][nsd], the geometry map at the points; without a geometry [npts][dim] = u (IGAProbeGeomMap).  IGXProbeGetInfo
+ *   tells nsd to a caller whose geometry came from a file (IGXRead), with the probe's npts and order.  IGXProbeCreate and IGXProbeGeomMap
+ *   are timed like IGXProbeEvaluate; a call on a probe of no points reports 0 ms and 0 launches.
+ * Several ranks: a point is evaluated by the one rank whose element box (elem_start, elem_width) holds its element; every other rank
+ *   writes zeros for it and IGXProbeGetLocal reports local = 0 there (the reference's non-collective behaviour, made unique), so adding
+ *   out over the ranks gives the full answer and the local flags partition the points.  U must hold its ghosts (IGXRefreshGhosts), as for
+ *   the actions; a periodic axis wrapped inside a rank goes through the row map the kernels use.
+ * Refusals, all decided before the first HIP call, each reason naming the probe.  IGX_ERR_ARG_WRONG: a null pointer; a vector of another
+ *   IGX or of another size (a vector of the probe's IGX changes size only through another IGXSetUp, after which the probe is stale and
+ *   IGX_ERR_ORDER comes first: the size check guards a route added later).  IGX_ERR_ARG_OUTOFRANGE: order outside 0..3 (order 4 by name: the device keeps derivative slots 0..3); der
+ *   outside 0..order; npts < 0; a point that is NaN or outside [U[p], U[n+1]] on some axis (the message gives the point's index and the
+ *   axis).  IGX_ERR_ORDER: before IGXSetUp; a stale probe.  IGX_ERR_SUP: a degree above 7 on some axis. */
+typedef struct _p_IGXProbe *IGXProbe;
+int IGXProbeCreate  (IGX iga,int order,int64_t npts,const double *u /* host [npts][dim], parametric */,IGXProbe *prb);
+int IGXProbeGetLocal(IGXProbe prb,int64_t *nlocal,unsigned char *local /* NULL or host [npts]: 1 = evaluated on this rank */);
+int IGXProbeGeomMap (IGXProbe prb,double *x /* host [npts][nsd]; no geometry: [npts][dim] = u */);
+int IGXProbeGetInfo (IGXProbe prb,int64_t *npts,int *order,int *nsd /* columns of IGXProbeGeomMap's x: the geometry's nsd, or dim */,
+                     int64_t *points_per_turn /* of the kernel's grid-stride loop */);   /* any pointer may be NULL */
+int IGXProbeEvaluate(IGXProbe prb,IGXVec U,int der,double *out /* host [npts][dof][dim^der] */);
+int IGXProbeDestroy (IGXProbe *prb);
+
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
  * ranks, and U must hold the ghost rows' values).  The point callbacks are the ones the reference's tests use:

@@ -173,6 +173,8 @@ def lib(build_if_needed=False):
         "IGXSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
         "IGXSolveNonlinear": [V, C.POINTER(IGXNewtonSpec), V, C.POINTER(IGXNewtonInfo), _dp, _ip],
         "IGXTimeStep": [V, C.POINTER(IGXTimeStepSpec), V, V, C.POINTER(IGXTimeStepInfo), C.POINTER(IGXTimeStepLog), C.c_int],
+        "IGXProbeCreate": [V, C.c_int, C.c_int64, _dp, C.POINTER(V)], "IGXProbeGetLocal": [V, C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)],
+        "IGXProbeGeomMap": [V, _dp], "IGXProbeGetInfo": [V, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)], "IGXProbeEvaluate": [V, V, C.c_int, _dp], "IGXProbeDestroy": [C.POINTER(V)],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -208,6 +210,65 @@ def lib(build_if_needed=False):
 def _ck(rc):
     if rc:
         raise IGXError(rc, lib().IGXGetLastError().decode())
+
+
+PROBE_GRID_POINTS = 2048 * 64      # points one turn of the probe kernel's grid-stride loop covers: Probe.info()["points_per_turn"] is the library's own figure
+
+
+class Probe:
+    """IGXProbe: a set of parametric points [npts, dim], located on the device once (IGX.probe).  It keeps its IGX alive."""
+
+    def __init__(self, iga, points, order=0):
+        self.iga = iga
+        self.h = C.c_void_p()
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, iga.dim)
+        assert pts.ndim == 2 and pts.shape[1] == iga.dim, "points: [npts, dim]"
+        self.npts, self.order = pts.shape[0], int(order)
+        _ck(lib().IGXProbeCreate(iga.h, int(order), self.npts, pts.ctypes.data_as(_dp) if self.npts else None, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().IGXProbeDestroy(C.byref(self.h))
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def local(self):
+        """bool [npts]: the point's element lies in this rank's element box (it is evaluated here; elsewhere it yields zeros)"""
+        flags = np.zeros(self.npts, dtype=np.uint8)
+        n = C.c_int64()
+        _ck(lib().IGXProbeGetLocal(self.h, C.byref(n), flags.ctypes.data_as(C.POINTER(C.c_ubyte)) if self.npts else None))
+        assert n.value == int(flags.sum())
+        return flags.astype(bool)
+
+    def geom_map(self):
+        """[npts, nsd]: the geometry map at the points; without a geometry the points themselves"""
+        x = np.empty((self.npts, self.info()["nsd"]))
+        _ck(lib().IGXProbeGeomMap(self.h, x.ctypes.data_as(_dp)))
+        return x
+
+    def info(self):
+        """IGXProbeGetInfo: npts, order, nsd (the columns of geom_map) and points_per_turn of the kernel's grid-stride loop"""
+        n, o, d, t = C.c_int64(), C.c_int(), C.c_int(), C.c_int64()
+        _ck(lib().IGXProbeGetInfo(self.h, C.byref(n), C.byref(o), C.byref(d), C.byref(t)))
+        return dict(npts=n.value, order=o.value, nsd=d.value, points_per_turn=t.value)
+
+    def evaluate(self, U, der=0, out=None):
+        """[npts, dof, dim, ...] (der axes of length dim): derivative der of every field of the vector U at the points"""
+        dim, dof = self.iga.dim, self.iga.dof
+        shape = (self.npts, dof) + (dim,) * max(int(der), 0)
+        if out is None:
+            out = np.empty(shape)
+        assert out.shape == shape and out.dtype == np.float64 and out.flags.c_contiguous
+        _ck(lib().IGXProbeEvaluate(self.h, U.h if U is not None else None, int(der), out.ctypes.data_as(_dp)))
+        return out
 
 
 class Vec:
@@ -615,6 +676,10 @@ class IGX:
         out["reason_name"] = TS_REASONS.get(info.reason, str(info.reason))
         out["log"] = np.frombuffer(log, dtype=TS_LOG_DTYPE, count=min(info.attempts, nlog)).copy()
         return out
+
+    def probe(self, points, order=0):
+        """IGXProbeCreate: a Probe of the parametric points [npts, dim]; order (0..3) is the highest derivative evaluate() may be asked for."""
+        return Probe(self, points, order)
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))
     def synchronize(self): _ck(lib().IGXSynchronize(self.h))
