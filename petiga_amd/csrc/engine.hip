@@ -117,7 +117,7 @@ struct _p_IGX {
   std::shared_ptr<KrylovState> krylov;                              // IGXSolve's work vectors and preconditioner storage, kept between solves
   std::shared_ptr<NewtonState> newton;                              // IGXSolveNonlinear's work vectors, kept between solves
   std::shared_ptr<TimeStepState> timestep;                          // IGXTimeStep's work vectors, U_{n-1} and h_{n-1}, kept between calls
-  std::string untimed_kernel;                                       // a call that set last_kernel without a launch to time (a probe of no points): IGXGetLastTiming keeps the zeros it stored
+  std::string self_timed;                                           // the value of last_kernel for which the call itself stored last_total_ms / last_kernel_ms (a solve loop; a probe of no points): IGXGetLastTiming keeps them
   unsigned long long setup_gen = 0;                                 // counts IGXSetUp calls: a probe made before the last one is stale (IGXProbeCreate)
 };
 
@@ -127,32 +127,7 @@ struct _p_IGXMat {
   DevBuf coo_i, coo_j;     // coordinate lists kept on the device for the hand-back (IGXMatGetCOODevice), or empty
 };
 struct _p_IGXVec { IGX iga; int64_t n; DevBuf a; };
-// IGXSolve keeps its vectors with the IGX (krylov.hpp; IGXSetUp drops them, IGXDestroy frees them)
-struct KrylovState {
-  int method = -1, pc = -1, dof = 0; int64_t n = 0;
-  std::vector<std::unique_ptr<_p_IGXVec>> work, pcv;     // r z p Ap (CG), r rhat p v s t y z (BiCGStab); the diagonal or the dof block columns
-  std::string name;                                      // the last solve's kernel name: while it is the last kernel IGXGetLastTiming reports the solve's own figures
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~KrylovState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-};
-// ... and so does IGXSolveNonlinear (newton.hpp)
-struct NewtonState {
-  int64_t n = 0; bool has_v = false;
-  std::vector<std::unique_ptr<_p_IGXVec>> work;          // F F_t d xs, and V for an IFunction
-  std::string name;                                      // the last solve's kernel name (IGXGetLastTiming, as for KrylovState)
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~NewtonState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-};
-// ... and IGXTimeStep (timestep.hpp), with what resume = 1 continues from
-struct TimeStepState {
-  int64_t n = 0;
-  std::vector<std::unique_ptr<_p_IGXVec>> work;          // W x, three rotating U (U0 U1 Uprev), two rotating V (V0 V1)
-  int u0 = 2, u1 = 3, uprev = 4, v0 = 5, v1 = 6;         // where the rotation stands
-  bool have_prev = false; double hprev = 0;              // U_{n-1} = work[uprev] and h_{n-1} of the last accepted step
-  std::string name;                                      // the last call's kernel name (IGXGetLastTiming, as for KrylovState)
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~TimeStepState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-};
+// (KrylovState, NewtonState, TimeStepState: solve_loops.hpp, the main unit)
 
 #ifndef IGX_TU_DISPATCH
 extern "C" const char *IGXGetLastError(void) { return g_err.c_str(); }
@@ -219,7 +194,7 @@ extern "C" int IGXAxisSetKnots(IGX g, int i, int m, const double U[]) { AXISCK(g
 static int apply_geometry(IGX g);
 static int apply_property(IGX g);
 extern "C" int IGXSetUp(IGX g) {
-  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; ++g->setup_gen; g->fd.reset(); g->krylov.reset(); g->newton.reset(); g->timestep.reset();
+  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; ++g->setup_gen; g->fd.reset(); g->krylov.reset(); g->newton.reset(); g->timestep.reset(); g->self_timed.clear();
   if (rc) return fail(rc, e);
   if (int rp = apply_property(g)) return rp;
   return apply_geometry(g);   // a control net given by IGXRead / an earlier IGXSetGeometry survives re-partitioning
@@ -613,8 +588,7 @@ extern "C" int IGXSetTiming(IGX g, int flag) {
 }
 extern "C" int IGXGetLastTiming(IGX g, double *total_ms, double *kernel_ms, int *launches) {
   NEEDIGA(g);
-  if (g->timing && g->ev[0] && !(g->krylov && g->krylov->name == g->last_kernel) && !(g->newton && g->newton->name == g->last_kernel) &&
-      !(g->timestep && g->timestep->name == g->last_kernel) && g->untimed_kernel != g->last_kernel) {      // (after IGXSolve / IGXSolveNonlinear / IGXTimeStep: the figures the call stored)
+  if (g->timing && g->ev[0] && g->self_timed != g->last_kernel) {      // (after IGXSolve / IGXSolveNonlinear / IGXTimeStep: the figures the call stored)
     HIPCK(hipEventSynchronize(g->ev[3]));
     float a = 0, b = 0;
     HIPCK(hipEventElapsedTime(&a, g->ev[0], g->ev[3]));
@@ -1260,6 +1234,22 @@ static int dispatch_by_dim(IGX g, const SpaceDev &S, const OutDev &out) {
 }
 
 // ------------------------------------------------------------------ the drivers
+// The overlap marks of an assembly with a communicator (IGX_OVERLAP): slab_done records "upper face of axis 2 assembled" on the engine
+// stream, face_done(axis) the same for axes 1 and 0 (IGX_OVERLAP=2: the mark of axis 2 alone, as in round 3).  Both stay empty without a
+// communicator or with the overlap off; slab_valid starts from 0 either way.
+static void overlap_marks(IGX g, IGXMat A, IGXVec b, std::function<void()> &slab_done, std::function<void(int)> &face_done) {
+  g->slab_valid = 0;
+  if (!g->comm || !g->s.env.overlap) return;
+  slab_done = [g, A, b]() {
+    if (!g->slab_ev && hipEventCreateWithFlags(&g->slab_ev, hipEventDisableTiming) != hipSuccess) return;
+    if (hipEventRecord(g->slab_ev, g->stream) == hipSuccess) { g->slab_valid |= 1; g->slab_A = A; g->slab_b = b; }
+  };
+  if (g->s.env.overlap != 2) face_done = [g, A, b](int axis) {
+    if (axis < 0 || axis > 1) return;
+    if (!g->face_ev[axis] && hipEventCreateWithFlags(&g->face_ev[axis], hipEventDisableTiming) != hipSuccess) return;
+    if (hipEventRecord(g->face_ev[axis], g->stream) == hipSuccess) { g->slab_valid |= (axis == 1 ? 2 : 4); g->slab_A = A; g->slab_b = b; }
+  };
+}
 // fused (IGXComputeFunctionJacobian / IGXComputeIFunctionIJacobian): op is the Jacobian's, b the Function's vector; one pass of the
 // walk forms both (state_pencil_kr).  *fused_done = false and nothing written when no fused kernel covers the case: the caller
 // then runs the two drivers one after the other.
@@ -1304,18 +1294,7 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
   if (g->kernel_choice != 1 && g->kernel_choice != 3 && s.form != IGX_FORM_SOURCE) {   // (a run-time form reaches the pencil walk through rtc.hpp)
     std::function<void()> slab_done;
     std::function<void(int)> face_done;
-    g->slab_valid = 0;
-    if (g->comm && s.env.overlap) {
-      slab_done = [&]() {
-        if (!g->slab_ev && hipEventCreateWithFlags(&g->slab_ev, hipEventDisableTiming) != hipSuccess) return;
-        if (hipEventRecord(g->slab_ev, g->stream) == hipSuccess) { g->slab_valid |= 1; g->slab_A = A; g->slab_b = b; }
-      };
-      if (s.env.overlap != 2) face_done = [&](int axis) {      // (IGX_OVERLAP=2: the mark of axis 2 alone, as in round 3)
-        if (axis < 0 || axis > 1) return;
-        if (!g->face_ev[axis] && hipEventCreateWithFlags(&g->face_ev[axis], hipEventDisableTiming) != hipSuccess) return;
-        if (hipEventRecord(g->face_ev[axis], g->stream) == hipSuccess) { g->slab_valid |= (axis == 1 ? 2 : 4); g->slab_A = A; g->slab_b = b; }
-      };
-    }
+    overlap_marks(g, A, b, slab_done, face_done);
     g->face_done = face_done;
     // the Tangent of a nonlinear scalar form without a geometry walks the same pencils (gram_mfma.hpp: state_pencil)
     PencilModule st; memset(&st.prm, 0, sizeof(st.prm));
@@ -1373,16 +1352,7 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
   }
   if (!done) {
     g->zero_matrix = zero_matrix;      // the feature kernel stores first touches and skips it; everything else zeroes first
-    g->slab_valid = 0;
-    if (g->comm && s.env.overlap) g->slab_done = [&]() {
-      if (!g->slab_ev && hipEventCreateWithFlags(&g->slab_ev, hipEventDisableTiming) != hipSuccess) return;
-      if (hipEventRecord(g->slab_ev, g->stream) == hipSuccess) { g->slab_valid |= 1; g->slab_A = A; g->slab_b = b; }
-    };
-    if (g->comm && s.env.overlap && s.env.overlap != 2) g->face_done = [&](int axis) {      // (run-time forms on the pencil walk: rtc.hpp; IGX_OVERLAP=2: the mark of axis 2 alone, as for the built-in forms)
-      if (axis < 0 || axis > 1) return;
-      if (!g->face_ev[axis] && hipEventCreateWithFlags(&g->face_ev[axis], hipEventDisableTiming) != hipSuccess) return;
-      if (hipEventRecord(g->face_ev[axis], g->stream) == hipSuccess) { g->slab_valid |= (axis == 1 ? 2 : 4); g->slab_A = A; g->slab_b = b; }
-    };
+    overlap_marks(g, A, b, g->slab_done, g->face_done);      // (the face marks: run-time forms on the pencil walk, rtc.hpp)
     rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
     g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
     if (rc) return rc;
@@ -1402,74 +1372,61 @@ extern "C" int IGXComputeFunction(IGX g, IGXVec U, IGXVec F) { if (!U) return fa
 extern "C" int IGXComputeJacobian(IGX g, IGXVec U, IGXMat J) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_JACOBIAN, J, nullptr, U, nullptr, 0, 0); }
 extern "C" int IGXComputeIFunction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec F) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_IFUNCTION, nullptr, F, U, V, a, t); }
 extern "C" int IGXComputeIJacobian(IGX g, double a, IGXVec V, double t, IGXVec U, IGXMat J) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_IJACOBIAN, J, nullptr, U, V, a, t); }
+// The matrix-free drivers: one pass of vec_sumfact (vec_sumfact.hpp) over the elements with the op's instantiation -- ACTION, DIAGONAL or
+// DIAGONAL + BLOCK -- or a refusal with IGX_ERR_SUP: there is no other kernel.  The nres result columns R are zeroed and assembled like
+// vectors; on several ranks X, U and V hold their ghosts and one IGXReduceGhostRows(iga, NULL, R[j]) per column completes the ghost rows.
+// The nine entries below check their own arguments; what they share is here, once.
+static int compute_matfree(IGX g, int op, IGXVec U, IGXVec V, IGXVec X, int nres, IGXVec *R, double shift, double t) {
+  const bool block = op_is_block_diagonal(op);
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  for (int j = 0; j < nres; ++j) if ((U && U == R[j]) || (V && V == R[j])) return fail(IGX_ERR_ARG_WRONG, block ? "a block column must not be a state vector" : "the result must not be a state vector");
+  if (int rc = ensure_device(g)) return rc;
+  const Space &s = g->s;
+  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  OutDev out; memset(&out, 0, sizeof(out));
+  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
+  if (block) for (int j = 0; j < nres; ++j) out.bcol[j] = R[j]->a.as<double>();
+  out.vec = R[0]->a.as<double>(); out.X = X ? X->a.as<double>() : nullptr;
+  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
+  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
+  for (int j = 0; j < nres; ++j) HIPCK(hipMemsetAsync(R[j]->a.p, 0, R[j]->a.bytes, g->stream));
+  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
+  const SpaceDev S = make_spacedev(g);
+  g->dom = DomInfo(); g->slab_valid = 0;
+  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
+  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
+  if (rc) return rc;
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
+  return 0;
+}
 // Matrix-free actions: Y = A X with A the matrix IGXComputeSystem (IGXComputeMatrix's K with the fix-up of IGAElementFixSystem) / Jacobian /
-// IJacobian would assemble on this rank, IGAElementFixJacobian included (a fixed column takes nothing, a fixed row receives X_row once per local element that holds the node).  Y is zeroed and
-// assembled like a vector; on several ranks X holds its ghosts and IGXReduceGhostRows(iga, NULL, Y) completes the ghost rows.  The
-// product is formed by vec_sumfact's ACTION instantiation (vec_sumfact.hpp) or refused with IGX_ERR_SUP: there is no other kernel.
-static int compute_action(IGX g, int op, IGXVec U, IGXVec V, IGXVec X, IGXVec Y, double shift, double t) {
+// IJacobian would assemble on this rank, IGAElementFixJacobian included (a fixed column takes nothing, a fixed row receives X_row once per
+// local element that holds the node).  No matrix is formed.
+static int action_args(IGX g, IGXVec X, IGXVec Y) {
   NEEDIGA(g);
   if (!X || !Y) return fail(IGX_ERR_ARG_WRONG, "null direction or result vector");
   if (X == Y) return fail(IGX_ERR_ARG_WRONG, "the direction and the result must be different vectors");
   if (X->iga != g || Y->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
-  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
-  if ((U && U == Y) || (V && V == Y)) return fail(IGX_ERR_ARG_WRONG, "the result must not be a state vector");
-  if (int rc = ensure_device(g)) return rc;
-  const Space &s = g->s;
-  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
-  OutDev out; memset(&out, 0, sizeof(out));
-  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
-  out.vec = Y->a.as<double>(); out.X = X->a.as<double>();
-  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
-  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
-  HIPCK(hipMemsetAsync(Y->a.p, 0, Y->a.bytes, g->stream));
-  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
-  const SpaceDev S = make_spacedev(g);
-  g->dom = DomInfo(); g->slab_valid = 0;
-  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
-  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
-  if (rc) return rc;
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
   return 0;
 }
-extern "C" int IGXComputeMatrixAction(IGX g, IGXVec X, IGXVec Y) { return compute_action(g, OP_MATRIX_ACTION, nullptr, nullptr, X, Y, 0, 0); }
-extern "C" int IGXComputeJacobianAction(IGX g, IGXVec U, IGXVec X, IGXVec Y) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_action(g, OP_JACOBIAN_ACTION, U, nullptr, X, Y, 0, 0); }
-extern "C" int IGXComputeIJacobianAction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec X, IGXVec Y) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_action(g, OP_IJACOBIAN_ACTION, U, V, X, Y, a, t); }
+extern "C" int IGXComputeMatrixAction(IGX g, IGXVec X, IGXVec Y) { if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_MATRIX_ACTION, nullptr, nullptr, X, 1, &Y, 0, 0); }
+extern "C" int IGXComputeJacobianAction(IGX g, IGXVec U, IGXVec X, IGXVec Y) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_JACOBIAN_ACTION, U, nullptr, X, 1, &Y, 0, 0); }
+extern "C" int IGXComputeIJacobianAction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec X, IGXVec Y) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_IJACOBIAN_ACTION, U, V, X, 1, &Y, a, t); }
 
 // Matrix-free diagonals: D = diag A of the matrix the matching action applies (IGAElementFixJacobian included: a fixed dof holds the
-// number of local elements at its node), formed by vec_sumfact's DIAGONAL instantiation (vec_sumfact.hpp) or refused with IGX_ERR_SUP.
-// D is zeroed and assembled like a vector; on several ranks U and V hold their ghosts and IGXReduceGhostRows(iga, NULL, D) completes the ghost rows.
-static int compute_diagonal(IGX g, int op, IGXVec U, IGXVec V, IGXVec D, double shift, double t) {
+// number of local elements at its node): what a Jacobi or Chebyshev preconditioner of the shell matrix needs.
+static int diagonal_args(IGX g, IGXVec D) {
   NEEDIGA(g);
   if (!D) return fail(IGX_ERR_ARG_WRONG, "null result vector");
   if (D->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
-  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
-  if ((U && U == D) || (V && V == D)) return fail(IGX_ERR_ARG_WRONG, "the result must not be a state vector");
-  if (int rc = ensure_device(g)) return rc;
-  const Space &s = g->s;
-  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
-  OutDev out; memset(&out, 0, sizeof(out));
-  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
-  out.vec = D->a.as<double>();
-  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
-  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
-  HIPCK(hipMemsetAsync(D->a.p, 0, D->a.bytes, g->stream));
-  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
-  const SpaceDev S = make_spacedev(g);
-  g->dom = DomInfo(); g->slab_valid = 0;
-  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
-  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
-  if (rc) return rc;
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
   return 0;
 }
-extern "C" int IGXComputeMatrixDiagonal(IGX g, IGXVec D) { return compute_diagonal(g, OP_MATRIX_DIAGONAL, nullptr, nullptr, D, 0, 0); }
-extern "C" int IGXComputeJacobianDiagonal(IGX g, IGXVec U, IGXVec D) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_diagonal(g, OP_JACOBIAN_DIAGONAL, U, nullptr, D, 0, 0); }
-extern "C" int IGXComputeIJacobianDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec D) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_diagonal(g, OP_IJACOBIAN_DIAGONAL, U, V, D, a, t); }
+extern "C" int IGXComputeMatrixDiagonal(IGX g, IGXVec D) { if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, OP_MATRIX_DIAGONAL, nullptr, nullptr, nullptr, 1, &D, 0, 0); }
+extern "C" int IGXComputeJacobianDiagonal(IGX g, IGXVec U, IGXVec D) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, OP_JACOBIAN_DIAGONAL, U, nullptr, nullptr, 1, &D, 0, 0); }
+extern "C" int IGXComputeIJacobianDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec D) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, OP_IJACOBIAN_DIAGONAL, U, V, nullptr, 1, &D, a, t); }
 
 // Matrix-free point-block diagonals: the dof x dof blocks A_(a,i),(a,j) of every node a of the same operator (what PCPBJACOBI /
 // MatInvertBlockDiagonal ask of a shell matrix), in dof ordinary vectors, one per block column: B[j][node * dof + i] = A_(node,i),(node,j).
-// vec_sumfact's DIAGONAL + BLOCK instantiation (vec_sumfact.hpp) or a refusal with IGX_ERR_SUP; the columns are zeroed and assembled like
-// vectors, and one IGXReduceGhostRows(iga, NULL, B[j]) per column completes the owned rows on several ranks.
 static int check_block_columns(IGX g, int nb, IGXVec *B) {
   if (nb != g->s.dof) return fail(IGX_ERR_ARG_WRONG, "the block diagonal has dof columns: nb must equal dof");
   if (nb < 1 || nb > MAXBC) return fail(IGX_ERR_ARG_WRONG, "the block diagonal needs dof <= 8");
@@ -1481,33 +1438,9 @@ static int check_block_columns(IGX g, int nb, IGXVec *B) {
   }
   return 0;
 }
-static int compute_block_diagonal(IGX g, int op, IGXVec U, IGXVec V, int nb, IGXVec *B, double shift, double t) {
-  NEEDIGA(g);
-  if (int rc = check_block_columns(g, nb, B)) return rc;
-  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
-  for (int j = 0; j < nb; ++j) if ((U && U == B[j]) || (V && V == B[j])) return fail(IGX_ERR_ARG_WRONG, "a block column must not be a state vector");
-  if (int rc = ensure_device(g)) return rc;
-  const Space &s = g->s;
-  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
-  OutDev out; memset(&out, 0, sizeof(out));
-  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
-  for (int j = 0; j < nb; ++j) out.bcol[j] = B[j]->a.as<double>();
-  out.vec = out.bcol[0];
-  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
-  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
-  for (int j = 0; j < nb; ++j) HIPCK(hipMemsetAsync(B[j]->a.p, 0, B[j]->a.bytes, g->stream));
-  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
-  const SpaceDev S = make_spacedev(g);
-  g->dom = DomInfo(); g->slab_valid = 0;
-  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
-  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
-  if (rc) return rc;
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
-  return 0;
-}
-extern "C" int IGXComputeMatrixBlockDiagonal(IGX g, int nb, IGXVec *B) { return compute_block_diagonal(g, OP_MATRIX_BLOCK_DIAGONAL, nullptr, nullptr, nb, B, 0, 0); }
-extern "C" int IGXComputeJacobianBlockDiagonal(IGX g, IGXVec U, int nb, IGXVec *B) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_block_diagonal(g, OP_JACOBIAN_BLOCK_DIAGONAL, U, nullptr, nb, B, 0, 0); }
-extern "C" int IGXComputeIJacobianBlockDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, int nb, IGXVec *B) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute_block_diagonal(g, OP_IJACOBIAN_BLOCK_DIAGONAL, U, V, nb, B, a, t); }
+extern "C" int IGXComputeMatrixBlockDiagonal(IGX g, int nb, IGXVec *B) { NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, OP_MATRIX_BLOCK_DIAGONAL, nullptr, nullptr, nullptr, nb, B, 0, 0); }
+extern "C" int IGXComputeJacobianBlockDiagonal(IGX g, IGXVec U, int nb, IGXVec *B) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, OP_JACOBIAN_BLOCK_DIAGONAL, U, nullptr, nullptr, nb, B, 0, 0); }
+extern "C" int IGXComputeIJacobianBlockDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, int nb, IGXVec *B) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, OP_IJACOBIAN_BLOCK_DIAGONAL, U, V, nullptr, nb, B, a, t); }
 
 // The blocks as a preconditioner (block_diag.hpp): B <- B^-1 block by block in place (every local row; on several ranks after the
 // reduction and a refresh of each column), and Y_node = B_node X_node.  nsingular: the number of blocks with a zero or non-finite pivot,
@@ -1794,575 +1727,10 @@ extern "C" int IGXGetClockProbe(IGX g, double *shader_mhz, int64_t *elements) {
 #include "fileio.hpp"
 #include "rtc.hpp"
 
-// ------------------------------------------------------------------ vector algebra on IGXVec and the Krylov loop (krylov.hpp)
-// (the last thing in the unit: every kernel above is compiled as it was before these existed)
-#include "krylov.hpp"
-// Everything is enqueued on the engine's stream; IGXVecDot / IGXVecNorm2 read their result back and so synchronise.  The sums run over the
-// rows this rank owns (a prefix of the row box on every axis, as in IGXChecksum): on several ranks the caller adds the parts.
-static int kr_scalars(IGX g) {
-  if (g->krscal.p) return 0;
-  if (g->krscal.alloc(KR_SCAL_DOUBLES * sizeof(double))) return fail(IGX_ERR_MEM, "device allocation of the partial-sum slabs failed");
-  HIPCK(hipMemset(g->krscal.p, 0, g->krscal.bytes));
-  return 0;
-}
-static double *kr_slab(IGX g, int k) { return g->krscal.as<double>() + (size_t)k * KR_G; }
-static double *kr_rec(IGX g) { return g->krscal.as<double>() + (size_t)KR_NSLAB * KR_G; }
-static int kr_vec_args(IGXVec a, IGXVec b = nullptr, IGXVec c = nullptr, bool three = false, bool two = false) {
-  if (!a || ((two || three) && !b) || (three && !c)) return fail(IGX_ERR_ARG_WRONG, "null vector");
-  if ((b && b->iga != a->iga) || (c && c->iga != a->iga)) return fail(IGX_ERR_ARG_WRONG, "vectors created by different IGX");
-  if ((b && b->n != a->n) || (c && c->n != a->n)) return fail(IGX_ERR_ARG_WRONG, "vectors of different sizes");
-  return 0;
-}
-#define KR_LAUNCH(kernel, grid, block, g, ...) do { hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (g)->stream, __VA_ARGS__); if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, #kernel ": kernel launch failed"); } while (0)
-extern "C" int IGXVecSet(IGXVec y, double value) {
-  if (int rc = kr_vec_args(y)) return rc;
-  y->iga->slab_valid = 0;
-  KR_LAUNCH(kr_set, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), value, (long long)y->n);
-  return 0;
-}
-extern "C" int IGXVecCopy(IGXVec x, IGXVec y) {
-  if (int rc = kr_vec_args(x, y, nullptr, false, true)) return rc;
-  y->iga->slab_valid = 0;
-  if (x != y) HIPCK(hipMemcpyAsync(y->a.p, x->a.p, x->a.bytes, hipMemcpyDeviceToDevice, y->iga->stream));
-  return 0;
-}
-extern "C" int IGXVecScale(IGXVec y, double a) {
-  if (int rc = kr_vec_args(y)) return rc;
-  y->iga->slab_valid = 0;
-  KR_LAUNCH(kr_scale, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), a, (long long)y->n);
-  return 0;
-}
-extern "C" int IGXVecAXPBY(IGXVec y, double a, IGXVec x, double b) {
-  if (int rc = kr_vec_args(y, x, nullptr, false, true)) return rc;
-  y->iga->slab_valid = 0;
-  KR_LAUNCH(kr_axpby, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), a, x->a.as<double>(), b, (long long)y->n);
-  return 0;
-}
-extern "C" int IGXVecPointwiseDivide(IGXVec z, IGXVec x, IGXVec d) {
-  if (int rc = kr_vec_args(z, x, d, true)) return rc;
-  z->iga->slab_valid = 0;
-  KR_LAUNCH(kr_pdiv, kr_grid(z->n), KR_T, z->iga, z->a.as<double>(), x->a.as<double>(), d->a.as<double>(), (long long)z->n);
-  return 0;
-}
-extern "C" int IGXVecDot(IGXVec x, IGXVec y, double *s) {
-  if (int rc = kr_vec_args(x, y, nullptr, false, true)) return rc;
-  if (!s) return fail(IGX_ERR_ARG_WRONG, "null result");
-  IGX g = x->iga;
-  if (int rc = kr_scalars(g)) return rc;
-  const Space &sp = g->s;
-  int nown[3]; bool all = true;
-  for (int d = 0; d < 3; ++d) {
-    const AxisLayout &L = sp.lay[d]; nown[d] = 0;
-    for (int r = 0; r < L.nrow; ++r) if (L.owned[r]) { if (nown[d] != r) return fail(IGX_ERR_PLIB, "owned rows are not a prefix of the row box"); nown[d]++; }
-    if (nown[d] != L.nrow) all = false;
-  }
-  double *slab = kr_slab(g, KS_USER), *rec = kr_rec(g);
-  if (all) KR_LAUNCH(kr_dot, KR_G, KR_T, g, x->a.as<double>(), y->a.as<double>(), (long long)x->n, slab);
-  else KR_LAUNCH(kr_dot_owned, KR_G, KR_T, g, x->a.as<double>(), y->a.as<double>(), nown[0], nown[1], nown[2], sp.lay[0].nrow, sp.lay[1].nrow, sp.dof, slab);
-  KrSlabs sl; memset(&sl, 0, sizeof(sl)); sl.s[0] = slab; sl.m = 1;
-  KR_LAUNCH(kr_record, 1, 64, g, sl, rec);
-  HIPCK(hipMemcpyAsync(s, rec, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-  HIPCK(hipStreamSynchronize(g->stream));
-  return 0;
-}
-extern "C" int IGXVecNorm2(IGXVec x, double *s) {
-  if (int rc = IGXVecDot(x, x, s)) return rc;
-  *s = std::sqrt(*s);
-  return 0;
-}
-
-// IGXSolve.  The operator is the action driver's internal entry (compute_action) at the state of the specification, the preconditioners
-// are the diagonal drivers' (compute_diagonal, compute_block_diagonal, block_diagonal_run) and IGXFastDiagApply: whatever they refuse the
-// solve refuses, with their reason under its own name.  The loops and their kernels: krylov.hpp.
-static const char *kr_solve_refusal(IGX g) {
-  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return "the Krylov solve needs one rank on every axis: the library has no sum across ranks (IGXVecDot gives each rank's part)";
-  return nullptr;
-}
-static int kr_refused(int rc) { return rc == IGX_ERR_SUP ? fail(rc, "the Krylov solve runs where its operator and its preconditioner run, and " + std::string(g_err)) : rc; }
-static bool kr_bad_host(double d) { return !(std::fabs(d) > 0.0) || !std::isfinite(d); }
-extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSolveInfo *info, double *history) {
-  NEEDIGA(g);
-  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null solve specification");
-  if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown method");
-  if (sp->op < IGX_OP_MATRIX || sp->op > IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown operator");
-  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown preconditioner");
-  if (sp->maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: maxit must not be negative");
-  if (!(sp->rtol >= 0) || !(sp->atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: the tolerances must not be negative");
-  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXSolve()");
-  if (const char *why = kr_solve_refusal(g)) return fail(IGX_ERR_SUP, why);
-  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
-  if (!b || !x) return fail(IGX_ERR_ARG_WRONG, "null right-hand side or solution vector");
-  if (b->iga != g || x->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
-  if (x == b) return fail(IGX_ERR_ARG_WRONG, "the solution and the right-hand side must be different vectors");
-  IGXVec U = sp->op == IGX_OP_MATRIX ? nullptr : sp->U, V = sp->op == IGX_OP_IJACOBIAN ? sp->V : nullptr;
-  if (sp->op != IGX_OP_MATRIX && !U) return fail(IGX_ERR_ARG_WRONG, "null state vector");
-  if (sp->op == IGX_OP_IJACOBIAN && !V) return fail(IGX_ERR_ARG_WRONG, "null state vector");
-  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
-  if ((U && U == x) || (V && V == x)) return fail(IGX_ERR_ARG_WRONG, "the solution must not be a state vector");
-  if (sp->pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() before IGXSolve() with IGX_PC_FASTDIAG");
-  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string("the Krylov solve runs where its operator and its preconditioner run, and ") + why);
-  if (int rc = ensure_device(g)) return rc;
-  const long long n = (long long)g->nbrows * g->s.dof;
-  if (b->n != n || x->n != n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
-  if (int rc = kr_scalars(g)) return rc;
-  const bool cg = sp->method == IGX_SOLVE_CG;
-  const int dof = g->s.dof, pc = sp->pc;
-  const double shift = sp->op == IGX_OP_IJACOBIAN ? sp->a : 0.0, t = sp->op == IGX_OP_IJACOBIAN ? sp->t : 0.0;
-  // work vectors: kept while the method and the preconditioner need the same set
-  if (!g->krylov || g->krylov->method != sp->method || g->krylov->pc != pc || g->krylov->dof != dof || g->krylov->n != n) {
-    g->krylov.reset();
-    std::shared_ptr<KrylovState> st(new KrylovState());
-    auto add = [&](std::vector<std::unique_ptr<_p_IGXVec>> &to) {
-      std::unique_ptr<_p_IGXVec> v(new _p_IGXVec()); v->iga = g; v->n = n;
-      if (v->a.alloc((size_t)n * sizeof(double)) || hipMemset(v->a.p, 0, v->a.bytes) != hipSuccess) return 1;
-      to.push_back(std::move(v)); return 0;
-    };
-    for (int k = 0; k < (cg ? 4 : 8); ++k) if (add(st->work)) return fail(IGX_ERR_MEM, "device allocation of the Krylov work vectors failed");
-    for (int k = 0; k < (pc == IGX_PC_JACOBI ? 1 : pc == IGX_PC_PBJACOBI ? dof : 0); ++k) if (add(st->pcv)) return fail(IGX_ERR_MEM, "device allocation of the preconditioner's vectors failed");
-    st->method = sp->method; st->pc = pc; st->dof = dof; st->n = n;
-    g->krylov = st;
-  }
-  KrylovState &st = *g->krylov;
-  const bool timing = g->timing;
-  if (timing) { for (auto &e : st.ev) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(st.ev[0], g->stream)); }
-  int launches = 0; double op_ms = 0; std::string opname;
-  auto account = [&](int own) -> int {      // after a driver's entry (own = 0: its launches and, timed, its kernel time) or own launches of this loop
-    if (own) { launches += own; return 0; }
-    launches += g->last_launches;
-    if (timing) { float ms = 0; HIPCK(hipEventSynchronize(g->ev[2])); HIPCK(hipEventElapsedTime(&ms, g->ev[1], g->ev[2])); op_ms += ms; }
-    return 0;
-  };
-  const int actop = sp->op == IGX_OP_MATRIX ? OP_MATRIX_ACTION : sp->op == IGX_OP_JACOBIAN ? OP_JACOBIAN_ACTION : OP_IJACOBIAN_ACTION;
-  auto A = [&](IGXVec in, IGXVec out) -> int {
-    if (int rc = compute_action(g, actop, U, V, in, out, shift, t)) return kr_refused(rc);
-    if (opname.empty()) opname = g->last_kernel;
-    return account(0);
-  };
-  std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
-  if (pc == IGX_PC_JACOBI) {
-    const int dop = sp->op == IGX_OP_MATRIX ? OP_MATRIX_DIAGONAL : sp->op == IGX_OP_JACOBIAN ? OP_JACOBIAN_DIAGONAL : OP_IJACOBIAN_DIAGONAL;
-    if (int rc = compute_diagonal(g, dop, U, V, cols[0], shift, t)) return kr_refused(rc);
-    if (int rc = account(0)) return rc;
-  } else if (pc == IGX_PC_PBJACOBI) {
-    const int bop = sp->op == IGX_OP_MATRIX ? OP_MATRIX_BLOCK_DIAGONAL : sp->op == IGX_OP_JACOBIAN ? OP_JACOBIAN_BLOCK_DIAGONAL : OP_IJACOBIAN_BLOCK_DIAGONAL;
-    if (int rc = compute_block_diagonal(g, bop, U, V, dof, cols.data(), shift, t)) return kr_refused(rc);
-    if (int rc = account(0)) return rc;
-    if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return kr_refused(rc);
-    if (int rc = account(0)) return rc;
-  }
-  // out = M^-1 in (IGX_PC_NONE: the caller aliases the two)
-  auto M = [&](IGXVec in, IGXVec out) -> int {
-    if (pc == IGX_PC_NONE) return 0;
-    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); return account(1); }
-    if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return kr_refused(rc);
-    return account(0);
-  };
-  double rec[KR_NREC];
-  double *drec = kr_rec(g), *dsc = drec + KR_NREC;
-  auto read_record = [&](int m) -> int { HIPCK(hipMemcpyAsync(rec, drec, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->stream)); HIPCK(hipStreamSynchronize(g->stream)); return 0; };
-  auto record = [&](std::initializer_list<int> slabs) -> int {
-    KrSlabs sl; memset(&sl, 0, sizeof(sl));
-    for (int k : slabs) sl.s[sl.m++] = kr_slab(g, k);
-    KR_LAUNCH(kr_record, 1, 64, g, sl, drec);
-    if (int rc = account(1)) return rc;
-    return read_record(sl.m);
-  };
-  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
-  double *xd = x->a.as<double>(); const double *bd = b->a.as<double>();
-  g->slab_valid = 0;
-  int its = 0, reason = 0;
-  double bnorm = 0, rnorm = 0, rnorm0 = 0, thr = 0;
-  // r = b - A x with |r| and |b|, shared by both methods: the product goes to work vector 3 (Ap / v), r is work vector 0
-  if (int rc = A(x, st.work[3].get())) return rc;
-  KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), bd, D(3), n, kr_slab(g, KS_RR), kr_slab(g, KS_BB));
-  account(1);
-  auto stop = [&]() {      // the test of the recurrence residual, 0 to go on
-    if (std::isnan(rnorm)) return (int)IGX_DIVERGED_NAN;
-    if (rnorm <= thr) return (int)(rnorm <= sp->rtol * bnorm ? IGX_CONVERGED_RTOL : IGX_CONVERGED_ATOL);
-    if (its >= sp->maxit) return (int)IGX_DIVERGED_ITS;
-    return 0;
-  };
-  auto start = [&]() -> bool {      // after the first record (rec[0] = r.r, rec[1] = b.b): true when the loop has something to do
-    bnorm = std::sqrt(rec[1]); rnorm0 = rnorm = std::sqrt(rec[0]); thr = std::max(sp->rtol * bnorm, sp->atol);
-    if (history) history[0] = rnorm;
-    if (std::isnan(bnorm)) { reason = IGX_DIVERGED_NAN; return false; }
-    if (bnorm == 0.0) { reason = IGX_CONVERGED_ATOL; return false; }
-    return true;
-  };
-  if (cg) {
-    IGXVec r = st.work[0].get(), z = pc == IGX_PC_NONE ? r : st.work[1].get(), p = st.work[2].get(), Ap = st.work[3].get();
-    int cur = 0;      // KS_A + cur holds the newest r.z, KS_A + 1 - cur the one before; KS_C holds p.Ap
-    auto precondition = [&](int slab) -> int {
-      if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, z->a.as<double>(), r->a.as<double>(), cols[0]->a.as<double>(), n, kr_slab(g, slab)); return account(1); }
-      if (int rc = M(r, z)) return rc;
-      KR_LAUNCH(kr_dot, KR_G, KR_T, g, r->a.as<double>(), z->a.as<double>(), n, kr_slab(g, slab));
-      return account(1);
-    };
-    if (int rc = precondition(KS_A)) return rc;
-    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
-    double rz = rec[2];
-    if (start()) {
-      HIPCK(hipMemcpyAsync(p->a.p, z->a.p, z->a.bytes, hipMemcpyDeviceToDevice, g->stream));
-      while (!(reason = stop())) {
-        if (kr_bad_host(rz)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
-        if (its > 0) { KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, p->a.as<double>(), z->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_A + 1 - cur)); account(1); }
-        if (int rc = A(p, Ap)) return rc;
-        KR_LAUNCH(kr_dot, KR_G, KR_T, g, p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C));
-        KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C), kr_slab(g, KS_A + cur), kr_slab(g, KS_RR));
-        account(2);
-        cur ^= 1;
-        if (int rc = precondition(KS_A + cur)) return rc;
-        if (int rc = record({KS_RR, KS_C, KS_A + cur})) return rc;
-        if (!(rec[1] > 0.0) || !std::isfinite(rec[1])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // p.Ap <= 0: the update kernel left x and r alone
-        ++its; rnorm = std::sqrt(rec[0]); rz = rec[2];
-        if (history) history[its] = rnorm;
-      }
-    }
-  } else {
-    IGXVec r = st.work[0].get(), rhat = st.work[1].get(), p = st.work[2].get(), v = st.work[3].get(), s = st.work[4].get(), tv = st.work[5].get();
-    IGXVec y = pc == IGX_PC_NONE ? p : st.work[6].get(), z = pc == IGX_PC_NONE ? s : st.work[7].get();
-    int cur = 0;      // KS_A + cur holds rho' = rhat.r of the iteration at hand; KS_C rhat.v, KS_D t.s, KS_E t.t
-    static const double one3[3] = {1.0, 1.0, 1.0};
-    HIPCK(hipMemcpyAsync(rhat->a.p, r->a.p, r->a.bytes, hipMemcpyDeviceToDevice, g->stream));
-    KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), r->a.as<double>(), n, kr_slab(g, KS_A));
-    account(1);
-    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
-    double rho_next = rec[2], omega = 1.0;
-    if (start()) {
-      HIPCK(hipMemsetAsync(v->a.p, 0, v->a.bytes, g->stream));
-      HIPCK(hipMemsetAsync(p->a.p, 0, p->a.bytes, g->stream));
-      HIPCK(hipMemcpyAsync(dsc, one3, sizeof(one3), hipMemcpyHostToDevice, g->stream));
-      while (!(reason = stop())) {
-        if (kr_bad_host(rho_next) || kr_bad_host(omega)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
-        KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), dsc);
-        account(1);
-        if (int rc = M(p, y)) return rc;
-        if (int rc = A(y, v)) return rc;
-        KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_C));
-        KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_C));
-        account(2);
-        if (int rc = M(s, z)) return rc;
-        if (int rc = A(z, tv)) return rc;
-        KR_LAUNCH(kr_dot2, KR_G, KR_T, g, tv->a.as<double>(), s->a.as<double>(), n, kr_slab(g, KS_D), kr_slab(g, KS_E));
-        KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(), n,
-                  kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_RR), kr_slab(g, KS_A + 1 - cur));
-        KR_LAUNCH(kr_bicg_record, 1, 64, g, kr_slab(g, KS_RR), kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_A + 1 - cur), drec, dsc);
-        account(3);
-        if (int rc = read_record(7)) return rc;
-        cur ^= 1;
-        if (kr_bad_host(rec[1]) || kr_bad_host(rec[2])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // rhat.v or t.t: the update kernel left x and r alone
-        ++its; rnorm = std::sqrt(rec[0]); rho_next = rec[4]; omega = rec[6];
-        if (history) history[its] = rnorm;
-      }
-    }
-  }
-  if (reason == IGX_CONVERGED_ATOL && bnorm == 0.0) {      // b = 0: the solution is 0
-    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, xd, 0.0, n);
-    account(1);
-    rnorm0 = rnorm = 0.0; if (history) history[0] = 0.0;
-    HIPCK(hipStreamSynchronize(g->stream));
-  }
-  static const char *const methods[2] = {"cg", "bicgstab"}, *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
-  st.name = std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)";
-  g->last_kernel = st.name; g->last_launches = launches;
-  if (timing) {
-    float ms = 0;
-    HIPCK(hipEventRecord(st.ev[1], g->stream)); HIPCK(hipEventSynchronize(st.ev[1])); HIPCK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
-    g->last_total_ms = ms; g->last_kernel_ms = op_ms;
-  }
-  if (info) { info->iterations = its; info->reason = reason; info->rnorm0 = rnorm0; info->rnorm = rnorm; info->bnorm = bnorm; }
-  return 0;
-}
-
-// ------------------------------------------------------------------ the Newton loop (newton.hpp)
-#include "newton.hpp"
-// IGXSolveNonlinear.  The residual is the vector driver's internal entry (compute: what IGXComputeFunction / IGXComputeIFunction call), the
-// linear solve is IGXSolve itself: whatever they refuse the Newton solve refuses, with their reason under its own name.  The loop is the
-// one the header states; between two operator calls a trial is one sweep of newton.hpp.
-static int nw_refused(int rc) { return rc == IGX_ERR_SUP ? fail(rc, "the Newton solve runs where its residual and its linear solve run, and " + std::string(g_err)) : rc; }
-// what the specification alone decides (IGXTimeStep asks the same of the spec it passes on)
-static int nw_spec_refusal(const IGXNewtonSpec *sp) {
-  if (sp->op == IGX_OP_MATRIX) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: a linear operator has no Newton loop (IGX_OP_MATRIX: call IGXSolve)");
-  if (sp->op != IGX_OP_JACOBIAN && sp->op != IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown operator");
-  if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown method");
-  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown preconditioner");
-  if (sp->linesearch != IGX_LINESEARCH_BASIC && sp->linesearch != IGX_LINESEARCH_BT) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown line search");
-  if (sp->forcing != IGX_FORCING_CONSTANT && sp->forcing != IGX_FORCING_EW2) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown forcing");
-  if (!(sp->lin_rtol >= 0) || !(sp->lin_atol >= 0) || !(sp->rtol >= 0) || !(sp->atol >= 0) || !(sp->stol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: the tolerances must not be negative");
-  if (sp->maxit < 0 || sp->lin_maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: maxit and lin_maxit must not be negative");
-  if (sp->max_backtracks < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: max_backtracks must not be negative");
-  return 0;
-}
-extern "C" int IGXSolveNonlinear(IGX g, const IGXNewtonSpec *sp, IGXVec x, IGXNewtonInfo *info, double *history, int *linear_its) {
-  NEEDIGA(g);
-  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null Newton specification");
-  if (int rc = nw_spec_refusal(sp)) return rc;
-  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXSolveNonlinear()");
-  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, "the Newton solve needs one rank on every axis: its norms and its linear solve have no sum across ranks");
-  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
-  if (sp->pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() before IGXSolveNonlinear() with IGX_PC_FASTDIAG");
-  const bool ifun = sp->op == IGX_OP_IJACOBIAN;
-  IGXVec W = ifun ? sp->W : nullptr;
-  if (ifun && !W) return fail(IGX_ERR_ARG_WRONG, "IGXSolveNonlinear: IGX_OP_IJACOBIAN needs the vector W of V = a U + W");
-  if (!x) return fail(IGX_ERR_ARG_WRONG, "null solution vector");
-  if (x->iga != g || (W && W->iga != g)) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
-  if (W == x) return fail(IGX_ERR_ARG_WRONG, "W and the solution must be different vectors");
-  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string("the Newton solve runs where its residual and its linear solve run, and ") + why);
-  if (int rc = ensure_device(g)) return rc;
-  const long long n = (long long)g->nbrows * g->s.dof;
-  if (x->n != n || (W && W->n != n)) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
-  if (int rc = kr_scalars(g)) return rc;
-  if (!g->newton || g->newton->n != n || g->newton->has_v != ifun) {
-    g->newton.reset();
-    std::shared_ptr<NewtonState> ns(new NewtonState());
-    for (int k = 0; k < (ifun ? 5 : 4); ++k) {
-      std::unique_ptr<_p_IGXVec> v(new _p_IGXVec()); v->iga = g; v->n = n;
-      if (v->a.alloc((size_t)n * sizeof(double)) || hipMemset(v->a.p, 0, v->a.bytes) != hipSuccess) return fail(IGX_ERR_MEM, "device allocation of the Newton work vectors failed");
-      ns->work.push_back(std::move(v));
-    }
-    ns->n = n; ns->has_v = ifun;
-    g->newton = ns;
-  }
-  NewtonState &st = *g->newton;
-  IGXVec F = st.work[0].get(), Ft = st.work[1].get(), d = st.work[2].get(), xs = st.work[3].get(), V = ifun ? st.work[4].get() : nullptr;
-  const bool timing = g->timing, bt = sp->linesearch == IGX_LINESEARCH_BT;
-  if (timing) { for (auto &e : st.ev) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(st.ev[0], g->stream)); }
-  int launches = 0; double op_ms = 0; std::string linname = "no linear solve";
-  double *xd = x->a.as<double>(), *Vd = V ? V->a.as<double>() : nullptr; const double *Wd = W ? W->a.as<double>() : nullptr;
-  const double shift = ifun ? sp->a : 0.0, t = ifun ? sp->t : 0.0;
-  double *drec = kr_rec(g), rec[3] = {0, 0, 0};
-  int evals = 0;
-  // F_out = G(x) with the state V as the last sweep left it; rec = (F.F, d.d, x.x), the last two only after a trial sweep
-  auto residual = [&](IGXVec out, int m) -> int {
-    if (int rc = compute(g, ifun ? OP_IFUNCTION : OP_FUNCTION, nullptr, out, x, V, shift, t)) return nw_refused(rc);
-    launches += g->last_launches;
-    if (timing) { float ms = 0; HIPCK(hipEventSynchronize(g->ev[2])); HIPCK(hipEventElapsedTime(&ms, g->ev[1], g->ev[2])); op_ms += ms; }
-    KR_LAUNCH(kr_dot, KR_G, KR_T, g, out->a.as<double>(), out->a.as<double>(), n, kr_slab(g, KS_RR));
-    KrSlabs sl; memset(&sl, 0, sizeof(sl)); sl.s[0] = kr_slab(g, KS_RR); sl.s[1] = kr_slab(g, KS_A); sl.s[2] = kr_slab(g, KS_B); sl.m = m;
-    KR_LAUNCH(kr_record, 1, 64, g, sl, drec);
-    launches += 2; ++evals;
-    HIPCK(hipMemcpyAsync(rec, drec, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->stream)); HIPCK(hipStreamSynchronize(g->stream));
-    return 0;
-  };
-  g->slab_valid = 0;
-  int its = 0, reason = 0, lin_total = 0, backtracks = 0, last_lin = 0;
-  double fnorm0 = 0, f = 0, snorm = 0, xnorm = 0, eta = sp->lin_rtol, fprev = 0;
-  if (ifun) { KR_LAUNCH(nw_state, kr_grid(n), KR_T, g, Vd, xd, Wd, shift, n); ++launches; }
-  if (int rc = residual(F, 1)) return rc;
-  fnorm0 = f = std::sqrt(rec[0]);
-  if (history) history[0] = f;
-  if (std::isnan(f)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN;
-  else if (f <= sp->atol) reason = IGX_NEWTON_CONVERGED_FNORM_ABS;
-  else if (sp->maxit == 0) reason = IGX_NEWTON_DIVERGED_MAX_IT;
-  while (!reason) {
-    // the linear solve J(x) d = F from d = 0, to eta
-    if (sp->forcing == IGX_FORCING_EW2 && its > 0) {
-      const double q = f / fprev, floor_ = 0.9 * (eta * eta);
-      double e = 0.9 * (q * q);
-      if (floor_ > 0.1 && e < floor_) e = floor_;
-      eta = e > 0.9 ? 0.9 : e;
-    }
-    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, d->a.as<double>(), 0.0, n); ++launches;
-    IGXSolveSpec ls; memset(&ls, 0, sizeof(ls));
-    ls.method = sp->method; ls.op = sp->op; ls.pc = sp->pc; ls.a = shift; ls.t = t; ls.V = V; ls.U = x; ls.rtol = eta; ls.atol = sp->lin_atol; ls.maxit = sp->lin_maxit;
-    IGXSolveInfo li; memset(&li, 0, sizeof(li));
-    if (int rc = IGXSolve(g, &ls, F, d, &li, nullptr)) return nw_refused(rc);
-    launches += g->last_launches; if (timing) op_ms += g->last_kernel_ms;
-    linname = g->krylov->name;
-    lin_total += li.iterations; last_lin = li.reason;
-    if (linear_its) linear_its[its] = li.iterations;
-    if (li.reason == IGX_DIVERGED_BREAKDOWN || li.reason == IGX_DIVERGED_NAN) { reason = IGX_NEWTON_DIVERGED_LINEAR_SOLVE; break; }
-    // the line search: one sweep and one residual per trial
-    double lambda = 1.0; int halvings = 0; bool accepted = false;
-    KR_LAUNCH(nw_first_trial, KR_G, KR_T, g, xd, xs->a.as<double>(), d->a.as<double>(), Vd, Wd, shift, n, kr_slab(g, KS_A), kr_slab(g, KS_B)); ++launches;
-    for (;;) {
-      if (int rc = residual(Ft, 3)) {      // x holds a trial that was never judged: hand back the last accepted iterate with the driver's error
-        (void)hipMemcpyAsync(x->a.p, xs->a.p, x->a.bytes, hipMemcpyDeviceToDevice, g->stream); (void)hipStreamSynchronize(g->stream);
-        return rc;
-      }
-      const double ft = std::sqrt(rec[0]);
-      if (!bt) { if (std::isnan(ft)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN; else accepted = true; }
-      else if (std::isfinite(ft) && ft <= (1.0 - 1e-4 * lambda) * f) accepted = true;
-      else if (halvings == sp->max_backtracks) reason = IGX_NEWTON_DIVERGED_LINE_SEARCH;
-      if (accepted) { fprev = f; f = ft; break; }
-      if (reason) break;
-      lambda *= 0.5; ++halvings; ++backtracks;
-      KR_LAUNCH(nw_back_trial, KR_G, KR_T, g, xd, xs->a.as<double>(), d->a.as<double>(), Vd, Wd, shift, lambda, n, kr_slab(g, KS_A), kr_slab(g, KS_B)); ++launches;
-    }
-    if (!accepted) {      // x is the last accepted iterate again, bit for bit
-      HIPCK(hipMemcpyAsync(x->a.p, xs->a.p, x->a.bytes, hipMemcpyDeviceToDevice, g->stream)); HIPCK(hipStreamSynchronize(g->stream));
-      break;
-    }
-    snorm = lambda * std::sqrt(rec[1]); xnorm = std::sqrt(rec[2]);
-    std::swap(F, Ft);
-    ++its;
-    if (history) history[its] = f;
-    if (std::isnan(f)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN;
-    else if (f <= sp->atol) reason = IGX_NEWTON_CONVERGED_FNORM_ABS;
-    else if (f <= sp->rtol * fnorm0) reason = IGX_NEWTON_CONVERGED_FNORM_RELATIVE;
-    else if (snorm <= sp->stol * xnorm) reason = IGX_NEWTON_CONVERGED_SNORM_RELATIVE;
-    else if (its >= sp->maxit) reason = IGX_NEWTON_DIVERGED_MAX_IT;
-  }
-  st.name = std::string("newton(") + (bt ? "bt" : "basic") + ", " + linname + ", " + std::to_string(its) + " iterations)";
-  g->last_kernel = st.name; g->last_launches = launches;
-  if (timing) {
-    float ms = 0;
-    HIPCK(hipEventRecord(st.ev[1], g->stream)); HIPCK(hipEventSynchronize(st.ev[1])); HIPCK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
-    g->last_total_ms = ms; g->last_kernel_ms = op_ms;
-  }
-  if (info) {
-    info->iterations = its; info->reason = reason; info->linear_iterations = lin_total; info->function_evaluations = evals; info->backtracks = backtracks;
-    info->last_linear_reason = last_lin; info->fnorm0 = fnorm0; info->fnorm = f; info->snorm = snorm; info->xnorm = xnorm;
-  }
-  return 0;
-}
-// ------------------------------------------------------------------ the generalized-alpha time loop (timestep.hpp)
-#include "timestep.hpp"
-// IGXTimeStep.  Every stage is IGXSolveNonlinear itself: whatever it refuses the stepper refuses, with its reason under the stepper's name.
-// The loop is the one the header states; around a Newton solve an attempt is the two sweeps of timestep.hpp and one record of two sums.
-static int ts_refused(int rc) { return fail(rc, "IGXTimeStep: the time stepper takes its stages with IGXSolveNonlinear, and " + std::string(g_err)); }
-extern "C" int IGXTimeStep(IGX g, const IGXTimeStepSpec *sp, IGXVec U, IGXVec V, IGXTimeStepInfo *info, IGXTimeStepLog *log, int nlog) {
-  NEEDIGA(g);
-  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null time-step specification");
-  if (sp->newton.op != IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: newton.op must be IGX_OP_IJACOBIAN (the stepper is first order in time on an IFunction)");
-  if (!(sp->alpha_m > 0) || !std::isfinite(sp->alpha_m)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: alpha_m must be positive and finite");
-  if (!(sp->alpha_f > 0) || !std::isfinite(sp->alpha_f)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: alpha_f must be positive and finite");
-  if (!(sp->gamma > 0) || !std::isfinite(sp->gamma)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: gamma must be positive and finite");
-  if (!(sp->dt > 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt must be positive");
-  if (!(sp->max_time >= sp->t0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_time must not be below t0");
-  if (sp->max_steps < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_steps must not be negative");
-  if (sp->max_rejections < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_rejections must not be negative");
-  if (!(sp->adapt_rtol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt_rtol must not be negative");
-  if (!(sp->adapt_atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt_atol must not be negative");
-  if (!(sp->dt_min >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_min must not be negative");
-  if (!(sp->dt_max >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_max must not be negative");
-  if (sp->dt_max < sp->dt_min) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_max must not be below dt_min");
-  if (sp->adapt && sp->adapt_rtol == 0 && sp->adapt_atol == 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt needs a positive adapt_rtol or adapt_atol");
-  if (int rc = nw_spec_refusal(&sp->newton)) return fail(rc, "IGXTimeStep: newton: " + std::string(g_err));
-  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXTimeStep()");
-  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, "the time stepper needs one rank on every axis: its norms and its Newton solve have no sum across ranks");
-  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
-  if (sp->newton.pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() before IGXTimeStep() with IGX_PC_FASTDIAG");
-  if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "IGXTimeStep: null U or V");
-  if (U->iga != g || V->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
-  if (U == V) return fail(IGX_ERR_ARG_WRONG, "IGXTimeStep: U and V must be different vectors");
-  if (U->n != V->n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
-  if (sp->resume && !(g->timestep && g->timestep->have_prev && g->timestep->n == U->n)) return fail(IGX_ERR_ORDER, "IGXTimeStep: resume = 1 without a previous call on vectors of this length whose U_{n-1} the IGX still holds");
-  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string("the time stepper runs where its Newton solve runs, and ") + why);
-  if (int rc = ensure_device(g)) return rc;
-  const long long n = (long long)g->nbrows * g->s.dof;
-  if (U->n != n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
-  IGXTimeStepInfo out; memset(&out, 0, sizeof(out));
-  out.t = sp->t0; out.dt_next = sp->dt;
-  if (sp->max_steps == 0 || sp->t0 == sp->max_time) {      // nothing to do, nothing launched
-    out.reason = sp->max_steps == 0 ? IGX_TS_CONVERGED_STEPS : IGX_TS_CONVERGED_TIME;
-    if (info) *info = out;
-    return 0;
-  }
-  if (int rc = kr_scalars(g)) return rc;
-  if (!g->timestep || g->timestep->n != n) {
-    g->timestep.reset();
-    std::shared_ptr<TimeStepState> ts(new TimeStepState());
-    for (int k = 0; k < 7; ++k) {
-      std::unique_ptr<_p_IGXVec> v(new _p_IGXVec()); v->iga = g; v->n = n;
-      if (v->a.alloc((size_t)n * sizeof(double)) || hipMemset(v->a.p, 0, v->a.bytes) != hipSuccess) return fail(IGX_ERR_MEM, "device allocation of the time stepper's work vectors failed");
-      ts->work.push_back(std::move(v));
-    }
-    ts->n = n;
-    g->timestep = ts;
-  }
-  TimeStepState &st = *g->timestep;
-  if (!sp->resume) st.have_prev = false;
-  IGXVec W = st.work[0].get(), x = st.work[1].get();
-  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
-  const bool timing = g->timing;
-  if (timing) { for (auto &e : st.ev) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(st.ev[0], g->stream)); }
-  int launches = 0; double op_ms = 0; std::string nwname = "no newton solve";
-  HIPCK(hipMemcpyAsync(D(st.u0), U->a.p, U->a.bytes, hipMemcpyDeviceToDevice, g->stream));
-  HIPCK(hipMemcpyAsync(D(st.v0), V->a.p, V->a.bytes, hipMemcpyDeviceToDevice, g->stream));
-  const double am = sp->alpha_m, af = sp->alpha_f, gm = sp->gamma;
-  double t = sp->t0, h = sp->dt;
-  double *drec = kr_rec(g), rec[2] = {0, 0};
-  int reason = 0, rc_out = 0;
-  while (!reason) {
-    int rejections = 0;
-    for (;;) {      // the attempts of one step
-      const double p = h;
-      const double left = sp->max_time - t;
-      const bool shortened = left <= (1.0 + 1e-9) * h;      // ... or a remainder of rounding size would be left over
-      if (shortened) h = left;
-      const double a = am / (af * gm * h), c0 = 1.0 - am / gm;
-      KR_LAUNCH(ts_stage, kr_grid(n), KR_T, g, D(0), D(1), D(st.u0), D(st.v0), c0, a, n); ++launches;
-      IGXNewtonSpec ns = sp->newton; ns.op = IGX_OP_IJACOBIAN; ns.a = a; ns.t = t + af * h; ns.W = W;
-      IGXNewtonInfo ni; memset(&ni, 0, sizeof(ni));
-      if (int rc = IGXSolveNonlinear(g, &ns, x, &ni, nullptr, nullptr)) { rc_out = ts_refused(rc); break; }
-      launches += g->last_launches; if (timing) op_ms += g->last_kernel_ms;
-      nwname = g->newton->name;
-      out.newton_iterations += ni.iterations; out.linear_iterations += ni.linear_iterations; out.function_evaluations += ni.function_evaluations;
-      IGXTimeStepLog *lg = log && out.attempts < nlog ? log + out.attempts : nullptr;
-      ++out.attempts;
-      if (lg) { lg->t = t; lg->dt = h; lg->wlte = -1.0; lg->accepted = 0; lg->newton_iterations = ni.iterations; lg->newton_reason = ni.reason; lg->linear_iterations = ni.linear_iterations; }
-      if (ni.reason < 0) {      // a failed attempt
-        if (!sp->adapt) { reason = IGX_TS_DIVERGED_NONLINEAR_SOLVE; break; }
-        ++rejections; ++out.rejections; h = h / 4;
-        if (rejections > sp->max_rejections || h < sp->dt_min) { reason = IGX_TS_DIVERGED_NONLINEAR_SOLVE; break; }
-        continue;
-      }
-      const bool estimate = sp->adapt && st.have_prev;
-      TsUpdate k; memset(&k, 0, sizeof(k));
-      k.c1 = 1.0 / af; k.c2 = 1.0 / (gm * h); k.c3 = 1.0 - 1.0 / gm; k.atol = sp->adapt_atol; k.rtol = sp->adapt_rtol;
-      if (estimate) { const double r = 1.0 + st.hprev / h; k.d1 = r; k.d2 = r - 1.0; k.d3 = r * (r - 1.0); }
-      if (estimate) KR_LAUNCH(ts_update<true>, KR_G, KR_T, g, D(st.u1), D(st.v1), D(1), D(st.u0), D(st.v0), D(st.uprev), k, n, kr_slab(g, KS_A), kr_slab(g, KS_B));
-      else KR_LAUNCH(ts_update<false>, KR_G, KR_T, g, D(st.u1), D(st.v1), D(1), D(st.u0), D(st.v0), (const double *)nullptr, k, n, kr_slab(g, KS_A), kr_slab(g, KS_B));
-      KrSlabs sl; memset(&sl, 0, sizeof(sl)); sl.s[0] = kr_slab(g, KS_A); sl.s[1] = kr_slab(g, KS_B); sl.m = 2;
-      KR_LAUNCH(kr_record, 1, 64, g, sl, drec);
-      launches += 2;
-      HIPCK(hipMemcpyAsync(rec, drec, 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream)); HIPCK(hipStreamSynchronize(g->stream));
-      const double unorm = std::sqrt(rec[0]), wlte = estimate ? std::sqrt(rec[1] / (double)n) : -1.0;
-      if (lg) lg->wlte = wlte;
-      if (std::isnan(unorm) || std::isnan(wlte)) { reason = IGX_TS_DIVERGED_NAN; break; }
-      double next = p;
-      if (estimate) {
-        const double fac = wlte == 0.0 ? 10.0 : std::min(10.0, std::max(0.1, 0.9 / std::sqrt(wlte)));
-        if (!(wlte <= 1.0)) {      // rejected by the estimate
-          ++rejections; ++out.rejections; h = fac * h;
-          if (rejections > sp->max_rejections || h < sp->dt_min) { reason = IGX_TS_DIVERGED_STEP_REJECTED; break; }
-          continue;
-        }
-        if (!shortened) next = std::min(sp->dt_max, std::max(sp->dt_min, fac * h));
-      }
-      // accepted: Uprev <- U0 <- U1, V0 <- V1 by pointer
-      if (lg) lg->accepted = 1;
-      { const int old = st.uprev; st.uprev = st.u0; st.u0 = st.u1; st.u1 = old; std::swap(st.v0, st.v1); }
-      st.have_prev = true; st.hprev = h;
-      t = shortened ? sp->max_time : t + h;
-      ++out.steps; out.dt_last = h; out.unorm = unorm;
-      h = next;
-      if (t == sp->max_time) reason = IGX_TS_CONVERGED_TIME;
-      else if (out.steps == sp->max_steps) reason = IGX_TS_CONVERGED_STEPS;
-      break;
-    }
-    if (rc_out) break;
-  }
-  // the caller's U and V are written once, here: the last accepted state
-  if (out.steps > 0) {
-    (void)hipMemcpyAsync(U->a.p, D(st.u0), U->a.bytes, hipMemcpyDeviceToDevice, g->stream);
-    (void)hipMemcpyAsync(V->a.p, D(st.v0), V->a.bytes, hipMemcpyDeviceToDevice, g->stream);
-  }
-  if (rc_out) { (void)hipStreamSynchronize(g->stream); return rc_out; }
-  HIPCK(hipStreamSynchronize(g->stream));
-  char scheme[96]; snprintf(scheme, sizeof(scheme), "timestep(am=%g, af=%g, g=%g, ", am, af, gm);
-  st.name = std::string(scheme) + nwname + ", " + std::to_string(out.steps) + " steps, " + std::to_string(out.rejections) + " rejections)";
-  g->last_kernel = st.name; g->last_launches = launches;
-  if (timing) {
-    float ms = 0;
-    HIPCK(hipEventRecord(st.ev[1], g->stream)); HIPCK(hipEventSynchronize(st.ev[1])); HIPCK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
-    g->last_total_ms = ms; g->last_kernel_ms = op_ms;
-  }
-  out.reason = reason; out.t = t; out.dt_next = h;
-  if (info) *info = out;
-  return 0;
-}
+// ------------------------------------------------------------------ vector algebra on IGXVec, IGXSolve, IGXSolveNonlinear, IGXTimeStep
+// (host code and, through it, krylov.hpp, newton.hpp and timestep.hpp: the last kernels but the probe's in the unit, so every kernel above is
+// compiled as it was before these existed)
+#include "solve_loops.hpp"
 // ------------------------------------------------------------------ point evaluation of a discrete field (probe.hpp)
 #include "probe.hpp"
 // IGXProbe: IGAProbe (src/petigaprobe.c) for many points at once.  The points are located on the device once, at IGXProbeCreate; every
@@ -2518,7 +1886,7 @@ extern "C" int IGXProbeEvaluate(IGXProbe prb, IGXVec U, int der, double *out) {
   if (!U) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: null vector: the probe evaluates the field an IGXVec holds");
   if (U->iga != g) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: the vector was created by another IGX than the probe's");
   if (U->n != (int64_t)s.lay[0].nrow * s.lay[1].nrow * s.lay[2].nrow * s.dof) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: the vector is of another size than the probe's space");
-  if (q->npts == 0) { g->last_kernel = g->untimed_kernel = probe_name(s, der, 0); g->last_launches = 0; g->last_total_ms = g->last_kernel_ms = 0; return 0; }
+  if (q->npts == 0) { g->last_kernel = g->self_timed = probe_name(s, der, 0); g->last_launches = 0; g->last_total_ms = g->last_kernel_ms = 0; return 0; }
   if (!out) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: null array for the probe's result");
   if (int rc = ensure_device(g)) return rc;
   int no = 1; for (int k = 0; k < der; ++k) no *= s.dim;

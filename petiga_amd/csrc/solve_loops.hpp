@@ -1,0 +1,618 @@
+// solve_loops.hpp -- the host side of the vector algebra on IGXVec and of the three device-resident loops: IGXSolve (kernels: krylov.hpp),
+// IGXSolveNonlinear (newton.hpp) and IGXTimeStep (timestep.hpp).  Host code only: it launches kernels and defines none.  Included by the
+// main unit of engine.hip as the last thing before the probe, so every kernel above is compiled as it was before these existed; the three
+// kernel headers are included here, where their loops begin, in that order.
+// What the loops share is written once, up front: the state kept between calls (LoopState), the accounting of launches and kernel time
+// (LoopClock), the blocking read of partial sums (read_sums), the entry checks in each solver's own words (SolverWords) and the map from
+// the public operator to the matrix-free driver's op (matfree_op).  A new loop costs its own loop.
+#pragma once
+
+// ------------------------------------------------------------------ what the loops share
+// count more zeroed vectors of length n at the end of a list
+static int add_vecs(IGX g, int64_t n, int count, std::vector<std::unique_ptr<_p_IGXVec>> &to, const char *failure) {
+  for (int k = 0; k < count; ++k) {
+    std::unique_ptr<_p_IGXVec> v(new _p_IGXVec()); v->iga = g; v->n = n;
+    if (v->a.alloc((size_t)n * sizeof(double)) || hipMemset(v->a.p, 0, v->a.bytes) != hipSuccess) return fail(IGX_ERR_MEM, failure);
+    to.push_back(std::move(v));
+  }
+  return 0;
+}
+// Work vectors and the two events of a loop's own clock, kept with the IGX between calls (IGXSetUp drops them, IGXDestroy frees them).
+struct LoopState {
+  int64_t n = 0;
+  std::vector<std::unique_ptr<_p_IGXVec>> work;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~LoopState() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+  int ensure(IGX g, int64_t len, int count, const char *failure) { n = len; return add_vecs(g, len, count, work, failure); }      // a new state's work vectors
+};
+struct KrylovState : LoopState {
+  int method = -1, pc = -1, dof = 0;
+  std::vector<std::unique_ptr<_p_IGXVec>> pcv;           // work: r z p Ap (CG), r rhat p v s t y z (BiCGStab); pcv: the diagonal or the dof block columns
+};
+struct NewtonState : LoopState {
+  bool has_v = false;                                    // work: F F_t d xs, and V for an IFunction
+};
+struct TimeStepState : LoopState {                       // work: W x, three rotating U (U0 U1 Uprev), two rotating V (V0 V1)
+  int u0 = 2, u1 = 3, uprev = 4, v0 = 5, v1 = 6;         // where the rotation stands
+  bool have_prev = false; double hprev = 0;              // U_{n-1} = work[uprev] and h_{n-1} of the last accepted step: what resume = 1 continues from
+};
+
+// A loop's figures for IGXGetLastTiming: every launch of the call, the whole call by the loop's own two events and, as kernel time, the
+// sum of the operators' own.  With timing on, driver() and finish() block on an event; with timing off nothing here touches the device.
+struct LoopClock {
+  LoopState &st; const bool timing; int launches = 0; double op_ms = 0;
+  LoopClock(IGX g, LoopState &s) : st(s), timing(g->timing) {}
+  int begin(IGX g) {
+    if (timing) { for (auto &e : st.ev) if (!e) HIPCK(hipEventCreate(&e)); HIPCK(hipEventRecord(st.ev[0], g->stream)); }
+    return 0;
+  }
+  void own(int k) { launches += k; }      // k launches of the loop's own
+  int driver(IGX g) {                     // after a driver's entry: its launches and, timed, its kernel time
+    launches += g->last_launches;
+    if (timing) { float ms = 0; HIPCK(hipEventSynchronize(g->ev[2])); HIPCK(hipEventElapsedTime(&ms, g->ev[1], g->ev[2])); op_ms += ms; }
+    return 0;
+  }
+  void solver(IGX g) { launches += g->last_launches; if (timing) op_ms += g->last_kernel_ms; }      // after an inner loop: the figures it stored
+  int finish(IGX g, const std::string &name) {
+    g->last_kernel = g->self_timed = name; g->last_launches = launches;
+    if (timing) {
+      float ms = 0;
+      HIPCK(hipEventRecord(st.ev[1], g->stream)); HIPCK(hipEventSynchronize(st.ev[1])); HIPCK(hipEventElapsedTime(&ms, st.ev[0], st.ev[1]));
+      g->last_total_ms = ms; g->last_kernel_ms = op_ms;
+    }
+    return 0;
+  }
+};
+
+// Each solver's words for the checks they share; the codes and the order are the same for all.  where: the prefix of "this solver runs where
+// ..., and <reason>", put before vec_action_refusal's reason and before an inner IGX_ERR_SUP.  inner: the stepper alone puts every inner
+// refusal, of any code, under a prefix of its own.
+struct SolverWords { const char *call, *one_rank, *where, *inner; };
+static const SolverWords kKrylovWords = {"IGXSolve", "the Krylov solve needs one rank on every axis: the library has no sum across ranks (IGXVecDot gives each rank's part)",
+                                         "the Krylov solve runs where its operator and its preconditioner run, and ", nullptr};
+static const SolverWords kNewtonWords = {"IGXSolveNonlinear", "the Newton solve needs one rank on every axis: its norms and its linear solve have no sum across ranks",
+                                         "the Newton solve runs where its residual and its linear solve run, and ", nullptr};
+static const SolverWords kTimeStepWords = {"IGXTimeStep", "the time stepper needs one rank on every axis: its norms and its Newton solve have no sum across ranks",
+                                           "the time stepper runs where its Newton solve runs, and ", "IGXTimeStep: the time stepper takes its stages with IGXSolveNonlinear, and "};
+static int solver_ready(IGX g, const SolverWords &w) {
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, std::string("Must call IGXSetUp() before ") + w.call + "()");
+  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, w.one_rank);
+  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  return 0;
+}
+static int solver_pc_ready(IGX g, const SolverWords &w, int pc) {
+  if (pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, std::string("Must call IGXFastDiagSetUp() before ") + w.call + "() with IGX_PC_FASTDIAG");
+  return 0;
+}
+static int solver_runs_here(IGX g, const SolverWords &w) {
+  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string(w.where) + why);
+  return 0;
+}
+// what an operator or an inner loop refused, with its reason under the solver's own name
+static int solver_refused(const SolverWords &w, int rc) {
+  if (w.inner) return fail(rc, w.inner + std::string(g_err));
+  return rc == IGX_ERR_SUP ? fail(rc, w.where + std::string(g_err)) : rc;
+}
+
+enum { MF_ACTION = 0, MF_DIAGONAL, MF_BLOCK_DIAGONAL };
+static int matfree_op(int igx_op, int kind) {
+  static const int ops[3][3] = {{OP_MATRIX_ACTION, OP_JACOBIAN_ACTION, OP_IJACOBIAN_ACTION}, {OP_MATRIX_DIAGONAL, OP_JACOBIAN_DIAGONAL, OP_IJACOBIAN_DIAGONAL},
+                                {OP_MATRIX_BLOCK_DIAGONAL, OP_JACOBIAN_BLOCK_DIAGONAL, OP_IJACOBIAN_BLOCK_DIAGONAL}};
+  return ops[kind][igx_op];
+}
+
+// ------------------------------------------------------------------ vector algebra on IGXVec and the Krylov loop (krylov.hpp)
+#include "krylov.hpp"
+// Everything is enqueued on the engine's stream; IGXVecDot / IGXVecNorm2 read their result back and so synchronise.  The sums run over the
+// rows this rank owns (a prefix of the row box on every axis, as in IGXChecksum): on several ranks the caller adds the parts.
+static int kr_scalars(IGX g) {
+  if (g->krscal.p) return 0;
+  if (g->krscal.alloc(KR_SCAL_DOUBLES * sizeof(double))) return fail(IGX_ERR_MEM, "device allocation of the partial-sum slabs failed");
+  HIPCK(hipMemset(g->krscal.p, 0, g->krscal.bytes));
+  return 0;
+}
+static double *kr_slab(IGX g, int k) { return g->krscal.as<double>() + (size_t)k * KR_G; }
+static double *kr_rec(IGX g) { return g->krscal.as<double>() + (size_t)KR_NSLAB * KR_G; }
+static int kr_vec_args(IGXVec a, IGXVec b = nullptr, IGXVec c = nullptr, bool three = false, bool two = false) {
+  if (!a || ((two || three) && !b) || (three && !c)) return fail(IGX_ERR_ARG_WRONG, "null vector");
+  if ((b && b->iga != a->iga) || (c && c->iga != a->iga)) return fail(IGX_ERR_ARG_WRONG, "vectors created by different IGX");
+  if ((b && b->n != a->n) || (c && c->n != a->n)) return fail(IGX_ERR_ARG_WRONG, "vectors of different sizes");
+  return 0;
+}
+#define KR_LAUNCH(kernel, grid, block, g, ...) do { hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (g)->stream, __VA_ARGS__); if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, #kernel ": kernel launch failed"); } while (0)
+// the host's blocking read: the first m doubles of the record
+static int read_record(IGX g, double *rec, int m) {
+  HIPCK(hipMemcpyAsync(rec, kr_rec(g), (size_t)m * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIPCK(hipStreamSynchronize(g->stream));
+  return 0;
+}
+// the sums of the slabs given, added in index order by kr_record (one launch) and read back
+static int read_sums(IGX g, std::initializer_list<int> slabs, double *rec) {
+  KrSlabs sl; memset(&sl, 0, sizeof(sl));
+  for (int k : slabs) sl.s[sl.m++] = kr_slab(g, k);
+  KR_LAUNCH(kr_record, 1, 64, g, sl, kr_rec(g));
+  return read_record(g, rec, sl.m);
+}
+extern "C" int IGXVecSet(IGXVec y, double value) {
+  if (int rc = kr_vec_args(y)) return rc;
+  y->iga->slab_valid = 0;
+  KR_LAUNCH(kr_set, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), value, (long long)y->n);
+  return 0;
+}
+extern "C" int IGXVecCopy(IGXVec x, IGXVec y) {
+  if (int rc = kr_vec_args(x, y, nullptr, false, true)) return rc;
+  y->iga->slab_valid = 0;
+  if (x != y) HIPCK(hipMemcpyAsync(y->a.p, x->a.p, x->a.bytes, hipMemcpyDeviceToDevice, y->iga->stream));
+  return 0;
+}
+extern "C" int IGXVecScale(IGXVec y, double a) {
+  if (int rc = kr_vec_args(y)) return rc;
+  y->iga->slab_valid = 0;
+  KR_LAUNCH(kr_scale, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), a, (long long)y->n);
+  return 0;
+}
+extern "C" int IGXVecAXPBY(IGXVec y, double a, IGXVec x, double b) {
+  if (int rc = kr_vec_args(y, x, nullptr, false, true)) return rc;
+  y->iga->slab_valid = 0;
+  KR_LAUNCH(kr_axpby, kr_grid(y->n), KR_T, y->iga, y->a.as<double>(), a, x->a.as<double>(), b, (long long)y->n);
+  return 0;
+}
+extern "C" int IGXVecPointwiseDivide(IGXVec z, IGXVec x, IGXVec d) {
+  if (int rc = kr_vec_args(z, x, d, true)) return rc;
+  z->iga->slab_valid = 0;
+  KR_LAUNCH(kr_pdiv, kr_grid(z->n), KR_T, z->iga, z->a.as<double>(), x->a.as<double>(), d->a.as<double>(), (long long)z->n);
+  return 0;
+}
+extern "C" int IGXVecDot(IGXVec x, IGXVec y, double *s) {
+  if (int rc = kr_vec_args(x, y, nullptr, false, true)) return rc;
+  if (!s) return fail(IGX_ERR_ARG_WRONG, "null result");
+  IGX g = x->iga;
+  if (int rc = kr_scalars(g)) return rc;
+  const Space &sp = g->s;
+  int nown[3]; bool all = true;
+  for (int d = 0; d < 3; ++d) {
+    const AxisLayout &L = sp.lay[d]; nown[d] = 0;
+    for (int r = 0; r < L.nrow; ++r) if (L.owned[r]) { if (nown[d] != r) return fail(IGX_ERR_PLIB, "owned rows are not a prefix of the row box"); nown[d]++; }
+    if (nown[d] != L.nrow) all = false;
+  }
+  double *slab = kr_slab(g, KS_USER);
+  if (all) KR_LAUNCH(kr_dot, KR_G, KR_T, g, x->a.as<double>(), y->a.as<double>(), (long long)x->n, slab);
+  else KR_LAUNCH(kr_dot_owned, KR_G, KR_T, g, x->a.as<double>(), y->a.as<double>(), nown[0], nown[1], nown[2], sp.lay[0].nrow, sp.lay[1].nrow, sp.dof, slab);
+  return read_sums(g, {KS_USER}, s);
+}
+extern "C" int IGXVecNorm2(IGXVec x, double *s) {
+  if (int rc = IGXVecDot(x, x, s)) return rc;
+  *s = std::sqrt(*s);
+  return 0;
+}
+
+// IGXSolve.  The operator is the matrix-free driver's internal entry (compute_matfree) at the state of the specification, the preconditioners
+// are the same driver's diagonals and point blocks with block_diagonal_run, and IGXFastDiagApply: whatever they refuse the solve refuses,
+// with their reason under its own name.  The loops and their kernels: krylov.hpp.
+static bool kr_bad_host(double d) { return !(std::fabs(d) > 0.0) || !std::isfinite(d); }
+extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSolveInfo *info, double *history) {
+  NEEDIGA(g);
+  const SolverWords &words = kKrylovWords;
+  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null solve specification");
+  if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown method");
+  if (sp->op < IGX_OP_MATRIX || sp->op > IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown operator");
+  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown preconditioner");
+  if (sp->maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: maxit must not be negative");
+  if (!(sp->rtol >= 0) || !(sp->atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: the tolerances must not be negative");
+  if (int rc = solver_ready(g, words)) return rc;
+  if (!b || !x) return fail(IGX_ERR_ARG_WRONG, "null right-hand side or solution vector");
+  if (b->iga != g || x->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if (x == b) return fail(IGX_ERR_ARG_WRONG, "the solution and the right-hand side must be different vectors");
+  IGXVec U = sp->op == IGX_OP_MATRIX ? nullptr : sp->U, V = sp->op == IGX_OP_IJACOBIAN ? sp->V : nullptr;
+  if (sp->op != IGX_OP_MATRIX && !U) return fail(IGX_ERR_ARG_WRONG, "null state vector");
+  if (sp->op == IGX_OP_IJACOBIAN && !V) return fail(IGX_ERR_ARG_WRONG, "null state vector");
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  if ((U && U == x) || (V && V == x)) return fail(IGX_ERR_ARG_WRONG, "the solution must not be a state vector");
+  if (int rc = solver_pc_ready(g, words, sp->pc)) return rc;
+  if (int rc = solver_runs_here(g, words)) return rc;
+  if (int rc = ensure_device(g)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  if (b->n != n || x->n != n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  if (int rc = kr_scalars(g)) return rc;
+  const bool cg = sp->method == IGX_SOLVE_CG;
+  const int dof = g->s.dof, pc = sp->pc;
+  const double shift = sp->op == IGX_OP_IJACOBIAN ? sp->a : 0.0, t = sp->op == IGX_OP_IJACOBIAN ? sp->t : 0.0;
+  // work vectors: kept while the method and the preconditioner need the same set
+  if (!g->krylov || g->krylov->method != sp->method || g->krylov->pc != pc || g->krylov->dof != dof || g->krylov->n != n) {
+    g->krylov.reset();
+    std::shared_ptr<KrylovState> ks(new KrylovState());
+    if (int rc = ks->ensure(g, n, cg ? 4 : 8, "device allocation of the Krylov work vectors failed")) return rc;
+    if (int rc = add_vecs(g, n, pc == IGX_PC_JACOBI ? 1 : pc == IGX_PC_PBJACOBI ? dof : 0, ks->pcv, "device allocation of the preconditioner's vectors failed")) return rc;
+    ks->method = sp->method; ks->pc = pc; ks->dof = dof;
+    g->krylov = ks;
+  }
+  KrylovState &st = *g->krylov;
+  LoopClock clk(g, st);
+  if (int rc = clk.begin(g)) return rc;
+  std::string opname;
+  auto A = [&](IGXVec in, IGXVec out) -> int {
+    if (int rc = compute_matfree(g, matfree_op(sp->op, MF_ACTION), U, V, in, 1, &out, shift, t)) return solver_refused(words, rc);
+    if (opname.empty()) opname = g->last_kernel;
+    return clk.driver(g);
+  };
+  std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
+  if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
+    if (int rc = compute_matfree(g, matfree_op(sp->op, pc == IGX_PC_JACOBI ? MF_DIAGONAL : MF_BLOCK_DIAGONAL), U, V, nullptr, (int)cols.size(), cols.data(), shift, t)) return solver_refused(words, rc);
+    if (int rc = clk.driver(g)) return rc;
+  }
+  if (pc == IGX_PC_PBJACOBI) {
+    if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return solver_refused(words, rc);
+    if (int rc = clk.driver(g)) return rc;
+  }
+  // out = M^-1 in (IGX_PC_NONE: the caller aliases the two)
+  auto M = [&](IGXVec in, IGXVec out) -> int {
+    if (pc == IGX_PC_NONE) return 0;
+    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); clk.own(1); return 0; }
+    if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return solver_refused(words, rc);
+    return clk.driver(g);
+  };
+  double rec[KR_NREC];
+  double *drec = kr_rec(g), *dsc = drec + KR_NREC;
+  auto record = [&](std::initializer_list<int> slabs) -> int { clk.own(1); return read_sums(g, slabs, rec); };
+  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
+  double *xd = x->a.as<double>(); const double *bd = b->a.as<double>();
+  g->slab_valid = 0;
+  int its = 0, reason = 0;
+  double bnorm = 0, rnorm = 0, rnorm0 = 0, thr = 0;
+  // r = b - A x with |r| and |b|, shared by both methods: the product goes to work vector 3 (Ap / v), r is work vector 0
+  if (int rc = A(x, st.work[3].get())) return rc;
+  KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), bd, D(3), n, kr_slab(g, KS_RR), kr_slab(g, KS_BB));
+  clk.own(1);
+  auto stop = [&]() {      // the test of the recurrence residual, 0 to go on
+    if (std::isnan(rnorm)) return (int)IGX_DIVERGED_NAN;
+    if (rnorm <= thr) return (int)(rnorm <= sp->rtol * bnorm ? IGX_CONVERGED_RTOL : IGX_CONVERGED_ATOL);
+    if (its >= sp->maxit) return (int)IGX_DIVERGED_ITS;
+    return 0;
+  };
+  auto start = [&]() -> bool {      // after the first record (rec[0] = r.r, rec[1] = b.b): true when the loop has something to do
+    bnorm = std::sqrt(rec[1]); rnorm0 = rnorm = std::sqrt(rec[0]); thr = std::max(sp->rtol * bnorm, sp->atol);
+    if (history) history[0] = rnorm;
+    if (std::isnan(bnorm)) { reason = IGX_DIVERGED_NAN; return false; }
+    if (bnorm == 0.0) { reason = IGX_CONVERGED_ATOL; return false; }
+    return true;
+  };
+  if (cg) {
+    IGXVec r = st.work[0].get(), z = pc == IGX_PC_NONE ? r : st.work[1].get(), p = st.work[2].get(), Ap = st.work[3].get();
+    int cur = 0;      // KS_A + cur holds the newest r.z, KS_A + 1 - cur the one before; KS_C holds p.Ap
+    auto precondition = [&](int slab) -> int {
+      if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, z->a.as<double>(), r->a.as<double>(), cols[0]->a.as<double>(), n, kr_slab(g, slab)); clk.own(1); return 0; }
+      if (int rc = M(r, z)) return rc;
+      KR_LAUNCH(kr_dot, KR_G, KR_T, g, r->a.as<double>(), z->a.as<double>(), n, kr_slab(g, slab));
+      clk.own(1);
+      return 0;
+    };
+    if (int rc = precondition(KS_A)) return rc;
+    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
+    double rz = rec[2];
+    if (start()) {
+      HIPCK(hipMemcpyAsync(p->a.p, z->a.p, z->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+      while (!(reason = stop())) {
+        if (kr_bad_host(rz)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
+        if (its > 0) { KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, p->a.as<double>(), z->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_A + 1 - cur)); clk.own(1); }
+        if (int rc = A(p, Ap)) return rc;
+        KR_LAUNCH(kr_dot, KR_G, KR_T, g, p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C));
+        KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C), kr_slab(g, KS_A + cur), kr_slab(g, KS_RR));
+        clk.own(2);
+        cur ^= 1;
+        if (int rc = precondition(KS_A + cur)) return rc;
+        if (int rc = record({KS_RR, KS_C, KS_A + cur})) return rc;
+        if (!(rec[1] > 0.0) || !std::isfinite(rec[1])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // p.Ap <= 0: the update kernel left x and r alone
+        ++its; rnorm = std::sqrt(rec[0]); rz = rec[2];
+        if (history) history[its] = rnorm;
+      }
+    }
+  } else {
+    IGXVec r = st.work[0].get(), rhat = st.work[1].get(), p = st.work[2].get(), v = st.work[3].get(), s = st.work[4].get(), tv = st.work[5].get();
+    IGXVec y = pc == IGX_PC_NONE ? p : st.work[6].get(), z = pc == IGX_PC_NONE ? s : st.work[7].get();
+    int cur = 0;      // KS_A + cur holds rho' = rhat.r of the iteration at hand; KS_C rhat.v, KS_D t.s, KS_E t.t
+    static const double one3[3] = {1.0, 1.0, 1.0};
+    HIPCK(hipMemcpyAsync(rhat->a.p, r->a.p, r->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+    KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), r->a.as<double>(), n, kr_slab(g, KS_A));
+    clk.own(1);
+    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
+    double rho_next = rec[2], omega = 1.0;
+    if (start()) {
+      HIPCK(hipMemsetAsync(v->a.p, 0, v->a.bytes, g->stream));
+      HIPCK(hipMemsetAsync(p->a.p, 0, p->a.bytes, g->stream));
+      HIPCK(hipMemcpyAsync(dsc, one3, sizeof(one3), hipMemcpyHostToDevice, g->stream));
+      while (!(reason = stop())) {
+        if (kr_bad_host(rho_next) || kr_bad_host(omega)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
+        KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), dsc);
+        clk.own(1);
+        if (int rc = M(p, y)) return rc;
+        if (int rc = A(y, v)) return rc;
+        KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_C));
+        KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_C));
+        clk.own(2);
+        if (int rc = M(s, z)) return rc;
+        if (int rc = A(z, tv)) return rc;
+        KR_LAUNCH(kr_dot2, KR_G, KR_T, g, tv->a.as<double>(), s->a.as<double>(), n, kr_slab(g, KS_D), kr_slab(g, KS_E));
+        KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(), n,
+                  kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_RR), kr_slab(g, KS_A + 1 - cur));
+        KR_LAUNCH(kr_bicg_record, 1, 64, g, kr_slab(g, KS_RR), kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_A + 1 - cur), drec, dsc);
+        clk.own(3);
+        if (int rc = read_record(g, rec, 7)) return rc;
+        cur ^= 1;
+        if (kr_bad_host(rec[1]) || kr_bad_host(rec[2])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // rhat.v or t.t: the update kernel left x and r alone
+        ++its; rnorm = std::sqrt(rec[0]); rho_next = rec[4]; omega = rec[6];
+        if (history) history[its] = rnorm;
+      }
+    }
+  }
+  if (reason == IGX_CONVERGED_ATOL && bnorm == 0.0) {      // b = 0: the solution is 0
+    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, xd, 0.0, n);
+    clk.own(1);
+    rnorm0 = rnorm = 0.0; if (history) history[0] = 0.0;
+    HIPCK(hipStreamSynchronize(g->stream));
+  }
+  static const char *const methods[2] = {"cg", "bicgstab"}, *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
+  if (int rc = clk.finish(g, std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)")) return rc;
+  if (info) { info->iterations = its; info->reason = reason; info->rnorm0 = rnorm0; info->rnorm = rnorm; info->bnorm = bnorm; }
+  return 0;
+}
+
+// ------------------------------------------------------------------ the Newton loop (newton.hpp)
+#include "newton.hpp"
+// IGXSolveNonlinear.  The residual is the vector driver's internal entry (compute: what IGXComputeFunction / IGXComputeIFunction call), the
+// linear solve is IGXSolve itself: whatever they refuse the Newton solve refuses, with their reason under its own name.  The loop is the
+// one the header states; between two operator calls a trial is one sweep of newton.hpp.
+// what the specification alone decides (IGXTimeStep asks the same of the spec it passes on)
+static int nw_spec_refusal(const IGXNewtonSpec *sp) {
+  if (sp->op == IGX_OP_MATRIX) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: a linear operator has no Newton loop (IGX_OP_MATRIX: call IGXSolve)");
+  if (sp->op != IGX_OP_JACOBIAN && sp->op != IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown operator");
+  if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown method");
+  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown preconditioner");
+  if (sp->linesearch != IGX_LINESEARCH_BASIC && sp->linesearch != IGX_LINESEARCH_BT) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown line search");
+  if (sp->forcing != IGX_FORCING_CONSTANT && sp->forcing != IGX_FORCING_EW2) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: unknown forcing");
+  if (!(sp->lin_rtol >= 0) || !(sp->lin_atol >= 0) || !(sp->rtol >= 0) || !(sp->atol >= 0) || !(sp->stol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: the tolerances must not be negative");
+  if (sp->maxit < 0 || sp->lin_maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: maxit and lin_maxit must not be negative");
+  if (sp->max_backtracks < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolveNonlinear: max_backtracks must not be negative");
+  return 0;
+}
+extern "C" int IGXSolveNonlinear(IGX g, const IGXNewtonSpec *sp, IGXVec x, IGXNewtonInfo *info, double *history, int *linear_its) {
+  NEEDIGA(g);
+  const SolverWords &words = kNewtonWords;
+  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null Newton specification");
+  if (int rc = nw_spec_refusal(sp)) return rc;
+  if (int rc = solver_ready(g, words)) return rc;
+  if (int rc = solver_pc_ready(g, words, sp->pc)) return rc;
+  const bool ifun = sp->op == IGX_OP_IJACOBIAN;
+  IGXVec W = ifun ? sp->W : nullptr;
+  if (ifun && !W) return fail(IGX_ERR_ARG_WRONG, "IGXSolveNonlinear: IGX_OP_IJACOBIAN needs the vector W of V = a U + W");
+  if (!x) return fail(IGX_ERR_ARG_WRONG, "null solution vector");
+  if (x->iga != g || (W && W->iga != g)) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if (W == x) return fail(IGX_ERR_ARG_WRONG, "W and the solution must be different vectors");
+  if (int rc = solver_runs_here(g, words)) return rc;
+  if (int rc = ensure_device(g)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  if (x->n != n || (W && W->n != n)) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  if (int rc = kr_scalars(g)) return rc;
+  if (!g->newton || g->newton->n != n || g->newton->has_v != ifun) {
+    g->newton.reset();
+    std::shared_ptr<NewtonState> ns(new NewtonState());
+    if (int rc = ns->ensure(g, n, ifun ? 5 : 4, "device allocation of the Newton work vectors failed")) return rc;
+    ns->has_v = ifun;
+    g->newton = ns;
+  }
+  NewtonState &st = *g->newton;
+  IGXVec F = st.work[0].get(), Ft = st.work[1].get(), d = st.work[2].get(), xs = st.work[3].get(), V = ifun ? st.work[4].get() : nullptr;
+  const bool bt = sp->linesearch == IGX_LINESEARCH_BT;
+  LoopClock clk(g, st);
+  if (int rc = clk.begin(g)) return rc;
+  std::string linname = "no linear solve";
+  double *xd = x->a.as<double>(), *Vd = V ? V->a.as<double>() : nullptr; const double *Wd = W ? W->a.as<double>() : nullptr;
+  const double shift = ifun ? sp->a : 0.0, t = ifun ? sp->t : 0.0;
+  double rec[3] = {0, 0, 0};
+  int evals = 0;
+  // F_out = G(x) with the state V as the last sweep left it; rec = (F.F, d.d, x.x), the last two only after a trial sweep
+  auto residual = [&](IGXVec out, bool trial) -> int {
+    if (int rc = compute(g, ifun ? OP_IFUNCTION : OP_FUNCTION, nullptr, out, x, V, shift, t)) return solver_refused(words, rc);
+    if (int rc = clk.driver(g)) return rc;
+    KR_LAUNCH(kr_dot, KR_G, KR_T, g, out->a.as<double>(), out->a.as<double>(), n, kr_slab(g, KS_RR));
+    clk.own(2); ++evals;
+    return trial ? read_sums(g, {KS_RR, KS_A, KS_B}, rec) : read_sums(g, {KS_RR}, rec);
+  };
+  g->slab_valid = 0;
+  int its = 0, reason = 0, lin_total = 0, backtracks = 0, last_lin = 0;
+  double fnorm0 = 0, f = 0, snorm = 0, xnorm = 0, eta = sp->lin_rtol, fprev = 0;
+  if (ifun) { KR_LAUNCH(nw_state, kr_grid(n), KR_T, g, Vd, xd, Wd, shift, n); clk.own(1); }
+  if (int rc = residual(F, false)) return rc;
+  fnorm0 = f = std::sqrt(rec[0]);
+  if (history) history[0] = f;
+  if (std::isnan(f)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN;
+  else if (f <= sp->atol) reason = IGX_NEWTON_CONVERGED_FNORM_ABS;
+  else if (sp->maxit == 0) reason = IGX_NEWTON_DIVERGED_MAX_IT;
+  while (!reason) {
+    // the linear solve J(x) d = F from d = 0, to eta
+    if (sp->forcing == IGX_FORCING_EW2 && its > 0) {
+      const double q = f / fprev, floor_ = 0.9 * (eta * eta);
+      double e = 0.9 * (q * q);
+      if (floor_ > 0.1 && e < floor_) e = floor_;
+      eta = e > 0.9 ? 0.9 : e;
+    }
+    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, d->a.as<double>(), 0.0, n); clk.own(1);
+    IGXSolveSpec ls; memset(&ls, 0, sizeof(ls));
+    ls.method = sp->method; ls.op = sp->op; ls.pc = sp->pc; ls.a = shift; ls.t = t; ls.V = V; ls.U = x; ls.rtol = eta; ls.atol = sp->lin_atol; ls.maxit = sp->lin_maxit;
+    IGXSolveInfo li; memset(&li, 0, sizeof(li));
+    if (int rc = IGXSolve(g, &ls, F, d, &li, nullptr)) return solver_refused(words, rc);
+    clk.solver(g);
+    linname = g->last_kernel;
+    lin_total += li.iterations; last_lin = li.reason;
+    if (linear_its) linear_its[its] = li.iterations;
+    if (li.reason == IGX_DIVERGED_BREAKDOWN || li.reason == IGX_DIVERGED_NAN) { reason = IGX_NEWTON_DIVERGED_LINEAR_SOLVE; break; }
+    // the line search: one sweep and one residual per trial
+    double lambda = 1.0; int halvings = 0; bool accepted = false;
+    KR_LAUNCH(nw_first_trial, KR_G, KR_T, g, xd, xs->a.as<double>(), d->a.as<double>(), Vd, Wd, shift, n, kr_slab(g, KS_A), kr_slab(g, KS_B)); clk.own(1);
+    for (;;) {
+      if (int rc = residual(Ft, true)) {      // x holds a trial that was never judged: hand back the last accepted iterate with the driver's error
+        (void)hipMemcpyAsync(x->a.p, xs->a.p, x->a.bytes, hipMemcpyDeviceToDevice, g->stream); (void)hipStreamSynchronize(g->stream);
+        return rc;
+      }
+      const double ft = std::sqrt(rec[0]);
+      if (!bt) { if (std::isnan(ft)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN; else accepted = true; }
+      else if (std::isfinite(ft) && ft <= (1.0 - 1e-4 * lambda) * f) accepted = true;
+      else if (halvings == sp->max_backtracks) reason = IGX_NEWTON_DIVERGED_LINE_SEARCH;
+      if (accepted) { fprev = f; f = ft; break; }
+      if (reason) break;
+      lambda *= 0.5; ++halvings; ++backtracks;
+      KR_LAUNCH(nw_back_trial, KR_G, KR_T, g, xd, xs->a.as<double>(), d->a.as<double>(), Vd, Wd, shift, lambda, n, kr_slab(g, KS_A), kr_slab(g, KS_B)); clk.own(1);
+    }
+    if (!accepted) {      // x is the last accepted iterate again, bit for bit
+      HIPCK(hipMemcpyAsync(x->a.p, xs->a.p, x->a.bytes, hipMemcpyDeviceToDevice, g->stream)); HIPCK(hipStreamSynchronize(g->stream));
+      break;
+    }
+    snorm = lambda * std::sqrt(rec[1]); xnorm = std::sqrt(rec[2]);
+    std::swap(F, Ft);
+    ++its;
+    if (history) history[its] = f;
+    if (std::isnan(f)) reason = IGX_NEWTON_DIVERGED_FNORM_NAN;
+    else if (f <= sp->atol) reason = IGX_NEWTON_CONVERGED_FNORM_ABS;
+    else if (f <= sp->rtol * fnorm0) reason = IGX_NEWTON_CONVERGED_FNORM_RELATIVE;
+    else if (snorm <= sp->stol * xnorm) reason = IGX_NEWTON_CONVERGED_SNORM_RELATIVE;
+    else if (its >= sp->maxit) reason = IGX_NEWTON_DIVERGED_MAX_IT;
+  }
+  if (int rc = clk.finish(g, std::string("newton(") + (bt ? "bt" : "basic") + ", " + linname + ", " + std::to_string(its) + " iterations)")) return rc;
+  if (info) {
+    info->iterations = its; info->reason = reason; info->linear_iterations = lin_total; info->function_evaluations = evals; info->backtracks = backtracks;
+    info->last_linear_reason = last_lin; info->fnorm0 = fnorm0; info->fnorm = f; info->snorm = snorm; info->xnorm = xnorm;
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------ the generalized-alpha time loop (timestep.hpp)
+#include "timestep.hpp"
+// IGXTimeStep.  Every stage is IGXSolveNonlinear itself: whatever it refuses the stepper refuses, with its reason under the stepper's name.
+// The loop is the one the header states; around a Newton solve an attempt is the two sweeps of timestep.hpp and one record of two sums.
+extern "C" int IGXTimeStep(IGX g, const IGXTimeStepSpec *sp, IGXVec U, IGXVec V, IGXTimeStepInfo *info, IGXTimeStepLog *log, int nlog) {
+  NEEDIGA(g);
+  const SolverWords &words = kTimeStepWords;
+  if (!sp) return fail(IGX_ERR_ARG_WRONG, "null time-step specification");
+  if (sp->newton.op != IGX_OP_IJACOBIAN) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: newton.op must be IGX_OP_IJACOBIAN (the stepper is first order in time on an IFunction)");
+  if (!(sp->alpha_m > 0) || !std::isfinite(sp->alpha_m)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: alpha_m must be positive and finite");
+  if (!(sp->alpha_f > 0) || !std::isfinite(sp->alpha_f)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: alpha_f must be positive and finite");
+  if (!(sp->gamma > 0) || !std::isfinite(sp->gamma)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: gamma must be positive and finite");
+  if (!(sp->dt > 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt must be positive");
+  if (!(sp->max_time >= sp->t0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_time must not be below t0");
+  if (sp->max_steps < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_steps must not be negative");
+  if (sp->max_rejections < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: max_rejections must not be negative");
+  if (!(sp->adapt_rtol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt_rtol must not be negative");
+  if (!(sp->adapt_atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt_atol must not be negative");
+  if (!(sp->dt_min >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_min must not be negative");
+  if (!(sp->dt_max >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_max must not be negative");
+  if (sp->dt_max < sp->dt_min) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: dt_max must not be below dt_min");
+  if (sp->adapt && sp->adapt_rtol == 0 && sp->adapt_atol == 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTimeStep: adapt needs a positive adapt_rtol or adapt_atol");
+  if (int rc = nw_spec_refusal(&sp->newton)) return fail(rc, "IGXTimeStep: newton: " + std::string(g_err));
+  if (int rc = solver_ready(g, words)) return rc;
+  if (int rc = solver_pc_ready(g, words, sp->newton.pc)) return rc;
+  if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "IGXTimeStep: null U or V");
+  if (U->iga != g || V->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  if (U == V) return fail(IGX_ERR_ARG_WRONG, "IGXTimeStep: U and V must be different vectors");
+  if (U->n != V->n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  if (sp->resume && !(g->timestep && g->timestep->have_prev && g->timestep->n == U->n)) return fail(IGX_ERR_ORDER, "IGXTimeStep: resume = 1 without a previous call on vectors of this length whose U_{n-1} the IGX still holds");
+  if (int rc = solver_runs_here(g, words)) return rc;
+  if (int rc = ensure_device(g)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  if (U->n != n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
+  IGXTimeStepInfo out; memset(&out, 0, sizeof(out));
+  out.t = sp->t0; out.dt_next = sp->dt;
+  if (sp->max_steps == 0 || sp->t0 == sp->max_time) {      // nothing to do, nothing launched
+    out.reason = sp->max_steps == 0 ? IGX_TS_CONVERGED_STEPS : IGX_TS_CONVERGED_TIME;
+    if (info) *info = out;
+    return 0;
+  }
+  if (int rc = kr_scalars(g)) return rc;
+  if (!g->timestep || g->timestep->n != n) {
+    g->timestep.reset();
+    std::shared_ptr<TimeStepState> ts(new TimeStepState());
+    if (int rc = ts->ensure(g, n, 7, "device allocation of the time stepper's work vectors failed")) return rc;
+    g->timestep = ts;
+  }
+  TimeStepState &st = *g->timestep;
+  if (!sp->resume) st.have_prev = false;
+  IGXVec W = st.work[0].get(), x = st.work[1].get();
+  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
+  LoopClock clk(g, st);
+  if (int rc = clk.begin(g)) return rc;
+  std::string nwname = "no newton solve";
+  HIPCK(hipMemcpyAsync(D(st.u0), U->a.p, U->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+  HIPCK(hipMemcpyAsync(D(st.v0), V->a.p, V->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+  const double am = sp->alpha_m, af = sp->alpha_f, gm = sp->gamma;
+  double t = sp->t0, h = sp->dt;
+  double rec[2] = {0, 0};
+  int reason = 0, rc_out = 0;
+  while (!reason) {
+    int rejections = 0;
+    for (;;) {      // the attempts of one step
+      const double p = h;
+      const double left = sp->max_time - t;
+      const bool shortened = left <= (1.0 + 1e-9) * h;      // ... or a remainder of rounding size would be left over
+      if (shortened) h = left;
+      const double a = am / (af * gm * h), c0 = 1.0 - am / gm;
+      KR_LAUNCH(ts_stage, kr_grid(n), KR_T, g, D(0), D(1), D(st.u0), D(st.v0), c0, a, n); clk.own(1);
+      IGXNewtonSpec ns = sp->newton; ns.op = IGX_OP_IJACOBIAN; ns.a = a; ns.t = t + af * h; ns.W = W;
+      IGXNewtonInfo ni; memset(&ni, 0, sizeof(ni));
+      if (int rc = IGXSolveNonlinear(g, &ns, x, &ni, nullptr, nullptr)) { rc_out = solver_refused(words, rc); break; }
+      clk.solver(g);
+      nwname = g->last_kernel;
+      out.newton_iterations += ni.iterations; out.linear_iterations += ni.linear_iterations; out.function_evaluations += ni.function_evaluations;
+      IGXTimeStepLog *lg = log && out.attempts < nlog ? log + out.attempts : nullptr;
+      ++out.attempts;
+      if (lg) { lg->t = t; lg->dt = h; lg->wlte = -1.0; lg->accepted = 0; lg->newton_iterations = ni.iterations; lg->newton_reason = ni.reason; lg->linear_iterations = ni.linear_iterations; }
+      if (ni.reason < 0) {      // a failed attempt
+        if (!sp->adapt) { reason = IGX_TS_DIVERGED_NONLINEAR_SOLVE; break; }
+        ++rejections; ++out.rejections; h = h / 4;
+        if (rejections > sp->max_rejections || h < sp->dt_min) { reason = IGX_TS_DIVERGED_NONLINEAR_SOLVE; break; }
+        continue;
+      }
+      const bool estimate = sp->adapt && st.have_prev;
+      TsUpdate k; memset(&k, 0, sizeof(k));
+      k.c1 = 1.0 / af; k.c2 = 1.0 / (gm * h); k.c3 = 1.0 - 1.0 / gm; k.atol = sp->adapt_atol; k.rtol = sp->adapt_rtol;
+      if (estimate) { const double r = 1.0 + st.hprev / h; k.d1 = r; k.d2 = r - 1.0; k.d3 = r * (r - 1.0); }
+      if (estimate) KR_LAUNCH(ts_update<true>, KR_G, KR_T, g, D(st.u1), D(st.v1), D(1), D(st.u0), D(st.v0), D(st.uprev), k, n, kr_slab(g, KS_A), kr_slab(g, KS_B));
+      else KR_LAUNCH(ts_update<false>, KR_G, KR_T, g, D(st.u1), D(st.v1), D(1), D(st.u0), D(st.v0), (const double *)nullptr, k, n, kr_slab(g, KS_A), kr_slab(g, KS_B));
+      clk.own(2);
+      if (int rc = read_sums(g, {KS_A, KS_B}, rec)) return rc;
+      const double unorm = std::sqrt(rec[0]), wlte = estimate ? std::sqrt(rec[1] / (double)n) : -1.0;
+      if (lg) lg->wlte = wlte;
+      if (std::isnan(unorm) || std::isnan(wlte)) { reason = IGX_TS_DIVERGED_NAN; break; }
+      double next = p;
+      if (estimate) {
+        const double fac = wlte == 0.0 ? 10.0 : std::min(10.0, std::max(0.1, 0.9 / std::sqrt(wlte)));
+        if (!(wlte <= 1.0)) {      // rejected by the estimate
+          ++rejections; ++out.rejections; h = fac * h;
+          if (rejections > sp->max_rejections || h < sp->dt_min) { reason = IGX_TS_DIVERGED_STEP_REJECTED; break; }
+          continue;
+        }
+        if (!shortened) next = std::min(sp->dt_max, std::max(sp->dt_min, fac * h));
+      }
+      // accepted: Uprev <- U0 <- U1, V0 <- V1 by pointer
+      if (lg) lg->accepted = 1;
+      { const int old = st.uprev; st.uprev = st.u0; st.u0 = st.u1; st.u1 = old; std::swap(st.v0, st.v1); }
+      st.have_prev = true; st.hprev = h;
+      t = shortened ? sp->max_time : t + h;
+      ++out.steps; out.dt_last = h; out.unorm = unorm;
+      h = next;
+      if (t == sp->max_time) reason = IGX_TS_CONVERGED_TIME;
+      else if (out.steps == sp->max_steps) reason = IGX_TS_CONVERGED_STEPS;
+      break;
+    }
+    if (rc_out) break;
+  }
+  // the caller's U and V are written once, here: the last accepted state
+  if (out.steps > 0) {
+    (void)hipMemcpyAsync(U->a.p, D(st.u0), U->a.bytes, hipMemcpyDeviceToDevice, g->stream);
+    (void)hipMemcpyAsync(V->a.p, D(st.v0), V->a.bytes, hipMemcpyDeviceToDevice, g->stream);
+  }
+  if (rc_out) { (void)hipStreamSynchronize(g->stream); return rc_out; }
+  HIPCK(hipStreamSynchronize(g->stream));
+  char scheme[96]; snprintf(scheme, sizeof(scheme), "timestep(am=%g, af=%g, g=%g, ", am, af, gm);
+  if (int rc = clk.finish(g, std::string(scheme) + nwname + ", " + std::to_string(out.steps) + " steps, " + std::to_string(out.rejections) + " rejections)")) return rc;
+  out.reason = reason; out.t = t; out.dt_next = h;
+  if (info) *info = out;
+  return 0;
+}
