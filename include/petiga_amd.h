@@ -601,6 +601,59 @@ int IGXProbeGetInfo (IGXProbe prb,int64_t *npts,int *order,int *nsd /* columns o
 int IGXProbeEvaluate(IGXProbe prb,IGXVec U,int der,double *out /* host [npts][dof][dim^der] */);
 int IGXProbeDestroy (IGXProbe *prb);
 
+/* Transfer between nested spline spaces: prolongation and restriction of vectors.  No entry of the reference (its DMRefine_IGA /
+ * DMCreateInterpolation_IGA are commented out in src/petigadm.c; the contract is the mathematical one below).
+ * The pair: two set-up IGX, coarse and fine, with the same dim and dof and, on every axis, the same degree, the same periodicity and the
+ *   same end knots (a clamped axis: its first and last p+1 knots; a periodic axis: U[p] and U[m-p]); every knot of the coarse axis appears
+ *   in the fine axis with at least its multiplicity (h-refinement by knot insertion: several knots in one span, raised multiplicity, axes
+ *   refined by different amounts or not at all).  Per axis there is then one nf x nc matrix T with B^c_j = sum_i T[i][j] B^f_i; a row has
+ *   at most p+1 non-zeros, consecutive, non-negative, of sum 1; an unrefined axis gives the identity with entries exactly 1.0 and a
+ *   clamped axis unit rows at both ends.  With vectors in the natural numbering [n2][n1][n0][dof], P = T2 (x) T1 (x) T0 (x) I_dof.
+ * IGXTransferCreate builds the tables on the host, every row directly by de Boor's triangle on the blossom (p levels of convex
+ *   combinations: rounding error O(p u) however many knots were inserted; no chain of single insertions), and touches no device; the
+ *   first Prolong / Restrict uploads them.  On a periodic axis the rows are built on the unwrapped knot sequence of one period,
+ *   U[p+1 .. p+nnp], and folded through the row map the kernels use (IGXMatGetAxisMaps: function i >= nnp is function i - nnp); the
+ *   vectors hold the unique functions only.  The transfer belongs to both IGX under IGXVec's lifetime rules (destroy it before either);
+ *   after another IGXSetUp on either one it is stale and every call on it returns IGX_ERR_ORDER.
+ * IGXTransferGetAxis (host only): the table of one axis (0..2; an axis beyond dim is the 1 x 1 identity): nf, nc, width = p+1, and per fine
+ *   row the first non-zero column first[i], the band's length count[i] and the entries T[i][0..count-1], zero past count.  On a periodic
+ *   axis first[i] lies in [0, nc) and entry k belongs to column (first[i] + k) mod nc.  Any pointer may be NULL.
+ * IGXTransferProlong: xf = P xc, or xf += P xc with add != 0 (a coarse-grid correction), one rounding for the addition.
+ * IGXTransferRestrict: rc = P^T rf, the transpose that carries residuals (not an injection, not a projection).
+ *   No Dirichlet masking happens inside: boundary rows move like any others.  The end rows of a clamped axis are unit rows, so a coarse
+ *   vector's boundary values are copied along that axis; a value that is constant over the face arrives bit for bit where its products
+ *   with the other axes' entries are exact (zero always; values of few bits on dyadic refinements), else within the rounding of a convex
+ *   combination of equal numbers.  A multigrid caller zeroes the fixed rows of a restricted residual itself.
+ *   On a rational geometry the library's basis is rational, R_j = w_j N_j / W: the vector of the SAME function on the fine space is
+ *   (P (w_c * x_c)) / w_f entry by entry with the two nets' weights (the fine net being the refinement of the coarse one); P x_c itself is
+ *   the same function only where the weights are constant.  The transfer never looks at a geometry.
+ *   Work is enqueued on the FINE IGX's stream and both IGX must have the same stream set; nothing synchronises unless timing is on.
+ *   Prolong runs one fused kernel where a box's coarse footprint fits its LDS budget (boxes of 16 x 8 x 8 fine rows, 64 KiB), else one
+ *   pass per refined axis; Restrict runs one gather pass per refined axis (a coarse row sums over its fine rows in ascending order: rows
+ *   of any length, no atomics).  Both are bit-repeatable, an entry does not depend on the box that computed it, identity axes add
+ *   nothing, and a transfer without any refinement is a bit-for-bit copy both ways (petiga_amd/csrc/transfer.hpp).
+ *   IGXSetTiming / IGXGetLastTiming / IGXGetKernelName on the fine IGX report the call (its own figures, as after a solve loop):
+ *   "transfer_prolong(3d, p=3,3,3, 17x17x17 -> 33x33x33, dof 1, fused)" or "..., axis passes)", "transfer_restrict(... 33x33x33 -> 17x17x17 ...)".
+ * IGXTransferSetPath (beyond the five calls of the contract): 0 automatic, 1 the fused kernel (IGX_ERR_SUP where the footprint does not
+ *   fit), 2 the axis passes; IGXTransferGetInfo: the box's fine rows per axis, the fused kernel's LDS bytes, whether Prolong runs fused.
+ * Refusals, all decided before the first HIP call, each reason naming the transfer, in this order.  IGXTransferCreate: a null pointer
+ *   (IGX_ERR_ARG_WRONG); either IGX before IGXSetUp (IGX_ERR_ORDER); different dim, dof, then per axis degree, periodicity, then different
+ *   streams (IGX_ERR_ARG_WRONG); more than one rank on an axis of either IGX, a degree above 7, a non-periodic axis that is not clamped
+ *   (IGX_ERR_SUP); spaces not nested (IGX_ERR_ARG_OUTOFRANGE: the message gives the axis and the first coarse knot that is missing or short
+ *   of multiplicity, or says that the end knots differ).  Prolong / Restrict: a null transfer (IGX_ERR_ARG_WRONG); a stale transfer
+ *   (IGX_ERR_ORDER); a null vector, a vector of the wrong IGX, of the wrong size, the same vector twice, different streams
+ *   (IGX_ERR_ARG_WRONG).  GetAxis / SetPath / GetInfo: null, stale, then the argument's range (IGX_ERR_ARG_OUTOFRANGE).
+ * Out of scope: degree elevation (p- and k-refinement), several ranks, the multigrid cycle itself. */
+typedef struct _p_IGXTransfer *IGXTransfer;
+int IGXTransferCreate (IGX coarse,IGX fine,IGXTransfer *tr);
+int IGXTransferGetAxis(IGXTransfer tr,int axis,int *nf,int *nc,int *width /* p+1 */,
+                       int first[] /* [nf] */,int count[] /* [nf] */,double T[] /* [nf][width], zero past count */);
+int IGXTransferProlong (IGXTransfer tr,IGXVec xc,IGXVec xf,int add);
+int IGXTransferRestrict(IGXTransfer tr,IGXVec rf,IGXVec rc);
+int IGXTransferSetPath (IGXTransfer tr,int path /* 0 automatic, 1 fused, 2 axis passes */);
+int IGXTransferGetInfo (IGXTransfer tr,int box[3],int64_t *lds_bytes,int *fused);   /* any pointer may be NULL */
+int IGXTransferDestroy (IGXTransfer *tr);
+
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
  * ranks, and U must hold the ghost rows' values).  The point callbacks are the ones the reference's tests use:

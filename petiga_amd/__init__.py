@@ -175,6 +175,8 @@ def lib(build_if_needed=False):
         "IGXTimeStep": [V, C.POINTER(IGXTimeStepSpec), V, V, C.POINTER(IGXTimeStepInfo), C.POINTER(IGXTimeStepLog), C.c_int],
         "IGXProbeCreate": [V, C.c_int, C.c_int64, _dp, C.POINTER(V)], "IGXProbeGetLocal": [V, C.POINTER(C.c_int64), C.POINTER(C.c_ubyte)],
         "IGXProbeGeomMap": [V, _dp], "IGXProbeGetInfo": [V, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)], "IGXProbeEvaluate": [V, V, C.c_int, _dp], "IGXProbeDestroy": [C.POINTER(V)],
+        "IGXTransferCreate": [V, V, C.POINTER(V)], "IGXTransferGetAxis": [V, C.c_int, _ip, _ip, _ip, _ip, _ip, _dp], "IGXTransferProlong": [V, V, V, C.c_int],
+        "IGXTransferRestrict": [V, V, V], "IGXTransferSetPath": [V, C.c_int], "IGXTransferGetInfo": [V, _ip, C.POINTER(C.c_int64), _ip], "IGXTransferDestroy": [C.POINTER(V)],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -269,6 +271,65 @@ class Probe:
         assert out.shape == shape and out.dtype == np.float64 and out.flags.c_contiguous
         _ck(lib().IGXProbeEvaluate(self.h, U.h if U is not None else None, int(der), out.ctypes.data_as(_dp)))
         return out
+
+
+TRANSFER_PATHS = {"auto": 0, "fused": 1, "axis": 2}
+
+
+class Transfer:
+    """IGXTransfer: prolongation and restriction between a coarse IGX and a fine one on nested knot vectors (IGX.transfer on the fine
+    object).  It keeps both alive; its tables are built on the host, the first prolong / restrict uploads them."""
+
+    def __init__(self, fine, coarse):
+        self.fine, self.coarse = fine, coarse
+        self.h = C.c_void_p()
+        _ck(lib().IGXTransferCreate(coarse.h if coarse is not None else None, fine.h, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().IGXTransferDestroy(C.byref(self.h))
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def axis(self, i):
+        """IGXTransferGetAxis: (first [nf], count [nf], T [nf, p+1]) of axis i; on a periodic axis entry k of row r is column (first[r] + k) mod nc"""
+        nf, nc, w = C.c_int(), C.c_int(), C.c_int()
+        _ck(lib().IGXTransferGetAxis(self.h, int(i), C.byref(nf), C.byref(nc), C.byref(w), None, None, None))
+        first, count, T = np.empty(nf.value, dtype=np.int32), np.empty(nf.value, dtype=np.int32), np.empty((nf.value, w.value))
+        _ck(lib().IGXTransferGetAxis(self.h, int(i), None, None, None, first.ctypes.data_as(_ip), count.ctypes.data_as(_ip), T.ctypes.data_as(_dp)))
+        return first, count, T
+
+    def sizes(self, i):
+        """(nf, nc, width) of axis i"""
+        nf, nc, w = C.c_int(), C.c_int(), C.c_int()
+        _ck(lib().IGXTransferGetAxis(self.h, int(i), C.byref(nf), C.byref(nc), C.byref(w), None, None, None))
+        return nf.value, nc.value, w.value
+
+    def set_path(self, path):
+        """"auto", "fused" (IGXError where a box's coarse footprint does not fit the LDS budget) or "axis": the kernel prolong runs"""
+        _ck(lib().IGXTransferSetPath(self.h, TRANSFER_PATHS[path] if isinstance(path, str) else int(path)))
+        return self
+
+    def info(self):
+        """IGXTransferGetInfo: the fused kernel's box (fine rows per axis), its LDS bytes and whether prolong runs fused"""
+        box, lds, fused = (C.c_int * 3)(), C.c_int64(), C.c_int()
+        _ck(lib().IGXTransferGetInfo(self.h, box, C.byref(lds), C.byref(fused)))
+        return dict(box=tuple(box), lds_bytes=lds.value, fused=bool(fused.value))
+
+    def prolong(self, xc, xf, add=False):
+        """xf = P xc (add: xf += P xc)"""
+        _ck(lib().IGXTransferProlong(self.h, xc.h if xc is not None else None, xf.h if xf is not None else None, int(bool(add))))
+        return xf
+
+    def restrict(self, rf, rc):
+        """rc = P^T rf"""
+        _ck(lib().IGXTransferRestrict(self.h, rf.h if rf is not None else None, rc.h if rc is not None else None))
+        return rc
 
 
 class Vec:
@@ -680,6 +741,10 @@ class IGX:
     def probe(self, points, order=0):
         """IGXProbeCreate: a Probe of the parametric points [npts, dim]; order (0..3) is the highest derivative evaluate() may be asked for."""
         return Probe(self, points, order)
+
+    def transfer(self, coarse):
+        """IGXTransferCreate: a Transfer from the IGX `coarse` to this one; the knot vectors must be nested (h-refinement by knot insertion)."""
+        return Transfer(self, coarse)
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))
     def synchronize(self): _ck(lib().IGXSynchronize(self.h))

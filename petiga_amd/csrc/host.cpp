@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <string>
 #include <cstdlib>
 
@@ -779,6 +780,97 @@ int space_layout(Space &s, std::string &err) {
     L.ncolors = std::min(regular, stride) + tail;
     if (L.ncolors < 1) L.ncolors = 1;
   }
+  return 0;
+}
+
+// ------------------------------------------------------------------ transfer between nested spline spaces (IGXTransferCreate)
+// Row i of T holds the coefficients of the coarse functions in the fine function i's dual functional: the blossom of the coarse spline's
+// polynomial piece on the coarse span [u_mu, u_mu+1) that holds the fine knot t_i, at the fine knots t_i+1 .. t_i+p.  It is evaluated by de
+// Boor's triangle on the unit vectors, with the arguments taken from t_i+p down to t_i+1: at level k every weight
+// (x - u_j) / (u_j+p+1-k - u_j) then lies in [0, 1] (u_mu <= t_i <= x = t_i+p+1-k <= u_mu+p+1-k, the coarse knots being fine knots too), so a
+// row is p levels of convex combinations whatever the number of inserted knots, weights of exactly 0 and 1 leave exact zeros and ones (an
+// unrefined axis gives the identity, a clamped end the unit row), and no chain of single insertions is applied.
+// A periodic axis is built on the unwrapped knot sequence: the knots of one period, U[p+1 .. p+nnp], continued to any index by the same
+// formula on both axes (so that equal knots stay equal); the row of the fine function i < nnp over unwrapped coarse columns is folded
+// column by column with j mod nc, the closed form of the row map (AxisLayout::rowmap).  Set-up grants nnp >= p + 1, so a row's columns
+// stay distinct.  The caller has checked: same degree and periodicity, a non-periodic axis clamped.
+int transfer_axis_setup(const Axis &c, const Axis &f, int axis, TransferAxis &t, std::string &err) {
+  const int p = f.p, mc = c.m, mf = f.m, per = f.periodic ? 1 : 0;
+  const std::string where = "axis " + std::to_string(axis) + ": ";
+  const double a = f.U[p], b = f.U[mf - p], L = b - a;
+  bool ends = c.U[p] == a && c.U[mc - p] == b;
+  if (!per) for (int k = 0; k <= p; ++k) ends = ends && c.U[k] == f.U[k] && c.U[mc - k] == f.U[mf - k];
+  if (!ends) { err = where + "the spaces are not nested: the end knots differ"; return IGX_ERR_ARG_OUTOFRANGE; }
+  {   // every coarse knot (periodic: of one period) with at least its multiplicity
+    const double *Kc = per ? c.U.data() + p + 1 : c.U.data(), *Kf = per ? f.U.data() + p + 1 : f.U.data();
+    const int nkc = per ? c.nnp : mc + 1, nkf = per ? f.nnp : mf + 1;
+    for (int ic = 0, jf = 0; ic < nkc;) {
+      const double v = Kc[ic]; int mcv = 0, mfv = 0;
+      while (ic < nkc && Kc[ic] == v) { ++mcv; ++ic; }
+      while (jf < nkf && Kf[jf] < v) ++jf;
+      while (jf < nkf && Kf[jf] == v) { ++mfv; ++jf; }
+      if (mfv < mcv) {
+        char buf[256];
+        if (!mfv) snprintf(buf, sizeof(buf), "the spaces are not nested: the coarse knot %.17g is missing in the fine axis", v);
+        else snprintf(buf, sizeof(buf), "the spaces are not nested: the coarse knot %.17g has multiplicity %d, in the fine axis %d", v, mcv, mfv);
+        err = where + buf; return IGX_ERR_ARG_OUTOFRANGE;
+      }
+    }
+  }
+  auto ext = [&](const Axis &A, int j) -> double {      // the periodic knot sequence at any index
+    const int nn = A.nnp, q = j - (p + 1), k = q >= 0 ? q / nn : -((-q + nn - 1) / nn), r = q - k * nn;
+    const double v = A.U[p + 1 + r];
+    if (!k) return v;
+    return k < 0 ? a - ((double)(-k - 1) * L + (b - v)) : b + ((double)(k - 1) * L + (v - a));
+  };
+  auto cu = [&](int j) -> double { return per ? ext(c, j) : c.U[j]; };
+  auto tf = [&](int i) -> double { return per ? ext(f, i) : f.U[i]; };
+  const int nf = f.nnp, nc = c.nnp, W = p + 1, ncl = mc - p - 1;      // ncl: the last coarse function of a clamped axis
+  t.p = p; t.nf = nf; t.nc = nc; t.width = W; t.periodic = per;
+  t.first.assign(nf, 0); t.count.assign(nf, 0); t.ufirst.assign(nf, 0); t.T.assign((size_t)nf * W, 0.0);
+  int mu = per ? -(nc + p + 1) : p;
+  double D[8][8];
+  for (int i = 0; i < nf; ++i) {
+    const double t0 = tf(i);
+    while ((per || mu + 1 <= ncl) && cu(mu + 1) <= t0) ++mu;
+    for (int r = 0; r <= p; ++r) for (int q = 0; q <= p; ++q) D[r][q] = r == q ? 1.0 : 0.0;
+    for (int k = 1; k <= p; ++k) {
+      const double x = tf(i + p + 1 - k);
+      for (int jj = p; jj >= k; --jj) {
+        const int j = mu - p + jj;
+        const double uj = cu(j), w = (x - uj) / (cu(j + p + 1 - k) - uj), w1 = 1.0 - w;
+        for (int q = 0; q <= p; ++q) D[jj][q] = w1 * D[jj - 1][q] + w * D[jj][q];
+      }
+    }
+    int lo = 0, hi = p;
+    while (lo < p && D[p][lo] == 0.0) ++lo;
+    while (hi > lo && D[p][hi] == 0.0) --hi;
+    t.ufirst[i] = mu - p + lo; t.count[i] = hi - lo + 1;
+    for (int k = 0; k <= hi - lo; ++k) t.T[(size_t)i * W + k] = D[p][lo + k];
+  }
+  if (per) {
+    const int u0 = t.ufirst[0], shift = (u0 >= 0 ? u0 / nc : -((-u0 + nc - 1) / nc)) * nc;
+    for (int i = 0; i < nf; ++i) t.ufirst[i] -= shift;
+  }
+  for (int i = 0; i < nf; ++i) {
+    if (t.ufirst[i] < 0 || (!per && t.ufirst[i] + t.count[i] > nc)) { err = where + "a row of the transfer table leaves the coarse axis"; return IGX_ERR_PLIB; }
+    t.first[i] = t.ufirst[i] % nc;
+  }
+  t.identity = nf == nc;
+  for (int i = 0; i < nf && t.identity; ++i) t.identity = t.count[i] == 1 && t.first[i] == i && t.T[(size_t)i * W] == 1.0;
+  // the rows as CSR with folded columns, and the transpose by counting: fine rows ascending in every coarse row
+  t.pptr.assign(nf + 1, 0); t.rptr.assign(nc + 1, 0);
+  for (int i = 0; i < nf; ++i) t.pptr[i + 1] = t.pptr[i] + t.count[i];
+  t.pidx.resize(t.pptr[nf]); t.pval.resize(t.pptr[nf]);
+  for (int i = 0; i < nf; ++i) for (int k = 0; k < t.count[i]; ++k) {
+    const int col = (t.first[i] + k) % nc;
+    t.pidx[t.pptr[i] + k] = col; t.pval[t.pptr[i] + k] = t.T[(size_t)i * W + k];
+    ++t.rptr[col + 1];
+  }
+  for (int j = 0; j < nc; ++j) t.rptr[j + 1] += t.rptr[j];
+  t.ridx.resize(t.rptr[nc]); t.rval.resize(t.rptr[nc]);
+  std::vector<int> fill(t.rptr.begin(), t.rptr.end() - 1);
+  for (int i = 0; i < nf; ++i) for (int e = t.pptr[i]; e < t.pptr[i + 1]; ++e) { const int at = fill[t.pidx[e]]++; t.ridx[at] = i; t.rval[at] = t.pval[e]; }
   return 0;
 }
 

@@ -171,6 +171,22 @@ struct FastDiag {
 void fast_diag_fixed_faces(const Space &s, bool fixed[3][2][MAXFD]);      // the Dirichlet faces as the element kernels read them
 int  fast_diag_setup(const Space &s, double alpha, const double beta[3], FastDiag &fd, std::string &err);
 
+// Transfer between nested spline spaces (IGXTransferCreate, host.cpp; the kernels: transfer.hpp).  Per axis the nf x nc matrix T with
+// B^c_j = sum_i T[i][j] B^f_i, by rows as a band of at most p + 1 consecutive columns, and its transpose as CSR by coarse row.
+struct TransferAxis {
+  int p = 0, nf = 1, nc = 1, width = 1, periodic = 0;
+  bool identity = true;            // nf = nc and every row is the unit row with the entry exactly 1.0
+  std::vector<int> first, count;   // [nf] first non-zero column (folded into [0, nc) on a periodic axis: column (first + k) mod nc) and the band's length
+  std::vector<int> ufirst;         // [nf] the same column before folding, shifted by a multiple of nc so that row 0's lies in [0, nc): the boxes' footprints
+  std::vector<double> T;           // [nf][width], zero past count
+  std::vector<int> pptr, pidx;     // the rows again as CSR with folded columns (the axis passes): [nf + 1], [pptr[nf]]
+  std::vector<double> pval;
+  std::vector<int> rptr, ridx;     // T^T as CSR by coarse row, fine rows ascending: [nc + 1], [rptr[nc]]
+  std::vector<double> rval;
+};
+// 0, or IGX_ERR_ARG_OUTOFRANGE with the reason in err: the spaces are not nested.  The caller has checked degree, periodicity and clamped ends.
+int  transfer_axis_setup(const Axis &coarse, const Axis &fine, int axis, TransferAxis &t, std::string &err);
+
 #endif   // !IGX_RTC
 
 // ------------------------------------------------------------------ device descriptors (POD, passed by value)
