@@ -15,6 +15,7 @@
 #include "generic_kernel.hpp"
 #include "feature_mfma.hpp"
 #include "first_touch.hpp"
+#include "element_sweep.hpp"
 #if defined(IGX_TU_DISPATCH) && IGX_TU_DIM == 3
 #include "vec_sumfact.hpp"
 #define IGX_HAVE_VEC_SUMFACT 1
@@ -673,174 +674,31 @@ template <class Form, int DIM, int TA, int NW, int DOFI, bool HASM, bool PEN = f
 static int launch_feature_plan(IGX g, const SpaceDev &S, const OutDev &out, bool &done) {
   const Space &s = g->s;
   constexpr int DOF = Form::DOF;
-  constexpr bool SECOND = Form::ORDER >= 2, SECOND_S = shape_order_of<Form>::v >= 2;
-  constexpr int D2 = DIM * DIM, NFS = SECOND_S ? 1 + DIM + D2 : 1 + DIM;
-  constexpr int NTA = (TA >= 8) ? TA : ((TA == 4) ? 16 / NW : 1);
-  constexpr int SCALN = nscalar_of<Form>::v;
-  int nq[3], na[3]; int NQ = 1, NE = 1;
-  for (int d = 0; d < 3; ++d) { nq[d] = s.basis[d].nqp; na[d] = s.basis[d].nen; NQ *= nq[d]; NE *= na[d]; }
-  const int NEP = 16 * TA, NQ4 = (NQ + 3) & ~3;
-  const bool vec_op = (out.op == OP_SYSTEM || out.op == OP_VECTOR || out.op == OP_FUNCTION || out.op == OP_IFUNCTION);
-  const unsigned need = (vec_op || SCALN > 0) ? Form::NEED : mat_need_of<Form>::v;   // as in the kernel: matrix-only drivers skip residual-only point data
-  const bool fields = (need & (NEED_U | NEED_UT | NEED_GU | NEED_HU)) != 0;
-  const size_t lds_limit = 160 * 1024 - 512;
-  // LDS budget per workgroup.  4-wave kernels (nen <= 32) are compiled for 2-4 waves per SIMD (fm_min_waves) and sized
-  // so that as many workgroups fit a CU: their latency-bound tabulation phases then overlap (CahnHilliard p=2 tangent
-  // 12.8 -> 21.6 M elements/s, residual 16.7 -> 28.9).  8-wave kernels (nen = 64) hold one workgroup per CU unless the
-  // form is scalar (16 accumulator VGPRs: Poisson p=3 on a NURBS geometry 8.2 vs 6.4 M/s); for the others the fewest
-  // chunks of points win (NS-VMS 0.92 vs 0.84, Elasticity 2.67 vs 2.24 M/s).
-  const int lds_kb_env = s.env.feature_lds_kb;   // experiment switch
+  constexpr FormFacts facts = facts_of<Form>();
+  constexpr int NFS = (facts.shape_order >= 2) ? 1 + DIM + DIM * DIM : 1 + DIM;
   constexpr int WGS = fm_min_waves<Form, TA, NW, DOFI, HASM, PEN>();
-  const size_t lds_auto = (NW == 4) ? (size_t)(160 * 1024 / WGS - 1024) : ((HASM && TA == 4 && DOF == 1) ? (size_t)78 * 1024 : lds_limit);
-  const size_t lds_target = lds_kb_env > 0 ? (size_t)lds_kb_env * 1024 : lds_auto;
-  FCarve cv; size_t lds_bytes = 0; bool fits = false;
-  for (int pass = 0; pass < 2 && !fits; ++pass) {
-    const size_t cap = pass == 0 ? lds_target : lds_limit;
-    for (int nchunk = 1; nchunk <= NQ4 / 4 && !fits; ++nchunk) {
-      const int QC = (((NQ4 + nchunk - 1) / nchunk) + 3) & ~3, NQP = QC * nchunk;
-      int pos = 0;
-      auto take = [&](int n) { int o = pos; pos += (n + 1) & ~1; return o; };
-      for (int d = 0; d < 3; ++d) { cv.t1d[d] = take(nq[d] * na[d] * NDER); cv.w1d[d] = take(2 * nq[d]); }
-      cv.gX = take(NE * DIM); cv.gW = take(NE); cv.Ue = take(NE * DOF); cv.Ve = take(NE * DOF);
-      cv.ufix = take(NE * DOF); cv.fixval = take(NE * DOF); cv.fixflag = take(NE * DOF); cv.flux = take(NE * DOF);
-      cv.JW = take(NQP); cv.xq = take(NQP * DIM); cv.E1 = take(s.nsd ? NQP * D2 : 0); cv.E2 = take((s.nsd && SECOND) ? NQP * DIM * D2 : 0);
-      cv.W0 = take(s.rational ? NQP : 0); cv.W1 = take(s.rational ? NQP * DIM : 0); cv.W2 = take((s.rational && SECOND) ? NQP * D2 : 0);
-      cv.G = take((Form::NEED & NEED_G) ? NQP * D2 : 0);
-      cv.u = take(fields ? QC * DOF : 0); cv.ut = take(fields ? QC * DOF : 0);
-      cv.gu = take((need & NEED_GU) ? QC * DOF * DIM : 0);
-      cv.hu = take((need & NEED_HU) ? ((SECOND && !SECOND_S) ? NQP : QC) * DOF * D2 : 0);
-      cv.hpart = 0;
-      cv.lift = take(SCALN > 0 ? QC * SCALN : (out.op == OP_SYSTEM ? QC * DOF * NFS : 0));
-      cv.rowbase = take(HASM ? NE : 0); cv.rowid = take(NE); cv.cc = take(NE); cv.pax = take(96); cv.adec = take(NEP / 2); cv.qdec = take((NQP + 1) / 2); cv.nrm = take(NQP * DIM);
-      // the sum-factorised geometry sums of phase 1 borrow the Phi region before Phi exists
-      // (and so do the sums behind the field Hessians of a form that reads them without second derivatives of N: DOF components)
-      constexpr bool HU_FLY = SECOND && !SECOND_S && (Form::NEED & NEED_HU) != 0;
-      cv.sfb = (NE > 64) ? 1 : DOF;      // large elements: one field at a time
-      const int sf_nc = std::max((s.nsd || s.rational) ? DIM + 1 : 0, (HU_FLY && (need & NEED_HU)) ? cv.sfb : 0);
-      const int sf_need = sf_nc * ((SECOND ? 3 : 2) * nq[0] * na[1] * na[2] + (SECOND ? 6 : 3) * nq[0] * nq[1] * na[2] + (SECOND ? 10 : 4) * NQ);
-      // pencil mode parks the 7 leaving tiles of every (i,j) block of a launch in the Phi region before they are written out
-      constexpr unsigned long long PR = mat_pair_mask_of<Form>::v;
-      const int stage_need = PEN ? 7 * 16 * 17 * (PR ? fm_popcount(fm_pairs_upper(PR)) : DOFI * DOF) : 0;   // the leaving tiles (feature_mfma.hpp)
-      cv.boff = 0;
-      constexpr int NPS = fm_popcount((unsigned long long)(phi_mask_of<Form>::v & ((1u << NFS) - 1u)));   // features kept in LDS
-      cv.phi = take(std::max(std::max(NPS * QC * NEP, sf_need), stage_need));
-      cv.total = pos; cv.QC = QC; cv.nchunk = nchunk; cv.NEP = NEP;
-      lds_bytes = (size_t)pos * sizeof(double);
-      if (lds_bytes <= cap) fits = true;
-    }
-  }
-  if (!fits) return 0;   // not covered: the generic kernel takes it
-  ParamsDev prm; memset(&prm, 0, sizeof(prm));
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
-  int launches = 0; bool first = true;
-  constexpr bool SCAL = nscalar_of<Form>::v > 0;
-  // first-touch stores instead of MatZeroEntries + read (same rule as the pencil kernel): regular e mod (p+1) colours on
-  // every axis; a rank with neighbours zeroes only the rows that keep neighbour-owned columns
-  bool first_touch = HASM && !s.env.no_first_touch;
-  for (int d = 0; d < DIM && first_touch; ++d) first_touch = axis_first_touch_ok(s, d);
-  OutDev out_ft = out; out_ft.first_touch = first_touch ? 1 : 0;
-  if (HASM) {
-    if (!first_touch) { if (g->zero_matrix) g->zero_matrix(); }
-    else if (s.proc_sizes[0] * s.proc_sizes[1] * s.proc_sizes[2] > 1) zero_neighbour_rows(s, out, g->stream);
-  }     // nothing is scattered: every element in one sweep, one partial row each
-  int64_t elem_base = 0;
-  int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
-  if (SCAL) nc[0] = nc[1] = nc[2] = 1;
-  if (g->timing && g->dom.ev0 && g->dom.launches == 0) (void)hipEventRecord(g->dom.ev0, g->stream);
-  constexpr bool pencil = PEN;
-  // Several ranks on axis 2 and a communicator: the elements within p layers of the upper face of axis 2 first (every colour),
-  // a mark for the exchange (g->slab_done), then the rest -- as the pencil kernel does (gram_mfma.hpp, try_gram_mfma).
-  const int n2 = s.elem_width[2], p2 = s.axis[2].p;
-  bool split = g->slab_done && !SCAL && DIM == 3 && s.proc_sizes[2] > 1 && (s.proc_ranks[2] < s.proc_sizes[2] - 1 || s.axis[2].periodic) && n2 >= 2 * (p2 + 1) && axis_first_touch_ok(s, 2);
-  for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) split = false;
-  const int npass = split ? 2 : 1;
-  for (int pass = 0; pass < npass; ++pass) {
-  const int lo2 = (split && pass == 1) ? 0 : (split ? n2 - p2 : 0), hi2 = (split && pass == 1) ? n2 - p2 : n2;
-  if (split) { out_ft.ft2_lo = lo2; out_ft.ft2_hi = hi2; out_ft.ft2_blocked = pass == 1 ? n2 - p2 : 0x7fffffff; }
-  if (split && pass == 1) g->slab_done();
-  if constexpr (PEN) {
-    {
-      for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) {
-        const int cc[3] = {0, c1, c2};
-        ColorRange cr; bool empty = false;
-        cr.start[0] = 0; cr.step[0] = 1; cr.count[0] = s.elem_width[0];
-        for (int d = 1; d < 3; ++d) {
-          const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d];
-          int firstel = -1, count = 0;
-          for (int e = (d == 2 ? lo2 : 0); e < (d == 2 ? hi2 : nel); ++e) if (L.color[e] == cc[d]) { if (firstel < 0) firstel = e; count++; }
-          if (count == 0) { empty = true; break; }
-          cr.start[d] = firstel; cr.step[d] = L.p + 1; cr.count[d] = count;
-        }
-        if (empty) continue;
-        const size_t nblocks = (size_t)cr.count[1] * cr.count[2];
-        launch_feature_passes<Form, DIM, TA, NW, DOFI, 0, HASM, true>(g, S, prm, out_ft, cr, cv, nblocks, lds_bytes, first, launches);
-        first = false;
-      }
-    }
-  }
-  if constexpr (!PEN) for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
-    const int cc[3] = {c0, c1, c2};
-    ColorRange cr; bool empty = false;
-    for (int d = 0; d < 3; ++d) {
-      const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d], stride = L.p + 1;
-      int firstel = -1, count = 0;
-      for (int e = (d == 2 ? lo2 : 0); e < (d == 2 ? hi2 : nel); ++e) if (L.color[e] == cc[d]) { if (firstel < 0) firstel = e; count++; }
-      if (SCAL) { firstel = 0; count = nel; }
-      if (count == 0) { empty = true; break; }
-      cr.start[d] = firstel; cr.step[d] = SCAL ? 1 : stride; cr.count[d] = count;
-    }
-    if (empty) continue;
-    const size_t per2 = (size_t)cr.count[0] * cr.count[1];
-    const int chunk2 = (int)std::max<size_t>(1, std::min<size_t>((size_t)cr.count[2], ((size_t)1 << 30) / std::max<size_t>(per2, 1)));
-    for (int k0 = 0; k0 < cr.count[2]; k0 += chunk2) {
-      ColorRange sub = cr; sub.start[2] = cr.start[2] + k0 * cr.step[2]; sub.count[2] = std::min(chunk2, cr.count[2] - k0);
-      const size_t nblocks = per2 * sub.count[2];
-      OutDev o2 = out_ft; o2.elem_base = elem_base; elem_base += (int64_t)nblocks;
-      launch_feature_passes<Form, DIM, TA, NW, DOFI, 0, HASM>(g, S, prm, o2, sub, cv, nblocks, lds_bytes, first, launches);
-      first = false;
-    }
-  }
-  }   // passes over axis 2
-  // boundary-form passes (IGAElementNextForm, src/petigaelem.c:427-447): the elements of this rank on a visited face,
-  // one point layer at the face; their K_e / F_e add to what the interior pass left (stream order)
-  if constexpr (!PEN) for (int bid = 0; bid < 2 * DIM; ++bid) {   // (the pencil plan is not chosen when a face is visited)
-    const int ax = bid / 2, sd = bid % 2;
-    if (!s.visit[ax][sd]) continue;
-    const int eface = sd ? s.elem_sizes[ax] - 1 : 0;
-    if (eface < s.elem_start[ax] || eface >= s.elem_start[ax] + s.elem_width[ax]) continue;   // face is on another rank
-    OutDev ob = out; ob.bid = bid;
-    int nc2[3] = {nc[0], nc[1], nc[2]}; nc2[ax] = 1;
-    for (int c2 = 0; c2 < nc2[2]; ++c2) for (int c1 = 0; c1 < nc2[1]; ++c1) for (int c0 = 0; c0 < nc2[0]; ++c0) {
-      const int cc[3] = {c0, c1, c2};
-      ColorRange cr; bool empty = false;
-      for (int d = 0; d < 3; ++d) {
-        if (d == ax) { cr.start[d] = eface - s.elem_start[ax]; cr.step[d] = 1; cr.count[d] = 1; continue; }
-        const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d], stride = L.p + 1;
-        int firstel = -1, count = 0;
-        for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (firstel < 0) firstel = e; count++; }
-        if (SCAL) { firstel = 0; count = nel; }
-        if (count == 0) { empty = true; break; }
-        cr.start[d] = firstel; cr.step[d] = SCAL ? 1 : stride; cr.count[d] = count;
-      }
-      if (empty) continue;
-      const size_t nblocks = (size_t)cr.count[0] * cr.count[1] * cr.count[2];
-      ob.elem_base = elem_base; elem_base += (int64_t)nblocks;
-      launch_feature_passes<Form, DIM, TA, NW, DOFI, 0, HASM>(g, S, prm, ob, cr, cv, nblocks, lds_bytes, first, launches);
-      first = false;
-    }
-  }
+  constexpr int NPS = fm_popcount((unsigned long long)(phi_mask_of<Form>::v & ((1u << NFS) - 1u)));   // features kept in LDS
+  // pencil mode parks the 7 leaving tiles of every (i,j) block of a launch in the Phi region before they are written out
+  constexpr unsigned long long PR = mat_pair_mask_of<Form>::v;
+  constexpr int stage_need = PEN ? 7 * 16 * 17 * (PR ? fm_popcount(fm_pairs_upper(PR)) : DOFI * DOF) : 0;   // the leaving tiles (feature_mfma.hpp)
+  const FeatureCarve fc = carve_feature(facts, s, out.op, TA, NW, HASM, WGS, NPS, stage_need);
+  if (!fc.fits) return 0;   // not covered: the generic kernel takes it
+  const FCarve &cv = fc.cv; const size_t lds_bytes = fc.lds_bytes;
+  const ParamsDev prm = params_of(s);
+  const bool fused = HASM && !PEN && DOFI < DOF && s.env.fuse_groups;   // one launch forms all groups of row fields of its elements
+  FeatureSweep fs;
+  fs.HASM = HASM; fs.pencil = PEN; fs.single = facts.nscalar > 0; fs.two_pass = true;
+  fs.dom_name = PEN ? "feature_assemble<pencil>" : "feature_assemble<element>";
+  fs.dom_groups = (HASM && !fused) ? (DOF / DOFI) : 1;
+  fs.flop_per_element = HASM ? feature_mfma_flop<Form, TA>(cv.QC * cv.nchunk) * (fused ? DOF : DOFI) / DOF : 0.0;
+  if (int rc = sweep_feature(g, out, fs, [&](const OutDev &o, const ColorRange &cr, size_t nblocks, bool first, int &launches) {
+        launch_feature_passes<Form, DIM, TA, NW, DOFI, 0, HASM, PEN>(g, S, prm, o, cr, cv, nblocks, lds_bytes, first, launches);
+        return 0;
+      })) return rc;
   HIPCK(hipGetLastError());
-  g->last_launches = launches;
-  if (g->dom.launches == 0) {   // dominant kernel of this assembly, for bench.py's roofline block
-    if (g->timing && g->dom.ev1) (void)hipEventRecord(g->dom.ev1, g->stream);
-    g->dom.name = std::string("feature_assemble<") + (pencil ? "pencil" : "element") + ">"; g->dom.launches = launches;
-    const bool fused = HASM && !pencil && DOFI < DOF && s.env.fuse_groups;   // one launch forms all groups of row fields of its elements
-    g->dom.elements = (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] * ((HASM && !fused) ? (DOF / DOFI) : 1);
-    g->dom.flop_per_element = HASM ? feature_mfma_flop<Form, TA>(cv.QC * cv.nchunk) * (fused ? DOF : DOFI) / DOF : 0.0;
-  }
   if (HASM) g->last_kernel = std::string("feature_assemble(mfma_f64_16x16x4,tiles=") + std::to_string(TA) + "x" + std::to_string(TA) + ",waves=" + char('0' + NW) +
-                   ",rowfields/launch=" + char('0' + DOFI) + ((!pencil && DOFI < DOF && s.env.fuse_groups) ? std::string("x") + char('0' + DOF / DOFI) + " fused" : std::string()) +
-                   ",chunks=" + std::to_string(cv.nchunk) + (pencil ? ",pencil walk axis 0" : "") + ")";
+                   ",rowfields/launch=" + char('0' + DOFI) + (fused ? std::string("x") + char('0' + DOF / DOFI) + " fused" : std::string()) +
+                   ",chunks=" + std::to_string(cv.nchunk) + (PEN ? ",pencil walk axis 0" : "") + ")";
   else g->last_kernel = std::string("feature_assemble(vector only,waves=") + char('0' + NW) + ",chunks=" + std::to_string(cv.nchunk) + ")";
   done = true;
   return 0;
@@ -855,7 +713,7 @@ static int launch_feature_ta(IGX g, const SpaceDev &S, const OutDev &out, bool &
   // launches of one row field with 4-wave workgroups, two per CU, 1.63 M elements/s (tabulation repeated per launch).
   if constexpr (nscalar_of<Form>::v > 0) return launch_feature_plan<Form, DIM, TA, NW, DOF, false>(g, S, out, done);
   else {
-    const bool hasM = (out.op == OP_SYSTEM || out.op == OP_MATRIX || out.op == OP_JACOBIAN || out.op == OP_IJACOBIAN);
+    const bool hasM = op_has_matrix(out.op);
     if (!hasM) return launch_feature_plan<Form, DIM, TA, NW, DOF, false>(g, S, out, done);
     // field Hessians on the fly live in the vector-only kernels unless the matrix callback reads them too (feature_mfma.hpp,
     // HU_HERE): IGAComputeSystem of such a form (NS-VMS: nobody calls it) is left to the point-form kernel
@@ -903,7 +761,7 @@ static int launch_feature(IGX g, const SpaceDev &S, const OutDev &out, bool &don
         for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) return 0;
         if constexpr (NACC16 == 1) return launch_feature_ta<Form, DIM, 16>(g, S, out, done);
         else {
-          const bool hasM = (out.op == OP_SYSTEM || out.op == OP_MATRIX || out.op == OP_JACOBIAN || out.op == OP_IJACOBIAN);
+          const bool hasM = op_has_matrix(out.op);
           if (hasM) return 0;
           return launch_feature_plan<Form, DIM, 16, 8, Form::DOF, false>(g, S, out, done);
         }
@@ -916,7 +774,7 @@ static int launch_feature(IGX g, const SpaceDev &S, const OutDev &out, bool &don
         for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) return 0;
         if constexpr (NACC8 <= 2) return launch_feature_ta<Form, DIM, 8>(g, S, out, done);
         else {   // more accumulator sets than a wave holds at 8 tiles each: the vector-only drivers still take the kernel
-          const bool hasM = (out.op == OP_SYSTEM || out.op == OP_MATRIX || out.op == OP_JACOBIAN || out.op == OP_IJACOBIAN);
+          const bool hasM = op_has_matrix(out.op);
           if (hasM) return 0;
           return launch_feature_plan<Form, DIM, 8, 8, Form::DOF, false>(g, S, out, done);
         }
@@ -933,11 +791,11 @@ template <class Form, int DIM>
 static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
   const Space &s = g->s;
   constexpr int DOF = Form::DOF;
-  constexpr bool SECOND = Form::ORDER >= 2, THIRD = Form::ORDER >= 3;
-  constexpr int NF = nfeat<DIM>(Form::ORDER), D2 = DIM * DIM, D3 = D2 * DIM;
+  constexpr bool THIRD = Form::ORDER >= 3;
   constexpr int NS = nscalar_of<Form>::v;
   // third-order tabulation, the property array and the point's shape table exist in the general kernel only
   constexpr bool GENERAL = general_only_of<Form>::v;
+  const ParamsDev prm = params_of(s);
   // the matrix-free actions (IGXCompute*Action): vec_sumfact's ACTION instantiation or a refusal that names the reason -- no other kernel forms them
   if (out.op == OP_MATRIX_ACTION || out.op == OP_JACOBIAN_ACTION || out.op == OP_IJACOBIAN_ACTION) {
 #ifdef IGX_HAVE_VEC_SUMFACT
@@ -945,8 +803,6 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
       if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);
       if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
       bool done = false;
-      ParamsDev prm; memset(&prm, 0, sizeof(prm));
-      for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
       if (int rc = try_vec_sumfact<Form, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
       return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix action it covers");
     } else
@@ -971,8 +827,6 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
     if constexpr (DIM == 3 && !GENERAL && NS == 0 && !has_boundary_of<Form>::v && shape_order_of<Form>::v < 2) {
       if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
       bool done = false;
-      ParamsDev prm; memset(&prm, 0, sizeof(prm));
-      for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
       if (int rc = blk ? try_vec_sumfact<Form, false, true, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)
                        : try_vec_sumfact<Form, false, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
       return done ? 0 : fail(IGX_ERR_PLIB, blk ? "vec_sumfact did not take a matrix block diagonal it covers" : "vec_sumfact did not take a matrix diagonal it covers");
@@ -990,8 +844,6 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
 #ifdef IGX_HAVE_VEC_SUMFACT
   if constexpr (DIM == 3 && !GENERAL) if (g->kernel_choice == 0 && !emb) {   // vector-only drivers: sum factorisation both ways (vec_sumfact.hpp)
     bool done = false;
-    ParamsDev prm; memset(&prm, 0, sizeof(prm));
-    for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
     if (int rc = try_vec_sumfact<Form>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
     if (done) return 0;
   }
@@ -999,8 +851,6 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
 #ifdef IGX_HAVE_BLOCK_PENCIL
   if constexpr (DIM == 3 && !GENERAL) if ((g->kernel_choice == 0 || g->kernel_choice == 4) && !emb) {   // band rows by node layer (block_pencil.hpp)
     bool done = false;
-    ParamsDev prm; memset(&prm, 0, sizeof(prm));
-    for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
     if (int rc = try_block_pencil<Form>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, g_err, done, g->dom, g->zero_matrix, g->slab_done)) return rc;
     if (done) return 0;
   }
@@ -1010,8 +860,6 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
   //  feature kernel's 2 x 2 tiles are as fast -- so the automatic choice keeps the feature kernel at p = 2)
   if constexpr (DIM == 3 && !GENERAL) if ((g->kernel_choice == 0 && s.axis[0].p == 3) || g->kernel_choice == 4) {   // band rows by node layer, point-dependent coefficients (band_pt.hpp)
     bool done = false;
-    ParamsDev prm; memset(&prm, 0, sizeof(prm));
-    for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
     if (int rc = try_band_pt<Form>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, g_err, done, g->dom, g->zero_matrix, g->slab_done)) return rc;
     if (done) return 0;
   }
@@ -1026,109 +874,21 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
   if (g->zero_matrix) g->zero_matrix();
   const bool fields = (Form::NEED & (NEED_U | NEED_UT | NEED_GU | NEED_HU | NEED_D3U)) != 0;
   if (s.dof != DOF && (NS == 0 || fields)) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
-  int nq[3], na[3]; int NQ = 1, NE = 1;
-  for (int d = 0; d < 3; ++d) { nq[d] = s.basis[d].nqp; na[d] = s.basis[d].nen; NQ *= nq[d]; NE *= na[d]; }
-  Carve cv; int pos = 0;
-  auto take = [&](int n) { int o = pos; pos += (n + 1) & ~1; return o; };   // keep 16-byte alignment
-  for (int d = 0; d < 3; ++d) { cv.t1d[d] = take(nq[d] * na[d] * NDER); cv.w1d[d] = take(nq[d]); }
-  const int nsd = s.nsd ? s.nsd : DIM;
-  cv.gX = take(NE * nsd); cv.gW = take(NE); cv.Ue = take(NE * DOF); cv.Ve = take(NE * DOF);
-  cv.ufix = take(NE * DOF); cv.fixval = take(NE * DOF); cv.fixflag = take(NE * DOF); cv.flux = take(NE * DOF);
-  cv.JW = take(NQ); cv.xq = take(NQ * nsd); cv.E1 = take((s.nsd && !emb) ? NQ * D2 : 0); cv.E2 = take((s.nsd && !emb && SECOND) ? NQ * DIM * D2 : 0);
-  cv.W0 = take(s.rational ? NQ : 0); cv.W1 = take(s.rational ? NQ * DIM : 0); cv.W2 = take((s.rational && SECOND) ? NQ * D2 : 0);
-  cv.G = take((Form::NEED & NEED_G) ? NQ * DIM * nsd : 0);
-  cv.X1m = take((Form::NEED & NEED_MAPX) ? NQ * nsd * DIM : 0); cv.X2m = take(((Form::NEED & NEED_MAPX) && SECOND) ? NQ * nsd * D2 : 0);
-  cv.E3 = take((s.nsd && !emb && THIRD) ? NQ * DIM * D3 : 0); cv.W3 = take((s.rational && THIRD) ? NQ * D3 : 0);
-  cv.d3u = take((THIRD && (Form::NEED & NEED_D3U)) ? NQ * DOF * D3 : 0); cv.gA = take(NE * S.npd);
-  cv.u = take(fields ? NQ * DOF : 0); cv.ut = take(fields ? NQ * DOF : 0);
-  cv.gu = take((Form::NEED & NEED_GU) ? NQ * DOF * DIM : 0); cv.hu = take((Form::NEED & NEED_HU) ? NQ * DOF * D2 : 0);
-  cv.lift = take(NS > 0 ? NQ * NS : (out.op == OP_SYSTEM ? NQ * DOF * NF : 0));
-  cv.nrm = take(NQ * nsd);
-  const size_t phi_doubles = (size_t)NQ * NE * NF;
   // Phi in LDS up to 64 KiB per workgroup, in an HBM slice beyond: a 131 KiB Phi (p = 3) in LDS leaves one workgroup per CU and
   // measured slower than the HBM slice with two (Poisson p=3 48^3: 0.91 vs 1.71 M elements/s, Elasticity 0.80 vs 1.28)
   const size_t lds_limit = 160 * 1024 - 512, phi_limit = 64 * 1024;
-  bool phi_in_lds = ((size_t)pos + phi_doubles) * sizeof(double) <= phi_limit;
-  if (phi_in_lds) cv.phi = take((int)phi_doubles); else cv.phi = -1;
-  cv.total = pos;
-  const size_t lds_bytes = (size_t)pos * sizeof(double);
+  const GenericCarve gc = carve_generic(facts_of<Form>(), s, S.npd, out.op, phi_limit);
+  const size_t lds_bytes = gc.lds_bytes;
   if (lds_bytes > lds_limit) return fail(IGX_ERR_SUP, "element work set exceeds the 160 KiB LDS");
   auto kern = generic_assemble<Form, DIM>;
   HIPCK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  ParamsDev prm; memset(&prm, 0, sizeof(prm));
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
-
-  const size_t scratch_cap = (size_t)2 << 30;   // HBM slice for Phi when it does not fit in LDS
-  size_t max_blocks = phi_in_lds ? ((size_t)1 << 30) : scratch_cap / (phi_doubles * sizeof(double));
-  if (max_blocks < 1) max_blocks = 1;
-  int launches = 0;
-  int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
-  if (NS > 0) nc[0] = nc[1] = nc[2] = 1;   // nothing is scattered: every element in one sweep
-  int64_t elem_base = 0;
-  for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
-    const int cc[3] = {c0, c1, c2};
-    ColorRange cr; bool empty = false;
-    for (int d = 0; d < 3; ++d) {
-      const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d], stride = L.p + 1;
-      int first = -1, count = 0;
-      for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (first < 0) first = e; count++; }
-      if (NS > 0) { first = 0; count = nel; }
-      if (count == 0) { empty = true; break; }
-      cr.start[d] = first; cr.step[d] = (NS > 0) ? 1 : stride; cr.count[d] = count;
-    }
-    if (empty) continue;
-    // split along axis 2 so that a launch never needs more scratch than the cap
-    const size_t per2 = (size_t)cr.count[0] * cr.count[1];
-    int chunk2 = (int)std::max<size_t>(1, std::min<size_t>((size_t)cr.count[2], max_blocks / std::max<size_t>(per2, 1)));
-    if (!phi_in_lds && per2 > max_blocks) return fail(IGX_ERR_SUP, "scratch too small for one element layer");
-    for (int k0 = 0; k0 < cr.count[2]; k0 += chunk2) {
-      ColorRange sub = cr; sub.start[2] = cr.start[2] + k0 * cr.step[2]; sub.count[2] = std::min(chunk2, cr.count[2] - k0);
-      const size_t nblocks = per2 * sub.count[2];
-      if (!phi_in_lds) {
-        const size_t need = nblocks * phi_doubles * sizeof(double);
-        if (g->scratch.bytes < need) { HIPCK(hipStreamSynchronize(g->stream)); if (g->scratch.alloc(need)) return fail(IGX_ERR_MEM, "scratch allocation failed"); }
-      }
-      OutDev o2 = out; o2.elem_base = elem_base; elem_base += (int64_t)nblocks;
-      hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_bytes, g->stream, S, prm, o2, sub, cv, g->scratch.as<double>(), phi_doubles);
-      launches++;
-    }
-  }
-  // boundary-form passes (IGAElementNextForm, src/petigaelem.c:427-447): the elements of this rank on a visited face, one point
-  // layer at the face; their K_e / F_e add to what the interior pass left (stream order)
-  for (int bid = 0; bid < 2 * DIM; ++bid) {
-    const int ax = bid / 2, sd = bid % 2;
-    if (!s.visit[ax][sd]) continue;
-    const int eface = sd ? s.elem_sizes[ax] - 1 : 0;
-    if (eface < s.elem_start[ax] || eface >= s.elem_start[ax] + s.elem_width[ax]) continue;   // the face is on another rank
-    OutDev ob = out; ob.bid = bid;
-    int nc2[3] = {nc[0], nc[1], nc[2]}; nc2[ax] = 1;
-    for (int c2 = 0; c2 < nc2[2]; ++c2) for (int c1 = 0; c1 < nc2[1]; ++c1) for (int c0 = 0; c0 < nc2[0]; ++c0) {
-      const int cc[3] = {c0, c1, c2};
-      ColorRange cr; bool empty = false;
-      for (int d = 0; d < 3; ++d) {
-        if (d == ax) { cr.start[d] = eface - s.elem_start[ax]; cr.step[d] = 1; cr.count[d] = 1; continue; }
-        const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d], stride = L.p + 1;
-        int first = -1, count = 0;
-        for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (first < 0) first = e; count++; }
-        if (NS > 0) { first = 0; count = nel; }
-        if (count == 0) { empty = true; break; }
-        cr.start[d] = first; cr.step[d] = (NS > 0) ? 1 : stride; cr.count[d] = count;
-      }
-      if (empty) continue;
-      const size_t nblocks = (size_t)cr.count[0] * cr.count[1] * cr.count[2];
-      if (!phi_in_lds) {
-        const size_t need = nblocks * phi_doubles * sizeof(double);
-        if (nblocks > max_blocks) return fail(IGX_ERR_SUP, "scratch too small for one face layer");
-        if (g->scratch.bytes < need) { HIPCK(hipStreamSynchronize(g->stream)); if (g->scratch.alloc(need)) return fail(IGX_ERR_MEM, "scratch allocation failed"); }
-      }
-      ob.elem_base = elem_base; elem_base += (int64_t)nblocks;
-      hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_bytes, g->stream, S, prm, ob, cr, cv, g->scratch.as<double>(), phi_doubles);
-      launches++;
-    }
-  }
+  if (int rc = sweep_generic(g, g_err, gc, NS > 0, [&](const ColorRange &cr, int bid, int64_t elem_base, size_t nblocks) {
+        OutDev o = out; o.bid = bid; o.elem_base = elem_base;
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_bytes, g->stream, S, prm, o, cr, gc.cv, g->scratch.template as<double>(), gc.phi_doubles);
+        return 0;
+      })) return rc;
   HIPCK(hipGetLastError());
-  g->last_launches = launches;
-  g->last_kernel = std::string("generic_assemble(") + (phi_in_lds ? "phi=LDS" : "phi=HBM") + ")";
+  g->last_kernel = std::string("generic_assemble(") + (gc.phi_in_lds ? "phi=LDS" : "phi=HBM") + ")";
   return 0;
 }
 
@@ -1268,8 +1028,8 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
     for (int d = 0; d < 3 && ok; ++d) for (int sd = 0; sd < 2; ++sd) if (s.load[d][sd].count || s.visit[d][sd]) ok = false;      // (loads: F_e[k] -= flux, src/petigaelem.c:1449-1454 -- the element kernels' business)
     if (!ok) return 0;
   }
-  const bool hasM = (op == OP_SYSTEM || op == OP_MATRIX || op == OP_JACOBIAN || op == OP_IJACOBIAN);
-  const bool hasV = fused || (op == OP_SYSTEM || op == OP_VECTOR || op == OP_FUNCTION || op == OP_IFUNCTION);
+  const bool hasM = op_has_matrix(op);
+  const bool hasV = fused || op_has_vector(op);
   if (hasM && (!A || A->iga != g)) return fail(IGX_ERR_ARG_WRONG, "matrix missing or created by another IGX");
   if (hasV && (!b || b->iga != g)) return fail(IGX_ERR_ARG_WRONG, "vector missing or created by another IGX");
   if (U && U->iga != g) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
@@ -1317,7 +1077,7 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
       }
       if (st.kfn) {
         st.state = true; st.state_geo = true; st.extra_lds = pencil_state_bytes() + pencil_sgeo_bytes() - pencil_geo_bytes();
-        for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) st.prm.v[i] = s.params[i];
+        st.prm = params_of(s);
       }
     }
     // (asked for by name, a Tangent on a mapped geometry at another degree is refused with the reason; the automatic choice goes on to the feature kernel)
@@ -1341,7 +1101,7 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
         if (fused) st.name += "+Residual";
         else st.patch_kfn = s.form == IGX_FORM_CAHNHILLIARD ? reinterpret_cast<const void *>(state_patch_p2<FormCahnHilliard<3>>) : reinterpret_cast<const void *>(state_patch_p2<FormBratu<3>>);
       }
-      if (st.kfn) { st.state = true; st.extra_lds = pencil_state_bytes() + (fused ? (size_t)8 * (RWIN_DOUBLES + 128) * 8 : 0) /* fused: the Residual's ring and the scratch of its u_t sums, per wavefront */; for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) st.prm.v[i] = s.params[i]; }
+      if (st.kfn) { st.state = true; st.extra_lds = pencil_state_bytes() + (fused ? (size_t)8 * (RWIN_DOUBLES + 128) * 8 : 0) /* fused: the Residual's ring and the scratch of its u_t sums, per wavefront */; st.prm = params_of(s); }
     }
     rc = try_gram_mfma(g->s, S, out, g->stream, g->kernel_choice == 2, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix, slab_done, st.kfn ? &st : nullptr, face_done);
     g->face_done = nullptr;

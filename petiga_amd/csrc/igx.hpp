@@ -258,6 +258,9 @@ struct OutDev {
 // The matrix-free actions (OP_MATRIX_ACTION / OP_JACOBIAN_ACTION / OP_IJACOBIAN_ACTION) run on vec_sumfact (vec_sumfact.hpp, ACTION) or not at all: why not, or null.
 // Boundary loads do not enter a matrix and are ignored.
 inline bool op_is_action(int op) { return op == OP_MATRIX_ACTION || op == OP_JACOBIAN_ACTION || op == OP_IJACOBIAN_ACTION; }
+// the drivers that assemble a matrix / a vector (IGAComputeSystem does both)
+inline bool op_has_matrix(int op) { return op == OP_SYSTEM || op == OP_MATRIX || op == OP_JACOBIAN || op == OP_IJACOBIAN; }
+inline bool op_has_vector(int op) { return op == OP_SYSTEM || op == OP_VECTOR || op == OP_FUNCTION || op == OP_IFUNCTION; }
 // basis functions and points of axis d: the basis' once the space is set up, before that what the axes and rules set so far will give (src/petigabasis.c:103)
 inline void vec_axis_sizes(const Space &s, int d, int &nen, int &nqp) {
   if (s.setup) { nen = s.basis[d].nen; nqp = s.basis[d].nqp; }

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include "first_touch.hpp"
+#include "element_sweep.hpp"
 #endif
 #include "igx.hpp"
 
@@ -105,12 +106,7 @@ inline hipError_t pool_alloc(void **ptr, size_t bytes, hipStream_t stream) {
   return rc;
 }
 
-// colour c of axis d restricted to [lo,hi): arithmetic sequence (regular colours) or a single element
-static bool color_range(const AxisLayout &L, int c, int lo, int hi, int &start, int &step, int &count) {
-  start = -1; count = 0; step = L.p + 1;
-  for (int e = lo; e < hi; ++e) if (L.color[e] == c) { if (start < 0) start = e; count++; }
-  return count > 0;
-}
+// (color_range, the colour c of an axis restricted to [lo,hi): element_sweep.hpp)
 
 #endif   // !IGX_RTC
 

@@ -66,7 +66,8 @@ struct RtcFeature {
   std::vector<char> code;
   std::vector<std::string> lowered;
   hipModule_t module = nullptr; std::vector<hipFunction_t> func;
-  int meta[4] = {0, 0, 0, 0};          // workgroups per CU the kernel is compiled for, features kept in LDS, executed MFMAs per k-step, 0
+  FeatureFacts facts;                  // feature_assemble: igx_feature_meta[4] by name (element_sweep.hpp)
+  int band_rec = 0, band_products = 0; bool band_guard = false;      // band_pt: igx_band_meta[4] (bpt_rec, bpt_products, the struct has its own band_params_ok)
   bool failed = false; std::string why;     // band_pt under the automatic choice: the instantiation did not compile; the form stays on the feature kernel
   ~RtcFeature() { if (module) (void)hipModuleUnload(module); }
 };
@@ -76,10 +77,7 @@ struct RtcForm {
   std::string name, source, lowered;
   int dim = 0;
   std::vector<char> code;
-  // DOF, ORDER, NEED, NSCALAR, SHAPE_ORDER, MAT_NEED, MAT_PAIR_MASK != 0, has an atboundary branch, MAT_TEST_MASK, MAT_SYMMETRIC,
-  // VEC_TEST_MASK, PENCIL_NFEAT or 0 (read from the module)
-  // [12] number of Gram pairs (bits of MAT_PAIR_MASK), [13] VEC_ZERO, [14] NCOEF / point_coef declared (band_pt.hpp), [15] 0
-  int meta[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  FormFacts facts;      // igx_user_meta[16] of the module by name (element_sweep.hpp); read by rtc_load
   hipModule_t module = nullptr; hipFunction_t func = nullptr;
   std::map<int, std::shared_ptr<RtcFeature>> feature;   // key: TA | NW << 4 | DOFI << 8 | HASM << 12
   std::map<int, std::shared_ptr<RtcFeature>> pencil;    // form_pencil instantiations; key: SYSTEM | P << 1 | IDENT << 4 | RAT << 5
@@ -215,8 +213,10 @@ static int rtc_load(IGX g, RtcForm &f) {
   HIPCK(hipModuleGetFunction(&f.func, f.module, f.lowered.c_str()));
   hipDeviceptr_t p = nullptr; size_t n = 0;
   HIPCK(hipModuleGetGlobal(&p, &n, f.module, "igx_user_meta"));
-  if (n != sizeof(f.meta)) return fail(IGX_ERR_LIB, "unexpected igx_user_meta size");
-  HIPCK(hipMemcpy(f.meta, p, sizeof(f.meta), hipMemcpyDeviceToHost));
+  int meta[16];
+  if (n != sizeof(meta)) return fail(IGX_ERR_LIB, "unexpected igx_user_meta size");
+  HIPCK(hipMemcpy(meta, p, sizeof(meta), hipMemcpyDeviceToHost));
+  f.facts = facts_from_meta(meta);
   return 0;
 }
 
@@ -252,8 +252,10 @@ static int rtc_feature_module(IGX g, RtcForm &F, int DIM, int DOF, int TA, int N
   for (const std::string &l : f->lowered) { hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, f->module, l.c_str())); f->func.push_back(fn); }
   hipDeviceptr_t p = nullptr; size_t n = 0;
   HIPCK(hipModuleGetGlobal(&p, &n, f->module, "igx_feature_meta"));
-  if (n != sizeof(f->meta)) return fail(IGX_ERR_LIB, "unexpected igx_feature_meta size");
-  HIPCK(hipMemcpy(f->meta, p, sizeof(f->meta), hipMemcpyDeviceToHost));
+  int meta[4];
+  if (n != sizeof(meta)) return fail(IGX_ERR_LIB, "unexpected igx_feature_meta size");
+  HIPCK(hipMemcpy(meta, p, sizeof(meta), hipMemcpyDeviceToHost));
+  f->facts = feature_facts_from_meta(meta);
   F.feature[key] = f; out = f;
   return 0;
 }
@@ -269,133 +271,39 @@ static void rtc_feature_layout(int NE, int DOF, bool GRAM, bool HASM, int &TA, i
 static int launch_feature_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done) {
   done = false;
   const Space &s = g->s;
-  const int DIM = s.dim, DOF = F.meta[0];
+  const int DIM = s.dim, DOF = F.facts.dof;
   if (DIM < 2 || DOF > 4) return 0;
-  int nq[3], na[3]; int NQ = 1, NE = 1;
-  for (int d = 0; d < 3; ++d) { nq[d] = s.basis[d].nqp; na[d] = s.basis[d].nen; NQ *= nq[d]; NE *= na[d]; }
+  int NE = 1;
+  for (int d = 0; d < 3; ++d) NE *= s.basis[d].nen;
   if (NE > 256) return 0;
-  const bool SECOND = F.meta[1] >= 2, SECOND_S = F.meta[4] >= 2, GRAM = F.meta[6] != 0;
+  const bool SECOND = F.facts.second(), SECOND_S = F.facts.shape_order >= 2, GRAM = F.facts.gram != 0;
   if (NE > 64 && (DIM != 3 || GRAM || DOF > 2)) return 0;      // 8x8 tiles: p = 4 in 3-D, at most two accumulator sets per wave
   if (NE > 128 && DOF > 1) return 0;                           // 16 tile rows x two column panels: p = 5 in 3-D, one set
   if (GRAM && DOF * DOF > 16) return 0;
-  const bool HASM = (out.op == OP_SYSTEM || out.op == OP_MATRIX || out.op == OP_JACOBIAN || out.op == OP_IJACOBIAN);
-  if (HASM && out.op == OP_SYSTEM && SECOND && !SECOND_S && ((unsigned)F.meta[2] & NEED_HU) && !((unsigned)F.meta[5] & NEED_HU)) return 0;   // (HU_HERE, feature_mfma.hpp)
+  const bool HASM = op_has_matrix(out.op);
+  if (HASM && out.op == OP_SYSTEM && SECOND && !SECOND_S && (F.facts.need & NEED_HU) && !(F.facts.mat_need & NEED_HU)) return 0;   // (HU_HERE, feature_mfma.hpp)
   int TA, NW, DOFI; rtc_feature_layout(NE, DOF, GRAM, HASM, TA, NW, DOFI);
   std::shared_ptr<RtcFeature> K;
   if (int rc = rtc_feature_module(g, F, DIM, DOF, TA, NW, DOFI, HASM, true, K)) return rc;
-  const int WGS = K->meta[0], NPS = K->meta[1];
-  const int D2 = DIM * DIM, NFS = SECOND_S ? 1 + DIM + D2 : 1 + DIM;
-  const int NEP = 16 * TA, NQ4 = (NQ + 3) & ~3;
-  const bool vec_op = (out.op == OP_SYSTEM || out.op == OP_VECTOR || out.op == OP_FUNCTION || out.op == OP_IFUNCTION);
-  const unsigned need = vec_op ? (unsigned)F.meta[2] : (unsigned)F.meta[5];
-  const bool fields = (need & (NEED_U | NEED_UT | NEED_GU | NEED_HU)) != 0;
-  // LDS budget as in launch_feature_plan (a module kernel takes more than 64 KiB of dynamic LDS like any other: measured)
-  const size_t lds_limit = 160 * 1024 - 512;
-  const size_t lds_auto = s.env.feature_lds_kb > 0 ? (size_t)s.env.feature_lds_kb * 1024
-                        : ((NW == 4) ? (size_t)(160 * 1024 / std::max(WGS, 1) - 1024) : ((HASM && TA == 4 && DOF == 1) ? (size_t)78 * 1024 : lds_limit));
-  FCarve cv; size_t lds_bytes = 0; bool fits = false;
-  for (int pass = 0; pass < 2 && !fits; ++pass) {
-    const size_t cap = pass == 0 ? lds_auto : lds_limit;
-    for (int nchunk = 1; nchunk <= NQ4 / 4 && !fits; ++nchunk) {
-      const int QC = (((NQ4 + nchunk - 1) / nchunk) + 3) & ~3, NQP = QC * nchunk;
-      int pos = 0;
-      auto take = [&](int n) { int o = pos; pos += (n + 1) & ~1; return o; };
-      memset(&cv, 0, sizeof(cv));
-      for (int d = 0; d < 3; ++d) { cv.t1d[d] = take(nq[d] * na[d] * NDER); cv.w1d[d] = take(2 * nq[d]); }
-      cv.gX = take(NE * DIM); cv.gW = take(NE); cv.Ue = take(NE * DOF); cv.Ve = take(NE * DOF);
-      cv.ufix = take(NE * DOF); cv.fixval = take(NE * DOF); cv.fixflag = take(NE * DOF); cv.flux = take(NE * DOF);
-      cv.JW = take(NQP); cv.xq = take(NQP * DIM); cv.E1 = take(s.nsd ? NQP * D2 : 0); cv.E2 = take((s.nsd && SECOND) ? NQP * DIM * D2 : 0);
-      cv.W0 = take(s.rational ? NQP : 0); cv.W1 = take(s.rational ? NQP * DIM : 0); cv.W2 = take((s.rational && SECOND) ? NQP * D2 : 0);
-      cv.G = take(((unsigned)F.meta[2] & NEED_G) ? NQP * D2 : 0);
-      cv.u = take(fields ? QC * DOF : 0); cv.ut = take(fields ? QC * DOF : 0);
-      cv.gu = take((need & NEED_GU) ? QC * DOF * DIM : 0);
-      cv.hu = take((need & NEED_HU) ? ((SECOND && !SECOND_S) ? NQP : QC) * DOF * D2 : 0);
-      cv.hpart = 0;
-      cv.lift = take(out.op == OP_SYSTEM ? QC * DOF * NFS : 0);
-      cv.rowbase = take(HASM ? NE : 0); cv.rowid = take(NE); cv.cc = take(NE); cv.pax = take(96); cv.adec = take(NEP / 2); cv.qdec = take((NQP + 1) / 2); cv.nrm = take(NQP * DIM);
-      const bool hu_fly = SECOND && !SECOND_S && ((unsigned)F.meta[2] & NEED_HU) != 0;
-      cv.sfb = (NE > 64) ? 1 : DOF;
-      const int sf_nc = std::max((s.nsd || s.rational) ? DIM + 1 : 0, (hu_fly && (need & NEED_HU)) ? cv.sfb : 0);
-      const int sf_need = sf_nc * ((SECOND ? 3 : 2) * nq[0] * na[1] * na[2] + (SECOND ? 6 : 3) * nq[0] * nq[1] * na[2] + (SECOND ? 10 : 4) * NQ);
-      cv.boff = 0;
-      cv.phi = take(std::max(NPS * QC * NEP, sf_need));
-      cv.total = pos; cv.QC = QC; cv.nchunk = nchunk; cv.NEP = NEP;
-      lds_bytes = (size_t)pos * sizeof(double);
-      if (lds_bytes <= cap) fits = true;
-    }
-  }
-  if (!fits) return 0;   // the generic kernel takes it
+  const FeatureCarve fc = carve_feature(F.facts, s, out.op, TA, NW, HASM, std::max(K->facts.wgs_per_cu, 1), K->facts.phi_in_lds, 0);
+  if (!fc.fits) return 0;   // the generic kernel takes it
+  const FCarve &cv = fc.cv;
   RtcFeatArgs args; memset(&args, 0, sizeof(args));
-  args.S = S; args.out = out; args.cv = cv;
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) args.prm.v[i] = s.params[i];
-  bool first_touch = HASM && !s.env.no_first_touch;
-  for (int d = 0; d < DIM && first_touch; ++d) first_touch = axis_first_touch_ok(s, d);
-  args.out.first_touch = first_touch ? 1 : 0;
-  if (HASM) {
-    if (!first_touch) { if (g->zero_matrix) g->zero_matrix(); }
-    else if (s.proc_sizes[0] * s.proc_sizes[1] * s.proc_sizes[2] > 1) zero_neighbour_rows(s, out, g->stream);
-  }
-  int launches = 0;
-  const int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
-  if (g->timing && g->dom.ev0 && g->dom.launches == 0) (void)hipEventRecord(g->dom.ev0, g->stream);
-  for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
-    const int cc[3] = {c0, c1, c2};
-    ColorRange cr; bool empty = false;
-    for (int d = 0; d < 3; ++d) {
-      const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d];
-      int firstel = -1, count = 0;
-      for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (firstel < 0) firstel = e; count++; }
-      if (count == 0) { empty = true; break; }
-      cr.start[d] = firstel; cr.step[d] = L.p + 1; cr.count[d] = count;
-    }
-    if (empty) continue;
-    const size_t nblocks = (size_t)cr.count[0] * cr.count[1] * cr.count[2];
-    args.cr = cr;
-    for (hipFunction_t fn : K->func) {
-      size_t asz = sizeof(args);
-      void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-      HIPCK(hipModuleLaunchKernel(fn, (unsigned)nblocks, 1, 1, (unsigned)(64 * NW), 1, 1, (unsigned)lds_bytes, g->stream, nullptr, cfg));
-      launches++;
-    }
-  }
-  // boundary-form passes (IGAElementNextForm, src/petigaelem.c:427-447), as launch_feature_plan makes them for a built-in form: the
-  // elements of this rank on a visited face, one point layer at the face, added to what the interior pass left (no first touch)
-  for (int bid = 0; bid < 2 * DIM; ++bid) {
-    const int ax = bid / 2, sd = bid % 2;
-    if (!s.visit[ax][sd]) continue;
-    const int eface = sd ? s.elem_sizes[ax] - 1 : 0;
-    if (eface < s.elem_start[ax] || eface >= s.elem_start[ax] + s.elem_width[ax]) continue;   // the face is on another rank
-    RtcFeatArgs fa = args; fa.out.bid = bid; fa.out.first_touch = 0;
-    int nc2[3] = {nc[0], nc[1], nc[2]}; nc2[ax] = 1;
-    for (int c2 = 0; c2 < nc2[2]; ++c2) for (int c1 = 0; c1 < nc2[1]; ++c1) for (int c0 = 0; c0 < nc2[0]; ++c0) {
-      const int cc[3] = {c0, c1, c2};
-      ColorRange cr; bool empty = false;
-      for (int d = 0; d < 3; ++d) {
-        if (d == ax) { cr.start[d] = eface - s.elem_start[ax]; cr.step[d] = 1; cr.count[d] = 1; continue; }
-        const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d];
-        int firstel = -1, count = 0;
-        for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (firstel < 0) firstel = e; count++; }
-        if (count == 0) { empty = true; break; }
-        cr.start[d] = firstel; cr.step[d] = L.p + 1; cr.count[d] = count;
-      }
-      if (empty) continue;
-      fa.cr = cr;
-      const size_t nblocks = (size_t)cr.count[0] * cr.count[1] * cr.count[2];
-      for (hipFunction_t fn : K->func) {
-        size_t asz = sizeof(fa);
-        void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &fa, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-        HIPCK(hipModuleLaunchKernel(fn, (unsigned)nblocks, 1, 1, (unsigned)(64 * NW), 1, 1, (unsigned)lds_bytes, g->stream, nullptr, cfg));
-        launches++;
-      }
-    }
-  }
-  g->last_launches = launches;
-  if (g->dom.launches == 0) {
-    if (g->timing && g->dom.ev1) (void)hipEventRecord(g->dom.ev1, g->stream);
-    g->dom.name = "feature_assemble<element, hiprtc>"; g->dom.launches = launches;
-    g->dom.elements = (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2];
-    g->dom.flop_per_element = HASM ? 2048.0 * K->meta[2] * TA * TA * (cv.QC * cv.nchunk / 4) : 0.0;
-  }
+  args.S = S; args.cv = cv; args.prm = params_of(s);
+  // (no functionals, no second pass over axis 2, no pencil mode: element mode, one or several functions per colour)
+  FeatureSweep fs;
+  fs.HASM = HASM; fs.dom_name = "feature_assemble<element, hiprtc>";
+  fs.flop_per_element = HASM ? 2048.0 * K->facts.mfma_per_kstep * TA * TA * (cv.QC * cv.nchunk / 4) : 0.0;
+  if (int rc = sweep_feature(g, out, fs, [&](const OutDev &o, const ColorRange &cr, size_t nblocks, bool, int &launches) -> int {
+        args.out = o; args.cr = cr;
+        for (hipFunction_t fn : K->func) {
+          size_t asz = sizeof(args);
+          void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
+          HIPCK(hipModuleLaunchKernel(fn, (unsigned)nblocks, 1, 1, (unsigned)(64 * NW), 1, 1, (unsigned)fc.lds_bytes, g->stream, nullptr, cfg));
+          launches++;
+        }
+        return 0;
+      })) return rc;
   if (HASM) g->last_kernel = std::string("feature_assemble<") + F.name + ">(hiprtc,mfma_f64_16x16x4,tiles=" + std::to_string(TA) + "x" + std::to_string(TA) + ",waves=" + char('0' + NW) +
                              ",rowfields/launch=" + char('0' + DOFI) + (DOFI < DOF ? std::string("x") + char('0' + DOF / DOFI) + " fused" : std::string()) + ",chunks=" + std::to_string(cv.nchunk) + ")";
   else g->last_kernel = std::string("feature_assemble<") + F.name + ">(hiprtc,vector only,waves=" + char('0' + NW) + ",chunks=" + std::to_string(cv.nchunk) + ")";
@@ -409,9 +317,9 @@ static int launch_feature_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev
 // Everything around the kernel -- colours, segments, first touch, the Dirichlet fix-up inside the walk, boundary loads, the
 // upper-face-first pass of a multi-rank assembly -- is try_gram_mfma itself.
 static bool rtc_pencil_eligible(const Space &s, const RtcForm &F, const OutDev &out) {
-  if (s.dim != 3 || F.meta[0] != 1 || F.meta[1] >= 2 || F.meta[4] >= 2 || F.meta[3] > 0 || F.meta[7]) return false;
-  if (((unsigned)F.meta[2] & ~NEED_X) != 0u) return false;
-  if (((unsigned)F.meta[8] & 0xfu) != 0xeu || !F.meta[9] || ((unsigned)F.meta[10] & 0xfu) != 0x1u) return false;
+  if (s.dim != 3 || F.facts.dof != 1 || F.facts.order >= 2 || F.facts.shape_order >= 2 || F.facts.nscalar > 0 || F.facts.has_boundary) return false;
+  if ((F.facts.need & ~NEED_X) != 0u) return false;
+  if ((F.facts.mat_test_mask & 0xfu) != 0xeu || !F.facts.mat_symmetric || (F.facts.vec_test_mask & 0xfu) != 0x1u) return false;
   if (out.op != OP_SYSTEM && out.op != OP_MATRIX) return false;
   if (s.nsd != 0 && s.nsd != 3) return false;
   const int deg = s.axis[0].p;
@@ -442,9 +350,8 @@ static int launch_pencil_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev 
     F.pencil[key] = K;
   }
   if (compile_only) { done = true; return 0; }
-  PencilModule mod; memset(&mod.prm, 0, sizeof(mod.prm));
+  PencilModule mod; mod.prm = params_of(s);
   mod.fn = K->func[0]; mod.name = F.name;
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) mod.prm.v[i] = s.params[i];
   std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
   return try_gram_mfma(s, S, out, g->stream, false, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, &mod, g->face_done);
 }
@@ -453,9 +360,9 @@ static int launch_pencil_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev 
 // per axis; the conditions of vec_sumfact_covers with the struct's constants read from the module
 struct RtcVecArgs { SpaceDev S; ParamsDev prm; OutDev out; ColorRange cr; long long nelem; };
 static bool rtc_vecsf_eligible(const Space &s, const RtcForm &F, const OutDev &out) {
-  if (!s.env.vec_sumfact || s.dim != 3 || F.meta[3] > 0 || F.meta[7]) return false;      // no functionals, no atboundary branch
+  if (!s.env.vec_sumfact || s.dim != 3 || F.facts.nscalar > 0 || F.facts.has_boundary) return false;      // no functionals, no atboundary branch
   if (out.op != OP_VECTOR && out.op != OP_FUNCTION && out.op != OP_IFUNCTION) return false;
-  if (s.dof != F.meta[0] || (s.nsd != 0 && s.nsd != 3)) return false;
+  if (s.dof != F.facts.dof || (s.nsd != 0 && s.nsd != 3)) return false;
   for (int d = 0; d < 3; ++d) {
     if (s.basis[d].nen > 4 || s.basis[d].nqp > 4) return false;
     for (int sd = 0; sd < 2; ++sd) { if (s.visit[d][sd]) return false; if (out.op != OP_VECTOR && s.load[d][sd].count) return false; }
@@ -493,28 +400,17 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   }
   if (compile_only) { done = true; return 0; }
   RtcVecArgs args; memset(&args, 0, sizeof(args));
-  args.S = S; args.out = out;
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) args.prm.v[i] = s.params[i];
+  args.S = S; args.out = out; args.prm = params_of(s);
   int launches = 0;
-  const int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
-  for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
-    const int cc[3] = {c0, c1, c2};
-    ColorRange cr; bool empty = false;
-    for (int d = 0; d < 3; ++d) {
-      const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d];
-      int first = -1, count = 0;
-      for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (first < 0) first = e; count++; }
-      if (count == 0) { empty = true; break; }
-      cr.start[d] = first; cr.step[d] = L.p + 1; cr.count[d] = count;
-    }
-    if (empty) continue;
+  if (int rc = color_sweeps(s, SweepSpec(), [&](const ColorRange &cr) -> int {
     args.cr = cr; args.nelem = (long long)cr.count[0] * cr.count[1] * cr.count[2];
     size_t asz = sizeof(args);
     void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
     const unsigned want = wg ? (unsigned)args.nelem : (unsigned)((args.nelem + (three ? 7 : 3)) / (three ? 8 : 4));      // (a wavefront walks a sequence of elements: vec_sumfact.hpp, round 6)
     HIPCK(hipModuleLaunchKernel(K->func[0], want, 1, 1, wg == 8 ? 512 : 256, 1, 1, 0, g->stream, nullptr, cfg));
     launches++;
-  }
+    return 0;
+  })) return rc;
   g->last_launches = launches;
   g->last_kernel = std::string("vec_sumfact<") + F.name + (block ? ">(hiprtc,matrix block diagonal: sum factorisation forward, product rows backward per field pair, " : diagonal ? ">(hiprtc,matrix diagonal: sum factorisation forward, product rows backward, " : (action ? ">(hiprtc,matrix action: sum factorisation forward and backward, " : ">(hiprtc,vector only: sum factorisation forward and backward, ")) + (wg == 8 ? "one workgroup per element, 8 x 8 x 8 lanes)" : (wg == 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : (three ? "two elements per wavefront)" : "one wavefront per element)")));
   done = true;
@@ -531,7 +427,7 @@ static int launch_state_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   const int deg = s.axis[0].p;
   if (s.dim != 3 || (deg != 2 && deg != 3)) return 0;
   // (the struct's constants are read from the loaded module: a compile-only check on a machine without a GPU takes the caller's word)
-  if (!compile_only && (F.meta[11] <= 0 || F.meta[0] != 1 || F.meta[3] > 0 || F.meta[7] || !s.env.state_pencil || (out.op != OP_JACOBIAN && out.op != OP_IJACOBIAN))) return 0;
+  if (!compile_only && (F.facts.pencil_nfeat <= 0 || F.facts.dof != 1 || F.facts.nscalar > 0 || F.facts.has_boundary || !s.env.state_pencil || (out.op != OP_JACOBIAN && out.op != OP_IJACOBIAN))) return 0;
   const bool geo = s.nsd != 0;
   if (geo && (s.nsd != 3 || deg != 2)) return 0;
   const bool pack = deg == 2 && s.env.p2_pack != 0;
@@ -555,12 +451,11 @@ static int launch_state_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
     F.state[key] = K;
   }
   if (compile_only) { done = true; return 0; }
-  PencilModule mod; memset(&mod.prm, 0, sizeof(mod.prm));
+  PencilModule mod; mod.prm = params_of(s);
   mod.fn = K->func[0]; mod.name = F.name + ",hiprtc"; mod.state = true; mod.state_geo = geo;
   mod.extra_lds = pencil_state_bytes() + (geo ? pencil_sgeo_bytes() - pencil_geo_bytes() : 0);
   mod.pack = pack ? (geo ? 2 : 1) : 0;
-  mod.flop_per_element = 2048.0 * F.meta[11] * (deg == 2 ? 7 * (pack ? 4 : 9) : 16 * 16);
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) mod.prm.v[i] = s.params[i];
+  mod.flop_per_element = 2048.0 * F.facts.pencil_nfeat * (deg == 2 ? 7 * (pack ? 4 : 9) : 16 * 16);
   std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
   return try_gram_mfma(s, S, out, g->stream, false, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, &mod, g->face_done);
 }
@@ -574,8 +469,8 @@ static int launch_block_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   const Space &s = g->s;
   if (s.dim != 3) return 0;
   if (!compile_only) {
-    const int DOF = F.meta[0];
-    if (F.meta[12] <= 0 || !F.meta[13] || DOF < 2 || DOF > 3 || F.meta[1] >= 2 || F.meta[4] >= 2 || F.meta[7] || F.meta[3] > 0) return 0;
+    const int DOF = F.facts.dof;
+    if (F.facts.npairs <= 0 || !F.facts.vec_zero || DOF < 2 || DOF > 3 || F.facts.order >= 2 || F.facts.shape_order >= 2 || F.facts.has_boundary || F.facts.nscalar > 0) return 0;
     if (!block_pencil_covers_space(s, S, out, DOF)) return 0;
   }
   const bool sysk = compile_only ? sys_only != 0 : out.op == OP_SYSTEM;
@@ -596,13 +491,12 @@ static int launch_block_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   std::shared_ptr<RtcFeature> K;
   if (int rc = module_of(sysk, K)) return rc;
   if (compile_only) { done = true; return 0; }
-  ParamsDev prm; memset(&prm, 0, sizeof(prm));
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
+  const ParamsDev prm = params_of(s);
   hipFunction_t fn = K->func[0];
   hipStream_t stream = g->stream;
   std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
   int lrc = 0;
-  const int rc = block_pencil_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, F.meta[0], F.meta[12],
+  const int rc = block_pencil_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, F.facts.dof, F.facts.npairs,
                                   [&](bool, unsigned grid, size_t lds, const BlockPencilArgs &pa) {
                                     RtcBlockArgs a; memset(&a, 0, sizeof(a));
                                     a.S = S; a.prm = prm; a.out = out; a.pa = pa;
@@ -611,7 +505,7 @@ static int launch_block_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
                                     if (lds > (size_t)160 * 1024 || hipModuleLaunchKernel(fn, grid, 1, 1, 512, 1, 1, (unsigned)lds, stream, nullptr, cfg) != hipSuccess) lrc = IGX_ERR_LIB;
                                   });
   if (rc == 0 && lrc) return fail(lrc, "block_pencil: launch of the run-time instantiation failed");
-  if (rc == 0 && done) g->last_kernel = std::string("block_pencil<") + F.name + ">(hiprtc,mfma_f64_16x16x4,p=3,dof=" + char('0' + F.meta[0]) + ",band rows by node layer)";
+  if (rc == 0 && done) g->last_kernel = std::string("block_pencil<") + F.name + ">(hiprtc,mfma_f64_16x16x4,p=3,dof=" + char('0' + F.facts.dof) + ",band rows by node layer)";
   return rc;
 }
 
@@ -627,7 +521,7 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
   const Space &s = g->s;
   if (s.dim != 3) return 0;
   if (!compile_only) {
-    if (!F.meta[14] || F.meta[0] != 4 || F.meta[4] >= 2 || F.meta[7] || F.meta[3] > 0 || F.meta[6] || (F.meta[5] & ~(int)(NEED_U | NEED_G))) return 0;
+    if (!F.facts.point_coef || F.facts.dof != 4 || F.facts.shape_order >= 2 || F.facts.has_boundary || F.facts.nscalar > 0 || F.facts.gram || (F.facts.mat_need & ~(NEED_U | NEED_G))) return 0;
     if (!band_pt_covers_space(s, S, out)) return 0;
   }
   const bool geo = compile_only ? (geo_only & 1) != 0 : s.nsd != 0, rat = compile_only ? (geo_only & 2) != 0 : s.rational != 0;
@@ -665,19 +559,20 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
       for (int k = 0; k < 2; ++k) { hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, K->module, K->lowered[k].c_str())); K->func.push_back(fn); }
       hipDeviceptr_t p = nullptr; size_t n = 0;
       HIPCK(hipModuleGetGlobal(&p, &n, K->module, "igx_band_meta"));
-      if (n != sizeof(K->meta)) return fail(IGX_ERR_LIB, "unexpected igx_band_meta size");
-      HIPCK(hipMemcpy(K->meta, p, sizeof(K->meta), hipMemcpyDeviceToHost));
+      int meta[4];
+      if (n != sizeof(meta)) return fail(IGX_ERR_LIB, "unexpected igx_band_meta size");
+      HIPCK(hipMemcpy(meta, p, sizeof(meta), hipMemcpyDeviceToHost));
+      K->band_rec = meta[0]; K->band_products = meta[1]; K->band_guard = meta[2] != 0;
     }
     F.band[key] = K;
   }
   if (compile_only) { done = true; return 0; }
-  ParamsDev prm; memset(&prm, 0, sizeof(prm));
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) prm.v[i] = s.params[i];
+  const ParamsDev prm = params_of(s);
   hipStream_t stream = g->stream;
   // The struct's guard on its parameters, as the built-in path has it (band_pt.hpp: Form::band_params_ok): band_coef / band_finish
   // may divide by a parameter (FormNSVMS: 1 / nu), and a struct that says no stays on the feature kernel.  Evaluated by the
   // module's one-lane kernel whenever the parameters differ from the ones it was last asked about.
-  if (K->meta[2]) {
+  if (K->band_guard) {
     const std::vector<double> now(prm.v, prm.v + MAXPARAM);
     if (!K->guard_known || now != K->guard_prm) {
       hipFunction_t gf = nullptr; hipDeviceptr_t pp = nullptr, po = nullptr; size_t n = 0; int ok = 0;
@@ -695,7 +590,7 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
   }
   int lrc = 0;
   std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
-  const int rc = band_pt_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, K->meta[0], K->meta[1],
+  const int rc = band_pt_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, K->band_rec, K->band_products,
                              [&](bool points, unsigned grid, size_t lds, bool, bool, int, const BandArgs &pa) {
                                RtcBandArgs a; memset(&a, 0, sizeof(a));
                                a.S = S; a.prm = prm; a.out = out; a.pa = pa;
@@ -710,9 +605,9 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
 
 // what of the struct itself keeps it off the DIAGONAL instantiation (meta: rtc.hpp:79), or null
 static const char *rtc_diagonal_refusal(const RtcForm &F) {
-  if (F.meta[1] >= 3 || ((unsigned)F.meta[2] & (NEED_PROP | NEED_D3U | NEED_MAPX))) return VEC_DIAGONAL_GENERAL;
-  if (F.meta[7]) return "the matrix diagonal does not cover forms with a boundary branch";
-  if (F.meta[4] >= 2) return VEC_DIAGONAL_SECOND;
+  if (F.facts.order >= 3 || (F.facts.need & (NEED_PROP | NEED_D3U | NEED_MAPX))) return VEC_DIAGONAL_GENERAL;
+  if (F.facts.has_boundary) return "the matrix diagonal does not cover forms with a boundary branch";
+  if (F.facts.shape_order >= 2) return VEC_DIAGONAL_SECOND;
   return nullptr;
 }
 
@@ -726,13 +621,13 @@ static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
   }
   RtcForm &F = *g->rtc;
   if (int rc = rtc_load(g, F)) return rc;
-  const int DOF = F.meta[0];
-  if (F.meta[3] > 0) return fail(IGX_ERR_SUP, "a struct with NSCALAR is a functional: IGXComputeScalarSource");
+  const int DOF = F.facts.dof;
+  if (F.facts.nscalar > 0) return fail(IGX_ERR_SUP, "a struct with NSCALAR is a functional: IGXComputeScalarSource");
   if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
   if (op_is_action(out.op)) {      // the matrix-free actions: vec_sumfact's ACTION instantiation of the struct or a refusal, as for the built-in forms
     if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);
-    if (F.meta[1] >= 3 || ((unsigned)F.meta[2] & (NEED_PROP | NEED_D3U | NEED_MAPX))) return fail(IGX_ERR_SUP, "the matrix action does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives");
-    if (F.meta[7]) return fail(IGX_ERR_SUP, "the matrix action does not cover forms with a boundary branch");
+    if (F.facts.order >= 3 || (F.facts.need & (NEED_PROP | NEED_D3U | NEED_MAPX))) return fail(IGX_ERR_SUP, "the matrix action does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives");
+    if (F.facts.has_boundary) return fail(IGX_ERR_SUP, "the matrix action does not cover forms with a boundary branch");
     bool done = false;
     if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, true)) return rc;
     return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix action it covers");
@@ -747,17 +642,17 @@ static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
   if (op_is_block_diagonal(out.op)) {    // the point-block diagonals: the DIAGONAL + BLOCK instantiation or the diagonal's refusal under the block diagonal's name
     { const std::string why = vec_block_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
     if (const char *why = rtc_diagonal_refusal(F)) return fail(IGX_ERR_SUP, vec_block_diagonal_reason(why));
-    if (s.dof != F.meta[0]) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
+    if (s.dof != F.facts.dof) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
     bool done = false;
     if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, false, true, true)) return rc;
     return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix block diagonal it covers");
   }
   // a struct of ORDER 3, or one that reads the property array / the point's shape table / third derivatives of the state: the general kernel (as launch_generic)
-  if (F.meta[1] >= 3 || ((unsigned)F.meta[2] & (NEED_PROP | NEED_D3U | NEED_MAPX)) || (s.nsd && s.nsd != s.dim)) {      // (... or a geometry with nsd != dim)
+  if (F.facts.order >= 3 || (F.facts.need & (NEED_PROP | NEED_D3U | NEED_MAPX)) || (s.nsd && s.nsd != s.dim)) {      // (... or a geometry with nsd != dim)
     if (g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a form of order 3 or one that reads the property array runs on the general kernel only");
-    if (((unsigned)F.meta[2] & NEED_PROP) && !S.npd) return fail(IGX_ERR_ARG_WRONGSTATE, "No property set");
-    if (((unsigned)F.meta[2] & NEED_MAPX) && !s.nsd) return fail(IGX_ERR_ARG_WRONGSTATE, "No geometry set");
-    if (F.meta[1] >= 3 && s.order < 3) return fail(IGX_ERR_ARG_WRONGSTATE, "the form reads third derivatives (p->shape[3]): call IGASetOrder(iga,3) first");
+    if ((F.facts.need & NEED_PROP) && !S.npd) return fail(IGX_ERR_ARG_WRONGSTATE, "No property set");
+    if ((F.facts.need & NEED_MAPX) && !s.nsd) return fail(IGX_ERR_ARG_WRONGSTATE, "No geometry set");
+    if (F.facts.order >= 3 && s.order < 3) return fail(IGX_ERR_ARG_WRONGSTATE, "the form reads third derivatives (p->shape[3]): call IGASetOrder(iga,3) first");
     if (g->zero_matrix) g->zero_matrix();
     return rtc_generic_launch(g, F, S, out);
   }
@@ -802,103 +697,21 @@ static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
 // (NSCALAR > 0: one sweep, a row of partial sums per element, as launch_generic does for the built-in ones)
 static int rtc_generic_launch(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out) {
   Space &s = g->s;
-  const int DOF = F.meta[0], DIM = s.dim, NS = F.meta[3]; const bool SECOND = F.meta[1] >= 2, THIRD = F.meta[1] >= 3; const unsigned NEED = (unsigned)F.meta[2];
-  const int D2 = DIM * DIM, D3 = D2 * DIM, NF = 1 + DIM + (SECOND ? D2 : 0) + (THIRD ? D3 : 0);
-  const bool fields = (NEED & (NEED_U | NEED_UT | NEED_GU | NEED_HU | NEED_D3U)) != 0;
-  int nq[3], na[3]; int NQ = 1, NE = 1;
-  for (int d = 0; d < 3; ++d) { nq[d] = s.basis[d].nqp; na[d] = s.basis[d].nen; NQ *= nq[d]; NE *= na[d]; }
-  Carve cv; int pos = 0;
-  auto take = [&](int n) { int o = pos; pos += (n + 1) & ~1; return o; };
-  for (int d = 0; d < 3; ++d) { cv.t1d[d] = take(nq[d] * na[d] * NDER); cv.w1d[d] = take(nq[d]); }
-  const int nsd = s.nsd ? s.nsd : DIM; const bool emb = s.nsd && s.nsd != DIM;
-  cv.gX = take(NE * nsd); cv.gW = take(NE); cv.Ue = take(NE * DOF); cv.Ve = take(NE * DOF);
-  cv.ufix = take(NE * DOF); cv.fixval = take(NE * DOF); cv.fixflag = take(NE * DOF); cv.flux = take(NE * DOF);
-  cv.JW = take(NQ); cv.xq = take(NQ * nsd); cv.E1 = take((s.nsd && !emb) ? NQ * D2 : 0); cv.E2 = take((s.nsd && !emb && SECOND) ? NQ * DIM * D2 : 0);
-  cv.W0 = take(s.rational ? NQ : 0); cv.W1 = take(s.rational ? NQ * DIM : 0); cv.W2 = take((s.rational && SECOND) ? NQ * D2 : 0);
-  cv.G = take((NEED & NEED_G) ? NQ * DIM * nsd : 0);
-  cv.X1m = take((NEED & NEED_MAPX) ? NQ * nsd * DIM : 0); cv.X2m = take(((NEED & NEED_MAPX) && SECOND) ? NQ * nsd * D2 : 0);
-  cv.E3 = take((s.nsd && !emb && THIRD) ? NQ * DIM * D3 : 0); cv.W3 = take((s.rational && THIRD) ? NQ * D3 : 0);
-  cv.d3u = take((THIRD && (NEED & NEED_D3U)) ? NQ * DOF * D3 : 0); cv.gA = take(NE * S.npd);
-  cv.u = take(fields ? NQ * DOF : 0); cv.ut = take(fields ? NQ * DOF : 0);
-  cv.gu = take((NEED & NEED_GU) ? NQ * DOF * DIM : 0); cv.hu = take((NEED & NEED_HU) ? NQ * DOF * D2 : 0);
-  cv.lift = take(NS > 0 ? NQ * NS : (out.op == OP_SYSTEM ? NQ * DOF * NF : 0));
-  cv.nrm = take(NQ * nsd);
-  const size_t phi_doubles = (size_t)NQ * NE * NF;
   const size_t lds_limit = 64 * 1024;   // as launch_generic: beyond it Phi goes to an HBM slice and two workgroups share a CU
-  const bool phi_in_lds = ((size_t)pos + phi_doubles) * sizeof(double) <= lds_limit;
-  if (phi_in_lds) cv.phi = take((int)phi_doubles); else cv.phi = -1;
-  cv.total = pos;
-  const size_t lds_bytes = (size_t)pos * sizeof(double);
-  if (lds_bytes > lds_limit) return fail(IGX_ERR_SUP, "element work set of the run-time form exceeds 64 KiB of LDS");
+  const GenericCarve gc = carve_generic(F.facts, s, S.npd, out.op, lds_limit);
+  if (gc.lds_bytes > lds_limit) return fail(IGX_ERR_SUP, "element work set of the run-time form exceeds 64 KiB of LDS");
   RtcArgs args; memset(&args, 0, sizeof(args));
-  args.S = S; args.out = out; args.cv = cv; args.phi_stride = phi_doubles;
-  for (size_t i = 0; i < s.params.size() && i < MAXPARAM; ++i) args.prm.v[i] = s.params[i];
-  const size_t scratch_cap = (size_t)2 << 30;
-  size_t max_blocks = phi_in_lds ? ((size_t)1 << 30) : scratch_cap / (phi_doubles * sizeof(double));
-  if (max_blocks < 1) max_blocks = 1;
-  int launches = 0;
-  int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
-  if (NS > 0) nc[0] = nc[1] = nc[2] = 1;   // nothing is scattered: every element in one sweep
-  int64_t elem_base = 0;
-  auto sweep = [&](ColorRange cr, int bid) -> int {      // one colour (or face layer), split along axis 2 under the scratch cap
-    const size_t per2 = (size_t)cr.count[0] * cr.count[1];
-    const int chunk2 = (int)std::max<size_t>(1, std::min<size_t>((size_t)cr.count[2], max_blocks / std::max<size_t>(per2, 1)));
-    if (!phi_in_lds && per2 > max_blocks) return fail(IGX_ERR_SUP, "scratch too small for one element layer");
-    for (int k0 = 0; k0 < cr.count[2]; k0 += chunk2) {
-      ColorRange sub = cr; sub.start[2] = cr.start[2] + k0 * cr.step[2]; sub.count[2] = std::min(chunk2, cr.count[2] - k0);
-      const size_t nblocks = per2 * sub.count[2];
-      if (!phi_in_lds) {
-        const size_t need = nblocks * phi_doubles * sizeof(double);
-        if (g->scratch.bytes < need) { HIPCK(hipStreamSynchronize(g->stream)); if (g->scratch.alloc(need)) return fail(IGX_ERR_MEM, "scratch allocation failed"); }
-      }
-      args.cr = sub; args.phi_global = g->scratch.as<double>(); args.out.bid = bid; args.out.elem_base = elem_base; elem_base += (int64_t)nblocks;
-      size_t asz = sizeof(args);
-      void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-      HIPCK(hipModuleLaunchKernel(F.func, (unsigned)nblocks, 1, 1, 256, 1, 1, (unsigned)lds_bytes, g->stream, nullptr, cfg));
-      launches++;
-    }
-    return 0;
-  };
-  for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
-    const int cc[3] = {c0, c1, c2};
-    ColorRange cr; bool empty = false;
-    for (int d = 0; d < 3; ++d) {
-      const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d];
-      int first = -1, count = 0;
-      for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (first < 0) first = e; count++; }
-      if (NS > 0) { first = 0; count = nel; }
-      if (count == 0) { empty = true; break; }
-      cr.start[d] = first; cr.step[d] = (NS > 0) ? 1 : L.p + 1; cr.count[d] = count;
-    }
-    if (empty) continue;
-    if (int rc = sweep(cr, -1)) return rc;
-  }
-  // boundary-form passes (IGAElementNextForm, src/petigaelem.c:427-447): the elements of this rank on a visited face, one point
-  // layer at the face; a struct with an atboundary branch supplies bmat / bvec (HAS_BOUNDARY), any other is integrated over the face
-  for (int bid = 0; bid < 2 * DIM; ++bid) {
-    const int ax = bid / 2, sd = bid % 2;
-    if (!s.visit[ax][sd]) continue;
-    const int eface = sd ? s.elem_sizes[ax] - 1 : 0;
-    if (eface < s.elem_start[ax] || eface >= s.elem_start[ax] + s.elem_width[ax]) continue;   // the face is on another rank
-    int nc2[3] = {nc[0], nc[1], nc[2]}; nc2[ax] = 1;
-    for (int c2 = 0; c2 < nc2[2]; ++c2) for (int c1 = 0; c1 < nc2[1]; ++c1) for (int c0 = 0; c0 < nc2[0]; ++c0) {
-      const int cc[3] = {c0, c1, c2};
-      ColorRange cr; bool empty = false;
-      for (int d = 0; d < 3; ++d) {
-        if (d == ax) { cr.start[d] = eface - s.elem_start[ax]; cr.step[d] = 1; cr.count[d] = 1; continue; }
-        const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d];
-        int first = -1, count = 0;
-        for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (first < 0) first = e; count++; }
-        if (NS > 0) { first = 0; count = nel; }
-        if (count == 0) { empty = true; break; }
-        cr.start[d] = first; cr.step[d] = (NS > 0) ? 1 : L.p + 1; cr.count[d] = count;
-      }
-      if (empty) continue;
-      if (int rc = sweep(cr, bid)) return rc;
-    }
-  }
-  g->last_launches = launches;
-  g->last_kernel = std::string("generic_assemble<") + F.name + "> (hiprtc," + (phi_in_lds ? "phi=LDS" : "phi=HBM") + ")";
+  args.S = S; args.out = out; args.cv = gc.cv; args.phi_stride = gc.phi_doubles; args.prm = params_of(s);
+  // matrix / vector forms: coloured sweeps + boundary-form passes; a struct with an atboundary branch supplies bmat / bvec
+  // (HAS_BOUNDARY), any other is integrated over the face
+  if (int rc = sweep_generic(g, g_err, gc, F.facts.nscalar > 0, [&](const ColorRange &cr, int bid, int64_t elem_base, size_t nblocks) -> int {
+        args.cr = cr; args.phi_global = g->scratch.as<double>(); args.out.bid = bid; args.out.elem_base = elem_base;
+        size_t asz = sizeof(args);
+        void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
+        HIPCK(hipModuleLaunchKernel(F.func, (unsigned)nblocks, 1, 1, 256, 1, 1, (unsigned)gc.lds_bytes, g->stream, nullptr, cfg));
+        return 0;
+      })) return rc;
+  g->last_kernel = std::string("generic_assemble<") + F.name + "> (hiprtc," + (gc.phi_in_lds ? "phi=LDS" : "phi=HBM") + ")";
   return 0;
 }
 
@@ -933,11 +746,11 @@ extern "C" int IGXComputeScalarSource(IGX g, IGXVec U, const char *source, const
   }
   RtcForm &F = *g->rtc_scalar;
   if (int rc = rtc_load(g, F)) return rc;
-  const int ns = F.meta[3];
+  const int ns = F.facts.nscalar;
   if (ns < 1) return fail(IGX_ERR_ARG_WRONG, "the struct is not a functional (no NSCALAR)");
   if (n != ns) return fail(IGX_ERR_ARG_WRONG, "this functional returns " + std::to_string(ns) + " scalars");
-  if (F.meta[0] != s.dof) return fail(IGX_ERR_ARG_WRONG, "functional does not match the number of fields (dof)");
-  if (((unsigned)F.meta[2] & (NEED_U | NEED_GU | NEED_HU)) && !U) return fail(IGX_ERR_ARG_WRONG, "the functional reads the state: null vector");
+  if (F.facts.dof != s.dof) return fail(IGX_ERR_ARG_WRONG, "functional does not match the number of fields (dof)");
+  if ((F.facts.need & (NEED_U | NEED_GU | NEED_HU)) && !U) return fail(IGX_ERR_ARG_WRONG, "the functional reads the state: null vector");
   int64_t nel = (int64_t)s.elem_width[0] * s.elem_width[1] * s.elem_width[2];
   for (int a = 0; a < s.dim; ++a) for (int sd = 0; sd < 2; ++sd) {   // one more partial row per element of a visited face
     const int eface = sd ? s.elem_sizes[a] - 1 : 0;

@@ -21,6 +21,7 @@
 // passes -- everything else stays on the feature kernel.
 #pragma once
 #include "feature_mfma.hpp"
+#include "element_sweep.hpp"
 
 namespace igx {
 
@@ -704,18 +705,7 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
   else {
   if constexpr (!ACTION && !DIAGONAL) { if (!vec_sumfact_covers<Form>(s, out)) return 0; }      // (ACTION, DIAGONAL: the caller has asked vec_action_refusal)
   launches = 0;
-  const int nc[3] = {s.lay[0].ncolors, s.lay[1].ncolors, s.lay[2].ncolors};
-  for (int c2 = 0; c2 < nc[2]; ++c2) for (int c1 = 0; c1 < nc[1]; ++c1) for (int c0 = 0; c0 < nc[0]; ++c0) {
-    const int cc[3] = {c0, c1, c2};
-    ColorRange cr; bool empty = false;
-    for (int d = 0; d < 3; ++d) {
-      const AxisLayout &L = s.lay[d]; const int nel = s.elem_width[d];
-      int first = -1, count = 0;
-      for (int e = 0; e < nel; ++e) if (L.color[e] == cc[d]) { if (first < 0) first = e; count++; }
-      if (count == 0) { empty = true; break; }
-      cr.start[d] = first; cr.step[d] = L.p + 1; cr.count[d] = count;
-    }
-    if (empty) continue;
+  color_sweeps(s, SweepSpec(), [&](const ColorRange &cr) -> int {
     const long long nelem = (long long)cr.count[0] * cr.count[1] * cr.count[2];
     // at most three basis functions and points per axis (p <= 2): two elements per wavefront (54 of 64 lanes instead of 27)
     bool three = !s.env.no_vec_pairs;
@@ -733,7 +723,7 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
           else hipLaunchKernelGGL((vec_sumfact<Form, false, 8, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
         }
         launches++;
-        continue;
+        return 0;
       }
     }
     const bool onepass = true;      // (UNITS = 1 in the kernel)      // (one pass per wavefront: the launch has a wavefront per unit)
@@ -747,7 +737,8 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
       else hipLaunchKernelGGL((vec_sumfact<Form, false, 4, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
     }
     launches++;
-  }
+    return 0;
+  });
   if (hipGetLastError() != hipSuccess) return IGX_ERR_LIB;
   {
     bool three = !s.env.no_vec_pairs;
