@@ -643,7 +643,7 @@ int IGXProbeDestroy (IGXProbe *prb);
  *   of multiplicity, or says that the end knots differ).  Prolong / Restrict: a null transfer (IGX_ERR_ARG_WRONG); a stale transfer
  *   (IGX_ERR_ORDER); a null vector, a vector of the wrong IGX, of the wrong size, the same vector twice, different streams
  *   (IGX_ERR_ARG_WRONG).  GetAxis / SetPath / GetInfo: null, stale, then the argument's range (IGX_ERR_ARG_OUTOFRANGE).
- * Out of scope: degree elevation (p- and k-refinement), several ranks, the multigrid cycle itself. */
+ * Out of scope: degree elevation (p- and k-refinement), several ranks.  The multigrid cycle on these transfers: IGXMultigrid, below. */
 typedef struct _p_IGXTransfer *IGXTransfer;
 int IGXTransferCreate (IGX coarse,IGX fine,IGXTransfer *tr);
 int IGXTransferGetAxis(IGXTransfer tr,int axis,int *nf,int *nc,int *width /* p+1 */,
@@ -653,6 +653,104 @@ int IGXTransferRestrict(IGXTransfer tr,IGXVec rf,IGXVec rc);
 int IGXTransferSetPath (IGXTransfer tr,int path /* 0 automatic, 1 fused, 2 axis passes */);
 int IGXTransferGetInfo (IGXTransfer tr,int box[3],int64_t *lds_bytes,int *fused);   /* any pointer may be NULL */
 int IGXTransferDestroy (IGXTransfer *tr);
+
+/* Geometric multigrid on the matrix-free operators: one V-cycle as a preconditioner application, and IGXSolve's loop preconditioned by it.
+ * No entry of the reference (PetIGA leaves multigrid to PCMG, which needs the interpolation its DM does not provide); the contract is the
+ * one below.  One rank only.
+ * The hierarchy: nlevels >= 2 set-up IGX, COARSEST FIRST, that the caller has prepared: every level has the same form with the same
+ *   parameters, the same Dirichlet faces per field (their values play no part: the cycle acts on residuals), the geometry refined to its own
+ *   knots (geometry.refine), the same stream, and each consecutive pair is a pair IGXTransferCreate accepts.  IGXMultigridCreate makes the
+ *   nlevels - 1 transfers itself, allocates nothing on a device and takes no vector.  Lifetime and staleness are IGXTransfer's: destroy the
+ *   multigrid before any of its levels; after IGXSetUp on any level every call on it returns IGX_ERR_ORDER.
+ * Notation.  Levels l = 0 .. L-1.  A_l: the action `op` at the level's state (IGXMultigridSetState; IGX_OP_MATRIX needs none).  D_l: its
+ *   diagonal (IGX_PC_JACOBI) or its inverted point blocks (IGX_PC_PBJACOBI), formed by IGXMultigridSetUp.  P_l: the transfer from level l-1
+ *   to level l.  lambda_l: the estimate of the largest eigenvalue of D_l^-1 A_l.  fl(.) is one rounding to double; no product is contracted.
+ * IGXMultigridSetUp, per level: work vectors (x b r d w, z with point blocks, and D or the dof block columns: kept with the multigrid), D_l,
+ *   and lambda_l by power_its steps of the power method on D_l^-1 A_l from the fixed start vector v_i = sin(1 + i) (i the entry's index,
+ *   written by the host): per step z = D^-1 A v, lambda = |z|_2 / |v|_2, v = (1 / |z|_2) z; lambda_l is the last step's.  The host reads
+ *   two norms per step.  Then, on the host in double and in this order: theta = (hi + lo) lambda / 2, delta = (hi - lo) lambda / 2,
+ *   sigma = theta / delta, rho_1 = 1 / sigma, rho_j = 1 / (2 sigma - rho_{j-1}).  Call it again after a state changed (SetState clears it).
+ *   Level 0 with coarse_maxit == 0 and coarse_pc IGX_PC_JACOBI or IGX_PC_PBJACOBI holds the coarse preconditioner's D instead of the smoother's.
+ *   The power method converges slowly from this start: 10 steps are 8 to 16 % short of the limit on 8^3 to 128^3 elements and hi = 1.1
+ *   covers 10; measured on 128^3 elements, 10 steps leave the cycle no contraction and 40 give the counts of DESIGN.md 3.19.  Give
+ *   power_its = 40 on meshes of 32^3 elements and beyond.
+ * Smooth(l, b, x, zero guess), the Chebyshev iteration on [lo lambda_l, hi lambda_l] with D_l^-1 (PETSc's KSPCHEBYSHEV with PCJACOBI):
+ *   step 1:            r = b, or w = A x and r = fl(b - w);  z = fl(r / D), the correctly rounded quotients (point blocks: z = B_node r_node,
+ *                      IGXBlockDiagonalApply's kernel);  d = fl((1 / theta) z);  x = d, or x = fl(x + d)
+ *   steps j = 2..degree: w = A d;  r = fl(r - w);  z = fl(r / D);  d = fl(fl((rho_j rho_{j-1}) d) + fl((2 rho_j / delta) z));  x = fl(x + d)
+ *   The constants 1 / theta, rho_j rho_{j-1} and 2 rho_j / delta are formed on the host.  With the diagonal a step between two operator calls
+ *   is ONE sweep (mg_cheb_first, mg_cheb_step: 8 doubles of traffic per entry); with point blocks it is r = r - w, the block apply and the
+ *   update, three launches (petiga_amd/csrc/multigrid.hpp).
+ * V(l, b):
+ *   l = 0: the coarse solve.  coarse_maxit > 0: x = 0 (IGXVecSet's kernel), then IGXSolve on level 0 with coarse_method, coarse_pc,
+ *     rtol = coarse_rtol, atol = 0, maxit = coarse_maxit at the level's state; its iterate is used whatever its reason (IGX_DIVERGED_ITS is
+ *     an inexact coarse solve).  coarse_maxit == 0: x = M_0^-1 b, ONE application of coarse_pc; a whole cycle then contains no host read.
+ *   l > 0:  1. x = Smooth(b, zero guess)
+ *           2. w = A d, r = fl(r - w)                      (r is now b - A x up to rounding)
+ *           3. b_{l-1} = P_l^T r (IGXTransferRestrict), then the rows of level l-1's Dirichlet faces are set to zero (mg_zero_fixed)
+ *           4. e = V(l-1, b_{l-1})
+ *           5. x = x + P_l e (IGXTransferProlong with add)
+ *           6. x = Smooth(b, x)
+ *   That is 2 degree actions per level and cycle.
+ * Facts.  The coarse fixed rows are zero on entry, so they stay exactly zero through the smoother and through CG (a fixed row of A is
+ *   count times the identity's and D holds the same count).  The clamped end rows of P are unit rows, so the correction is exactly zero on
+ *   the fine level's fixed rows.  Fixed rows are eigenvectors of D^-1 A with eigenvalue 1: the smoother treats them like any row.  With the
+ *   same polynomial before and after and a LINEAR coarse solve (coarse_maxit == 0) B is symmetric positive definite where A is.  An
+ *   iterative coarse solve makes B only approximately linear: under CG give it a tight coarse_rtol (1e-12), or use BiCGStab outside.
+ *   A Jacobi smoother is not robust in the degree on splines: the iteration counts are flat in the mesh but grow with p (about 3 to 4 times
+ *   from p = 2 to p = 3), so at p = 3 the cycle pays off in operator applications on large meshes only.
+ * IGXMultigridApply: z = B r, one V-cycle from a zero guess on the finest level, z != r; everything is enqueued on the levels' stream and,
+ *   with timing off and coarse_maxit == 0, nothing touches the host.  Bit-repeatable.  IGXMultigridGetInfo: lambda_l, the length of level l's
+ *   vectors and the launches the LAST cycle made on level l (its smoother and residuals, the transfers to and from the level below and the
+ *   zeroing of that level's fixed rows; level 0: the coarse solve; 0 before the first cycle); their sum over the levels is what
+ *   IGXGetLastTiming reports on the finest IGX after Apply.  Any pointer may be NULL.
+ * IGXMultigridSolve: IGXSolve's loop (the same code: krylov_loop in solve_loops.hpp) on the finest level's action with z = B r as the
+ *   preconditioner, CG or right-preconditioned BiCGStab, from the guess x holds.  Outcomes, the stop test, history, the b = 0 rule and
+ *   IGXSolveInfo are IGXSolve's.  Its work vectors are kept with the multigrid.
+ * IGXSetTiming / IGXGetLastTiming / IGXGetKernelName on the FINEST IGX report the call: "multigrid(3 levels, chebyshev-jacobi 2, coarse
+ *   fastdiag x1, <the fine action's name>)" after Apply (an iterative coarse solve: "coarse cg+jacobi"), "krylov(cg, pc=multigrid(...),
+ *   <action>, <k> iterations)" after Solve.  Kernel time is summed over the levels whose own IGX has timing on.
+ * Refusals, each decided before the first HIP call, each reason naming the multigrid, in this order.
+ *    1. null pointers (levels, a level, spec, mg; a null multigrid in the other calls): IGX_ERR_ARG_WRONG
+ *    2. nlevels < 2: IGX_ERR_ARG_OUTOFRANGE
+ *    3. the spec, all IGX_ERR_ARG_OUTOFRANGE: an unknown op or smoother_pc; degree < 1; lo, hi not finite with 0 < lo < hi; power_its < 1; an
+ *       unknown coarse method or coarse pc; coarse_maxit < 0; a negative coarse_rtol; coarse_maxit == 0 with IGX_PC_NONE
+ *    4. a level before IGXSetUp: IGX_ERR_ORDER (and, after Create, a stale multigrid in every call)
+ *    5. no form on a level: IGX_ERR_ARG_WRONGSTATE
+ *    6. different forms, or Dirichlet faces per field that differ between levels: IGX_ERR_ARG_WRONG
+ *    7. a fix table on any level: IGX_ERR_SUP; then different streams: IGX_ERR_ARG_WRONG
+ *    8. whatever IGXTransferCreate refuses, under its code, with the level pair in the message
+ *    9. IGX_PC_FASTDIAG as coarse pc without IGXFastDiagSetUp on level 0: IGX_ERR_ORDER, at SetUp (so a caller may set it up after Create)
+ *   10. Apply and Solve before SetUp: IGX_ERR_ORDER
+ *   11. vectors that are null, foreign, of the wrong size or aliased: IGX_ERR_ARG_WRONG (Solve first refuses an unknown method, a negative
+ *       maxit or tolerance with IGX_ERR_ARG_OUTOFRANGE, as IGXSolve does)
+ *   12. a missing state for op != IGX_OP_MATRIX: IGX_ERR_ARG_WRONG, at SetUp
+ *   13. what the actions or diagonals refuse (Cahn-Hilliard's diagonal): IGX_ERR_SUP with their reason under the multigrid's name
+ * Out of scope: several ranks; degree elevation; the multigrid as pc of IGXSolveNonlinear and IGXTimeStep; singular operators (pure
+ *   Neumann: no null-space handling); a restriction fused with the residual; W- and F-cycles. */
+typedef struct _p_IGXMultigrid *IGXMultigrid;
+typedef struct {
+  int op;                    /* IGXSolveOperator, the same on every level */
+  double a, t;               /* IGX_OP_IJACOBIAN only */
+  int smoother_pc;           /* IGX_PC_JACOBI or IGX_PC_PBJACOBI: the D of the Chebyshev smoother */
+  int degree;                /* Chebyshev steps per smoothing, >= 1; pre- and post-smoothing use the same */
+  double lo, hi;             /* the smoother works on [lo lambda_l, hi lambda_l], 0 < lo < hi (PETSc's 0.1, 1.1) */
+  int power_its;             /* power iterations for lambda_l, >= 1 */
+  int coarse_method, coarse_pc;  /* level 0: IGXSolve's method and pc */
+  double coarse_rtol; int coarse_maxit;   /* coarse_maxit == 0: ONE application of coarse_pc (not IGX_PC_NONE), no host read */
+} IGXMultigridSpec;
+int IGXMultigridCreate (int nlevels,IGX levels[] /* coarsest first */,const IGXMultigridSpec *spec,IGXMultigrid *mg);
+int IGXMultigridSetState(IGXMultigrid mg,int level,IGXVec V,IGXVec U);     /* the state of level's operator; MATRIX needs none */
+int IGXMultigridSetUp  (IGXMultigrid mg);   /* diagonals (inverted blocks) and lambda_l on every level; again after a state changed */
+int IGXMultigridGetInfo(IGXMultigrid mg,int level,double *lambda,int64_t *n,int *launches_per_cycle);
+int IGXMultigridApply  (IGXMultigrid mg,IGXVec r,IGXVec z);                /* z = B r: one V-cycle from a zero guess; z != r */
+int IGXMultigridSolve  (IGXMultigrid mg,int method,double rtol,double atol,int maxit,IGXVec b,IGXVec x,IGXSolveInfo *info,double *history);
+int IGXMultigridDestroy(IGXMultigrid *mg);
+/* Beyond the seven calls of the contract, for scripts/multigrid_rate.py: one fused Chebyshev step (mg_cheb_step) against the four IGXVec
+ * kernels it replaces (AXPBY, PointwiseDivide, AXPBY, AXPBY) on level's work vectors, `reps` launches of each between two events per round,
+ * the two alternating; fused_ms / split_ms ([rounds] each) receive the time of ONE step per round.  After IGXMultigridSetUp, with the
+ * diagonal as D (point blocks: IGX_ERR_SUP); it overwrites the level's x and d, which every cycle rewrites anyway. */
+int IGXMultigridMeasureStep(IGXMultigrid mg,int level,int reps,int rounds,double *fused_ms,double *split_ms);
 
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the

@@ -47,6 +47,11 @@ class IGXSolveInfo(C.Structure):
     _fields_ = [("iterations", C.c_int), ("reason", C.c_int), ("rnorm0", C.c_double), ("rnorm", C.c_double), ("bnorm", C.c_double)]
 
 
+class IGXMultigridSpec(C.Structure):
+    _fields_ = [("op", C.c_int), ("a", C.c_double), ("t", C.c_double), ("smoother_pc", C.c_int), ("degree", C.c_int), ("lo", C.c_double), ("hi", C.c_double),
+                ("power_its", C.c_int), ("coarse_method", C.c_int), ("coarse_pc", C.c_int), ("coarse_rtol", C.c_double), ("coarse_maxit", C.c_int)]
+
+
 class IGXNewtonSpec(C.Structure):
     _fields_ = [("op", C.c_int), ("a", C.c_double), ("t", C.c_double), ("W", C.c_void_p), ("method", C.c_int), ("pc", C.c_int),
                 ("lin_rtol", C.c_double), ("lin_atol", C.c_double), ("lin_maxit", C.c_int), ("forcing", C.c_int),
@@ -177,6 +182,10 @@ def lib(build_if_needed=False):
         "IGXProbeGeomMap": [V, _dp], "IGXProbeGetInfo": [V, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)], "IGXProbeEvaluate": [V, V, C.c_int, _dp], "IGXProbeDestroy": [C.POINTER(V)],
         "IGXTransferCreate": [V, V, C.POINTER(V)], "IGXTransferGetAxis": [V, C.c_int, _ip, _ip, _ip, _ip, _ip, _dp], "IGXTransferProlong": [V, V, V, C.c_int],
         "IGXTransferRestrict": [V, V, V], "IGXTransferSetPath": [V, C.c_int], "IGXTransferGetInfo": [V, _ip, C.POINTER(C.c_int64), _ip], "IGXTransferDestroy": [C.POINTER(V)],
+        "IGXMultigridCreate": [C.c_int, C.POINTER(V), C.POINTER(IGXMultigridSpec), C.POINTER(V)], "IGXMultigridSetState": [V, C.c_int, V, V], "IGXMultigridSetUp": [V],
+        "IGXMultigridGetInfo": [V, C.c_int, _dp, C.POINTER(C.c_int64), _ip], "IGXMultigridApply": [V, V, V],
+        "IGXMultigridSolve": [V, C.c_int, C.c_double, C.c_double, C.c_int, V, V, C.POINTER(IGXSolveInfo), _dp], "IGXMultigridDestroy": [C.POINTER(V)],
+        "IGXMultigridMeasureStep": [V, C.c_int, C.c_int, C.c_int, _dp, _dp],
         "IGXSetStream": [V, V], "IGXSynchronize": [V], "IGXSetKernel": [V, C.c_int], "IGXGetKernelName": [V, C.c_char_p, C.c_int],
         "IGXSetTiming": [V, C.c_int], "IGXGetLastTiming": [V, _dp, _dp, _ip],
         "IGXGetDominantKernelTiming": [V, C.c_char_p, C.c_int, _dp, _ip, C.POINTER(C.c_int64), _dp],
@@ -330,6 +339,78 @@ class Transfer:
         """rc = P^T rf"""
         _ck(lib().IGXTransferRestrict(self.h, rf.h if rf is not None else None, rc.h if rc is not None else None))
         return rc
+
+
+class Multigrid:
+    """IGXMultigrid: a V-cycle over the set-up IGX `levels` (coarsest first; IGX.multigrid on the finest object) with a Chebyshev smoother on
+    the diagonal ("jacobi") or the point blocks ("pbjacobi") of the action `op`, as a preconditioner (apply) and under CG / BiCGStab (solve).
+    coarse: a dict of method, pc, rtol, maxit for level 0; maxit = 0 is ONE application of pc.  power_its: the steps of the power method for
+    lambda; give 40 on meshes of 32^3 elements and beyond (10 underestimate lambda by more than hi covers there).  It keeps its levels alive."""
+
+    def __init__(self, levels, op="matrix", smoother="jacobi", degree=2, lo=0.1, hi=1.1, power_its=10, coarse=None, a=0.0, t=0.0):
+        code = lambda table, v: table[v] if isinstance(v, str) else int(v)
+        c = dict(method="cg", pc="jacobi", rtol=1e-12, maxit=1000)
+        c.update(coarse or {})
+        self.levels = list(levels)
+        self.spec = IGXMultigridSpec(code(SOLVE_OPERATORS, op), float(a), float(t), code(SOLVE_PCS, smoother), int(degree), float(lo), float(hi), int(power_its),
+                                     code(SOLVE_METHODS, c["method"]), code(SOLVE_PCS, c["pc"]), float(c["rtol"]), int(c["maxit"]))
+        self.h = C.c_void_p()
+        self._states = {}
+        hs = (C.c_void_p * max(len(self.levels), 1))(*[g.h.value if g is not None else None for g in self.levels])
+        _ck(lib().IGXMultigridCreate(len(self.levels), hs, C.byref(self.spec), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().IGXMultigridDestroy(C.byref(self.h))
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_state(self, level, U=None, V=None):
+        """the state of level's operator: U for "jacobian", V and U for "ijacobian" (the multigrid keeps the vectors alive)"""
+        _ck(lib().IGXMultigridSetState(self.h, int(level), V.h if V is not None else None, U.h if U is not None else None))
+        self._states[int(level)] = (U, V)
+        return self
+
+    def setup(self):
+        """IGXMultigridSetUp: the diagonals (inverted blocks) and lambda on every level; again after a state changed"""
+        _ck(lib().IGXMultigridSetUp(self.h))
+        return self
+
+    def info(self, level):
+        """IGXMultigridGetInfo: dict(lambda_, n, launches) of a level; launches: what the last cycle spent there"""
+        lam, n, k = C.c_double(), C.c_int64(), C.c_int()
+        _ck(lib().IGXMultigridGetInfo(self.h, int(level), C.byref(lam), C.byref(n), C.byref(k)))
+        return dict(lambda_=lam.value, n=n.value, launches=k.value)
+
+    def measure_step(self, level, reps=200, rounds=7):
+        """IGXMultigridMeasureStep: (fused_ms [rounds], split_ms [rounds]), the time of one fused Chebyshev step and of the four IGXVec kernels
+        it replaces on the level's work vectors, the two alternating round by round"""
+        fused, split = np.zeros(int(rounds)), np.zeros(int(rounds))
+        _ck(lib().IGXMultigridMeasureStep(self.h, int(level), int(reps), int(rounds), fused.ctypes.data_as(_dp), split.ctypes.data_as(_dp)))
+        return fused, split
+
+    def apply(self, r, z):
+        """z = B r: one V-cycle from a zero guess"""
+        _ck(lib().IGXMultigridApply(self.h, r.h if r is not None else None, z.h if z is not None else None))
+        return z
+
+    def solve(self, b, x, method="cg", rtol=1e-10, atol=0.0, maxit=1000, history=False):
+        """IGXMultigridSolve: the finest level's A x = b by CG or BiCGStab preconditioned by the cycle, from the guess x holds; returns
+        the dict IGX.solve returns"""
+        info = IGXSolveInfo()
+        hist = np.zeros(max(int(maxit), 0) + 1) if history else None
+        _ck(lib().IGXMultigridSolve(self.h, SOLVE_METHODS[method] if isinstance(method, str) else int(method), float(rtol), float(atol), int(maxit),
+                                    b.h if b is not None else None, x.h if x is not None else None, C.byref(info), hist.ctypes.data_as(_dp) if history else None))
+        out = dict(iterations=info.iterations, reason=info.reason, reason_name=SOLVE_REASONS.get(info.reason, str(info.reason)),
+                   rnorm0=info.rnorm0, rnorm=info.rnorm, bnorm=info.bnorm)
+        if history:
+            out["history"] = hist[:info.iterations + 1].copy()
+        return out
 
 
 class Vec:
@@ -745,6 +826,10 @@ class IGX:
     def transfer(self, coarse):
         """IGXTransferCreate: a Transfer from the IGX `coarse` to this one; the knot vectors must be nested (h-refinement by knot insertion)."""
         return Transfer(self, coarse)
+
+    def multigrid(self, coarser_levels, **kw):
+        """IGXMultigridCreate: a Multigrid over `coarser_levels` (coarsest first) and this IGX as the finest level; keywords: Multigrid's."""
+        return Multigrid(list(coarser_levels) + [self], **kw)
 
     def set_stream(self, stream): _ck(lib().IGXSetStream(self.h, stream))
     def synchronize(self): _ck(lib().IGXSynchronize(self.h))

@@ -1,10 +1,11 @@
 // solve_loops.hpp -- the host side of the vector algebra on IGXVec and of the three device-resident loops: IGXSolve (kernels: krylov.hpp),
 // IGXSolveNonlinear (newton.hpp) and IGXTimeStep (timestep.hpp).  Host code only: it launches kernels and defines none.  Included by the
 // main unit of engine.hip as the last thing before the probe, so every kernel above is compiled as it was before these existed; the three
-// kernel headers are included here, where their loops begin, in that order.
+// kernel headers are included here, where their loops begin, in that order, and multigrid.hpp (the sweeps of IGXMultigrid's cycle) at the end.
 // What the loops share is written once, up front: the state kept between calls (LoopState), the accounting of launches and kernel time
 // (LoopClock), the blocking read of partial sums (read_sums), the entry checks in each solver's own words (SolverWords) and the map from
-// the public operator to the matrix-free driver's op (matfree_op).  A new loop costs its own loop.
+// the public operator to the matrix-free driver's op (matfree_op).  A new loop costs its own loop.  IGXSolve's two loops are written on
+// callables (krylov_loop), so that a second caller with another operator and preconditioner -- IGXMultigridSolve -- runs the same code.
 #pragma once
 
 // ------------------------------------------------------------------ what the loops share
@@ -186,10 +187,123 @@ extern "C" int IGXVecNorm2(IGXVec x, double *s) {
   return 0;
 }
 
+// The two loops of IGXSolve on callables: A(in, out) is the operator, M(in, out) the preconditioner (not called where kp.pc_none says there is
+// none: the loops alias the vectors instead), kp.jacobi the diagonal of a Jacobi preconditioner, whose quotient CG fuses with r . z.  Both
+// account their own launches on clk.  IGXSolve passes the matrix-free action and its four preconditioners, IGXMultigridSolve the V-cycle.
+// st.work: r z p Ap (CG), r rhat p v s t y z (BiCGStab), of length st.n on g.
+static bool kr_bad_host(double d) { return !(std::fabs(d) > 0.0) || !std::isfinite(d); }
+struct KrylovPlan { int method; double rtol, atol; int maxit; bool pc_none; const double *jacobi; };
+template <class FA, class FM>
+static int krylov_loop(IGX g, KrylovState &st, LoopClock &clk, const KrylovPlan &kp, FA &&A, FM &&M, IGXVec b, IGXVec x, IGXSolveInfo *info, int *iterations, double *history) {
+  const long long n = (long long)st.n;
+  double rec[KR_NREC];
+  double *drec = kr_rec(g), *dsc = drec + KR_NREC;
+  auto record = [&](std::initializer_list<int> slabs) -> int { clk.own(1); return read_sums(g, slabs, rec); };
+  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
+  double *xd = x->a.as<double>(); const double *bd = b->a.as<double>();
+  g->slab_valid = 0;
+  int its = 0, reason = 0;
+  double bnorm = 0, rnorm = 0, rnorm0 = 0, thr = 0;
+  // r = b - A x with |r| and |b|, shared by both methods: the product goes to work vector 3 (Ap / v), r is work vector 0
+  if (int rc = A(x, st.work[3].get())) return rc;
+  KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), bd, D(3), n, kr_slab(g, KS_RR), kr_slab(g, KS_BB));
+  clk.own(1);
+  auto stop = [&]() {      // the test of the recurrence residual, 0 to go on
+    if (std::isnan(rnorm)) return (int)IGX_DIVERGED_NAN;
+    if (rnorm <= thr) return (int)(rnorm <= kp.rtol * bnorm ? IGX_CONVERGED_RTOL : IGX_CONVERGED_ATOL);
+    if (its >= kp.maxit) return (int)IGX_DIVERGED_ITS;
+    return 0;
+  };
+  auto start = [&]() -> bool {      // after the first record (rec[0] = r.r, rec[1] = b.b): true when the loop has something to do
+    bnorm = std::sqrt(rec[1]); rnorm0 = rnorm = std::sqrt(rec[0]); thr = std::max(kp.rtol * bnorm, kp.atol);
+    if (history) history[0] = rnorm;
+    if (std::isnan(bnorm)) { reason = IGX_DIVERGED_NAN; return false; }
+    if (bnorm == 0.0) { reason = IGX_CONVERGED_ATOL; return false; }
+    return true;
+  };
+  const bool cg = kp.method == IGX_SOLVE_CG;
+  if (cg) {
+    IGXVec r = st.work[0].get(), z = kp.pc_none ? r : st.work[1].get(), p = st.work[2].get(), Ap = st.work[3].get();
+    int cur = 0;      // KS_A + cur holds the newest r.z, KS_A + 1 - cur the one before; KS_C holds p.Ap
+    auto precondition = [&](int slab) -> int {
+      if (kp.jacobi) { KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, z->a.as<double>(), r->a.as<double>(), kp.jacobi, n, kr_slab(g, slab)); clk.own(1); return 0; }
+      if (int rc = M(r, z)) return rc;
+      KR_LAUNCH(kr_dot, KR_G, KR_T, g, r->a.as<double>(), z->a.as<double>(), n, kr_slab(g, slab));
+      clk.own(1);
+      return 0;
+    };
+    if (int rc = precondition(KS_A)) return rc;
+    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
+    double rz = rec[2];
+    if (start()) {
+      HIPCK(hipMemcpyAsync(p->a.p, z->a.p, z->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+      while (!(reason = stop())) {
+        if (kr_bad_host(rz)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
+        if (its > 0) { KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, p->a.as<double>(), z->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_A + 1 - cur)); clk.own(1); }
+        if (int rc = A(p, Ap)) return rc;
+        KR_LAUNCH(kr_dot, KR_G, KR_T, g, p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C));
+        KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C), kr_slab(g, KS_A + cur), kr_slab(g, KS_RR));
+        clk.own(2);
+        cur ^= 1;
+        if (int rc = precondition(KS_A + cur)) return rc;
+        if (int rc = record({KS_RR, KS_C, KS_A + cur})) return rc;
+        if (!(rec[1] > 0.0) || !std::isfinite(rec[1])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // p.Ap <= 0: the update kernel left x and r alone
+        ++its; rnorm = std::sqrt(rec[0]); rz = rec[2];
+        if (history) history[its] = rnorm;
+      }
+    }
+  } else {
+    IGXVec r = st.work[0].get(), rhat = st.work[1].get(), p = st.work[2].get(), v = st.work[3].get(), s = st.work[4].get(), tv = st.work[5].get();
+    IGXVec y = kp.pc_none ? p : st.work[6].get(), z = kp.pc_none ? s : st.work[7].get();
+    int cur = 0;      // KS_A + cur holds rho' = rhat.r of the iteration at hand; KS_C rhat.v, KS_D t.s, KS_E t.t
+    static const double one3[3] = {1.0, 1.0, 1.0};
+    HIPCK(hipMemcpyAsync(rhat->a.p, r->a.p, r->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+    KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), r->a.as<double>(), n, kr_slab(g, KS_A));
+    clk.own(1);
+    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
+    double rho_next = rec[2], omega = 1.0;
+    if (start()) {
+      HIPCK(hipMemsetAsync(v->a.p, 0, v->a.bytes, g->stream));
+      HIPCK(hipMemsetAsync(p->a.p, 0, p->a.bytes, g->stream));
+      HIPCK(hipMemcpyAsync(dsc, one3, sizeof(one3), hipMemcpyHostToDevice, g->stream));
+      while (!(reason = stop())) {
+        if (kr_bad_host(rho_next) || kr_bad_host(omega)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
+        KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), dsc);
+        clk.own(1);
+        if (int rc = M(p, y)) return rc;
+        if (int rc = A(y, v)) return rc;
+        KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_C));
+        KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_C));
+        clk.own(2);
+        if (int rc = M(s, z)) return rc;
+        if (int rc = A(z, tv)) return rc;
+        KR_LAUNCH(kr_dot2, KR_G, KR_T, g, tv->a.as<double>(), s->a.as<double>(), n, kr_slab(g, KS_D), kr_slab(g, KS_E));
+        KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(), n,
+                  kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_RR), kr_slab(g, KS_A + 1 - cur));
+        KR_LAUNCH(kr_bicg_record, 1, 64, g, kr_slab(g, KS_RR), kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_A + 1 - cur), drec, dsc);
+        clk.own(3);
+        if (int rc = read_record(g, rec, 7)) return rc;
+        cur ^= 1;
+        if (kr_bad_host(rec[1]) || kr_bad_host(rec[2])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // rhat.v or t.t: the update kernel left x and r alone
+        ++its; rnorm = std::sqrt(rec[0]); rho_next = rec[4]; omega = rec[6];
+        if (history) history[its] = rnorm;
+      }
+    }
+  }
+  if (reason == IGX_CONVERGED_ATOL && bnorm == 0.0) {      // b = 0: the solution is 0
+    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, xd, 0.0, n);
+    clk.own(1);
+    rnorm0 = rnorm = 0.0; if (history) history[0] = 0.0;
+    HIPCK(hipStreamSynchronize(g->stream));
+  }
+  if (info) { info->iterations = its; info->reason = reason; info->rnorm0 = rnorm0; info->rnorm = rnorm; info->bnorm = bnorm; }
+  *iterations = its;
+  return 0;
+}
+
 // IGXSolve.  The operator is the matrix-free driver's internal entry (compute_matfree) at the state of the specification, the preconditioners
 // are the same driver's diagonals and point blocks with block_diagonal_run, and IGXFastDiagApply: whatever they refuse the solve refuses,
 // with their reason under its own name.  The loops and their kernels: krylov.hpp.
-static bool kr_bad_host(double d) { return !(std::fabs(d) > 0.0) || !std::isfinite(d); }
 extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSolveInfo *info, double *history) {
   NEEDIGA(g);
   const SolverWords &words = kKrylovWords;
@@ -251,109 +365,11 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
     if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return solver_refused(words, rc);
     return clk.driver(g);
   };
-  double rec[KR_NREC];
-  double *drec = kr_rec(g), *dsc = drec + KR_NREC;
-  auto record = [&](std::initializer_list<int> slabs) -> int { clk.own(1); return read_sums(g, slabs, rec); };
-  auto D = [&](int k) { return st.work[k]->a.as<double>(); };
-  double *xd = x->a.as<double>(); const double *bd = b->a.as<double>();
-  g->slab_valid = 0;
-  int its = 0, reason = 0;
-  double bnorm = 0, rnorm = 0, rnorm0 = 0, thr = 0;
-  // r = b - A x with |r| and |b|, shared by both methods: the product goes to work vector 3 (Ap / v), r is work vector 0
-  if (int rc = A(x, st.work[3].get())) return rc;
-  KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), bd, D(3), n, kr_slab(g, KS_RR), kr_slab(g, KS_BB));
-  clk.own(1);
-  auto stop = [&]() {      // the test of the recurrence residual, 0 to go on
-    if (std::isnan(rnorm)) return (int)IGX_DIVERGED_NAN;
-    if (rnorm <= thr) return (int)(rnorm <= sp->rtol * bnorm ? IGX_CONVERGED_RTOL : IGX_CONVERGED_ATOL);
-    if (its >= sp->maxit) return (int)IGX_DIVERGED_ITS;
-    return 0;
-  };
-  auto start = [&]() -> bool {      // after the first record (rec[0] = r.r, rec[1] = b.b): true when the loop has something to do
-    bnorm = std::sqrt(rec[1]); rnorm0 = rnorm = std::sqrt(rec[0]); thr = std::max(sp->rtol * bnorm, sp->atol);
-    if (history) history[0] = rnorm;
-    if (std::isnan(bnorm)) { reason = IGX_DIVERGED_NAN; return false; }
-    if (bnorm == 0.0) { reason = IGX_CONVERGED_ATOL; return false; }
-    return true;
-  };
-  if (cg) {
-    IGXVec r = st.work[0].get(), z = pc == IGX_PC_NONE ? r : st.work[1].get(), p = st.work[2].get(), Ap = st.work[3].get();
-    int cur = 0;      // KS_A + cur holds the newest r.z, KS_A + 1 - cur the one before; KS_C holds p.Ap
-    auto precondition = [&](int slab) -> int {
-      if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, z->a.as<double>(), r->a.as<double>(), cols[0]->a.as<double>(), n, kr_slab(g, slab)); clk.own(1); return 0; }
-      if (int rc = M(r, z)) return rc;
-      KR_LAUNCH(kr_dot, KR_G, KR_T, g, r->a.as<double>(), z->a.as<double>(), n, kr_slab(g, slab));
-      clk.own(1);
-      return 0;
-    };
-    if (int rc = precondition(KS_A)) return rc;
-    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
-    double rz = rec[2];
-    if (start()) {
-      HIPCK(hipMemcpyAsync(p->a.p, z->a.p, z->a.bytes, hipMemcpyDeviceToDevice, g->stream));
-      while (!(reason = stop())) {
-        if (kr_bad_host(rz)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
-        if (its > 0) { KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, p->a.as<double>(), z->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_A + 1 - cur)); clk.own(1); }
-        if (int rc = A(p, Ap)) return rc;
-        KR_LAUNCH(kr_dot, KR_G, KR_T, g, p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C));
-        KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C), kr_slab(g, KS_A + cur), kr_slab(g, KS_RR));
-        clk.own(2);
-        cur ^= 1;
-        if (int rc = precondition(KS_A + cur)) return rc;
-        if (int rc = record({KS_RR, KS_C, KS_A + cur})) return rc;
-        if (!(rec[1] > 0.0) || !std::isfinite(rec[1])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // p.Ap <= 0: the update kernel left x and r alone
-        ++its; rnorm = std::sqrt(rec[0]); rz = rec[2];
-        if (history) history[its] = rnorm;
-      }
-    }
-  } else {
-    IGXVec r = st.work[0].get(), rhat = st.work[1].get(), p = st.work[2].get(), v = st.work[3].get(), s = st.work[4].get(), tv = st.work[5].get();
-    IGXVec y = pc == IGX_PC_NONE ? p : st.work[6].get(), z = pc == IGX_PC_NONE ? s : st.work[7].get();
-    int cur = 0;      // KS_A + cur holds rho' = rhat.r of the iteration at hand; KS_C rhat.v, KS_D t.s, KS_E t.t
-    static const double one3[3] = {1.0, 1.0, 1.0};
-    HIPCK(hipMemcpyAsync(rhat->a.p, r->a.p, r->a.bytes, hipMemcpyDeviceToDevice, g->stream));
-    KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), r->a.as<double>(), n, kr_slab(g, KS_A));
-    clk.own(1);
-    if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
-    double rho_next = rec[2], omega = 1.0;
-    if (start()) {
-      HIPCK(hipMemsetAsync(v->a.p, 0, v->a.bytes, g->stream));
-      HIPCK(hipMemsetAsync(p->a.p, 0, p->a.bytes, g->stream));
-      HIPCK(hipMemcpyAsync(dsc, one3, sizeof(one3), hipMemcpyHostToDevice, g->stream));
-      while (!(reason = stop())) {
-        if (kr_bad_host(rho_next) || kr_bad_host(omega)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
-        KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), dsc);
-        clk.own(1);
-        if (int rc = M(p, y)) return rc;
-        if (int rc = A(y, v)) return rc;
-        KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_C));
-        KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_C));
-        clk.own(2);
-        if (int rc = M(s, z)) return rc;
-        if (int rc = A(z, tv)) return rc;
-        KR_LAUNCH(kr_dot2, KR_G, KR_T, g, tv->a.as<double>(), s->a.as<double>(), n, kr_slab(g, KS_D), kr_slab(g, KS_E));
-        KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(), n,
-                  kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_RR), kr_slab(g, KS_A + 1 - cur));
-        KR_LAUNCH(kr_bicg_record, 1, 64, g, kr_slab(g, KS_RR), kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_A + 1 - cur), drec, dsc);
-        clk.own(3);
-        if (int rc = read_record(g, rec, 7)) return rc;
-        cur ^= 1;
-        if (kr_bad_host(rec[1]) || kr_bad_host(rec[2])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // rhat.v or t.t: the update kernel left x and r alone
-        ++its; rnorm = std::sqrt(rec[0]); rho_next = rec[4]; omega = rec[6];
-        if (history) history[its] = rnorm;
-      }
-    }
-  }
-  if (reason == IGX_CONVERGED_ATOL && bnorm == 0.0) {      // b = 0: the solution is 0
-    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, xd, 0.0, n);
-    clk.own(1);
-    rnorm0 = rnorm = 0.0; if (history) history[0] = 0.0;
-    HIPCK(hipStreamSynchronize(g->stream));
-  }
+  const KrylovPlan kp = {sp->method, sp->rtol, sp->atol, sp->maxit, pc == IGX_PC_NONE, pc == IGX_PC_JACOBI ? cols[0]->a.as<double>() : nullptr};
+  int its = 0;
+  if (int rc = krylov_loop(g, st, clk, kp, A, M, b, x, info, &its, history)) return rc;
   static const char *const methods[2] = {"cg", "bicgstab"}, *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
-  if (int rc = clk.finish(g, std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)")) return rc;
-  if (info) { info->iterations = its; info->reason = reason; info->rnorm0 = rnorm0; info->rnorm = rnorm; info->bnorm = bnorm; }
-  return 0;
+  return clk.finish(g, std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)");
 }
 
 // ------------------------------------------------------------------ the Newton loop (newton.hpp)
@@ -616,3 +632,7 @@ extern "C" int IGXTimeStep(IGX g, const IGXTimeStepSpec *sp, IGXVec U, IGXVec V,
   if (info) *info = out;
   return 0;
 }
+
+// ------------------------------------------------------------------ the multigrid cycle's sweeps (multigrid.hpp)
+#include "multigrid.hpp"
+// IGXMultigrid's host side calls the transfer and so stands behind it, at the end of engine.hip; its outer loop is krylov_loop above.
