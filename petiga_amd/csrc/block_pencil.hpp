@@ -474,7 +474,7 @@ block_pencil(SpaceDev S, ParamsDev prm, OutDev out, BlockPencilArgs pa) {
 }
 
 #ifndef IGX_RTC
-// ---- boundary loads of a multi-field form on the identity geometry: gram_mfma.hpp's k_boundary_loads per field
+// ---- boundary loads of a multi-field form on the identity geometry: boundary_loads.hpp's k_boundary_loads per field
 // (IGAElementBuildFix: AddFlux, src/petigaelem.c:1191-1212; a Dirichlet value on the same dof discards the flux, :1371-1387)
 static __global__ void k_boundary_loads_field(FluxArgs F, int nr0, int nr1, int dof, int field, double *vec) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

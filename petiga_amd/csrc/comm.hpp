@@ -109,7 +109,7 @@ static int comm_common_init(IGX g, std::unique_ptr<IgxComm> &c) {
 }
 
 // The rate a face message travels at, measured once per communicator: the face-first decision of the pencil walks weighs the cost
-// of its extra passes against (largest face) / (this rate) (gram_mfma.hpp), and a constant (60 GB/s per direction was the guess
+// of its extra passes against (largest face) / (this rate) (pencil_launch.hpp: assembly_passes), and a constant (60 GB/s per direction was the guess
 // of rounds 3-5) would make the first run on real links a matter of luck.  Every rank exchanges IGX_LINK_PROBE_MB (default 64) MB
 // with each FACE neighbour of its ghost-row reduction -- the same grouped ncclSend / ncclRecv, the same stream, the same
 // direction as the real exchange, all faces at once as they travel in the real exchange -- twice: the first group also pays

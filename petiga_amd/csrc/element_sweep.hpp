@@ -290,7 +290,7 @@ static int sweep_feature(Engine g, const OutDev &out, const FeatureSweep &fs, La
   if (g->timing && g->dom.ev0 && g->dom.launches == 0) (void)hipEventRecord(g->dom.ev0, g->stream);
   RankFace faces[6]; const int nfaces = faces_on_rank(s, faces);
   // the upper face of axis 2 first (every colour), a mark for the exchange (g->slab_done), then the rest -- as the pencil kernel does
-  // (gram_mfma.hpp, try_gram_mfma)
+  // (pencil_launch.hpp, try_gram_mfma)
   const int n2 = s.elem_width[2], p2 = s.axis[2].p;
   bool split = fs.two_pass && g->slab_done && !fs.single && DIM == 3 && s.proc_sizes[2] > 1 && (s.proc_ranks[2] < s.proc_sizes[2] - 1 || s.axis[2].periodic) && n2 >= 2 * (p2 + 1) && axis_first_touch_ok(s, 2);
   for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) split = false;

@@ -23,9 +23,7 @@
 #ifndef IGX_TU_DISPATCH
 #include "block_diag.hpp"
 #include "fast_diag.hpp"
-#include "gram_mfma.hpp"
-#include "gram_patch.hpp"
-#include "gram_patch3.hpp"
+#include "pencil_launch.hpp"      // (the Gram walks: gram_mfma.hpp, gram_patch.hpp, gram_patch3.hpp, boundary_loads.hpp, pencil_stamps.hpp and their host side)
 #include "block_pencil.hpp"      // (the host launcher, for run-time forms: rtc.hpp; no kernel of it is instantiated in this unit)
 #include "band_pt.hpp"           // (likewise: band_pt_run)
 #elif IGX_TU_DIM == 3 && (IGX_TU_GROUP < 0 || IGX_TU_GROUP == 1)
@@ -40,7 +38,7 @@
 using namespace igx;
 
 // The library is built from several translation units of this one source (see petiga_amd/build.py): the main unit
-// (C ABI, set-up, drivers) and, compiled with -DIGX_TU_DISPATCH -DIGX_TU_DIM=d -DIGX_TU_GROUP=g, units that hold only
+// (C ABI, set-up, drivers; the Gram walks with their host side, pencil_launch.hpp) and, compiled with -DIGX_TU_DISPATCH -DIGX_TU_DIM=d -DIGX_TU_GROUP=g, units that hold only
 // the kernel instantiations of one dimension / form group.  The last-error text is one object for all of them.
 inline std::string &igx_err_slot() { static thread_local std::string e; return e; }
 #define g_err igx_err_slot()
@@ -112,7 +110,7 @@ struct _p_IGX {
   // slab_valid: bit 0 = the mark of axis 2 (slab_ev), bit 1 = axis 1, bit 2 = axis 0 (face_ev[1], face_ev[0]: the pencil walk's three passes)
   hipEvent_t slab_ev = nullptr; int slab_valid = 0; IGXMat slab_A = nullptr; IGXVec slab_b = nullptr;
   hipEvent_t face_ev[2] = {nullptr, nullptr};
-  std::function<void(int)> face_done;  // marks "upper face of axis 1 / 0 assembled" (gram_mfma.hpp)
+  std::function<void(int)> face_done;  // marks "upper face of axis 1 / 0 assembled" (pencil_launch.hpp)
   std::shared_ptr<RtcForm> rtc; std::string rtc_source, rtc_name;   // run-time compiled user form (rtc.hpp)
   std::shared_ptr<RtcForm> rtc_scalar;                              // ... and the last user functional (IGXComputeScalarSource)
   std::shared_ptr<FastDiagState> fd;                                // fast diagonalisation (IGXFastDiagSetUp; fast_diag.hpp)
@@ -1058,52 +1056,13 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
     std::function<void(int)> face_done;
     overlap_marks(g, A, b, slab_done, face_done);
     g->face_done = face_done;
-    // the Tangent of a nonlinear scalar form without a geometry walks the same pencils (gram_mfma.hpp: state_pencil)
-    PencilModule st; memset(&st.prm, 0, sizeof(st.prm));
-    if ((op == OP_JACOBIAN || op == OP_IJACOBIAN) && s.dim == 3 && s.nsd == 3 && s.axis[0].p == 2 && s.env.state_pencil && (g->kernel_choice == 0 || g->kernel_choice == 2)) {
-      // ... and on a mapped geometry at p = 2 (state_pencil_geo: the map's second derivatives and the state's in one sum factorisation)
-      if (s.form == IGX_FORM_CAHNHILLIARD) {
-        st.kfn = s.rational ? state_pencil_geo<2, true, FormCahnHilliard<3>> : state_pencil_geo<2, false, FormCahnHilliard<3>>; st.name = "CahnHilliard";
-        st.flop_per_element = 2048.0 * FormCahnHilliard<3>::PENCIL_NFEAT * 7 * 9;
-      }
-      if (s.form == IGX_FORM_BRATU) {
-        st.kfn = s.rational ? state_pencil_geo<2, true, FormBratu<3>> : state_pencil_geo<2, false, FormBratu<3>>; st.name = "Bratu";
-        st.flop_per_element = 2048.0 * FormBratu<3>::PENCIL_NFEAT * 7 * 9;
-      }
-      if (st.kfn && s.env.p2_pack != 0) {      // packed tiles (state_pencil_geo_k): 4 MFMAs per feature and k-step instead of 9
-        st.pack = 2;
-        if (s.form == IGX_FORM_CAHNHILLIARD) { st.kfn = s.rational ? state_pencil_geo_k<true, FormCahnHilliard<3>> : state_pencil_geo_k<false, FormCahnHilliard<3>>; st.flop_per_element = 2048.0 * FormCahnHilliard<3>::PENCIL_NFEAT * 7 * 4; }
-        else { st.kfn = s.rational ? state_pencil_geo_k<true, FormBratu<3>> : state_pencil_geo_k<false, FormBratu<3>>; st.flop_per_element = 2048.0 * FormBratu<3>::PENCIL_NFEAT * 7 * 4; }
-      }
-      if (st.kfn) {
-        st.state = true; st.state_geo = true; st.extra_lds = pencil_state_bytes() + pencil_sgeo_bytes() - pencil_geo_bytes();
-        st.prm = params_of(s);
-      }
-    }
+    // the Tangent of a nonlinear scalar form walks the same pencils (pencil_launch.hpp: state_pencil_module)
+    PencilModule st;
+    const bool tangent = state_pencil_module(s, op, g->kernel_choice, fused, st);
     // (asked for by name, a Tangent on a mapped geometry at another degree is refused with the reason; the automatic choice goes on to the feature kernel)
     if ((op == OP_JACOBIAN || op == OP_IJACOBIAN) && s.dim == 3 && s.nsd == 3 && s.axis[0].p != 2 && g->kernel_choice == 2 && (s.form == IGX_FORM_CAHNHILLIARD || s.form == IGX_FORM_BRATU))
       return fail(IGX_ERR_SUP, "a Tangent on a mapped geometry takes the walk at p = 2 only (state_pencil_geo); the feature kernel covers the other degrees");
-    if ((op == OP_JACOBIAN || op == OP_IJACOBIAN) && s.dim == 3 && s.nsd == 0 && s.env.state_pencil && (g->kernel_choice == 0 || g->kernel_choice == 2)) {
-      const int deg = s.axis[0].p;
-      if (s.form == IGX_FORM_CAHNHILLIARD && (deg == 2 || deg == 3)) {
-        st.kfn = deg == 2 ? state_pencil<2, FormCahnHilliard<3>> : state_pencil<3, FormCahnHilliard<3>>; st.name = "CahnHilliard";
-        st.flop_per_element = 2048.0 * FormCahnHilliard<3>::PENCIL_NFEAT * (deg == 2 ? 7 * 9 : 16 * 16);     // executed: k-steps x tiles x features
-      }
-      if (s.form == IGX_FORM_BRATU && (deg == 2 || deg == 3)) {
-        st.kfn = deg == 2 ? state_pencil<2, FormBratu<3>> : state_pencil<3, FormBratu<3>>; st.name = "Bratu";
-        st.flop_per_element = 2048.0 * FormBratu<3>::PENCIL_NFEAT * (deg == 2 ? 7 * 9 : 16 * 16);
-      }
-      // p = 2: packed tiles (state_pencil_k: 4 MFMAs per feature and k-step instead of 9; IGX_P2_PACK=0: the layer-pair tiles)
-      if (st.kfn && deg == 2 && s.env.p2_pack != 0) {
-        st.pack = 1;
-        if (s.form == IGX_FORM_CAHNHILLIARD) { st.kfn = fused ? state_pencil_kr<FormCahnHilliard<3>> : state_pencil_k<FormCahnHilliard<3>>; st.flop_per_element = 2048.0 * FormCahnHilliard<3>::PENCIL_NFEAT * 7 * 4; }
-        else { st.kfn = fused ? state_pencil_kr<FormBratu<3>> : state_pencil_k<FormBratu<3>>; st.flop_per_element = 2048.0 * FormBratu<3>::PENCIL_NFEAT * 7 * 4; }
-        if (fused) st.name += "+Residual";
-        else st.patch_kfn = s.form == IGX_FORM_CAHNHILLIARD ? reinterpret_cast<const void *>(state_patch_p2<FormCahnHilliard<3>>) : reinterpret_cast<const void *>(state_patch_p2<FormBratu<3>>);
-      }
-      if (st.kfn) { st.state = true; st.extra_lds = pencil_state_bytes() + (fused ? (size_t)8 * (RWIN_DOUBLES + 128) * 8 : 0) /* fused: the Residual's ring and the scratch of its u_t sums, per wavefront */; st.prm = params_of(s); }
-    }
-    rc = try_gram_mfma(g->s, S, out, g->stream, g->kernel_choice == 2, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix, slab_done, st.kfn ? &st : nullptr, face_done);
+    rc = try_gram_mfma(g->s, S, out, g->stream, g->kernel_choice == 2, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix, slab_done, tangent ? &st : nullptr, face_done);
     g->face_done = nullptr;
     if (rc) return rc;
   }

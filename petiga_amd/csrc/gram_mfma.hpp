@@ -2447,664 +2447,4 @@ state_pencil_geo(SpaceDev S, OutDev out, PencilArgs pa, ParamsDev prm) {
   gram_pencil_body<false, 0, P, true, RAT, false, Form, false>(S, out, pa, prm.v);
 }
 
-#ifndef IGX_RTC
-// ------------------------------------------------------------------ dispatch
-
-template <bool SYSTEM>
-static void launch_elements(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, const Box &bx, const GramArgs &g0, int &launches) {
-  for (int d = 0; d < 3; ++d) if (bx.hi[d] <= bx.lo[d]) return;
-  for (int c2 = 0; c2 < s.lay[2].ncolors; ++c2) for (int c1 = 0; c1 < s.lay[1].ncolors; ++c1) for (int c0 = 0; c0 < s.lay[0].ncolors; ++c0) {
-    const int cc[3] = {c0, c1, c2};
-    ColorRange cr; bool ok = true;
-    for (int d = 0; d < 3 && ok; ++d) ok = color_range(s.lay[d], cc[d], bx.lo[d], bx.hi[d], cr.start[d], cr.step[d], cr.count[d]);
-    if (!ok) continue;
-    GramArgs ga = g0; ga.nwaves = cr.count[0] * cr.count[1] * cr.count[2];
-    hipLaunchKernelGGL((gram_p3_element<SYSTEM>), dim3((unsigned)((ga.nwaves + 3) / 4)), dim3(256), 0, stream, S, out, cr, ga);
-    launches++;
-  }
-}
-
-// a run-time form's instantiation of the walk (rtc.hpp): the module function for this driver / degree / geometry, its parameters
-// ... or a compiled-in instantiation for a built-in form (state_pencil: kfn, its extra LDS, flops per element for the roofline line)
-typedef void (*PencilKernel)(SpaceDev, OutDev, PencilArgs, ParamsDev);
-// one pass of an assembly that comes in several (the elements next to the upper faces first, a mark for the exchange after each):
-// the first-touch rule of axis X (like fty for axis Y), and, when the pass is a part of the walk axis, how its ends join the others
-struct PencilPass { int ftx[3] = {0, 0x7fffffff, 0x7fffffff}; int halo_lo = -1; bool open_hi = false; };
-struct PencilModule { hipFunction_t fn = nullptr; ParamsDev prm; std::string name; PencilKernel kfn = nullptr; size_t extra_lds = 0; bool state = false; double flop_per_element = 0;
-                      bool state_geo = false;         // state_geo: the instantiation is state_pencil_geo (evaluates the geometry itself)
-                      int pack = 0;
-                      const void *patch_kfn = nullptr; };      // gram_patch.hpp: state_patch_p2<Form> of the same form (p = 2, no geometry)                // pack: packed tiles, the window of band rows in the place of the hold areas (1: state_pencil_k; 2: the compact window, state_pencil_geo_k)
-
-static inline int nseg_min_lds(int nw) { return std::max(1, (nw + 159) / 160); }
-// a launch that could not be made (the LDS of the chosen segments beyond the device's, a module launch refused): try_gram_mfma
-// reports it instead of the generic "kernel launch failed" of a later call
-inline const char *&pencil_launch_error() { static thread_local const char *e = nullptr; return e; }
-
-// Segments of one launch (the pencils of one colour, nw walked elements): as few as possible -- every segment re-computes P halo
-// elements -- but enough workgroups for the CUs.  One 8-pencil workgroup per CU at a time (LDS; two where the tables are small), so a
-// launch takes ceil(workgroups / slots) rounds of (segment length + halo): the count with the least rounds x length.  Returns the
-// count; *cost = that product (element-steps of the launch's critical path).
-static inline int pencil_cus() {
-  static const int ncu = [] { int dev = 0; hipDeviceProp_t pr; return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-  return ncu;
-}
-static inline int pencil_segments(long long pencils, int nw, int P, bool geo, bool walk0, size_t extra_lds, bool halo_always, long long *cost_out = nullptr, int wpb = 8) {
-  const int ncu = pencil_cus();
-  const long long bps = (pencils + wpb - 1) / wpb;
-  int nseg = std::max(1, (nw + 159) / 160);
-  long long best = -1; int best_n = nseg;
-  // (round 6: segments down to two elements.  A pencil's elements are sequential -- 12.8 us of MFMA issue each at p = 3 -- so on a small
-  //  mesh, where the CUs outnumber the workgroups, the walk's LENGTH is the launch's duration: 32^3 took 365 us per launch with the old
-  //  floor of eight elements per segment, 250 us with four.  The "+ 1" is a workgroup's set-up in units of a step.)
-  for (int n = nseg; n <= std::max(nseg, nw / 2); ++n) {
-    const int len = (nw + n - 1) / n, ns = (nw + len - 1) / len;
-    const size_t lds_n = pencil_lds_bytes(len + 3, geo, wpb) + (walk0 ? pencil_hold_bytes(P) * wpb / 8 : 0) + (geo ? pencil_geo_bytes() : 0) + extra_lds;
-    // (next to the metric areas of a mapped geometry the tables of 128 + 3 elements no longer fit: 256^3 takes three segments there)
-    if (lds_n > (size_t)160 * 1024) { if (best < 0) best_n = n + 1; continue; }
-    const long long slots = (long long)ncu * std::max<long long>(1, std::min<long long>(2, (long long)(160 * 1024) / (long long)lds_n));   // resident workgroups
-    const long long cost = ((bps * ns + slots - 1) / slots) * (len + ((ns > 1 || halo_always) ? P : 0) + 1);
-    if (best < 0 || cost < best) { best = cost; best_n = n; }
-  }
-  if (cost_out) *cost_out = best < 0 ? 0 : best;
-  return best_n;
-}
-// the same summed over the colour launches of a box of elements (axis-0 walk): what a pass of an assembly costs
-// waves per workgroup of the axis-0 walk: twelve for the free-running p = 2 kernel on the identity geometry (gram_pencil_w6), else eight
-static inline int pencil_wpb(const Space &s, int P, bool geo, bool fixt, bool has_mod) {
-  static const int wpb_env = [] { const char *e = getenv("IGX_WPB"); return e ? atoi(e) : 0; }();
-  const int free_run = s.env.free_run >= 0 ? s.env.free_run : ((P == 2 && !geo && !has_mod) ? 1 : 0);
-  return (P == 2 && !geo && !fixt && !has_mod && free_run && wpb_env != 8) ? 12 : 8;
-}
-// ... and whether that kernel packs the element's 27 functions into two tiles (pencil_mfma_p2k; IGX_P2_PACK=0: the layer-pair tiles)
-static inline bool pencil_p2_pack(const Space &s, int P, bool geo, bool fixt, bool has_mod) {
-  return s.env.p2_pack != 0 && pencil_wpb(s, P, geo, fixt, has_mod) == 12;
-}
-// LDS the packed p = 2 walks take on top of what pencil_segments counts itself: the window of band rows in the place of the hold
-// areas (about + 28 KB at eight waves, + 43 KB at twelve).  One function for the launcher and for the pass-cost model, so that the
-// model's resident-workgroup count and LDS-limited segment lengths are those of the launch.
-static size_t pencil_win_extra(const Space &s, int P, bool geo, bool fixt, const PencilModule *mod, int wpb) {
-  const bool pack = pencil_p2_pack(s, P, geo, fixt, mod != nullptr) || (mod && mod->pack);
-  if (!pack) return 0;
-  const size_t win_bytes = (mod && mod->pack == 2) ? pencil_winc_bytes(wpb) : pencil_win_bytes(wpb);
-  return win_bytes - pencil_hold_bytes(P) * wpb / 8;
-}
-
-static long long pencil_box_cost(const Space &s, int P, bool geo, size_t extra_lds, const Box &bx, bool halo_always, int wpb = 8) {
-  long long total = 0;
-  for (int d = 0; d < 3; ++d) if (bx.hi[d] <= bx.lo[d]) return 0;
-  for (int cy = 0; cy < s.lay[2].ncolors; ++cy) for (int cx = 0; cx < s.lay[1].ncolors; ++cx) {
-    int st, sp, nx, ny;
-    if (!color_range(s.lay[1], cx, bx.lo[1], bx.hi[1], st, sp, nx) || !color_range(s.lay[2], cy, bx.lo[2], bx.hi[2], st, sp, ny)) continue;
-    long long c = 0;
-    (void)pencil_segments((long long)nx * ny, bx.hi[0] - bx.lo[0], P, geo, true, extra_lds, halo_always || s.lay[0].alias, &c, wpb);
-    total += c;
-  }
-  return total;
-}
-
-template <bool SYSTEM, int W, int P, bool GEO = false, bool RAT = false, bool FIXT = false>
-// fty (axis-0 walk): {lo, hi, blocked} of the first-touch rule on axis Y when the assembly comes in two passes over that axis
-// (first_touch_axis); null: one pass over the whole axis
-static void launch_pencils(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, const Box &bx, double forcing, int &launches, bool first_touch = false, const int *fty = nullptr,
-                           const PencilModule *mod = nullptr, const PencilPass *pass = nullptr) {
-  constexpr int X = (W == 0) ? 1 : 0, Y = (W == 2) ? 1 : 2;
-  for (int d = 0; d < 3; ++d) if (bx.hi[d] <= bx.lo[d]) return;
-  const int nw = bx.hi[W] - bx.lo[W];
-  for (int cy = 0; cy < s.lay[Y].ncolors; ++cy) for (int cx = 0; cx < s.lay[X].ncolors; ++cx) {
-    PencilArgs pa; pa.forcing = forcing;
-    pa.first_touch = (W == 0 && first_touch) ? 1 : 0; pa.nelx = s.elem_width[X]; pa.nely = s.elem_width[Y];
-    pa.alias0 = (W == 0 && s.lay[0].alias) ? 1 : 0;
-    pa.fty_lo = fty ? fty[0] : 0; pa.fty_hi = fty ? fty[1] : 0x7fffffff; pa.fty_blocked = fty ? fty[2] : 0x7fffffff;
-    pa.ftx_lo = pass ? pass->ftx[0] : 0; pa.ftx_hi = pass ? pass->ftx[1] : 0x7fffffff; pa.ftx_blocked = pass ? pass->ftx[2] : 0x7fffffff;
-    pa.w_halo_lo = (pass && pass->halo_lo >= 0) ? pass->halo_lo : bx.lo[W]; pa.open_hi = (pass && pass->open_hi) ? 1 : 0;
-    if (!color_range(s.lay[X], cx, bx.lo[X], bx.hi[X], pa.ex_start, pa.ex_step, pa.ex_count)) continue;
-    if (!color_range(s.lay[Y], cy, bx.lo[Y], bx.hi[Y], pa.ey_start, pa.ey_step, pa.ey_count)) continue;
-    const long long pencils = (long long)pa.ex_count * pa.ey_count;
-    const bool sf = P == 3 && !GEO && !mod && s.env.gram_sumfact != 0;
-    // p = 2 on the identity geometry: the flush is the longer phase and the rigid ping-pong makes the MFMA wave wait for it; left to
-    // the SIMD's own arbitration the walk gains 5 % (128^3: 166.7 -> 175.3 M el/s).  Everything at p = 3, mapped geometries and
-    // Tangents lose 6-8 % without the barriers (256^3: 64.8 -> 59.5).  IGX_FREE_RUN=0/1 overrides.
-    pa.free_run = s.env.free_run >= 0 ? s.env.free_run : ((P == 2 && !GEO && !(mod && mod->state)) ? 1 : 0);
-    // ... and free of the pairing, six-wave workgroups put three waves on every SIMD (gram_pencil_w6; IGX_WPB=8: the eight-wave kernel)
-    const bool w6 = W == 0 && pencil_wpb(s, P, GEO, FIXT, mod != nullptr) == 12;
-    pa.wpb = w6 ? 12 : 8;
-    const bool pack = W == 0 && (pencil_p2_pack(s, P, GEO, FIXT, mod != nullptr) || (mod && mod->pack));      // (p = 2 on the identity geometry: packed tiles, the band rows combined in an LDS window instead of the hold areas)
-    const size_t win_bytes = (mod && mod->pack == 2) ? pencil_winc_bytes(pa.wpb) : pencil_win_bytes(pa.wpb);
-    const size_t win_extra = W == 0 ? pencil_win_extra(s, P, GEO, FIXT, mod, pa.wpb) : 0;
-    int nseg = pencil_segments(pencils, nw, P, GEO, W == 0, (mod ? mod->extra_lds : 0) + win_extra, (W == 0 && s.lay[0].alias) || (pass && pass->halo_lo >= 0 && pass->halo_lo < bx.lo[W]), nullptr, pa.wpb);
-    if (s.env.nseg > 0) nseg = std::max(nseg_min_lds(nw), std::min(s.env.nseg, std::max(1, nw / 2)));   // experiment switch
-    pa.seg_len = (nw + nseg - 1) / nseg; pa.nseg = (nw + pa.seg_len - 1) / pa.seg_len;
-    pa.w_lo = bx.lo[W]; pa.w_hi = bx.hi[W];
-    pa.blocks_per_seg = (int)((pencils + pa.wpb - 1) / pa.wpb);
-    // Launches that do not fill the chip (small and medium meshes), the plain Gram walk: segments AND workgroup size from a model of the
-    // step -- measured at p = 3 (profiles/r06_small_meshes.txt): a step of the walk takes 20 us with one wavefront on the SIMD (its
-    // MFMAs, then its flush), 31 us with two (the ping-pong pair), 14 us per wavefront beyond; four-wavefront workgroups (one per SIMD,
-    // free-running) spread the pencils over twice the CUs.  time = rounds x (length + halo + 1) x step(wavefronts per SIMD on the
-    // fullest CU).  Large meshes come out as before (eight wavefronts, the fewest segments that fit the LDS).  IGX_SMALL_WPB=0: off;
-    // IGX_NSEG forces the segments and keeps the eight.
-    if (W == 0 && !GEO && !mod && pa.wpb == 8 && s.env.small_wpb && s.env.nseg <= 0) {
-      const int ncu = pencil_cus();
-      const bool halo_always = (W == 0 && s.lay[0].alias) || (pass && pass->halo_lo >= 0 && pass->halo_lo < bx.lo[W]);
-      double best = 1e300; int bn = nseg, bw = 8;
-      for (int wc = 8; wc >= 4; wc -= 4)
-        for (int n = nseg_min_lds(nw); n <= std::max(nseg_min_lds(nw), nw / 2); ++n) {
-          const int len = (nw + n - 1) / n, ns = (nw + len - 1) / len;
-          const size_t lds_n = pencil_lds_bytes(len + 3, false, wc) + pencil_hold_bytes(P) * wc / 8;
-          if (lds_n > (size_t)160 * 1024) continue;
-          const long long rmax = std::max<long long>(1, std::min<long long>(wc == 8 ? 2 : 4, (long long)(160 * 1024) / (long long)lds_n));
-          const long long wgs = ((pencils + wc - 1) / wc) * ns, m = (wgs + ncu - 1) / ncu, rounds = (m + rmax - 1) / rmax;
-          const long long wsimd = std::min(m, rmax) * wc / 4;
-          double step = wsimd <= 1 ? 20.0 : (wsimd == 2 ? 31.0 : 14.0 * (double)wsimd);
-          if (wc == 4 && wsimd >= 2) step *= 1.08;      // (without the barriers the p = 3 walk loses 6-8 % once wavefronts share a SIMD)
-          const double cost = (double)rounds * (double)(len + ((ns > 1 || halo_always) ? P : 0) + 1) * step;
-          if (cost < best * (1.0 - 1e-9)) { best = cost; bn = n; bw = wc; }
-        }
-      nseg = bn;
-      pa.seg_len = (nw + nseg - 1) / nseg; pa.nseg = (nw + pa.seg_len - 1) / pa.seg_len;
-      if (bw == 4) { pa.wpb = 4; pa.free_run = 1; }
-      pa.blocks_per_seg = (int)((pencils + pa.wpb - 1) / pa.wpb);
-    }
-    pa.ne_max = pa.seg_len + 3;
-    pa.debug_noflush = s.env.debug_noflush; pa.debug_noprio = s.env.debug_noprio;
-    pa.debug_buf = nullptr;
-    static int dbg_done = 0, dbg_seen = 0;
-    // IGX_DEBUG_TIMING=n: the n-th pencil launch of the process is the one that is stamped (1: the first)
-    const bool dbg_t = kDebug && s.env.debug_timing && !dbg_done && ++dbg_seen >= std::max(1, atoi(getenv("IGX_DEBUG_TIMING") ? getenv("IGX_DEBUG_TIMING") : "1"));
-    const size_t dbg_blocks = (size_t)pa.blocks_per_seg * pa.nseg;
-    const size_t dbg_n = dbg_blocks * 2 * 64 * 4 + dbg_blocks * 4;
-    if (dbg_t) { (void)hipMalloc((void **)&pa.debug_buf, dbg_n * 8); (void)hipMemset(pa.debug_buf, 0, dbg_n * 8); }
-    const size_t lds = pencil_lds_bytes(pa.ne_max, GEO, pa.wpb) + (W == 0 ? (pack ? win_bytes : pencil_hold_bytes(P) * pa.wpb / 8) : 0) + (GEO ? pencil_geo_bytes() : 0) + (mod ? mod->extra_lds : 0);      // (the hold areas are per wavefront and come last when there is no metric area)
-    if (lds > (size_t)160 * 1024) { pencil_launch_error() = "the pencil walk's tables do not fit the 160 KB of LDS for any segment length"; return; }
-    if (mod && mod->kfn) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(mod->kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(mod->kfn, dim3((unsigned)(pa.blocks_per_seg * pa.nseg)), dim3(512), lds, stream, S, out, pa, mod->prm);
-    } else if (mod) {      // form_pencil<SYSTEM, P, IDENT, RAT, UserForm> of a run-time form: a module function (rtc.hpp)
-      struct { SpaceDev S; OutDev out; PencilArgs pa; ParamsDev prm; } args;
-      memset(&args, 0, sizeof(args));
-      args.S = S; args.out = out; args.pa = pa; args.prm = mod->prm;
-      size_t asz = sizeof(args);
-      void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-      if (hipModuleLaunchKernel(mod->fn, (unsigned)(pa.blocks_per_seg * pa.nseg), 1, 1, 512, 1, 1, (unsigned)lds, stream, nullptr, cfg) != hipSuccess) { pencil_launch_error() = "launch of the run-time instantiation of the pencil walk failed"; return; }
-    } else {
-    constexpr bool SFOK = P == 3 && !GEO;      // the sum-factorised Gram walk (pencil_mfma_sf; IGX_GRAM_SUMFACT=0: pencil_mfma)
-    void (*kern)(SpaceDev, OutDev, PencilArgs) = gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT>;
-    if constexpr (SFOK && W != 0) { if (sf) kern = gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, -1, true>; }
-    if constexpr (W == 0 && !GEO) {
-      if (sf) kern = pa.alias0 ? gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 1, SFOK> : gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 0, SFOK>;
-      else kern = pa.alias0 ? gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 1> : gram_pencil<SYSTEM, W, P, GEO, RAT, FIXT, 0>;
-    }
-    if constexpr (W == 0 && P == 2 && !GEO && !FIXT) {
-      if (pack) kern = pa.alias0 ? gram_pencil_w6<SYSTEM, P, 1, true> : gram_pencil_w6<SYSTEM, P, 0, true>;
-      else if (w6) kern = pa.alias0 ? gram_pencil_w6<SYSTEM, P, 1> : gram_pencil_w6<SYSTEM, P, 0>;
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(pa.blocks_per_seg * pa.nseg)), dim3((unsigned)(pa.wpb * 64)), lds, stream, S, out, pa);
-    }
-    if (dbg_t) {   // IGX_DEBUG_TIMING=1: cycle stamps of the ping-pong phases of the first launch (diagnostic only)
-      dbg_done = 1;
-      (void)hipStreamSynchronize(stream);
-      std::vector<long long> h(dbg_n);
-      (void)hipMemcpy(h.data(), pa.debug_buf, dbg_n * 8, hipMemcpyDeviceToHost);
-      double sm = 0, sw = 0, sf = 0, sp = 0; long long cnt = 0; long long hist[16] = {0};
-      for (size_t b = 0; b < dbg_blocks * 2; ++b) for (int e = 4; e < 60; ++e) {
-        const long long *d = &h[(b * 64 + e) * 4], *dn = &h[(b * 64 + e + 1) * 4];
-        if (!d[3] || !dn[0]) continue;
-        sm += (double)(d[1] - d[0]); sw += (double)(d[2] - d[1]); sf += (double)(d[3] - d[2]); sp += (double)(dn[0] - d[0]); cnt++;
-        long long fb = (d[3] - d[2]) / 8192; if (fb > 15) fb = 15; hist[fb]++;
-      }
-      fprintf(stderr, "[igx pencil timing] blocks=%d seg_len=%d n=%lld cycles: mfma %.0f | wait@barrier %.0f | flush %.0f | period %.0f\n   flush histogram (8192-cycle bins):",
-              pa.blocks_per_seg * pa.nseg, pa.seg_len, cnt, sm / cnt, sw / cnt, sf / cnt, sp / cnt);
-      for (int i = 0; i < 16; ++i) fprintf(stderr, " %lld", hist[i]);
-      fprintf(stderr, "\n");
-      {   // the life of a workgroup (wave 0): entry -> tables staged -> first element -> last element -> end
-        double a = 0, b2 = 0, c = 0, d2 = 0, nel = 0; long long nb = 0;
-        for (size_t b = 0; b < dbg_blocks; ++b) {
-          const long long *d = &h[((b * 2) * 64 + 62) * 4];
-          if (!d[0] || !d[4]) continue;
-          a += (double)(d[1] - d[0]); b2 += (double)(d[2] - d[1]); c += (double)(d[3] - d[2]); d2 += (double)(d[4] - d[3]); nel += (double)d[5]; nb++;
-        }
-        if (nb) fprintf(stderr, "[igx pencil timing] workgroup life (wave 0, mean of %lld): staging %.0f | lane set-up %.0f | walk %.0f (%.1f elements) | trailing leaves %.0f cycles\n", nb, a / nb, b2 / nb, c / nb, nel / nb, d2 / nb);
-        // ... its spread, per segment of the pencils, and the span of the launch (first entry to last end) on the same counter
-        for (int sg = 0; sg < pa.nseg; ++sg) {
-          double mn = 1e30, mx = 0, sm2 = 0; long long n2 = 0;
-          for (int bb = 0; bb < pa.blocks_per_seg; ++bb) {
-            const long long *d = &h[(((size_t)sg * pa.blocks_per_seg + bb) * 2 * 64 + 62) * 4];
-            if (!d[0] || !d[4]) continue;
-            const double life = (double)(d[4] - d[0]); mn = std::min(mn, life); mx = std::max(mx, life); sm2 += life; n2++;
-          }
-          if (n2) fprintf(stderr, "[igx pencil timing]   segment %d: %lld workgroups, life min %.0f mean %.0f max %.0f\n", sg, n2, mn, sm2 / n2, mx);
-        }
-      }
-      {   // The launch as a timeline on the 100 MHz clock the XCCs share: where the time between the first entry and the last exit
-          // goes.  Per CU (XCC, SE, SH, CU of HW_ID) the workgroups in the order they ran: how late the first one starts (dispatch
-          // ramp), the gap between one workgroup's exit and the next one's entry, the tail after its last exit.
-        const long long *wr = &h[dbg_blocks * 2 * 64 * 4];
-        long long t0 = LLONG_MAX, t1 = 0;
-        std::map<long long, std::vector<std::pair<long long, long long>>> cu;
-        for (size_t b = 0; b < dbg_blocks; ++b) {
-          const long long *w = wr + b * 4;
-          if (!w[0] || !w[1]) continue;
-          t0 = std::min(t0, w[0]); t1 = std::max(t1, w[1]);
-          const long long hw = w[2], key = ((w[3] & 15) << 12) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 15);
-          cu[key].push_back({w[0], w[1]});
-        }
-        if (t1 > t0 && !cu.empty()) {
-          const double span = (double)(t1 - t0);
-          double busy = 0, ramp = 0, gap = 0, tail = 0, life1 = 0, life2 = 0, ramp_max = 0; long long n1 = 0, n2 = 0, ngap = 0; int rounds_max = 0;
-          for (auto &kv : cu) {
-            auto &v = kv.second; std::sort(v.begin(), v.end());
-            ramp += (double)(v.front().first - t0); ramp_max = std::max(ramp_max, (double)(v.front().first - t0));
-            tail += (double)(t1 - v.back().second);
-            rounds_max = std::max(rounds_max, (int)v.size());
-            for (size_t i = 0; i < v.size(); ++i) {
-              busy += (double)(v[i].second - v[i].first);
-              if (i == 0) { life1 += (double)(v[i].second - v[i].first); n1++; } else { life2 += (double)(v[i].second - v[i].first); n2++; gap += (double)(v[i].first - v[i - 1].second); ngap++; }
-            }
-          }
-          const double ncu = (double)cu.size();
-          fprintf(stderr, "[igx pencil timing]   timeline (100 MHz ticks = 10 ns): span %.0f = %.1f us over %d CUs that ran a workgroup, at most %d workgroups on one CU\n", span, span * 0.01, (int)cu.size(), rounds_max);
-          fprintf(stderr, "[igx pencil timing]   per CU, mean ticks: first entry after the launch's first %.0f (max %.0f) | busy %.0f | between workgroups %.1f (x %.2f per CU) | idle after its last exit %.0f\n",
-                  ramp / ncu, ramp_max, busy / ncu, ngap ? gap / ngap : 0.0, (double)ngap / ncu, tail / ncu);
-          fprintf(stderr, "[igx pencil timing]   workgroup life, ticks: first on its CU %.0f (%lld) | later ones %.0f (%lld); CU-time in a workgroup's life %.3f of span x CUs (x %.3f of 256 CUs)\n",
-                  n1 ? life1 / n1 : 0.0, n1, n2 ? life2 / n2 : 0.0, n2, busy / (span * ncu), busy / (span * 256.0));
-        }
-      }
-      (void)hipFree(pa.debug_buf);
-    }
-    launches++;
-  }
-}
-
-// ---- boundary loads on the identity geometry (IGAElementBuildFix: AddFlux with BoundaryArea's no-geometry branch,
-// src/petigaelem.c:1118-1132,1191-1212; IGAElementFixSystem adds them to F_e before the fixed rows are set, :1371-1376).
-// A boundary element lumps load * 4 * prod_{i != d} (J_i / nen_i) onto each of its basis functions on the face, so a face node
-// receives load * 4 * (sum over its elements on axis t of J_t / nen_t) * (the same on axis u): the two 1-D sums come from the
-// host, one thread per face node adds the product to its F row -- unless a Dirichlet value holds that dof (FixSystem discards
-// the flux of a fixed row).  Sequential launches per face: one writer per row and launch, fixed order.
-static __global__ void k_boundary_loads(FluxArgs F, int nr0, int nr1, double *vec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= F.nt * F.nu) return;
-  int r[3]; r[F.d] = F.rd; r[F.t] = i % F.nt; r[F.u] = i / F.nt;
-  for (int a = 0; a < 3; ++a) {        // a row on a Dirichlet face keeps the fixed value
-    const int gi = F.gfirst[a] + r[a];
-    if ((F.fixlo[a] && gi == 0) || (F.fixhi[a] && gi == F.glast[a])) return;
-  }
-  const double v = F.value * F.st[r[F.t]] * F.su[r[F.u]];
-  if (v != 0.0) vec[(size_t)r[0] + (size_t)nr0 * ((size_t)r[1] + (size_t)nr1 * (size_t)r[2])] += v;
-}
-
-// ---- the same on a mapped geometry (BoundaryArea's geometry branch, src/petigaelem.c:1133-1165): the lumped value of a face
-// element is load * prod_{i != d} (J_i / nen_i) * dS with dS = sum_q w_t w_u |x_,t x x_,u| over its Gauss points on the face
-// (basis of axis d at the end knot: only the first / last layer of the element's control points counts; the routine's own
-// Rationalize for NURBS).  One thread per face element fills area[e_u][e_t]; one thread per face node then adds the areas of the
-// elements that hold it, in a fixed order (sums over <= (p+1)^2 elements).
-struct FaceAreaArgs {
-  int d, t, u, side;
-  int nt, nu;                    // face elements of the rank on axes t, u
-  double *area;                  // [nu][nt]
-};
-static __global__ void k_face_areas(SpaceDev S, FaceAreaArgs F) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= F.nt * F.nu) return;
-  int el[3]; el[F.t] = i % F.nt; el[F.u] = i / F.nt; el[F.d] = F.side ? S.ax[F.d].nel - 1 : 0;
-  const AxisDev &At = S.ax[F.t], &Au = S.ax[F.u], &Ad = S.ax[F.d];
-  const int n0 = At.nen, n1 = Au.nen, q0n = At.nqp, q1n = Au.nqp;
-  const double *t0 = At.tab + (size_t)el[F.t] * q0n * n0 * NDER, *t1 = Au.tab + (size_t)el[F.u] * q1n * n1 * NDER;
-  const double *w0 = At.w + (size_t)el[F.t] * q0n, *w1 = Au.w + (size_t)el[F.u] * q1n;
-  const bool rat = S.rational != 0;
-  int off[3]; for (int a = 0; a < 3; ++a) off[a] = S.ax[a].off[el[a]];
-  const int ld = off[F.d] + (F.side ? Ad.nen - 1 : 0);      // the face layer of the control points
-  auto node = [&](int a0, int a1) { int g[3]; g[F.d] = ld; g[F.t] = off[F.t] + a0; g[F.u] = off[F.u] + a1; return (size_t)g[0] + (size_t)S.ax[0].gwidth * ((size_t)g[1] + (size_t)S.ax[1].gwidth * (size_t)g[2]); };
-  double dS = 0;
-  for (int q1 = 0; q1 < q1n; ++q1) for (int q0 = 0; q0 < q0n; ++q0) {
-    double W0 = 1, S1[2] = {0, 0};
-    if (rat) {
-      W0 = 0;
-      for (int a1 = 0; a1 < n1; ++a1) for (int a0 = 0; a0 < n0; ++a0) {
-        const double *r0 = t0 + (q0 * n0 + a0) * NDER, *r1 = t1 + (q1 * n1 + a1) * NDER;
-        const double w = S.W[node(a0, a1)];
-        W0 += w * r0[0] * r1[0]; S1[0] += w * r0[1] * r1[0]; S1[1] += w * r0[0] * r1[1];
-      }
-    }
-    double G[2][3] = {{0, 0, 0}, {0, 0, 0}};
-    for (int a1 = 0; a1 < n1; ++a1) for (int a0 = 0; a0 < n0; ++a0) {
-      const double *r0 = t0 + (q0 * n0 + a0) * NDER, *r1 = t1 + (q1 * n1 + a1) * NDER;
-      const size_t g = node(a0, a1);
-      double N0 = r0[0] * r1[0], N1[2] = {r0[1] * r1[0], r0[0] * r1[1]};
-      if (rat) { const double w = S.W[g]; N0 = w * N0 / W0; for (int r = 0; r < 2; ++r) N1[r] = (w * N1[r] - N0 * S1[r]) / W0; }
-      for (int r = 0; r < 2; ++r) for (int c = 0; c < 3; ++c) G[r][c] += N1[r] * S.X[g * 3 + c];
-    }
-    double M[2][2] = {{0, 0}, {0, 0}};
-    for (int r = 0; r < 2; ++r) for (int c2 = 0; c2 < 2; ++c2) for (int c = 0; c < 3; ++c) M[r][c2] += G[r][c] * G[c2][c];
-    dS += sqrt(fabs(M[0][0] * M[1][1] - M[0][1] * M[1][0])) * w0[q0] * w1[q1];
-  }
-  F.area[i] = dS * (At.J[el[F.t]] / (double)n0) * (Au.J[el[F.u]] / (double)n1);
-}
-static __global__ void k_boundary_loads_mapped(SpaceDev S, FluxArgs F, FaceAreaArgs A, int nr0, int nr1, double *vec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= F.nt * F.nu) return;
-  int r[3]; r[F.d] = F.rd; r[F.t] = i % F.nt; r[F.u] = i / F.nt;
-  for (int a = 0; a < 3; ++a) {
-    const int gi = F.gfirst[a] + r[a];
-    if ((F.fixlo[a] && gi == 0) || (F.fixhi[a] && gi == F.glast[a])) return;
-  }
-  const AxisDev &At = S.ax[F.t], &Au = S.ax[F.u];
-  double sum = 0;
-  for (int eu = 0; eu < A.nu; ++eu) {
-    const int ou = Au.off[eu];
-    if (r[F.u] < ou || r[F.u] >= ou + Au.nen) continue;
-    for (int et = 0; et < A.nt; ++et) {
-      const int ot = At.off[et];
-      if (r[F.t] < ot || r[F.t] >= ot + At.nen) continue;
-      sum += A.area[eu * A.nt + et];
-    }
-  }
-  const double v = F.value * sum;      // (F.value = the load itself here)
-  if (v != 0.0) vec[(size_t)r[0] + (size_t)nr0 * ((size_t)r[1] + (size_t)nr1 * (size_t)r[2])] += v;
-}
-
-// dof = 1, dim = 3, no geometry, no axis wrapped inside the rank on the loaded faces' axes (rows = ghosted nodes)
-static bool boundary_loads_supported(const Space &s) {
-  for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) {
-    if (!s.load[d][sd].count) continue;
-    for (int a = 0; a < 3; ++a) if (s.lay[a].alias) return false;
-  }
-  return true;
-}
-
-static int launch_boundary_loads(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, std::string &err) {
-  for (int d = 0; d < 3; ++d) for (int sd = 0; sd < 2; ++sd) {
-    const BC &bl = s.load[d][sd];
-    if (!bl.count || s.axis[d].periodic) continue;
-    // the rank holds elements on this face?
-    if (sd == 0 ? s.elem_start[d] != 0 : s.elem_start[d] + s.elem_width[d] != s.elem_sizes[d]) continue;
-    double load = 0; bool any = false;
-    for (int k = 0; k < bl.count; ++k) if (bl.field[k] == 0) { load += bl.value[k]; any = true; }     // (dof = 1: field 0)
-    if (!any) continue;
-    const int t = (d + 1) % 3, u = (d + 2) % 3;
-    FluxArgs F; F.d = d; F.t = t; F.u = u; F.value = load * 4.0;
-    F.rd = sd == 0 ? 0 : s.axis[d].nnp - 1 - s.lay[d].gstart;
-    std::vector<double> sum[2];
-    const int ax2[2] = {t, u};
-    for (int k = 0; k < 2; ++k) {
-      const int a = ax2[k]; const AxisLayout &L = s.lay[a]; const Basis1D &b = s.basis[a];
-      sum[k].assign((size_t)L.nrow, 0.0);
-      for (int e = 0; e < s.elem_width[a]; ++e) {
-        const int ge = s.elem_start[a] + e, first = b.offset[ge] - L.gstart;   // ghost-local index of the element's first basis function
-        for (int j = 0; j < b.nen; ++j) { const int i = first + j; if (i >= 0 && i < L.nrow) sum[k][(size_t)i] += b.detJac[ge] / (double)b.nen; }
-      }
-    }
-    F.nt = s.lay[t].nrow; F.nu = s.lay[u].nrow;
-    for (int a = 0; a < 3; ++a) {
-      F.gfirst[a] = s.lay[a].gstart; F.glast[a] = s.axis[a].nnp - 1;
-      auto holds = [&](const BC &bv) { for (int k = 0; k < bv.count; ++k) if (bv.field[k] == 0) return 1; return 0; };
-      F.fixlo[a] = s.axis[a].periodic ? 0 : holds(s.value[a][0]); F.fixhi[a] = s.axis[a].periodic ? 0 : holds(s.value[a][1]);
-    }
-    if (s.nsd) {      // mapped geometry: face areas per element on the device, then the per-node sums
-      FaceAreaArgs A; A.d = d; A.t = t; A.u = u; A.side = sd; A.nt = s.elem_width[t]; A.nu = s.elem_width[u];
-      const int ne = A.nt * A.nu, nn = F.nt * F.nu;
-      if (pool_alloc(reinterpret_cast<void **>(&A.area), (size_t)ne * sizeof(double), stream) != hipSuccess) { err = "device allocation of the face areas failed"; return IGX_ERR_MEM; }
-      F.value = load; F.st = F.su = nullptr;
-      hipLaunchKernelGGL(k_face_areas, dim3((unsigned)((ne + 63) / 64)), dim3(64), 0, stream, S, A);
-      hipLaunchKernelGGL(k_boundary_loads_mapped, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, stream, S, F, A, s.lay[0].nrow, s.lay[1].nrow, out.vec);
-      (void)hipFreeAsync(A.area, stream);
-      continue;
-    }
-    // the two short tables live for this launch only: stream-ordered allocation, copy, kernel, free
-    double *dt = nullptr;
-    const size_t bytes = (sum[0].size() + sum[1].size()) * sizeof(double);
-    if (pool_alloc(reinterpret_cast<void **>(&dt), bytes, stream) != hipSuccess) { err = "device allocation of the boundary-load sums failed"; return IGX_ERR_MEM; }
-    (void)hipMemcpyAsync(dt, sum[0].data(), sum[0].size() * sizeof(double), hipMemcpyHostToDevice, stream);
-    (void)hipMemcpyAsync(dt + sum[0].size(), sum[1].data(), sum[1].size() * sizeof(double), hipMemcpyHostToDevice, stream);
-    (void)hipStreamSynchronize(stream);      // (pageable host memory: the vectors go out of scope below; a face with loads is rare and small)
-    F.st = dt; F.su = dt + sum[0].size();
-    const int n = F.nt * F.nu;
-    hipLaunchKernelGGL(k_boundary_loads, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, F, s.lay[0].nrow, s.lay[1].nrow, out.vec);
-    (void)hipFreeAsync(dt, stream);
-  }
-  return 0;
-}
-
-
-// zero_matrix: MatZeroEntries of the caller; called before the first launch unless the axis-0 walk stores first touches
-// slab_done (may be empty): called between the two passes of an assembly that forms the elements next to the upper face of axis
-// 2 first -- the ghost rows of that face are complete then and their exchange can run under the rest of the launches
-// gram_patch.hpp (round 6): the p = 2 walk of patches of pencils
-static void launch_patches_p2(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch);
-static void launch_state_patches_p2(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, bool first_touch, const void *kernel, const ParamsDev &prm);
-// gram_patch3.hpp (round 8): the p = 3 walk of MX x MY patches of pencils
-template <int MX, int MY>
-static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch);
-// one rank, no axis wrapped inside it, one new node per element on axes 1 and 2 (a patch's nodes are consecutive)
-static bool patch_walk_covers(const Space &s) {
-  if (s.proc_sizes[0] * s.proc_sizes[1] * s.proc_sizes[2] != 1) return false;
-  for (int d = 0; d < 3; ++d) if (s.lay[d].alias) return false;
-  for (int d = 1; d < 3; ++d)
-    for (int e = 0; e + 1 < s.elem_width[d]; ++e) if (s.basis[d].offset[s.elem_start[d] + e + 1] != s.basis[d].offset[s.elem_start[d] + e] + 1) return false;
-  return true;
-}
-
-// the p = 3 patch walk's shape (pencils on axes 1, 2) and where it is the automatic choice (IGX_PATCH3=1).  Measured against the pencil
-// walk on cubes of 16^3 to 256^3 elements (System driver, profiles/r08_gram_patch_p3.txt) it was faster at every size, 1.57x at 16^3 and
-// 1.6-1.9x from 24^3 to 256^3; below 16^3 nothing was measured and the pencil walk stays.
-constexpr int PATCH3_MX = 4, PATCH3_MY = 2;
-constexpr long long PATCH3_MIN_ELEMENTS = 16 * 16 * 16;
-static bool patch3_pays(const Space &s) {
-  return (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] >= PATCH3_MIN_ELEMENTS;
-}
-
-static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, bool forced,
-                         std::string &kname, int &launches, std::string &err, bool &done, DomInfo &dom, const std::function<void()> &zero_matrix,
-                         const std::function<void()> &slab_done = std::function<void()>(), const PencilModule *mod = nullptr,
-                         const std::function<void(int)> &face_done = std::function<void(int)>()) {
-  done = false;
-  auto no = [&](const char *why) { if (forced) { err = std::string("MFMA kernel does not cover this configuration: ") + why; return (int)IGX_ERR_SUP; } return 0; };
-  if (!mod && s.form != IGX_FORM_POISSON && s.form != IGX_FORM_POISSON_F) return no("form is not a scalar gradient-Gram form");
-  const bool state = mod && mod->state;       // a Tangent (state_pencil): Jacobian / IJacobian drivers, no geometry
-  if (state ? (out.op != OP_JACOBIAN && out.op != OP_IJACOBIAN) : (out.op != OP_SYSTEM && out.op != OP_MATRIX)) return no("only System / Matrix drivers (a Tangent: Jacobian / IJacobian)");
-  if (s.dim != 3 || s.dof != 1) return no("needs dim=3, dof=1");
-  const bool geo = s.nsd != 0;
-  if (geo && s.nsd != 3) return no("mapped geometry of another dimension");
-  if (state && geo != mod->state_geo) return no("a Tangent on a mapped geometry takes the walk at p = 2 only");
-  for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) return no("boundary-form passes");
-  const int deg = s.axis[0].p;
-  if (deg != 2 && deg != 3) return no("needs p=2 or p=3");
-  for (int d = 0; d < 3; ++d) {
-    if (s.axis[d].p != deg || s.basis[d].nqp != deg + 1) return no("needs the same degree p and p+1 Gauss points on every axis");
-    for (int sd = 0; sd < 2; ++sd) if (s.load[d][sd].count && out.op == OP_SYSTEM && !boundary_loads_supported(s)) return no("boundary loads next to an axis wrapped inside the rank");
-  }
-  GramArgs ga; ga.forcing = (s.form == IGX_FORM_POISSON) ? 1.0 : -6.0; ga.nwaves = 0;
-  launches = 0;
-  const bool sys = out.op == OP_SYSTEM;
-  // walk axis: the slowest-varying mesh axis that qualifies keeps axis 0 (contiguous CSR columns) on the lanes
-  int walk_axis = -1;
-  { const int pref[3] = {s.env.walk_axis, 2, 1};
-    for (int k = 0; k < 3 && walk_axis < 0; ++k) if (pref[k] >= 0 && pref[k] < 3 && axis_walkable(s, pref[k], pref[k] == 0)) walk_axis = pref[k]; }
-  const bool walk = walk_axis >= 0;
-  if (deg == 2 && walk_axis != 0) return no("p=2 needs a walkable axis 0");
-  if ((geo || mod) && walk_axis != 0) return no("a mapped geometry / a run-time form needs a walkable axis 0");
-  const bool fixt = S.fixtable != nullptr && sys;       // IGASetFixTable: Dirichlet values per node (the Matrix driver applies none)
-  if (fixt && walk_axis != 0) return no("fix table without a walkable axis 0");
-  if (fixt && mod) return no("fix table with a run-time form");
-  Box all; for (int d = 0; d < 3; ++d) { all.lo[d] = 0; all.hi[d] = s.elem_width[d]; }
-  if (!walk && deg != 3) return no("p=2 needs a walkable axis 0");
-  const bool first_touch = walk_axis == 0 && !s.env.no_first_touch && out.val && axis_first_touch_ok(s, 1) && axis_first_touch_ok(s, 2);
-  if (!first_touch) zero_matrix();
-  else if (s.proc_sizes[0] * s.proc_sizes[1] * s.proc_sizes[2] > 1) zero_neighbour_rows(s, out, stream);   // the only entries no local element reaches
-  // boundary loads first: F is zeroed and only added to, so the order is free -- and the ghost rows of the upper face of axis 2
-  // must be complete when the first pass of a multi-rank assembly ends (slab_done below)
-  if (sys) { if (int rc = launch_boundary_loads(s, S, out, stream, err)) return rc; }
-  // (round 6: IGX_PATCH=1) p = 2 on the identity geometry, one rank: the walk of 4 x 3 patches of pencils whose band rows leave through the whole
-  // workgroup (gram_patch.hpp): 4 colours, 190 instead of 405 entries per element read-add-written
-  if (deg == 2 && walk_axis == 0 && s.env.patch && !geo && !mod && !fixt && (out.op == OP_MATRIX || out.op == OP_SYSTEM) && patch_walk_covers(s)) {
-    if (dom.ev0) (void)hipEventRecord(dom.ev0, stream);
-    launch_patches_p2(s, S, out, stream, launches, ga.forcing, first_touch);
-    if (dom.ev1) (void)hipEventRecord(dom.ev1, stream);
-    if (pencil_launch_error()) { err = pencil_launch_error(); pencil_launch_error() = nullptr; (void)hipGetLastError(); return IGX_ERR_LIB; }
-    if (hipGetLastError() != hipSuccess) { err = "gram_patch kernel launch failed"; return IGX_ERR_LIB; }
-    dom.name = "gram_patch<p=2>"; dom.launches = launches; dom.elements = (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2]; dom.flop_per_element = 2048.0 * 21 * 3;
-    kname = "gram_patch(mfma_f64_16x16x4,p=2,walk=0,packed tiles,4x3 pencils per workgroup,one window)";
-    done = true;
-    return 0;
-  }
-  // (round 8: IGX_PATCH3) p = 3 on the identity geometry, one rank, the sum-factorised Gram phase: the walk of 4 x 2 patches of pencils whose
-  // band rows leave through the whole workgroup (gram_patch3.hpp): 6 colours, 745 instead of 1792 entries per element read-add-written.
-  // It reports itself as a Gram pencil walk: the same element phase, bit-repeatable like it.
-  if (deg == 3 && walk_axis == 0 && !geo && !mod && !fixt && (out.op == OP_MATRIX || out.op == OP_SYSTEM) && s.env.gram_sumfact != 0 && patch_walk_covers(s) &&
-      (s.env.patch3 == 2 || (s.env.patch3 == 1 && patch3_pays(s)))) {
-    if (dom.ev0) (void)hipEventRecord(dom.ev0, stream);
-    launch_patches_p3<PATCH3_MX, PATCH3_MY>(s, S, out, stream, launches, ga.forcing, first_touch);
-    if (dom.ev1) (void)hipEventRecord(dom.ev1, stream);
-    if (pencil_launch_error()) { err = pencil_launch_error(); pencil_launch_error() = nullptr; (void)hipGetLastError(); return IGX_ERR_LIB; }
-    if (hipGetLastError() != hipSuccess) { err = "gram_pencil_patch3 kernel launch failed"; return IGX_ERR_LIB; }
-    dom.name = "gram_pencil<walk=0,p=3,patch>"; dom.launches = launches; dom.elements = (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2];
-    dom.flop_per_element = 2.0 * 2 * 4 * 64 * 10;      // (the element phase of the sum-factorised walk: pencil_mfma_sf on 10 tiles)
-    kname = "gram_pencil(mfma_f64_16x16x4,p=3,walk=0," + std::to_string(PATCH3_MX) + "x" + std::to_string(PATCH3_MY) + " pencils per workgroup,one window)";
-    done = true;
-    return 0;
-  }
-  // p = 2, a Tangent (IGX_PATCH_STATE=1): 4 x 2 pencils per workgroup, state_patch_p2
-  if (deg == 2 && walk_axis == 0 && s.env.patch_state && state && !geo && mod->patch_kfn && patch_walk_covers(s)) {
-    if (dom.ev0) (void)hipEventRecord(dom.ev0, stream);
-    launch_state_patches_p2(s, S, out, stream, launches, first_touch, mod->patch_kfn, mod->prm);
-    if (dom.ev1) (void)hipEventRecord(dom.ev1, stream);
-    if (pencil_launch_error()) { err = pencil_launch_error(); pencil_launch_error() = nullptr; (void)hipGetLastError(); return IGX_ERR_LIB; }
-    if (hipGetLastError() != hipSuccess) { err = "state_patch kernel launch failed"; return IGX_ERR_LIB; }
-    dom.name = "state_patch<p=2>"; dom.launches = launches; dom.elements = (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2]; dom.flop_per_element = mod->flop_per_element;
-    kname = "state_patch<" + mod->name + ">(mfma_f64_16x16x4,p=2,walk=0,packed tiles,4x2 pencils per workgroup,one window)";
-    done = true;
-    return 0;
-  }
-  if (!walk) {
-    if (dom.ev0) (void)hipEventRecord(dom.ev0, stream);
-    if (sys) launch_elements<true>(s, S, out, stream, all, ga, launches); else launch_elements<false>(s, S, out, stream, all, ga, launches);
-    if (dom.ev1) (void)hipEventRecord(dom.ev1, stream);
-    dom.name = "gram_p3_element"; dom.launches = launches; dom.elements = (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2]; dom.flop_per_element = 2048.0 * 48 * 16;
-    kname = "gram_p3_element(mfma_f64_16x16x4)";
-  } else {
-    // P = elements without a Dirichlet face (pencil kernel), E = the rest (element kernel, which owns the BC logic)
-    Box P = all;
-    // (the axis-0 walk applies the Dirichlet fix-up itself; the other walks leave face elements to gram_p3_element)
-    if (sys && walk_axis != 0) for (int d = 0; d < 3; ++d) {
-      if (s.axis[d].periodic) continue;
-      if (s.value[d][0].count && s.elem_start[d] == 0) P.lo[d] = 1;
-      if (s.value[d][1].count && s.elem_start[d] + s.elem_width[d] == s.elem_sizes[d]) P.hi[d] = s.elem_width[d] - 1;
-    }
-    const int l0 = launches;
-    if (dom.ev0) (void)hipEventRecord(dom.ev0, stream);
-    auto run = [&](const Box &P, const int *fty, const PencilPass *pp = nullptr) {
-    if (geo && fixt) {
-      switch ((deg == 2 ? 0 : 2) + (s.rational ? 1 : 0)) {
-      case 0: launch_pencils<true, 0, 2, true, false, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp); break;
-      case 1: launch_pencils<true, 0, 2, true, true, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp); break;
-      case 2: launch_pencils<true, 0, 3, true, false, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp); break;
-      default: launch_pencils<true, 0, 3, true, true, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp); break;
-      }
-    } else if (geo || mod) {   // metric tensor per Gauss point from the wavefront's own geometry evaluation (a run-time form: its own coefficients)
-      const int v = (deg == 2 ? 0 : 4) + (sys ? 2 : 0) + (s.rational ? 1 : 0);
-      switch (v) {
-      case 0: launch_pencils<false, 0, 2, true, false>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      case 1: launch_pencils<false, 0, 2, true, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      case 2: launch_pencils<true, 0, 2, true, false>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      case 3: launch_pencils<true, 0, 2, true, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      case 4: launch_pencils<false, 0, 3, true, false>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      case 5: launch_pencils<false, 0, 3, true, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      case 6: launch_pencils<true, 0, 3, true, false>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      default: launch_pencils<true, 0, 3, true, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, mod, pp); break;
-      }
-    } else if (fixt) {
-      if (deg == 2) launch_pencils<true, 0, 2, false, false, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp);
-      else launch_pencils<true, 0, 3, false, false, true>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp);
-    } else if (deg == 2) {
-      if (sys) launch_pencils<true, 0, 2>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp); else launch_pencils<false, 0, 2>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp);
-    } else switch (walk_axis * 2 + (sys ? 1 : 0)) {
-    case 0: launch_pencils<false, 0, 3>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp); break;
-    case 1: launch_pencils<true, 0, 3>(s, S, out, stream, P, ga.forcing, launches, first_touch, fty, nullptr, pp); break;
-    case 2: launch_pencils<false, 1, 3>(s, S, out, stream, P, ga.forcing, launches); break;
-    case 3: launch_pencils<true, 1, 3>(s, S, out, stream, P, ga.forcing, launches); break;
-    case 4: launch_pencils<false, 2, 3>(s, S, out, stream, P, ga.forcing, launches); break;
-    default: launch_pencils<true, 2, 3>(s, S, out, stream, P, ga.forcing, launches); break;
-    }
-    };
-    // Upper faces first (multi-rank, axis-0 walk): the upper half of axis 2 in every colour, a mark for the exchange (slab_done); of
-    // what is left, the upper half of axis 1, a mark (face_done(1)); then the upper half of every remaining pencil -- the upper face
-    // of axis 0: segments of their own, the first of which re-computes p halo elements and owns the rows from its first layer on --
-    // and a mark (face_done(0)); then the rest, whose last segment owns no row past its elements.  The ghost rows of a face get nothing from the passes after its mark: its messages travel under them (comm.hpp).
-    // First touch makes the launch order part of the result: per pass the rule applies to the elements of that pass alone, and an
-    // entry an earlier pass reaches as well is only added to (fty / ftx: {lo, hi, blocked}).
-    const int n0 = s.elem_width[0], n1 = s.elem_width[1], n2 = s.elem_width[2];
-    auto upper = [&](int d) { return s.proc_sizes[d] > 1 && (s.proc_ranks[d] < s.proc_sizes[d] - 1 || s.axis[d].periodic); };
-    const bool whole = walk_axis == 0 && P.lo[0] == 0 && P.hi[0] == n0 && P.lo[1] == 0 && P.hi[1] == n1 && P.lo[2] == 0 && P.hi[2] == n2;
-    const bool can2 = slab_done && whole && upper(2) && n2 >= 2 * (deg + 1);
-    const bool can1 = face_done && whole && upper(1) && n1 >= 2 * (deg + 1) && !s.lay[1].alias;
-    const bool can0 = face_done && whole && upper(0) && n0 >= 16 && !s.lay[0].alias;
-    bool faces_first = can2 || can1 || can0;
-    const int c2 = face_cut(n2, deg), c1 = face_cut(n1, deg), c0 = std::max(8, face_cut(n0, deg));      // (thick passes: pencil_common.hpp)
-    if (faces_first && s.env.overlap < 0) {
-      // IGX_OVERLAP unset: make the passes only when they cost less than what they hide.  Cost: the launcher's own measure (rounds x
-      // segment length, summed over the launches) of the passes against one pass, times the time of an element-step.  Gain: the
-      // largest face message at the link's rate -- the faces travel on different links, at once (IGX_LINK_GBS, default 60 GB/s per
-      // direction).  At 8 ranks of the metric configuration (128^3 per rank) three passes cost 6 ms of a 33 ms assembly and a face
-      // is 141 MB = 2.4 ms: one pass; at 2 ranks (256 x 256 x 128) the pass costs 2.3 ms and the face is 552 MB = 9 ms: faces first
-      // (scripts/time_rank_box.py, profiles/r04_face_passes.txt).
-      const int wpb = pencil_wpb(s, deg, geo, fixt, mod != nullptr);      // (the workgroup count the launches will really have)
-      const size_t xl = (mod ? mod->extra_lds : 0) + pencil_win_extra(s, deg, geo, fixt, mod, wpb);      // (and their LDS: the window of the packed walks)
-      Box R = P; long long multi = 0;
-      if (can2) { Box A = R; A.lo[2] = c2; R.hi[2] = c2; multi += pencil_box_cost(s, deg, geo || mod, xl, A, false, wpb); }
-      if (can1) { Box B = R; B.lo[1] = c1; R.hi[1] = c1; multi += pencil_box_cost(s, deg, geo || mod, xl, B, false, wpb); }
-      if (can0) { Box C = R; C.lo[0] = c0; R.hi[0] = c0; multi += pencil_box_cost(s, deg, geo || mod, xl, C, true, wpb); }
-      multi += pencil_box_cost(s, deg, geo || mod, xl, R, false, wpb);
-      const long long single = pencil_box_cost(s, deg, geo || mod, xl, P, false, wpb);
-      const double t_step = (deg == 3 ? 30e-6 : 9e-6) * ((geo || mod) ? 1.4 : 1.0);      // s per element-step of a launch (256^3: 16 ms / (4 rounds x 131))
-      const double cost_s = (double)(multi - single) * t_step;
-      // (the communicator's figure: $IGX_LINK_GBS, else what IGXCommInitRCCL measured on this rank's own links, else 60)
-      const char *lr = getenv("IGX_LINK_GBS"); const double rate = (lr && atof(lr) > 0 ? atof(lr) : (s.link_gbs > 0 ? s.link_gbs : 60.0)) * 1e9;
-      double face = 0; const double rowb = 8.0 * (2 * deg + 1) * (2 * deg + 1) * (2 * deg + 1);
-      const double nr[3] = {(double)s.lay[0].nrow, (double)s.lay[1].nrow, (double)s.lay[2].nrow};
-      if (can2) face = std::max(face, deg * nr[0] * nr[1] * rowb);
-      if (can1) face = std::max(face, deg * nr[0] * nr[2] * rowb);
-      if (can0) face = std::max(face, deg * nr[1] * nr[2] * rowb);
-      faces_first = face / rate > cost_s;
-    }
-    dom.passes = faces_first ? 1 + (can2 ? 1 : 0) + (can1 ? 1 : 0) + (can0 ? 1 : 0) : 1;
-    if (faces_first) {
-      Box R = P;
-      auto pass_of = [&](const Box &b, bool face0, bool rest0, int *fty, PencilPass &pp) {
-        fty[0] = b.lo[2]; fty[1] = b.hi[2]; fty[2] = (can2 && b.hi[2] <= c2) ? c2 : 0x7fffffff;
-        pp.ftx[0] = b.lo[1]; pp.ftx[1] = b.hi[1]; pp.ftx[2] = (can1 && b.hi[1] <= c1) ? c1 : 0x7fffffff;
-        pp.halo_lo = face0 ? 0 : -1; pp.open_hi = rest0;
-      };
-      if (can2) { Box A = R; A.lo[2] = c2; R.hi[2] = c2; int fty[3]; PencilPass pp; pass_of(A, false, false, fty, pp); run(A, fty, &pp); slab_done(); }
-      if (can1) { Box B = R; B.lo[1] = c1; R.hi[1] = c1; int fty[3]; PencilPass pp; pass_of(B, false, false, fty, pp); run(B, fty, &pp); face_done(1); }
-      if (can0) { Box C = R; C.lo[0] = c0; R.hi[0] = c0; int fty[3]; PencilPass pp; pass_of(C, true, false, fty, pp); run(C, fty, &pp); face_done(0); }
-      { int fty[3]; PencilPass pp; pass_of(R, false, can0, fty, pp); run(R, fty, &pp); }
-    } else run(P, nullptr);
-    if (dom.ev1) (void)hipEventRecord(dom.ev1, stream);
-    dom.name = std::string(state ? "state_pencil<walk=" : mod ? "form_pencil<hiprtc,walk=" : "gram_pencil<walk=") + char('0' + walk_axis) + ",p=" + char('0' + deg) + (geo ? ",geometry" : "") + ">"; dom.launches = launches - l0;
-    dom.elements = (long long)std::max(0, P.hi[0] - P.lo[0]) * std::max(0, P.hi[1] - P.lo[1]) * std::max(0, P.hi[2] - P.lo[2]);
-    // executed MFMA flops per element: 2*16*16*4 per v_mfma_f64_16x16x4, 48 k-steps, 10 (symmetric, walk 0) or 16 tiles
-    // (p = 2: 21 k-steps x 6 layer-pair tiles, or x 3 packed tiles)
-    dom.flop_per_element = 2048.0 * (deg == 3 ? 48 * (walk_axis == 0 ? 10 : 16) : 21 * ((walk_axis == 0 && pencil_p2_pack(s, deg, geo, fixt, mod != nullptr)) ? 3 : 6));
-    if (state) dom.flop_per_element = mod->flop_per_element;
-    // the sum-factorised p = 3 Gram walk (pencil_mfma_sf): 2 fp64 FMAs on each of the 4 accumulator doubles of a tile, 64 lanes (its 12
-    // MFMAs are once per pencil)
-    else if (deg == 3 && !geo && !mod && s.env.gram_sumfact != 0) dom.flop_per_element = 2.0 * 2 * 4 * 64 * (walk_axis == 0 ? 10 : 16);
-    // E as disjoint slabs: axis 0 faces (full), axis 1 faces (inside P along 0), axis 2 faces (inside P along 0,1)
-    for (int d = 0; d < 3; ++d) for (int side = 0; side < 2; ++side) {
-      Box b = all;
-      for (int k = 0; k < d; ++k) { b.lo[k] = P.lo[k]; b.hi[k] = P.hi[k]; }
-      if (side == 0) { b.lo[d] = all.lo[d]; b.hi[d] = std::min(P.lo[d], P.hi[d]); }
-      else { b.lo[d] = std::max(P.hi[d], P.lo[d]); b.hi[d] = all.hi[d]; }
-      if (sys) launch_elements<true>(s, S, out, stream, b, ga, launches); else launch_elements<false>(s, S, out, stream, b, ga, launches);
-    }
-    kname = (state ? std::string("state_pencil<") + mod->name + ">(mfma_f64_16x16x4,p=" : mod ? std::string("form_pencil<") + mod->name + ">(hiprtc,mfma_f64_16x16x4,p=" : std::string("gram_pencil(mfma_f64_16x16x4,p=")) + char('0' + deg) + ",walk=" + char('0' + walk_axis) + (geo ? ",mapped geometry" : "") + ((deg == 2 && walk_axis == 0 && (pencil_p2_pack(s, deg, geo, fixt, mod != nullptr) || (mod && mod->pack))) ? ",packed tiles" : "") + (walk_axis == 0 ? ")" : ")+gram_p3_element(faces)");
-  }
-  if (pencil_launch_error()) { err = pencil_launch_error(); pencil_launch_error() = nullptr; (void)hipGetLastError(); return IGX_ERR_LIB; }
-  if (hipGetLastError() != hipSuccess) { err = "gram MFMA kernel launch failed"; return IGX_ERR_LIB; }
-  done = true;
-  return 0;
-}
-
-#endif   // !IGX_RTC
-
 }  // namespace igx

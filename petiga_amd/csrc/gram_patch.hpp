@@ -445,71 +445,5 @@ state_patch_p2(SpaceDev S, OutDev out, PatchArgs A, ParamsDev prm) {
   for (int li = ne - lag; li <= last; ++li) { leave(li, run); fetch(li + 1, run); }
 }
 
-#ifndef IGX_RTC
-// the launches of an assembly: 2 x 2 colours of patches, cy-major (the first-touch rule knows the order)
-static void launch_patches_p2(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch) {
-  using G = PatchP2;
-  const bool sys = out.op == OP_SYSTEM;
-  for (int cy = 0; cy < G::SY; ++cy) for (int cx = 0; cx < G::SX; ++cx) {
-    PatchArgs A; size_t lds = 0;
-    if (!patch_colour_args<G>(s, cx, cy, forcing, first_touch, patch_lds_bytes, "the patch walk's tables do not fit the LDS", A, lds)) { if (pencil_launch_error()) return; continue; }
-    PencilArgs &pa = A.pa;
-    const long long patches = pa.blocks_per_seg;
-    auto kern = sys ? gram_patch_p2<true> : gram_patch_p2<false>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static int dbg_done = 0, dbg_seen = 0;      // -DIGX_DEBUG, IGX_DEBUG_TIMING=n: the n-th patch launch of the process is stamped
-    const bool dbg_t = kDebug && s.env.debug_timing && !dbg_done && ++dbg_seen >= std::max(1, atoi(getenv("IGX_DEBUG_TIMING") ? getenv("IGX_DEBUG_TIMING") : "1"));
-    const size_t nwg = (size_t)(patches * pa.nseg), dbg_n = nwg * G::W * 4 + nwg * 4;
-    if (dbg_t) { (void)hipMalloc((void **)&pa.debug_buf, dbg_n * 8); (void)hipMemset(pa.debug_buf, 0, dbg_n * 8); }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(patches * pa.nseg)), dim3(G::W * 64), lds, stream, S, out, A);
-    if (dbg_t) {
-      dbg_done = 1;
-      (void)hipStreamSynchronize(stream);
-      std::vector<long long> h(dbg_n);
-      (void)hipMemcpy(h.data(), pa.debug_buf, dbg_n * 8, hipMemcpyDeviceToHost);
-      double sm[3][3] = {{0}}; long long cnt[3] = {0}; double el = 0;
-      for (size_t b = 0; b < nwg; ++b) for (int w = 0; w < G::W; ++w) {
-        const long long *d = &h[(b * G::W + w) * 4];
-        if (!d[3]) continue;
-        const int k = w < 7 ? 0 : (w < G::W - 1 ? 1 : 2);      // wavefronts whose every lane owns a run | partly or none | the one with the F rows
-        for (int c = 0; c < 3; ++c) sm[k][c] += (double)d[c] / (double)d[3];
-        cnt[k]++; el += (double)d[3];
-      }
-      const char *nm[3] = {"wavefronts 0-6 (64 runs each)", "wavefronts 7-10 (8 runs / none)", "wavefront 11 (the F rows)"};
-      fprintf(stderr, "[igx patch timing] colour (%d,%d): %zu workgroups, seg_len %d nseg %d; cycles per element and wavefront:\n", cx, cy, nwg, pa.seg_len, pa.nseg);
-      for (int k = 0; k < 3; ++k) if (cnt[k]) fprintf(stderr, "[igx patch timing]   %s: MFMAs + window adds %.0f | wait at the barrier %.0f | leave + next fetch %.0f | period %.0f\n", nm[k], sm[k][0] / cnt[k], sm[k][1] / cnt[k], sm[k][2] / cnt[k], (sm[k][0] + sm[k][1] + sm[k][2]) / cnt[k]);
-      {   // the launch as a per-CU timeline on the 100 MHz clock (as launch_pencils prints it)
-        const long long *wr = &h[nwg * G::W * 4];
-        long long t0 = LLONG_MAX, t1 = 0; std::map<long long, std::vector<std::pair<long long, long long>>> cu;
-        for (size_t b = 0; b < nwg; ++b) { const long long *w = wr + b * 4; if (!w[0] || !w[1]) continue; t0 = std::min(t0, w[0]); t1 = std::max(t1, w[1]);
-          const long long hw = w[2]; cu[((w[3] & 15) << 12) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 15)].push_back({w[0], w[1]}); }
-        if (t1 > t0 && !cu.empty()) {
-          double busy = 0; int rmax = 0;
-          for (auto &kv : cu) { rmax = std::max(rmax, (int)kv.second.size()); for (auto &iv : kv.second) busy += (double)(iv.second - iv.first); }
-          fprintf(stderr, "[igx patch timing]   timeline: span %.1f us (walks only) over %d CUs, at most %d workgroups on one CU; CU-time inside a walk %.3f of span x 256 CUs\n",
-                  (t1 - t0) * 0.01, (int)cu.size(), rmax, busy / ((double)(t1 - t0) * 256.0));
-        }
-      }
-      (void)hipFree(pa.debug_buf); pa.debug_buf = nullptr;
-    }
-    launches++;
-  }
-}
-// ... of a Tangent (Jacobian / IJacobian): `kern` = state_patch_p2<Form>
-typedef void (*StatePatchKernel)(SpaceDev, OutDev, PatchArgs, ParamsDev);
-static void launch_state_patches_p2(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, bool first_touch, const void *kernel, const ParamsDev &prm) {
-  StatePatchKernel kern = reinterpret_cast<StatePatchKernel>(const_cast<void *>(kernel));
-  using G = StatePatchP2;
-  for (int cy = 0; cy < G::SY; ++cy) for (int cx = 0; cx < G::SX; ++cx) {
-    PatchArgs A; size_t lds = 0;
-    if (!patch_colour_args<G>(s, cx, cy, 0.0, first_touch, spatch_lds_bytes, "the patch walk's tables do not fit the LDS", A, lds)) { if (pencil_launch_error()) return; continue; }
-    const PencilArgs &pa = A.pa;
-    const long long patches = pa.blocks_per_seg;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(patches * pa.nseg)), dim3(G::W * 64), lds, stream, S, out, A, prm);
-    launches++;
-  }
-}
-#endif
 
 }  // namespace igx

@@ -311,44 +311,5 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
   }
 }
 
-#ifndef IGX_RTC
-// the launches of an assembly: SX x SY colours of patches, cy-major (the first-touch rule knows the order); pencil_launch_error
-// is set when no segment length fits the LDS
-template <int MX, int MY>
-static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch) {
-  using G = Patch3<MX, MY>;
-  const bool sys = out.op == OP_SYSTEM;
-  for (int cy = 0; cy < G::SY; ++cy) for (int cx = 0; cx < G::SX; ++cx) {
-    PatchArgs A; size_t lds = 0;
-    if (!patch_colour_args<G>(s, cx, cy, forcing, first_touch, patch3_lds_bytes<MX, MY>, "the p = 3 patch walk's tables do not fit the LDS", A, lds)) { if (pencil_launch_error()) return; continue; }
-    PencilArgs &pa = A.pa;
-    const long long patches = pa.blocks_per_seg;
-    auto kern = sys ? gram_pencil_patch3<true, MX, MY> : gram_pencil_patch3<false, MX, MY>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    static int dbg_done = 0, dbg_seen = 0;      // -DIGX_DEBUG, IGX_DEBUG_TIMING=n: the n-th launch of the process is stamped (as launch_patches_p2)
-    const bool dbg_t = kDebug && s.env.debug_timing && !dbg_done && ++dbg_seen >= std::max(1, atoi(getenv("IGX_DEBUG_TIMING") ? getenv("IGX_DEBUG_TIMING") : "1"));
-    const size_t nwg = (size_t)(patches * pa.nseg), dbg_n = nwg * G::W * 5;
-    if (dbg_t) { (void)hipMalloc((void **)&pa.debug_buf, dbg_n * 8); (void)hipMemset(pa.debug_buf, 0, dbg_n * 8); }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(patches * pa.nseg)), dim3(G::W * 64), lds, stream, S, out, A);
-    if (dbg_t) {
-      dbg_done = 1;
-      (void)hipStreamSynchronize(stream);
-      std::vector<long long> h(dbg_n);
-      (void)hipMemcpy(h.data(), pa.debug_buf, dbg_n * 8, hipMemcpyDeviceToHost);
-      double sm[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}; long long cnt = 0;
-      for (size_t i = 0; i < nwg * G::W; ++i) {
-        const long long *d = &h[i * 5];
-        if (!d[4]) continue;
-        for (int c = 0; c < 4; ++c) { const double x = (double)d[c] / (double)d[4]; sm[c] += x; mx[c] = std::max(mx[c], x); }
-        cnt++;
-      }
-      if (cnt) fprintf(stderr, "[igx patch3 timing] colour (%d,%d): %zu workgroups, seg_len %d nseg %d; cycles per element step, mean (max) over %lld wavefronts: sub-phases %.0f (%.0f) | wait for the old values %.0f (%.0f) | window, stores, next loads %.0f (%.0f) | closing barrier + F %.0f (%.0f) | step %.0f\n",
-                       cx, cy, nwg, pa.seg_len, pa.nseg, cnt, sm[0] / cnt, mx[0], sm[1] / cnt, mx[1], sm[2] / cnt, mx[2], sm[3] / cnt, mx[3], (sm[0] + sm[1] + sm[2] + sm[3]) / cnt);
-      (void)hipFree(pa.debug_buf); pa.debug_buf = nullptr;
-    }
-    launches++;
-  }
-}
-#endif
 
 }  // namespace igx

@@ -5,7 +5,7 @@
 // "pair" of an axis is two nodes of the patch that share one of its elements, a RUN the 2p + 1 walk-axis entries of one (y pair, x pair)
 // and node layer.  Here, once, templated on the degree P (and the patch shape where it enters): the shape's constants, the decode of a
 // workgroup, the walk-axis layer table, the pair tables, the Dirichlet fix-up of a combined run, a run's matrix address and first-touch
-// rule, the load / add / store of a run, and the host's arguments and segments of one colour.  What differs for measured reasons stays
+// rule, the load / add / store of a run (the host's arguments and segments of one colour: pencil_launch.hpp).  What differs for measured reasons stays
 // with each kernel: the LDS carve-up, the window and its zeroing, the element phase, the F and lifting stages, which thread owns which
 // run, the barriers.
 //
@@ -212,40 +212,5 @@ __device__ __forceinline__ void patch_run_add_store(double *val, long long base,
   }
 }
 
-#ifndef IGX_RTC
-// ---- host: the arguments of the launch of colour (cx, cy) -- the colours are launched cy-major, patch_first_touch knows the order -- its
-// segments and its LDS (lds_bytes(ne_max) of the kernel).  Returns whether the colour has patches to launch; pencil_launch_error is
-// set (and nothing is to be launched) when no segment length fits the LDS.
-// Segments: the count with the fewest rounds x (length + halo + set-up) over the slots for resident workgroups.
-template <class G, class LdsBytes>
-static bool patch_colour_args(const Space &s, int cx, int cy, double forcing, bool first_touch, LdsBytes lds_bytes, const char *no_fit, PatchArgs &A, size_t &lds) {
-  const int nx = s.elem_width[1], ny = s.elem_width[2], nw = s.elem_width[0];
-  const int npx = (nx + G::MX - 1) / G::MX, npy = (ny + G::MY - 1) / G::MY;
-  memset(&A, 0, sizeof(A));
-  A.px_start = cx; A.px_step = G::SX; A.px_count = (npx - cx + G::SX - 1) / G::SX;
-  A.py_start = cy; A.py_step = G::SY; A.py_count = (npy - cy + G::SY - 1) / G::SY;
-  if (A.px_count <= 0 || A.py_count <= 0) return false;
-  PencilArgs &pa = A.pa;
-  pa.forcing = forcing; pa.first_touch = first_touch ? 1 : 0;
-  pa.nelx = nx; pa.nely = ny; pa.w_lo = 0; pa.w_hi = nw; pa.w_halo_lo = 0; pa.open_hi = 0; pa.wpb = G::W;
-  const long long patches = (long long)A.px_count * A.py_count;
-  const int ncu = pencil_cus();
-  int best = 1; long long bc = -1;
-  for (int n = 1; n <= std::max(1, nw / 2); ++n) {      // (down to two elements per segment: pencil_segments)
-    const int len = (nw + n - 1) / n, ns = (nw + len - 1) / len;
-    const size_t lds_n = lds_bytes(len + 3);
-    if (lds_n > (size_t)160 * 1024) continue;
-    const long long slots = G::SLOTS_FROM_LDS ? (long long)ncu * std::max<long long>(1, (long long)(160 * 1024) / (long long)lds_n) : ncu;
-    const long long cost = ((patches * ns + slots - 1) / slots) * (len + (ns > 1 ? G::P : 0) + 1);
-    if (bc < 0 || cost < bc) { bc = cost; best = n; }
-  }
-  if (s.env.nseg > 0) best = std::min(s.env.nseg, std::max(1, nw / 2));
-  pa.seg_len = (nw + best - 1) / best; pa.nseg = (nw + pa.seg_len - 1) / pa.seg_len;
-  pa.blocks_per_seg = (int)patches; pa.ne_max = pa.seg_len + 3;
-  lds = lds_bytes(pa.ne_max);
-  if (lds > (size_t)160 * 1024) { pencil_launch_error() = no_fit; return false; }
-  return true;
-}
-#endif
 
 }  // namespace igx

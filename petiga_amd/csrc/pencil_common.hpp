@@ -110,7 +110,7 @@ inline hipError_t pool_alloc(void **ptr, size_t bytes, hipStream_t stream) {
 
 #endif   // !IGX_RTC
 
-// boundary loads on the identity geometry: see k_boundary_loads (gram_mfma.hpp)
+// boundary loads on the identity geometry: see k_boundary_loads (boundary_loads.hpp)
 struct FluxArgs {
   int d, t, u;                 // face axis and the two axes of the face
   int rd;                      // row index of the face nodes on axis d
