@@ -752,6 +752,73 @@ int IGXMultigridDestroy(IGXMultigrid *mg);
  * diagonal as D (point blocks: IGX_ERR_SUP); it overwrites the level's x and d, which every cycle rewrites anyway. */
 int IGXMultigridMeasureStep(IGXMultigrid mg,int level,int reps,int rounds,double *fused_ms,double *split_ms);
 
+/* Block-vector algebra on blocks of IGXVec, petiga_amd/csrc/block_vec.hpp: PETSc's VecMDot and VecMAXPY for two blocks of 1 <= nx, ny <= 48
+ * vectors of ONE IGX.
+ *   IGXVecMDot   G[i][j] = X_i . Y_j, G on the host, row-major [nx][ny]; synchronises.  X and Y may share vectors (X == Y: a Gram
+ *                matrix).  One pass over the rows on v_mfma_f64_16x16x4_f64 with the row as the contraction index; columns past nx / ny
+ *                and rows past n feed zeros and are never read.  A capped grid; every workgroup adds its rows in a fixed order and stores
+ *                its partial tile in its own slot, a finishing kernel adds the slots in index order: no atomics, bit-repeatable.
+ *   IGXVecMAXPY  Y_j = beta Y_j + sum_i C[i][j] X_i, C on the host, row-major [nx][ny]; beta == 0 writes Y_j whatever it held
+ *                (IGXVecAXPBY's rule).  Every entry starts from beta Y_j and adds the terms in ascending i.  Every Y_j must differ from
+ *                every X_i and from the other Y.  Enqueued; C is copied before the call returns.
+ * IGX_ERR_ARG_WRONG: a null array or entry, vectors of different IGX, an aliased Y.  IGX_ERR_ARG_OUTOFRANGE: nx or ny outside [1, 48].
+ * IGX_ERR_SUP: several ranks on an axis (the solve loops' rule: the library has no sum across ranks).
+ * IGXSetTiming / IGXGetLastTiming / IGXGetKernelName cover both calls. */
+int IGXVecMDot (int nx,IGXVec X[],int ny,IGXVec Y[],double G[] /* host [nx][ny] */);
+int IGXVecMAXPY(int ny,IGXVec Y[],int nx,IGXVec X[],const double C[] /* host [nx][ny] */,double beta);
+
+/* The nev lowest eigenpairs of A x = lambda B x on the device, without SLEPc: LOBPCG (Knyazev, SIAM J. Sci. Comput. 23, 2001) with a block
+ * of m = block columns, nev <= m <= 16.  A is IGXComputeMatrixAction of `stiff`; B that of `mass`, a second set-up IGX on the same space
+ * (typically the Mass form), or the identity with mass == NULL.  Both forms must be symmetric (Poisson, Elasticity, Mass are): that is the
+ * caller's responsibility.  IGX_OP_MATRIX only.  X holds the start block on entry and the B-orthonormal Ritz vectors on return; lambda is
+ * ascending; resid (may be NULL) receives |A x_j - lambda_j B x_j|_2.  T is the preconditioner pc names, as in IGXSolve: none, the
+ * diagonal, the inverted point blocks, or the state of the caller's IGXFastDiagSetUp on stiff.
+ * Dirichlet rows: the solve first zeroes the start block's fixed rows (mg_zero_fixed).  A fixed row of either action then returns
+ * count x 0 = 0 and every T maps 0 to 0 there, so the iteration stays in the free space with no further masking (the fact the multigrid
+ * relies on): the returned vectors are exactly zero on the fixed rows.
+ * The loop, with S = [X W P] (the first iteration and the one after a restart have no P):
+ *   0. AX = A X, BX = B X (mass == NULL: BX is X, no action and no copy); G_A = X^T AX, G_B = X^T BX (two IGXVecMDot); Rayleigh-Ritz as in
+ *      step 6 on X alone; X, AX, BX <- (.) C (IGXVecMAXPY into the second buffer set).  G_B not positive definite here: BREAKDOWN.
+ *   1. R_j = AX_j - theta_j BX_j for the whole block in ONE sweep, which also emits the slab partials of |R_j|^2 and |AX_j|^2; a finishing
+ *      kernel adds them in index order and the host reads ONE record of 2 m sums per iteration.  history[k][j] = |R_j| at iteration k.
+ *   2. Column j has converged when |R_j| <= max(rtol |AX_j|, atol); the solve stops with IGX_EIGEN_CONVERGED when the columns 0 .. nev-1
+ *      all have, with IGX_EIGEN_DIVERGED_NAN on a NaN norm, with IGX_EIGEN_DIVERGED_ITS after maxit iterations.  No locking: every column
+ *      keeps iterating.
+ *   3. W_j = T R_j (pc none: the sweep of step 1 writes R into W).
+ *   4. AW = A W, BW = B W: with AX and BX carried along, 2 m actions per iteration (m with mass == NULL).
+ *   5. G_A = S^T [AX AW AP], G_B = S^T [BX BW BP]: two IGXVecMDot launches of 3m x 3m (2m x 2m without P).
+ *   6. Rayleigh-Ritz on the host: both matrices are symmetrised ((G + G^T) / 2) and scaled by d_i d_j with d = 1 / sqrt(diag G_B); the
+ *      dense symmetric-definite solver (Cholesky in long double, cyclic Jacobi, refinement) gives the pairs of (G_A, G_B), of which the m
+ *      lowest are taken, C = d .* U.  If G_B is not positive definite (or its diagonal not positive and finite) while P is present: P is
+ *      dropped, restarts += 1, and the step is redone on [X W] from the same Gram blocks.  Without P: IGX_EIGEN_DIVERGED_BREAKDOWN.
+ *   7. P' = [W P] C_WP, X' = X C_X + P', and the same for the A. and B. blocks (IGXVecMAXPY into the second buffer set, then the sets
+ *      swap); theta = the m Ritz values; go to 1.
+ * A solve that does not converge returns 0 with the reason in info, as IGXSolve does; X, lambda and resid then hold the last iterate.
+ * info->actions counts the calls of either action, info->nconverged the columns among 0 .. nev-1 that met the test at the last iteration. Work vectors are kept with stiff between calls and dropped by IGXSetUp; the vectors
+ * the mass action works on are the solver's business (the action of mass runs on stiff's vectors: same space, same layout).
+ * IGXGetKernelName: "eigen(lobpcg, block 6, pc=fastdiag, <the action's name>, <k> iterations)"; IGXGetLastTiming: the whole solve with
+ * the exact launch count.
+ * Refusals, each decided before the first HIP call, each naming the eigen solve, in this order:
+ *   1. a null stiff, spec, X, lambda or info: IGX_ERR_ARG_WRONG
+ *   2. the spec: nev < 1; block < nev or block > 16; an unknown pc; a negative or NaN tolerance; maxit < 0: IGX_ERR_ARG_OUTOFRANGE;
+ *      nx != block: IGX_ERR_ARG_WRONG
+ *   3. stiff, then mass, before IGXSetUp: IGX_ERR_ORDER
+ *   4. no form on stiff, then on mass: IGX_ERR_ARG_WRONGSTATE
+ *   5. mass differs from stiff in dim, dof, then per axis degree, knots, periodicity, then the Dirichlet faces per field, then the
+ *      stream: IGX_ERR_ARG_WRONG
+ *   6. several ranks on an axis, or a fix table (IGXSetFixTable: its fixed rows are not a union of faces) on either: IGX_ERR_SUP
+ *   7. an entry of X that is null, of another IGX than stiff, or repeated: IGX_ERR_ARG_WRONG
+ *   8. IGX_PC_FASTDIAG without IGXFastDiagSetUp on stiff: IGX_ERR_ORDER
+ *   9. whatever the actions or the diagonals refuse, with their reason under the eigen solve's name.
+ * Out of scope: a batched action on several columns per launch (the obvious next step: the 2 m actions dominate), locking of converged
+ * columns, interior or largest eigenvalues, Jacobian operators at a state, several ranks, the multigrid as T. */
+typedef enum { IGX_EIGEN_CONVERGED = 1, IGX_EIGEN_DIVERGED_ITS = -1, IGX_EIGEN_DIVERGED_BREAKDOWN = -2, IGX_EIGEN_DIVERGED_NAN = -3 } IGXEigenReason;
+typedef struct { int nev, block, pc; double rtol, atol; int maxit; } IGXEigenSpec;
+typedef struct { int iterations, reason, nconverged, restarts, actions; } IGXEigenInfo;
+int IGXEigenSolve(IGX stiff,IGX mass /* NULL: B = I */,const IGXEigenSpec *spec,int nx,IGXVec X[] /* [block], of stiff */,
+                  double lambda[] /* [block] */,double resid[] /* [block], may be NULL */,IGXEigenInfo *info,
+                  double *history /* NULL or [maxit+1][block]: |r_j|_2 */);
+
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the
  * ranks, and U must hold the ghost rows' values).  The point callbacks are the ones the reference's tests use:

@@ -52,6 +52,14 @@ class IGXMultigridSpec(C.Structure):
                 ("power_its", C.c_int), ("coarse_method", C.c_int), ("coarse_pc", C.c_int), ("coarse_rtol", C.c_double), ("coarse_maxit", C.c_int)]
 
 
+class IGXEigenSpec(C.Structure):
+    _fields_ = [("nev", C.c_int), ("block", C.c_int), ("pc", C.c_int), ("rtol", C.c_double), ("atol", C.c_double), ("maxit", C.c_int)]
+
+
+class IGXEigenInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("reason", C.c_int), ("nconverged", C.c_int), ("restarts", C.c_int), ("actions", C.c_int)]
+
+
 class IGXNewtonSpec(C.Structure):
     _fields_ = [("op", C.c_int), ("a", C.c_double), ("t", C.c_double), ("W", C.c_void_p), ("method", C.c_int), ("pc", C.c_int),
                 ("lin_rtol", C.c_double), ("lin_atol", C.c_double), ("lin_maxit", C.c_int), ("forcing", C.c_int),
@@ -83,6 +91,7 @@ SOLVE_METHODS = dict(cg=0, bicgstab=1)
 SOLVE_OPERATORS = dict(matrix=0, jacobian=1, ijacobian=2)
 SOLVE_PCS = dict(none=0, jacobi=1, pbjacobi=2, fastdiag=3)
 SOLVE_REASONS = {1: "converged_rtol", 2: "converged_atol", -1: "diverged_its", -2: "diverged_breakdown", -3: "diverged_nan"}
+EIGEN_REASONS = {1: "converged", -1: "diverged_its", -2: "diverged_breakdown", -3: "diverged_nan", 0: "iterating"}
 NEWTON_LINESEARCHES = dict(basic=0, bt=1)
 NEWTON_FORCINGS = dict(constant=0, ew2=1)
 NEWTON_REASONS = {2: "converged_fnorm_abs", 3: "converged_fnorm_relative", 4: "converged_snorm_relative", -3: "diverged_linear_solve", -4: "diverged_fnorm_nan",
@@ -175,6 +184,8 @@ def lib(build_if_needed=False):
         "IGXFastDiagGetAxis": [V, C.c_int, C.c_int, _ip, _ip, _dp, _dp],
         "IGXVecSet": [V, C.c_double], "IGXVecCopy": [V, V], "IGXVecScale": [V, C.c_double], "IGXVecAXPBY": [V, C.c_double, V, C.c_double],
         "IGXVecPointwiseDivide": [V, V, V], "IGXVecDot": [V, V, _dp], "IGXVecNorm2": [V, _dp],
+        "IGXVecMDot": [C.c_int, C.POINTER(V), C.c_int, C.POINTER(V), _dp], "IGXVecMAXPY": [C.c_int, C.POINTER(V), C.c_int, C.POINTER(V), _dp, C.c_double],
+        "IGXEigenSolve": [V, V, C.POINTER(IGXEigenSpec), C.c_int, C.POINTER(V), _dp, _dp, C.POINTER(IGXEigenInfo), _dp],
         "IGXSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
         "IGXSolveNonlinear": [V, C.POINTER(IGXNewtonSpec), V, C.POINTER(IGXNewtonInfo), _dp, _ip],
         "IGXTimeStep": [V, C.POINTER(IGXTimeStepSpec), V, V, C.POINTER(IGXTimeStepInfo), C.POINTER(IGXTimeStepLog), C.c_int],
@@ -485,6 +496,32 @@ class Vec:
         return a
 
 
+def _vec_array(vs):
+    return (C.c_void_p * max(len(vs), 1))(*[v.h.value if v is not None else None for v in vs])
+
+
+def _mdot(X, Y):
+    """IGXVecMDot: G [len(X), len(Y)] with G[i, j] = X[i] . Y[j], in one pass over the rows on the FP64 matrix cores (1 to 48 vectors of one
+    IGX per block; X and Y may share vectors); synchronises"""
+    X, Y = list(X), list(Y)
+    G = np.zeros((max(len(X), 1), max(len(Y), 1)))
+    _ck(lib().IGXVecMDot(len(X), _vec_array(X), len(Y), _vec_array(Y), G.ctypes.data_as(_dp)))
+    return G[:len(X), :len(Y)]
+
+
+def _maxpy(Y, X, Cm, beta=0.0):
+    """IGXVecMAXPY: Y[j] = beta Y[j] + sum_i Cm[i, j] X[i] (beta == 0 writes Y[j] whatever it held); every Y[j] differs from every X[i]"""
+    X, Y = list(X), list(Y)
+    Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+    assert Cm.shape == (len(X), len(Y)), "C: [len(X), len(Y)]"
+    _ck(lib().IGXVecMAXPY(len(Y), _vec_array(Y), len(X), _vec_array(X), Cm.ctypes.data_as(_dp), float(beta)))
+    return Y
+
+
+Vec.mdot = staticmethod(_mdot)
+Vec.maxpy = staticmethod(_maxpy)
+
+
 class Mat:
     def __init__(self, iga):
         self.iga = iga
@@ -772,6 +809,35 @@ class IGX:
                    rnorm0=info.rnorm0, rnorm=info.rnorm, bnorm=info.bnorm)
         if history:
             out["history"] = hist[:info.iterations + 1].copy()
+        return out
+
+    def eigen(self, nev, mass=None, block=None, pc="none", rtol=1e-8, atol=0.0, maxit=200, X=None, history=False):
+        """IGXEigenSolve: the nev lowest eigenpairs of A x = lambda B x by LOBPCG on the device, A this IGX's matrix action, B that of the
+        IGX `mass` on the same space (None: the identity).  block (default min(16, nev + 2)) columns iterate; X: the start block, a list of
+        block Vecs (default: numpy.random.default_rng(0).standard_normal, written from the host).  Returns a dict: "lambda" [block]
+        ascending, "X" (the Vecs, B-orthonormal Ritz vectors), "resid" [block], the info fields (iterations, reason, reason_name, nconverged,
+        restarts, actions) and, with history=True, "history" [iterations + 1, block] of |r_j|."""
+        nev = int(nev)
+        m = min(16, nev + 2) if block is None else int(block)
+        if X is None:
+            X = []
+            if 1 <= nev <= m <= 16:      # (otherwise the call refuses the specification before it looks at the block)
+                rng = np.random.default_rng(0)
+                for _ in range(m):
+                    v = self.create_vec()
+                    X.append(v.set(rng.standard_normal(v.n)))
+        X = list(X)
+        spec = IGXEigenSpec(nev, m, SOLVE_PCS[pc] if isinstance(pc, str) else int(pc), float(rtol), float(atol), int(maxit))
+        info = IGXEigenInfo()
+        lam, res = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        hist = np.zeros((max(int(maxit), 0) + 1, max(m, 1))) if history else None
+        _ck(lib().IGXEigenSolve(self.h, mass.h if mass is not None else None, C.byref(spec), len(X), _vec_array(X), lam.ctypes.data_as(_dp), res.ctypes.data_as(_dp),
+                                C.byref(info), hist.ctypes.data_as(_dp) if history else None))
+        out = {k: getattr(info, k) for k, _ in IGXEigenInfo._fields_}
+        out["reason_name"] = EIGEN_REASONS.get(info.reason, str(info.reason))
+        out["lambda"], out["X"], out["resid"] = lam[:m].copy(), X, res[:m].copy()
+        if history:
+            out["history"] = hist[:info.iterations + 1, :m].copy()
         return out
 
     def solve_nonlinear(self, x, op="jacobian", W=None, a=0.0, t=0.0, method="bicgstab", pc="none", lin_rtol=1e-5, lin_atol=0.0, lin_maxit=1000,

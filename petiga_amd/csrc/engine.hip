@@ -78,6 +78,8 @@ struct RtcForm;
 struct KrylovState;
 struct NewtonState;
 struct TimeStepState;
+struct BlockVecState;
+struct EigenState;
 // IGXFastDiagSetUp's host result and the device copies IGXFastDiagApply makes of it at its first call
 struct FastDiagState {
   FastDiag h;
@@ -118,6 +120,8 @@ struct _p_IGX {
   std::shared_ptr<KrylovState> krylov;                              // IGXSolve's work vectors and preconditioner storage, kept between solves
   std::shared_ptr<NewtonState> newton;                              // IGXSolveNonlinear's work vectors, kept between solves
   std::shared_ptr<TimeStepState> timestep;                          // IGXTimeStep's work vectors, U_{n-1} and h_{n-1}, kept between calls
+  std::shared_ptr<BlockVecState> blockvec;                          // IGXVecMDot / IGXVecMAXPY: the slab of partial tiles, the coefficient ring and the record (block_vec.hpp)
+  std::shared_ptr<EigenState> eigen;                                // IGXEigenSolve's work vectors, kept between solves
   std::string self_timed;                                           // the value of last_kernel for which the call itself stored last_total_ms / last_kernel_ms (a solve loop; a probe of no points): IGXGetLastTiming keeps them
   unsigned long long setup_gen = 0;                                 // counts IGXSetUp calls: a probe made before the last one is stale (IGXProbeCreate)
 };
@@ -128,7 +132,7 @@ struct _p_IGXMat {
   DevBuf coo_i, coo_j;     // coordinate lists kept on the device for the hand-back (IGXMatGetCOODevice), or empty
 };
 struct _p_IGXVec { IGX iga; int64_t n; DevBuf a; };
-// (KrylovState, NewtonState, TimeStepState: solve_loops.hpp, the main unit)
+// (KrylovState, NewtonState, TimeStepState, BlockVecState, EigenState: solve_loops.hpp, the main unit)
 
 #ifndef IGX_TU_DISPATCH
 extern "C" const char *IGXGetLastError(void) { return g_err.c_str(); }
@@ -195,7 +199,7 @@ extern "C" int IGXAxisSetKnots(IGX g, int i, int m, const double U[]) { AXISCK(g
 static int apply_geometry(IGX g);
 static int apply_property(IGX g);
 extern "C" int IGXSetUp(IGX g) {
-  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; ++g->setup_gen; g->fd.reset(); g->krylov.reset(); g->newton.reset(); g->timestep.reset(); g->self_timed.clear();
+  NEEDIGA(g); std::string e; int rc = space_setup(g->s, e); g->on_device = false; ++g->setup_gen; g->fd.reset(); g->krylov.reset(); g->newton.reset(); g->timestep.reset(); g->eigen.reset(); g->self_timed.clear();
   if (rc) return fail(rc, e);
   if (int rp = apply_property(g)) return rp;
   return apply_geometry(g);   // a control net given by IGXRead / an earlier IGXSetGeometry survives re-partitioning

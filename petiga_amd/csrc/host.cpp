@@ -386,7 +386,9 @@ void refine_eigen(int m, const std::vector<long double> &C, std::vector<double> 
   for (int k = 0; k < m; ++k) { lam[k] = (double)l[order[k]]; std::copy(&W[(size_t)order[k] * m], &W[(size_t)order[k] * m] + m, &Q[(size_t)k * m]); }
 }
 
-// K U = M U Lambda, U^T M U = I for the symmetric positive definite M and symmetric K, both [m][m]
+}  // namespace
+
+// K U = M U Lambda, U^T M U = I for the symmetric positive definite M and symmetric K, both [m][m] (IGX_ERR_PLIB: M is not positive definite)
 int generalised_eigen(int m, const std::vector<double> &M, const std::vector<double> &K, FastDiagEig &out, std::string &err) {
   typedef long double ld;
   out.lambda.clear(); out.U.clear();
@@ -435,7 +437,6 @@ int generalised_eigen(int m, const std::vector<double> &M, const std::vector<dou
   }
   return 0;
 }
-}  // namespace
 
 int fast_diag_setup(const Space &s, double alpha, const double beta[3], FastDiag &fd, std::string &err) {
   fd = FastDiag();

@@ -170,6 +170,8 @@ struct FastDiag {
 };
 void fast_diag_fixed_faces(const Space &s, bool fixed[3][2][MAXFD]);      // the Dirichlet faces as the element kernels read them
 int  fast_diag_setup(const Space &s, double alpha, const double beta[3], FastDiag &fd, std::string &err);
+// the dense symmetric-definite eigen-solver behind it (Cholesky in long double, cyclic Jacobi, refinement), also IGXEigenSolve's Rayleigh-Ritz step
+int  generalised_eigen(int m, const std::vector<double> &M, const std::vector<double> &K, FastDiagEig &out, std::string &err);
 
 // Transfer between nested spline spaces (IGXTransferCreate, host.cpp; the kernels: transfer.hpp).  Per axis the nf x nc matrix T with
 // B^c_j = sum_i T[i][j] B^f_i, by rows as a band of at most p + 1 consecutive columns, and its transpose as CSR by coarse row.

@@ -1,7 +1,8 @@
-// solve_loops.hpp -- the host side of the vector algebra on IGXVec and of the three device-resident loops: IGXSolve (kernels: krylov.hpp),
-// IGXSolveNonlinear (newton.hpp) and IGXTimeStep (timestep.hpp).  Host code only: it launches kernels and defines none.  Included by the
+// solve_loops.hpp -- the host side of the vector algebra on IGXVec and of the device-resident loops: IGXSolve (kernels: krylov.hpp),
+// IGXSolveNonlinear (newton.hpp), IGXTimeStep (timestep.hpp) and IGXEigenSolve (block_vec.hpp).  Host code only: it launches kernels and defines none.  Included by the
 // main unit of engine.hip as the last thing before the probe, so every kernel above is compiled as it was before these existed; the three
-// kernel headers are included here, where their loops begin, in that order, and multigrid.hpp (the sweeps of IGXMultigrid's cycle) at the end.
+// kernel headers are included here, where their loops begin, in that order, block_vec.hpp (IGXVecMDot / IGXVecMAXPY) behind the vector algebra,
+// and multigrid.hpp (the sweeps of IGXMultigrid's cycle) at the end, before IGXEigenSolve, which zeroes its start block's fixed rows with them.
 // What the loops share is written once, up front: the state kept between calls (LoopState), the accounting of launches and kernel time
 // (LoopClock), the blocking read of partial sums (read_sums), the entry checks in each solver's own words (SolverWords) and the map from
 // the public operator to the matrix-free driver's op (matfree_op).  A new loop costs its own loop.  IGXSolve's two loops are written on
@@ -185,6 +186,107 @@ extern "C" int IGXVecNorm2(IGXVec x, double *s) {
   if (int rc = IGXVecDot(x, x, s)) return rc;
   *s = std::sqrt(*s);
   return 0;
+}
+
+// ------------------------------------------------------------------ block-vector algebra (block_vec.hpp)
+#include "block_vec.hpp"
+// IGXVecMDot / IGXVecMAXPY and what IGXEigenSolve launches between its actions.  The state is kept with the IGX: the slab of partial tiles
+// (KR_G slots of BV_MAX x BV_MAX), the Gram matrix on the device, the residual sweep's slabs and record, and a ring of BV_RING coefficient
+// buffers -- pinned on the host, plain on the device -- so that IGXVecMAXPY can copy C and return without a synchronisation: a slot is
+// written again only after the event behind its last copy.
+constexpr int BV_RING = 16;
+struct BlockVecState : LoopState {
+  DevBuf slab, gram, rslab, rrec, cdev;
+  double *chost = nullptr; hipEvent_t cev[BV_RING]; bool used[BV_RING]; int next = 0;
+  BlockVecState() { for (int k = 0; k < BV_RING; ++k) { cev[k] = nullptr; used[k] = false; } }
+  ~BlockVecState() { for (auto &e : cev) if (e) (void)hipEventDestroy(e); if (chost) (void)hipHostFree(chost); }
+};
+static int bv_state(IGX g) {
+  if (g->blockvec) return 0;
+  std::shared_ptr<BlockVecState> st(new BlockVecState());
+  const size_t tile = (size_t)BV_MAX * BV_MAX;
+  if (st->slab.alloc((size_t)KR_G * tile * sizeof(double)) || st->gram.alloc(tile * sizeof(double)) || st->rslab.alloc((size_t)2 * BV_EIG_MAX * KR_G * sizeof(double)) ||
+      st->rrec.alloc((size_t)2 * BV_EIG_MAX * sizeof(double)) || st->cdev.alloc((size_t)BV_RING * tile * sizeof(double)))
+    return fail(IGX_ERR_MEM, "device allocation of the block-vector buffers failed");
+  HIPCK(hipHostMalloc((void **)&st->chost, (size_t)BV_RING * tile * sizeof(double), hipHostMallocDefault));
+  for (auto &e : st->cev) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  g->blockvec = st;
+  return 0;
+}
+// the checks of a pair of blocks, in each call's words: null arrays, the ranges, null entries, one IGX and one length, one rank per axis
+static int bv_block_args(const char *fn, int nx, IGXVec X[], int ny, IGXVec Y[], IGX *owner) {
+  if (!X || !Y) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null array of vectors");
+  if (nx < 1 || nx > BV_MAX || ny < 1 || ny > BV_MAX) return fail(IGX_ERR_ARG_OUTOFRANGE, std::string(fn) + ": a block holds 1 to " + std::to_string(BV_MAX) + " vectors, got " + std::to_string(nx) + " and " + std::to_string(ny));
+  for (int i = 0; i < nx; ++i) if (!X[i]) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null vector in a block");
+  for (int j = 0; j < ny; ++j) if (!Y[j]) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null vector in a block");
+  IGX g = X[0]->iga;
+  for (int i = 0; i < nx; ++i) if (X[i]->iga != g || X[i]->n != X[0]->n) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": vectors created by different IGX");
+  for (int j = 0; j < ny; ++j) if (Y[j]->iga != g || Y[j]->n != X[0]->n) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": vectors created by different IGX");
+  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, std::string(fn) + ": the block-vector algebra needs one rank on every axis: the library has no sum across ranks");
+  *owner = g;
+  return 0;
+}
+static void bv_cols(BvCols &c, int n, IGXVec V[]) { memset(&c, 0, sizeof(c)); for (int k = 0; k < n; ++k) c.p[k] = V[k]->a.as<double>(); }
+// G = X^T Y on the host: two launches and the blocking read
+static int bv_mdot_run(IGX g, int nx, IGXVec X[], int ny, IGXVec Y[], double G[]) {
+  BlockVecState &st = *g->blockvec;
+  BvCols xc, yc; bv_cols(xc, nx, X); bv_cols(yc, ny, Y);
+  const long long n = (long long)X[0]->n;
+  const unsigned grid = bv_mdot_grid(n);
+  const int count = nx * ny;
+  KR_LAUNCH(bv_mdot_kernel((nx + 15) / 16, (ny + 15) / 16), grid, KR_T, g, xc, nx, yc, ny, n, st.slab.as<double>());
+  KR_LAUNCH(bv_mdot_finish, (count + 255) / 256, 256, g, st.slab.as<double>(), (int)grid, count, st.gram.as<double>());
+  HIPCK(hipMemcpyAsync(G, st.gram.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIPCK(hipStreamSynchronize(g->stream));
+  return 0;
+}
+// Y = beta Y + X C, enqueued: one launch behind the copy of C through the ring
+static int bv_maxpy_run(IGX g, int ny, IGXVec Y[], int nx, IGXVec X[], const double C[], double beta) {
+  BlockVecState &st = *g->blockvec;
+  const int nxb = (nx + 7) / 8, nxp = 8 * nxb, slot = st.next;
+  st.next = (st.next + 1) % BV_RING;
+  if (st.used[slot]) HIPCK(hipEventSynchronize(st.cev[slot]));
+  double *hc = st.chost + (size_t)slot * BV_MAX * BV_MAX, *dc = st.cdev.as<double>() + (size_t)slot * BV_MAX * BV_MAX;
+  for (int j = 0; j < ny; ++j) for (int i = 0; i < nxp; ++i) hc[j * nxp + i] = i < nx ? C[i * ny + j] : 0.0;
+  HIPCK(hipMemcpyAsync(dc, hc, (size_t)ny * nxp * sizeof(double), hipMemcpyHostToDevice, g->stream));
+  HIPCK(hipEventRecord(st.cev[slot], g->stream));
+  st.used[slot] = true;
+  BvCols xc, yc; bv_cols(xc, nx, X); bv_cols(yc, ny, Y);
+  const long long n = (long long)X[0]->n;
+  g->slab_valid = 0;
+  KR_LAUNCH(bv_maxpy_kernel(nxb), bv_maxpy_grid(n), KR_T, g, yc, ny, xc, nx, dc, beta, n);
+  return 0;
+}
+static int bv_finish(IGX g, LoopClock &clk, const std::string &name) {
+  if (int rc = clk.finish(g, name)) return rc;
+  if (clk.timing) g->last_kernel_ms = g->last_total_ms;      // nothing but kernels between the two events
+  return 0;
+}
+extern "C" int IGXVecMDot(int nx, IGXVec X[], int ny, IGXVec Y[], double G[]) {
+  IGX g = nullptr;
+  if (!G) return fail(IGX_ERR_ARG_WRONG, "IGXVecMDot: null result");
+  if (int rc = bv_block_args("IGXVecMDot", nx, X, ny, Y, &g)) return rc;
+  if (int rc = bv_state(g)) return rc;
+  LoopClock clk(g, *g->blockvec);
+  if (int rc = clk.begin(g)) return rc;
+  if (int rc = bv_mdot_run(g, nx, X, ny, Y, G)) return rc;
+  clk.own(2);
+  return bv_finish(g, clk, "vec_mdot(" + std::to_string(nx) + " x " + std::to_string(ny) + ", mfma_f64_16x16x4, " + std::to_string((nx + 15) / 16) + " x " + std::to_string((ny + 15) / 16) + " tiles, " + std::to_string(bv_mdot_grid((long long)X[0]->n)) + " slots)");
+}
+extern "C" int IGXVecMAXPY(int ny, IGXVec Y[], int nx, IGXVec X[], const double C[], double beta) {
+  IGX g = nullptr;
+  if (!C) return fail(IGX_ERR_ARG_WRONG, "IGXVecMAXPY: null coefficients");
+  if (int rc = bv_block_args("IGXVecMAXPY", nx, X, ny, Y, &g)) return rc;
+  for (int j = 0; j < ny; ++j) {
+    for (int i = 0; i < nx; ++i) if (Y[j] == X[i]) return fail(IGX_ERR_ARG_WRONG, "IGXVecMAXPY: a vector of Y is also a vector of X: every Y_j must differ from every X_i");
+    for (int k = 0; k < j; ++k) if (Y[j] == Y[k]) return fail(IGX_ERR_ARG_WRONG, "IGXVecMAXPY: a vector appears twice in Y");
+  }
+  if (int rc = bv_state(g)) return rc;
+  LoopClock clk(g, *g->blockvec);
+  if (int rc = clk.begin(g)) return rc;
+  if (int rc = bv_maxpy_run(g, ny, Y, nx, X, C, beta)) return rc;
+  clk.own(1);
+  return bv_finish(g, clk, "vec_maxpy(" + std::to_string(nx) + " -> " + std::to_string(ny) + ", one row per thread, fma in ascending order)");
 }
 
 // The two loops of IGXSolve on callables: A(in, out) is the operator, M(in, out) the preconditioner (not called where kp.pc_none says there is
@@ -636,3 +738,235 @@ extern "C" int IGXTimeStep(IGX g, const IGXTimeStepSpec *sp, IGXVec U, IGXVec V,
 // ------------------------------------------------------------------ the multigrid cycle's sweeps (multigrid.hpp)
 #include "multigrid.hpp"
 // IGXMultigrid's host side calls the transfer and so stands behind it, at the end of engine.hip; its outer loop is krylov_loop above.
+
+// ------------------------------------------------------------------ the eigen solve (LOBPCG; its sweeps: block_vec.hpp)
+// IGXEigenSolve.  The two operators are the matrix-free driver's internal entry on stiff and on mass (both on stiff's vectors: the same
+// space and layout), the preconditioners are IGXSolve's, the Gram matrices and the updates are the block-vector algebra above, the
+// Rayleigh-Ritz step is host.cpp's dense symmetric-definite solver.  The loop is the one the header states, line by line.
+struct EigenState : LoopState {
+  int m = 0, pc = -1, dof = 0, nblocks = 0;
+  std::vector<std::unique_ptr<_p_IGXVec>> pcv;           // the diagonal or the dof block columns
+};
+static const SolverWords kEigenWords = {"IGXEigenSolve", "IGXEigenSolve: the eigen solve needs one rank on every axis: its Gram matrices have no sum across ranks",
+                                        "IGXEigenSolve: the eigen solve runs where its actions and its preconditioner run, and ",
+                                        "IGXEigenSolve: the eigen solve takes its actions and its preconditioner from the matrix-free drivers, and "};
+// 0: C [q][m] and theta [m] are the m lowest pairs of the leading q x q blocks of (GA, GB), both [.][ld]; 1: GB is not positive definite
+// (or its diagonal not positive and finite); 2: an entry is not finite
+static int eig_rayleigh_ritz(int q, int m, int ld, const std::vector<double> &GA, const std::vector<double> &GB, std::vector<double> &C, std::vector<double> &theta) {
+  std::vector<double> A((size_t)q * q), B((size_t)q * q), d(q);
+  for (int i = 0; i < q; ++i) for (int j = 0; j < q; ++j) if (!std::isfinite(GA[(size_t)i * ld + j]) || !std::isfinite(GB[(size_t)i * ld + j])) return 2;
+  for (int i = 0; i < q; ++i) { const double b = GB[(size_t)i * ld + i]; if (!(b > 0.0)) return 1; d[i] = 1.0 / std::sqrt(b); }
+  for (int i = 0; i < q; ++i) for (int j = 0; j < q; ++j) {
+    A[(size_t)i * q + j] = 0.5 * (GA[(size_t)i * ld + j] + GA[(size_t)j * ld + i]) * d[i] * d[j];
+    B[(size_t)i * q + j] = 0.5 * (GB[(size_t)i * ld + j] + GB[(size_t)j * ld + i]) * d[i] * d[j];
+  }
+  FastDiagEig E; std::string err;
+  if (generalised_eigen(q, B, A, E, err)) return 1;
+  C.assign((size_t)q * m, 0.0); theta.assign(m, 0.0);
+  for (int j = 0; j < m; ++j) { theta[j] = E.lambda[j]; for (int i = 0; i < q; ++i) C[(size_t)i * m + j] = d[i] * E.U[(size_t)i + (size_t)q * j]; }
+  return 0;
+}
+extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IGXVec X[], double lambda[], double resid[], IGXEigenInfo *info, double *history) {
+  const SolverWords &words = kEigenWords;
+  if (!g || !sp || !X || !lambda || !info) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: null pointer: the eigen solve takes the stiffness IGX, a specification, the block X, lambda and info");
+  auto range = [](const char *what) { return fail(IGX_ERR_ARG_OUTOFRANGE, std::string("IGXEigenSolve: the eigen solve's specification: ") + what); };
+  if (sp->nev < 1) return range("nev must be 1 at the least");
+  if (sp->block < sp->nev || sp->block > BV_EIG_MAX) return range("block must be in range [nev,16]");
+  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return range("unknown preconditioner");
+  if (!(sp->rtol >= 0) || !(sp->atol >= 0)) return range("the tolerances must not be negative");
+  if (sp->maxit < 0) return range("maxit must not be negative");
+  if (nx != sp->block) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve takes a start block of spec->block vectors, got " + std::to_string(nx));
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() on the stiffness IGX before IGXEigenSolve(): the eigen solve needs a set-up space");
+  if (mass && !mass->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() on the mass IGX before IGXEigenSolve(): the eigen solve needs a set-up space");
+  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() on the stiffness IGX first: the eigen solve has no operator A");
+  if (mass && mass->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() on the mass IGX first: the eigen solve has no operator B");
+  bool faces[3][2][MAXFD];
+  fast_diag_fixed_faces(g->s, faces);
+  if (mass) {
+    const Space &a = g->s, &b = mass->s;
+    auto differs = [](const std::string &what) { return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve needs the mass IGX on the space of the stiffness IGX: " + what + " differs"); };
+    if (a.dim != b.dim) return differs("dim");
+    if (a.dof != b.dof) return differs("dof");
+    for (int d = 0; d < a.dim; ++d) {
+      if (a.axis[d].p != b.axis[d].p) return differs("the degree of axis " + std::to_string(d));
+      if (a.axis[d].U != b.axis[d].U) return differs("the knot vector of axis " + std::to_string(d));
+      if (a.axis[d].periodic != b.axis[d].periodic) return differs("the periodicity of axis " + std::to_string(d));
+    }
+    bool fb[3][2][MAXFD];
+    fast_diag_fixed_faces(b, fb);
+    if (memcmp(faces, fb, sizeof(fb)) != 0) return differs("the set of Dirichlet faces per field");
+    if (g->stream != mass->stream) return differs("the stream (IGXSetStream)");
+  }
+  for (IGX h : {g, mass}) if (h) for (int d = 0; d < h->s.dim; ++d) if (h->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, words.one_rank);
+  for (IGX h : {g, mass}) if (h && h->fixtable.p) return fail(IGX_ERR_SUP, "IGXEigenSolve: the eigen solve does not cover a fix table (IGXSetFixTable): its fixed rows are not a union of faces");
+  const int m = sp->block, pc = sp->pc;
+  for (int j = 0; j < m; ++j) {
+    if (!X[j]) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a null vector");
+    if (X[j]->iga != g) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a vector created by another IGX than the stiffness IGX");
+    for (int k = 0; k < j; ++k) if (X[k] == X[j]) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a vector twice");
+  }
+  if (pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() on the stiffness IGX before IGXEigenSolve() with IGX_PC_FASTDIAG");
+  for (IGX h : {g, mass}) if (h) if (int rc = solver_runs_here(h, words)) return rc;
+  if (int rc = ensure_device(g)) return rc;
+  if (mass) if (int rc = ensure_device(mass)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  for (int j = 0; j < m; ++j) if (X[j]->n != n) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: vector of another size than the space's");
+  if (mass && (long long)mass->nbrows * mass->s.dof != n) return fail(IGX_ERR_PLIB, "IGXEigenSolve: the row boxes of the two IGX differ");
+  if (int rc = bv_state(g)) return rc;
+  const int dof = g->s.dof;
+  // work vectors, in blocks of m: X' ; AX AX' ; W AW ; P P' AP AP' ; with a preconditioner R ; with a mass BX BX' BW BP BP'
+  const int nblocks = 9 + (pc != IGX_PC_NONE ? 1 : 0) + (mass ? 5 : 0);
+  if (!g->eigen || g->eigen->m != m || g->eigen->pc != pc || g->eigen->dof != dof || g->eigen->n != n || g->eigen->nblocks != nblocks) {
+    g->eigen.reset();
+    std::shared_ptr<EigenState> es(new EigenState());
+    if (int rc = es->ensure(g, n, nblocks * m, "device allocation of the eigen solve's work vectors failed")) return rc;
+    if (int rc = add_vecs(g, n, pc == IGX_PC_JACOBI ? 1 : pc == IGX_PC_PBJACOBI ? dof : 0, es->pcv, "device allocation of the eigen solve's preconditioner failed")) return rc;
+    es->m = m; es->pc = pc; es->dof = dof; es->nblocks = nblocks;
+    g->eigen = es;
+  }
+  EigenState &st = *g->eigen;
+  BlockVecState &bv = *g->blockvec;
+  typedef std::vector<IGXVec> Block;
+  int next_block = 0;
+  auto block = [&]() { Block b(m); for (int j = 0; j < m; ++j) b[j] = st.work[(size_t)next_block * m + j].get(); ++next_block; return b; };
+  Block Xb[2] = {Block(X, X + m), block()}, AX[2] = {block(), block()}, W = block(), AW = block(), P[2] = {block(), block()}, AP[2] = {block(), block()};
+  Block R = pc != IGX_PC_NONE ? block() : W;
+  Block BX[2] = {Xb[0], Xb[1]}, BW = W, BP[2] = {P[0], P[1]};
+  if (mass) { BX[0] = block(); BX[1] = block(); BW = block(); BP[0] = block(); BP[1] = block(); }
+  LoopClock clk(g, st);
+  if (int rc = clk.begin(g)) return rc;
+  g->slab_valid = 0;
+  std::string opname;
+  int actions = 0;
+  auto actA = [&](IGXVec in, IGXVec out) -> int {
+    if (int rc = compute_matfree(g, OP_MATRIX_ACTION, nullptr, nullptr, in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
+    if (opname.empty()) opname = g->last_kernel;
+    ++actions;
+    return clk.driver(g);
+  };
+  auto actB = [&](IGXVec in, IGXVec out) -> int {      // the mass IGX's figures: its own launches and, where it is timed too, its own events
+    if (int rc = compute_matfree(mass, OP_MATRIX_ACTION, nullptr, nullptr, in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
+    ++actions;
+    clk.launches += mass->last_launches;
+    if (clk.timing && mass->timing) { float ms = 0; HIPCK(hipEventSynchronize(mass->ev[2])); HIPCK(hipEventElapsedTime(&ms, mass->ev[1], mass->ev[2])); clk.op_ms += ms; }
+    return 0;
+  };
+  auto act_block = [&](const Block &in, const Block &aout, const Block &bout) -> int {
+    for (int j = 0; j < m; ++j) if (int rc = actA(in[j], aout[j])) return rc;
+    if (mass) for (int j = 0; j < m; ++j) if (int rc = actB(in[j], bout[j])) return rc;
+    return 0;
+  };
+  auto mdot = [&](Block &S, Block &T, std::vector<double> &G) -> int { clk.own(2); return bv_mdot_run(g, (int)S.size(), S.data(), (int)T.size(), T.data(), G.data()); };
+  auto maxpy = [&](Block &Y, Block &S, const double *C) -> int { clk.own(1); return bv_maxpy_run(g, (int)Y.size(), Y.data(), (int)S.size(), S.data(), C, 0.0); };
+  auto join = [](std::initializer_list<const Block *> parts) { Block b; for (const Block *p : parts) b.insert(b.end(), p->begin(), p->end()); return b; };
+  // the fixed rows of the start block
+  {
+    MgFaces F; memset(&F, 0, sizeof(F));
+    long long nodes = 1, face_nodes = 0;
+    F.dof = dof;
+    for (int d = 0; d < 3; ++d) { F.n[d] = d < g->s.dim ? g->s.lay[d].nrow : 1; nodes *= F.n[d]; }
+    for (int d = 0; d < g->s.dim; ++d) for (int sd = 0; sd < 2; ++sd) {
+      unsigned mask = 0;
+      for (int f = 0; f < dof; ++f) if (faces[d][sd][f]) mask |= 1u << f;
+      if (!mask) continue;
+      F.axis[F.nface] = d; F.at[F.nface] = sd ? F.n[d] - 1 : 0; F.mask[F.nface] = mask; ++F.nface;
+      face_nodes = std::max(face_nodes, nodes / F.n[d]);
+    }
+    if (nodes * dof != n) return fail(IGX_ERR_PLIB, "IGXEigenSolve: the eigen solve's vectors and the row box differ");
+    if (F.nface) for (int j = 0; j < m; ++j) {
+      hipLaunchKernelGGL(mg_zero_fixed, dim3((unsigned)std::min<long long>(256, (face_nodes + MG_FACE_T - 1) / MG_FACE_T), (unsigned)F.nface), dim3(MG_FACE_T), 0, g->stream, X[j]->a.as<double>(), F);
+      if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "mg_zero_fixed: kernel launch failed");
+      clk.own(1);
+    }
+  }
+  // the preconditioner T of stiff: its diagonal, or its inverted point blocks
+  std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
+  if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
+    if (int rc = compute_matfree(g, pc == IGX_PC_JACOBI ? OP_MATRIX_DIAGONAL : OP_MATRIX_BLOCK_DIAGONAL, nullptr, nullptr, nullptr, (int)cols.size(), cols.data(), 0.0, 0.0)) return solver_refused(words, rc);
+    if (int rc = clk.driver(g)) return rc;
+  }
+  if (pc == IGX_PC_PBJACOBI) {
+    if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return solver_refused(words, rc);
+    if (int rc = clk.driver(g)) return rc;
+  }
+  auto T = [&](IGXVec in, IGXVec out) -> int {
+    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); clk.own(1); return 0; }
+    if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return solver_refused(words, rc);
+    return clk.driver(g);
+  };
+  int c = 0, its = 0, reason = 0, restarts = 0, nconv = 0;
+  bool haveP = false;
+  std::vector<double> GA((size_t)9 * m * m), GB((size_t)9 * m * m), C, theta(m, 0.0), rec((size_t)2 * m, 0.0), rn(m, 0.0);
+  std::vector<double> CX((size_t)2 * m * m);
+  // 0. Rayleigh-Ritz on the start block
+  if (int rc = act_block(Xb[0], AX[0], BX[0])) return rc;
+  if (int rc = mdot(Xb[0], AX[0], GA)) return rc;
+  if (int rc = mdot(Xb[0], BX[0], GB)) return rc;
+  if (const int bad = eig_rayleigh_ritz(m, m, m, GA, GB, C, theta)) reason = bad == 2 ? IGX_EIGEN_DIVERGED_NAN : IGX_EIGEN_DIVERGED_BREAKDOWN;
+  else {
+    if (int rc = maxpy(Xb[1], Xb[0], C.data())) return rc;
+    if (int rc = maxpy(AX[1], AX[0], C.data())) return rc;
+    if (mass) if (int rc = maxpy(BX[1], BX[0], C.data())) return rc;
+    c = 1;
+  }
+  while (!reason) {
+    // 1. the residuals of the block and the norms, one record
+    BvEigCols rc_, ac_, bc_; BvTheta th;
+    memset(&rc_, 0, sizeof(rc_)); memset(&ac_, 0, sizeof(ac_)); memset(&bc_, 0, sizeof(bc_)); memset(&th, 0, sizeof(th));
+    for (int j = 0; j < m; ++j) { rc_.p[j] = R[j]->a.as<double>(); ac_.p[j] = AX[c][j]->a.as<double>(); bc_.p[j] = BX[c][j]->a.as<double>(); th.v[j] = theta[j]; }
+    KR_LAUNCH(bv_resid, KR_G, KR_T, g, rc_, ac_, bc_, th, m, n, bv.rslab.as<double>());
+    KR_LAUNCH(bv_record, 1, 64, g, bv.rslab.as<double>(), 2 * m, bv.rrec.as<double>());
+    clk.own(2);
+    HIPCK(hipMemcpyAsync(rec.data(), bv.rrec.p, (size_t)2 * m * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIPCK(hipStreamSynchronize(g->stream));
+    // 2. the stop test
+    bool nan = false;
+    nconv = 0;
+    for (int j = 0; j < m; ++j) {
+      rn[j] = std::sqrt(rec[2 * j]);
+      if (history) history[(size_t)its * m + j] = rn[j];
+      if (std::isnan(rn[j])) nan = true;
+      if (j < sp->nev && rn[j] <= std::max(sp->rtol * std::sqrt(rec[2 * j + 1]), sp->atol)) ++nconv;
+    }
+    if (nan) { reason = IGX_EIGEN_DIVERGED_NAN; break; }
+    if (nconv == sp->nev) { reason = IGX_EIGEN_CONVERGED; break; }
+    if (its >= sp->maxit) { reason = IGX_EIGEN_DIVERGED_ITS; break; }
+    // 3. W = T R (no preconditioner: R is W)
+    if (pc != IGX_PC_NONE) for (int j = 0; j < m; ++j) if (int rc = T(R[j], W[j])) return rc;
+    // 4. the actions on W
+    if (int rc = act_block(W, AW, BW)) return rc;
+    // 5. the two Gram matrices of S = [X W P]
+    Block S = haveP ? join({&Xb[c], &W, &P[c]}) : join({&Xb[c], &W});
+    Block AS = haveP ? join({&AX[c], &AW, &AP[c]}) : join({&AX[c], &AW});
+    Block BS = haveP ? join({&BX[c], &BW, &BP[c]}) : join({&BX[c], &BW});
+    int q = (int)S.size();
+    if (int rc = mdot(S, AS, GA)) return rc;
+    if (int rc = mdot(S, BS, GB)) return rc;
+    // 6. Rayleigh-Ritz; without a positive definite G_B: once more without P
+    const int ld = q;
+    int bad = eig_rayleigh_ritz(q, m, ld, GA, GB, C, theta);
+    if (bad == 1 && haveP) { haveP = false; ++restarts; q = 2 * m; bad = eig_rayleigh_ritz(q, m, ld, GA, GB, C, theta); }
+    if (bad) { reason = bad == 2 ? IGX_EIGEN_DIVERGED_NAN : IGX_EIGEN_DIVERGED_BREAKDOWN; break; }
+    // 7. P' = [W P] C_WP, X' = X C_X + P', and the same for A. and B.
+    for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) { CX[(size_t)i * m + j] = C[(size_t)i * m + j]; CX[(size_t)(m + i) * m + j] = i == j ? 1.0 : 0.0; }
+    const double *CWP = C.data() + (size_t)m * m;
+    Block WP = haveP ? join({&W, &P[c]}) : W, AWP = haveP ? join({&AW, &AP[c]}) : AW, BWP = haveP ? join({&BW, &BP[c]}) : BW;
+    Block XP = join({&Xb[c], &P[1 - c]}), AXP = join({&AX[c], &AP[1 - c]}), BXP = join({&BX[c], &BP[1 - c]});
+    if (int rc = maxpy(P[1 - c], WP, CWP)) return rc;
+    if (int rc = maxpy(Xb[1 - c], XP, CX.data())) return rc;
+    if (int rc = maxpy(AP[1 - c], AWP, CWP)) return rc;
+    if (int rc = maxpy(AX[1 - c], AXP, CX.data())) return rc;
+    if (mass) {
+      if (int rc = maxpy(BP[1 - c], BWP, CWP)) return rc;
+      if (int rc = maxpy(BX[1 - c], BXP, CX.data())) return rc;
+    }
+    c = 1 - c; haveP = true; ++its;
+  }
+  // the caller's block receives the last iterate
+  if (c == 1) for (int j = 0; j < m; ++j) HIPCK(hipMemcpyAsync(X[j]->a.p, Xb[1][j]->a.p, X[j]->a.bytes, hipMemcpyDeviceToDevice, g->stream));
+  HIPCK(hipStreamSynchronize(g->stream));
+  for (int j = 0; j < m; ++j) { lambda[j] = theta[j]; if (resid) resid[j] = rn[j]; }
+  info->iterations = its; info->reason = reason; info->nconverged = nconv; info->restarts = restarts; info->actions = actions;
+  static const char *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
+  return clk.finish(g, "eigen(lobpcg, block " + std::to_string(m) + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)");
+}
