@@ -11,11 +11,17 @@
 // entries for MX MY elements: 745 entries per element at 4 x 2 instead of 1792, and 6 colours instead of 16.
 //
 // The element phase is the pencil walk's: pencil_sf_planes once per pencil, then 2 x 4 v_fma_f64 per tile on the staged walk-axis Gram
-// sums.  Bit-repeatable like every walk but gram_patch_p2: an element step is split into ten sub-phases between barriers; in sub-phase
-// k wavefront w adds its tile (k + w) mod 10, so no two wavefronts touch one block at once and every window entry takes its adds in a
-// fixed order.  Within a sub-phase a block belongs to one wavefront and an entry to one lane, so the add is a plain LDS read, add and
-// write, not an atomic (round 10: the stamps put nearly half of a step in the sub-phases, each one LDS round trip after another between
-// two barriers; ds_add_f64 was the longest of them, the read of the tile's Gram sums another -- those are read ahead of the sub-phases).
+// sums.  A tile (ta, tb) of element e belongs to block (e + ta, e + tb), and every tile of a pencil uses the same planes and the same
+// window offsets, so a pencil's part of a block is summed over its 4 - d elements in REGISTERS (round 11): a wavefront keeps the ten
+// blocks of its four open rows, adds element e's tiles to them (rows e .. e + 3), and row e is then complete: its four blocks go to the
+// window once, in eight TICKS between barriers -- in tick k wavefront w adds block d = (k + w) mod 8, if d <= 3 -- and the rows slide.
+// 32 LDS instructions and 8 barriers per wavefront and step, where adding every tile to the window took 80 and 10 (round 10 had
+// stamped nearly half of a step there).  Every element is still formed from its own Gauss-point data, and the walk-axis Gram sums are
+// not summed across elements before the product: only where the partial sums wait has changed.  Bit-repeatable like every walk but
+// gram_patch_p2: between two barriers a block belongs to one wavefront and an entry to one lane (a plain LDS read, add and write, no
+// atomic), and an entry takes its adds in the order of the ticks (Patch3Ticks and its static_asserts).  Behind the last element of the
+// last segment three rows are complete in registers only: one more round of the ticks adds all three to the window before the
+// trailing layers leave.  Other segments drop theirs: the next segment's halo forms them again.
 // The F stage and the lifting of the Dirichlet rows are summed in a fixed order too (per-run liftings in LDS, gathered
 // per node).  Every thread owns RUNS runs for the whole walk; their old values are requested a step ahead and consumed behind the
 // barrier that completes the layer.
@@ -35,7 +41,31 @@ template <int MX, int MY> struct Patch3 : PatchShape<3, MX, MY> {
   static_assert(G::NXP == 7 * MX + 9 && G::NYP == 7 * MY + 9 && G::SX == (MX >= 3 ? 2 : 3) && G::SY == (MY >= 3 ? 2 : 3), "the patch at p = 3");
   static_assert(G::W <= 10, "at most one wavefront per tile of the element");
   static_assert(G::NODES <= 64 * G::W, "one thread per F row of the patch");
+  // the ticks of a step: in tick k wavefront w adds block d = (k + w) mod TICKS of its completed row to the window, if d <= 3
+  static constexpr int TICKS = G::W < 4 ? 4 : G::W;
+  static constexpr int tick_block(int k, int w) { return (k + w) % TICKS < 4 ? (k + w) % TICKS : -1; }
 };
+// the table (tick, wavefront) -> block of the row, and what makes the walk bit-repeatable: every wavefront adds each of its four blocks
+// once in a step, and no two wavefronts add to one block between two barriers (a window entry takes its adds in the order of the ticks)
+template <class G> struct Patch3Ticks { int d[G::TICKS][G::W]; };
+template <class G> constexpr Patch3Ticks<G> patch3_ticks() {
+  Patch3Ticks<G> t{};
+  for (int k = 0; k < G::TICKS; ++k) for (int w = 0; w < G::W; ++w) t.d[k][w] = G::tick_block(k, w);
+  return t;
+}
+template <class G> constexpr bool patch3_ticks_once_each(const Patch3Ticks<G> t) {
+  for (int w = 0; w < G::W; ++w) for (int d = 0; d < 4; ++d) {
+    int n = 0;
+    for (int k = 0; k < G::TICKS; ++k) n += t.d[k][w] == d;
+    if (n != 1) return false;
+  }
+  return true;
+}
+template <class G> constexpr bool patch3_ticks_one_owner(const Patch3Ticks<G> t) {
+  for (int k = 0; k < G::TICKS; ++k) for (int w = 0; w < G::W; ++w) for (int v = w + 1; v < G::W; ++v)
+    if (t.d[k][w] >= 0 && t.d[k][w] == t.d[k][v]) return false;
+  return true;
+}
 
 // LDS behind the walk's tables: the window, the per-run liftings of two layers, the F stage of two layers, the pair tables (ints)
 template <int MX, int MY>
@@ -50,8 +80,12 @@ __global__ void __launch_bounds__(MX * MY * 64, 1)
 gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
   using G = Patch3<MX, MY>;
   constexpr int P = G::P, NB = 4, BW = G::BW, W = G::W, NX = G::NX, NY = G::NY, BLK = G::BLK, NTHR = W * 64;
+  static_assert(patch3_ticks_once_each<G>(patch3_ticks<G>()), "a wavefront adds each block of its completed row once in a step");
+  static_assert(patch3_ticks_one_owner<G>(patch3_ticks<G>()), "one wavefront per window block between two barriers");
   extern __shared__ __attribute__((aligned(16))) double pencil_sm[];
   const PencilArgs &pa = A.pa;
+  const bool stamped = kDebug && pa.debug_buf;
+  const long long st_wall0 = stamped ? wall_clock64() : 0;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const PatchWalk D = patch_decode<G>(S, A, wave);
@@ -167,11 +201,10 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
       patch_run_load<BW>(out.val, r.base, p0, full, (ucode[j] >> 16) & 1, r.o);
     }
   };
-  long long st[4] = {0, 0, 0, 0}, st_t = 0;      // -DIGX_DEBUG: cycles of [sub-phases | wait for the old values | leave's window and stores, the next loads | closing barrier + F]
-  const bool stamped = kDebug && pa.debug_buf;
+  long long st[5] = {0, 0, 0, 0, 0}, st_t = 0;      // -DIGX_DEBUG: cycles of [products | ticks | wait for the old values | leave's window and stores, the next loads | closing barrier + F]
   auto stamp = [&](int k) { if (stamped) { const long long t = __builtin_readcyclecounter(); st[k] += t - st_t; st_t = t; } };
   auto leave = [&](int li, const Run (&rr)[G::RUNS]) {
-    if (stamped) { __builtin_amdgcn_s_waitcnt(0x0F70); stamp(1); }      // (stamped launch only: the wait for the old values, at the top of leave)
+    if (stamped) { __builtin_amdgcn_s_waitcnt(0x0F70); stamp(2); }      // (stamped launch only: the wait for the old values, at the top of leave)
     const int c0 = li & 3;
     const bool bcl = SYSTEM && ron && fx.reaches(T.lay0 + li);
 #pragma unroll
@@ -245,56 +278,100 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
     }
   };
 
+  // ---- the pencil's open band rows: acc[i][d][r] = this lane's four entries of block (ei + i, ei + i + d), d = 0 .. 3 - i, summed over
+  // the elements walked so far.  Row ei is complete once element ei is in: its four blocks go to the window in the ticks, the rows slide.
+  double acc[4][4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[i][d][r] = 0.0;
+  auto products = [&](int ei) {      // element ei's ten tiles (ta, tb), ta <= tb, into rows ei + ta: 2 x 4 v_fma_f64 each
+    if (!valid) return;
+    const double *g = T.zt + ei * 32;
+#pragma unroll
+    for (int ta = 0; ta < 4; ++ta)
+#pragma unroll
+      for (int tb = ta; tb < 4; ++tb) {
+        const double g0 = g[(ta * 4 + tb) * 2 + 0], g1 = g[(ta * 4 + tb) * 2 + 1];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[ta][tb - ta][r] = __builtin_fma(g0, mxy[r], __builtin_fma(g1, mw[r], acc[ta][tb - ta][r]));
+      }
+  };
+  // the ticks of row li: in tick k wavefront w adds its block d = tick_block(k, w) of the row to window block (li, li + d).  One
+  // wavefront per block between two barriers, an entry of it one lane's: a plain read, add and write.  Then the rows slide.
+  auto tick_add = [&](double *blk, const double (&a)[4]) {
+    double w[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w[r] = blk[woff[r]];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) blk[woff[r]] = w[r] + a[r];
+  };
+  auto window_block = [&](int r, int d) { return win + (((r + d) & 3) * 4 + d) * BLK; };      // block (r, r + d)
+  auto ticks = [&](int li) {
+#pragma unroll
+    for (int k = 0; k < G::TICKS; ++k) {
+      const int d = G::tick_block(k, wave);      // (wave-uniform: branches, not a register index)
+      if (valid && d >= 0) {
+        double *blk = window_block(li, d);
+        if (d == 0) tick_add(blk, acc[0][0]);
+        else if (d == 1) tick_add(blk, acc[0][1]);
+        else if (d == 2) tick_add(blk, acc[0][2]);
+        else tick_add(blk, acc[0][3]);
+      }
+      if (SYSTEM && k == 0) {      // F_a += f J prod_d sum_q w N: the walk-axis factor was staged with the Gram sums
+        Facc += sxy * T.wq[li * 4 + fslot];
+        f_stage(li);
+      }
+      __syncthreads();      // (the last one: every wavefront's row li is in the window, layer li is complete, its F sums are staged)
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {      // row li + 1 + i takes the place of row li + i; its last block and the new last row start at zero
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int d = 0; d < 3 - i; ++d) acc[i][d][r] = acc[i + 1][d][r];
+        acc[i][3 - i][r] = 0.0;
+      }
+      acc[3][0][r] = 0.0;
+    }
+  };
+
   Run run[G::RUNS];
   long long tk0 = 0, tw0 = 0;
   if (out.clk) { tk0 = __builtin_readcyclecounter(); tw0 = wall_clock64(); }
+  const long long st_wall1 = stamped ? wall_clock64() : 0;
   fetch(0, run);
   for (int ei = 0; ei < ne; ++ei) {
     if (stamped) st_t = __builtin_readcyclecounter();
-    const double *g = T.zt + ei * 32;
-    // this wavefront's Gram sums of the step's ten tiles, read ahead of the sub-phases: one LDS round trip for the ten, not one in each
-    // sub-phase (the table is not written during the walk)
-    double gk[10][2];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-      const int t = k + wave >= 10 ? k + wave - 10 : k + wave;
-      const int ta = (int)((0x3221110000ull >> (4 * t)) & 15), tb = (int)((0x3323213210ull >> (4 * t)) & 15);
-      gk[k][0] = g[(ta * 4 + tb) * 2 + 0]; gk[k][1] = g[(ta * 4 + tb) * 2 + 1];
-    }
-    // ten sub-phases: in sub-phase k wavefront w adds tile t = (k + w) mod 10 = (ta, tb), ta <= tb, of its element to block (ei + ta, ei + tb)
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-      if (valid) {
-        const int t = k + wave >= 10 ? k + wave - 10 : k + wave;
-        const int ta = (int)((0x3221110000ull >> (4 * t)) & 15), tb = (int)((0x3323213210ull >> (4 * t)) & 15);
-        double *blk = win + (((ei + tb) & 3) * 4 + (tb - ta)) * BLK;
-        const double g0 = gk[k][0], g1 = gk[k][1];
-        // (a plain read, add and write: no other wavefront touches this block before the barrier, and a lane's four entries are its own)
-        double w[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) w[r] = blk[woff[r]];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) blk[woff[r]] = w[r] + __builtin_fma(g0, mxy[r], g1 * mw[r]);
-      }
-      if (SYSTEM && k == 0) {      // F_a += f J prod_d sum_q w N: the walk-axis factor was staged with the Gram sums
-        Facc += sxy * T.wq[ei * 4 + fslot];
-        f_stage(ei);
-      }
-      __syncthreads();      // (the last one: every wavefront's element ei is in the window, layer ei is complete, its F sums are staged)
-    }
+    products(ei);
     stamp(0);
+    ticks(ei);
+    stamp(1);
     leave(ei, run);
     fetch(ei + 1, run);
-    stamp(2);
+    stamp(3);
     __syncthreads();      // the slots of column layer ei are zero again; the liftings of layer ei are staged
     leave_f(ei);
-    stamp(3);
+    stamp(4);
   }
-  if (stamped && lane == 0) {      // -DIGX_DEBUG: per wavefront, the four parts of a step summed over the walk, and its elements
-    long long *d = pa.debug_buf + ((size_t)blockIdx.x * W + wave) * 5;
-    d[0] = st[0]; d[1] = st[1]; d[2] = st[2]; d[3] = st[3]; d[4] = ne;
-  }
-  if (seg == pa.nseg - 1 && !pa.open_hi)      // the last segment owns the layers beyond its last element too
+  const long long st_wall2 = stamped ? wall_clock64() : 0;
+  if (seg == pa.nseg - 1 && !pa.open_hi) {
+    // the last segment owns the layers beyond its last element too (other segments drop theirs: the next one's halo forms them again).
+    // Their rows ne .. ne + 2 are complete in registers: acc[i][d], d <= 2 - i (there is no column layer ne + 3).  One round of the
+    // ticks adds all three to the window -- blocks (ne + i, ne + i + d), whose slots the layers up to ne - 1 have left -- in tick k
+    // wavefront w the blocks d of every row; then the layers leave as they always did.
+#pragma unroll
+    for (int k = 0; k < G::TICKS; ++k) {
+      const int d = G::tick_block(k, wave);
+      if (valid && d >= 0) {
+        if (d == 0) { tick_add(window_block(ne, 0), acc[0][0]); tick_add(window_block(ne + 1, 0), acc[1][0]); tick_add(window_block(ne + 2, 0), acc[2][0]); }
+        else if (d == 1) { tick_add(window_block(ne, 1), acc[0][1]); tick_add(window_block(ne + 1, 1), acc[1][1]); }
+        else if (d == 2) tick_add(window_block(ne, 2), acc[0][2]);
+      }
+      __syncthreads();
+    }
     for (int li = ne; li < nl; ++li) {
       f_stage(li);
       leave(li, run);
@@ -303,6 +380,15 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
       leave_f(li);
       __syncthreads();
     }
+  }
+  if (stamped && lane == 0) {
+    // -DIGX_DEBUG: per wavefront, the five parts of a step summed over the walk, its elements, and on the 100 MHz clock the set-up before
+    // the walk and the trailing layers behind it; behind them the workgroup's record {entry, exit, HW_ID, XCC_ID}
+    long long *d = pa.debug_buf + ((size_t)blockIdx.x * W + wave) * 8;
+    const long long st_wall3 = wall_clock64();
+    d[0] = st[0]; d[1] = st[1]; d[2] = st[2]; d[3] = st[3]; d[4] = st[4]; d[5] = ne; d[6] = st_wall1 - st_wall0; d[7] = st_wall3 - st_wall2;
+    if (wave == 0) { long long *w = pa.debug_buf + (size_t)gridDim.x * W * 8 + (size_t)blockIdx.x * 4; w[0] = st_wall0; w[1] = st_wall3; w[2] = __builtin_amdgcn_s_getreg((16 - 1) << 11 | 4); w[3] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20); }
+  }
   if (out.clk && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && tid == 0) {
     // IGX_CLOCK_PROBE: s_memtime against the 100 MHz s_memrealtime over the walk, first and last workgroup of every launch (as gram_pencil_body)
     atomicAdd(reinterpret_cast<unsigned long long *>(out.clk), (unsigned long long)(__builtin_readcyclecounter() - tk0));

@@ -1,7 +1,7 @@
 // pencil_stamps.hpp -- the cycle-stamp reports of the Gram walks (-DIGX_DEBUG, IGX_DEBUG_TIMING=n: the n-th launch of a launcher is the
 // one that is stamped; diagnostic only).  The launchers (pencil_launch.hpp) ask a StampGate whether this launch is due, hand the kernel a
-// zeroed buffer, and pass what it wrote to the report of their walk.  The per-CU timeline is gathered once, for the pencil walk and for
-// the p = 2 patch walk.
+// zeroed buffer, and pass what it wrote to the report of their walk.  The per-CU timeline is gathered and summed up once, for the pencil walk and
+// the two patch walks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -51,6 +51,47 @@ static inline CuTimeline cu_timeline(const long long *wr, size_t nwg) {
   return T;
 }
 
+// where the time between the first entry and the last exit goes: per CU the workgroups in the order they ran, how late the first
+// one starts (dispatch ramp), the gap between one workgroup's exit and the next one's entry, the tail after its last exit
+static void report_cu_timeline(const char *tag, CuTimeline &T) {
+  if (!T.any()) return;
+  const long long t0 = T.t0, t1 = T.t1;
+  const double span = (double)(t1 - t0);
+  double busy = 0, ramp = 0, gap = 0, tail = 0, life1 = 0, life2 = 0, ramp_max = 0; long long n1 = 0, n2 = 0, ngap = 0; int rounds_max = 0;
+  for (auto &kv : T.cu) {
+    auto &v = kv.second; std::sort(v.begin(), v.end());
+    ramp += (double)(v.front().first - t0); ramp_max = std::max(ramp_max, (double)(v.front().first - t0));
+    tail += (double)(t1 - v.back().second);
+    rounds_max = std::max(rounds_max, (int)v.size());
+    for (size_t i = 0; i < v.size(); ++i) {
+      busy += (double)(v[i].second - v[i].first);
+      if (i == 0) { life1 += (double)(v[i].second - v[i].first); n1++; } else { life2 += (double)(v[i].second - v[i].first); n2++; gap += (double)(v[i].first - v[i - 1].second); ngap++; }
+    }
+  }
+  const double ncu = (double)T.cu.size();
+  fprintf(stderr, "%s   timeline (100 MHz ticks = 10 ns): span %.0f = %.1f us over %d CUs that ran a workgroup, at most %d workgroups on one CU\n", tag, span, span * 0.01, (int)T.cu.size(), rounds_max);
+  fprintf(stderr, "%s   per CU, mean ticks: first entry after the launch's first %.0f (max %.0f) | busy %.0f | between workgroups %.1f (x %.2f per CU) | idle after its last exit %.0f\n",
+          tag, ramp / ncu, ramp_max, busy / ncu, ngap ? gap / ngap : 0.0, (double)ngap / ncu, tail / ncu);
+  fprintf(stderr, "%s   workgroup life, ticks: first on its CU %.0f (%lld) | later ones %.0f (%lld); CU-time in a workgroup's life %.3f of span x CUs (x %.3f of 256 CUs)\n",
+          tag, n1 ? life1 / n1 : 0.0, n1, n2 ? life2 / n2 : 0.0, n2, busy / (span * ncu), busy / (span * 256.0));
+  // ... and per XCC (the key's bits 12-15): its CUs and workgroups, the mean and the extremes of a workgroup's life, when its CUs
+  // leave their last workgroup as a share of the span -- a launch waits for its slowest XCC
+  struct Xcc { int cus = 0; long long n = 0; double life = 0, lmin = 1e30, lmax = 0, last = 0, last_min = 1e30, last_max = 0; };
+  std::map<long long, Xcc> xc;
+  for (auto &kv : T.cu) {
+    Xcc &x = xc[kv.first >> 12];
+    x.cus++;
+    for (auto &iv : kv.second) { const double l = (double)(iv.second - iv.first); x.n++; x.life += l; x.lmin = std::min(x.lmin, l); x.lmax = std::max(x.lmax, l); }
+    const double e = (double)(kv.second.back().second - t0) / span;
+    x.last += e; x.last_min = std::min(x.last_min, e); x.last_max = std::max(x.last_max, e);
+  }
+  for (auto &kv : xc) {
+    const Xcc &x = kv.second;
+    fprintf(stderr, "%s   XCC %lld: %d CUs, %lld workgroups, life mean %.0f (min %.0f, max %.0f) ticks; last exit of a CU at %.3f of the span (min %.3f, max %.3f)\n",
+            tag, kv.first, x.cus, x.n, x.life / x.n, x.lmin, x.lmax, x.last / x.cus, x.last_min, x.last_max);
+  }
+}
+
 // gram_pencil_body's stamps: [workgroup][2 waves][64 entries][4] phase stamps, then the workgroups' records
 static inline size_t pencil_stamp_count(const PencilArgs &pa) { const size_t nwg = (size_t)pa.blocks_per_seg * pa.nseg; return nwg * 2 * 64 * 4 + nwg * 4; }
 static void report_pencil_stamps(const std::vector<long long> &h, const PencilArgs &pa) {
@@ -85,29 +126,8 @@ static void report_pencil_stamps(const std::vector<long long> &h, const PencilAr
       if (n2) fprintf(stderr, "[igx pencil timing]   segment %d: %lld workgroups, life min %.0f mean %.0f max %.0f\n", sg, n2, mn, sm2 / n2, mx);
     }
   }
-  // where the time between the first entry and the last exit goes: per CU the workgroups in the order they ran, how late the first
-  // one starts (dispatch ramp), the gap between one workgroup's exit and the next one's entry, the tail after its last exit
   CuTimeline T = cu_timeline(&h[dbg_blocks * 2 * 64 * 4], dbg_blocks);
-  if (!T.any()) return;
-  const long long t0 = T.t0, t1 = T.t1;
-  const double span = (double)(t1 - t0);
-  double busy = 0, ramp = 0, gap = 0, tail = 0, life1 = 0, life2 = 0, ramp_max = 0; long long n1 = 0, n2 = 0, ngap = 0; int rounds_max = 0;
-  for (auto &kv : T.cu) {
-    auto &v = kv.second; std::sort(v.begin(), v.end());
-    ramp += (double)(v.front().first - t0); ramp_max = std::max(ramp_max, (double)(v.front().first - t0));
-    tail += (double)(t1 - v.back().second);
-    rounds_max = std::max(rounds_max, (int)v.size());
-    for (size_t i = 0; i < v.size(); ++i) {
-      busy += (double)(v[i].second - v[i].first);
-      if (i == 0) { life1 += (double)(v[i].second - v[i].first); n1++; } else { life2 += (double)(v[i].second - v[i].first); n2++; gap += (double)(v[i].first - v[i - 1].second); ngap++; }
-    }
-  }
-  const double ncu = (double)T.cu.size();
-  fprintf(stderr, "[igx pencil timing]   timeline (100 MHz ticks = 10 ns): span %.0f = %.1f us over %d CUs that ran a workgroup, at most %d workgroups on one CU\n", span, span * 0.01, (int)T.cu.size(), rounds_max);
-  fprintf(stderr, "[igx pencil timing]   per CU, mean ticks: first entry after the launch's first %.0f (max %.0f) | busy %.0f | between workgroups %.1f (x %.2f per CU) | idle after its last exit %.0f\n",
-          ramp / ncu, ramp_max, busy / ncu, ngap ? gap / ngap : 0.0, (double)ngap / ncu, tail / ncu);
-  fprintf(stderr, "[igx pencil timing]   workgroup life, ticks: first on its CU %.0f (%lld) | later ones %.0f (%lld); CU-time in a workgroup's life %.3f of span x CUs (x %.3f of 256 CUs)\n",
-          n1 ? life1 / n1 : 0.0, n1, n2 ? life2 / n2 : 0.0, n2, busy / (span * ncu), busy / (span * 256.0));
+  report_cu_timeline("[igx pencil timing]", T);
 }
 
 // gram_patch_p2's stamps: [workgroup][W wavefronts][4] = cycles in three phases and the elements walked, then the workgroups' records
@@ -133,19 +153,30 @@ static void report_patch2_stamps(const std::vector<long long> &h, const PencilAr
           (T.t1 - T.t0) * 0.01, (int)T.cu.size(), rmax, busy / ((double)(T.t1 - T.t0) * 256.0));
 }
 
-// gram_pencil_patch3's stamps: [workgroup][W wavefronts][5] = cycles in four phases and the element steps
-static inline size_t patch3_stamp_count(const PencilArgs &pa, int W) { return (size_t)pa.blocks_per_seg * pa.nseg * W * 5; }
+// gram_pencil_patch3's stamps: [workgroup][W wavefronts][8] = cycles in five parts of a step, the element steps, and on the 100 MHz clock
+// the set-up before the walk and the trailing layers behind it; then the workgroups' records
+static inline size_t patch3_stamp_count(const PencilArgs &pa, int W) { const size_t nwg = (size_t)pa.blocks_per_seg * pa.nseg; return nwg * W * 8 + nwg * 4; }
 static void report_patch3_stamps(const std::vector<long long> &h, const PencilArgs &pa, int W, int cx, int cy) {
   const size_t nwg = (size_t)pa.blocks_per_seg * pa.nseg;
-  double sm[4] = {0, 0, 0, 0}, mx[4] = {0, 0, 0, 0}; long long cnt = 0;
+  double sm[5] = {0, 0, 0, 0, 0}, mx[5] = {0, 0, 0, 0, 0}, steps = 0, setup = 0, trail = 0; long long cnt = 0;
   for (size_t i = 0; i < nwg * W; ++i) {
-    const long long *d = &h[i * 5];
-    if (!d[4]) continue;
-    for (int c = 0; c < 4; ++c) { const double x = (double)d[c] / (double)d[4]; sm[c] += x; mx[c] = std::max(mx[c], x); }
+    const long long *d = &h[i * 8];
+    if (!d[5]) continue;
+    for (int c = 0; c < 5; ++c) { const double x = (double)d[c] / (double)d[5]; sm[c] += x; mx[c] = std::max(mx[c], x); }
     cnt++;
+    if (i % W == 0) { steps += (double)d[5]; setup += (double)d[6]; trail += (double)d[7]; }
   }
-  if (cnt) fprintf(stderr, "[igx patch3 timing] colour (%d,%d): %zu workgroups, seg_len %d nseg %d; cycles per element step, mean (max) over %lld wavefronts: sub-phases %.0f (%.0f) | wait for the old values %.0f (%.0f) | window, stores, next loads %.0f (%.0f) | closing barrier + F %.0f (%.0f) | step %.0f\n",
-                   cx, cy, nwg, pa.seg_len, pa.nseg, cnt, sm[0] / cnt, mx[0], sm[1] / cnt, mx[1], sm[2] / cnt, mx[2], sm[3] / cnt, mx[3], (sm[0] + sm[1] + sm[2] + sm[3]) / cnt);
+  if (cnt) fprintf(stderr, "[igx patch3 timing] colour (%d,%d): %zu workgroups, seg_len %d nseg %d; cycles per element step, mean (max) over %lld wavefronts: products %.0f (%.0f) | ticks %.0f (%.0f) | wait for the old values %.0f (%.0f) | window, stores, next loads %.0f (%.0f) | closing barrier + F %.0f (%.0f) | step %.0f\n",
+                   cx, cy, nwg, pa.seg_len, pa.nseg, cnt, sm[0] / cnt, mx[0], sm[1] / cnt, mx[1], sm[2] / cnt, mx[2], sm[3] / cnt, mx[3], sm[4] / cnt, mx[4], (sm[0] + sm[1] + sm[2] + sm[3] + sm[4]) / cnt);
+  CuTimeline T = cu_timeline(&h[nwg * W * 8], nwg);
+  if (!T.any()) return;
+  report_cu_timeline("[igx patch3 timing]", T);
+  // the launch's CU-time outside the element steps: set-up and trailing layers inside a workgroup's life, the rest of the span outside it
+  double busy = 0;
+  for (auto &kv : T.cu) for (auto &iv : kv.second) busy += (double)(iv.second - iv.first);
+  const double span = (double)(T.t1 - T.t0), walk = busy - setup - trail;
+  fprintf(stderr, "[igx patch3 timing]   %.0f element steps in all, %.1f per CU of 256; of span x 256 CUs: inside a walk's steps %.3f | set-up before the walk %.3f | trailing layers %.3f | no workgroup on the CU %.3f; ticks per step inside a walk %.2f\n",
+          steps, steps / 256.0, walk / (span * 256.0), setup / (span * 256.0), trail / (span * 256.0), 1.0 - busy / (span * 256.0), steps ? walk / steps : 0.0);
 }
 
 }  // namespace igx
