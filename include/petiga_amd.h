@@ -325,6 +325,33 @@ int IGXComputeFunctionJacobian(IGX iga,IGXVec U,IGXVec F,IGXMat J);
 int IGXComputeMatrixAction   (IGX iga,IGXVec X,IGXVec Y);                                        /* Y = K X,    K of IGXComputeSystem    */
 int IGXComputeJacobianAction (IGX iga,IGXVec U,IGXVec X,IGXVec Y);                               /* Y = J(U) X, J of IGXComputeJacobian  */
 int IGXComputeIJacobianAction(IGX iga,double a,IGXVec V,double t,IGXVec U,IGXVec X,IGXVec Y);    /* J of IGXComputeIJacobian             */
+/* The same actions on a block of vectors: Y_j = A X_j for j = 0 .. nx-1, 1 <= nx <= 48 (the block-vector limit of IGXVecMDot), in one
+ * walk over the colours per chunk of IGX_ACTION_MAXCOLS columns (vec_sumfact, BATCH).  Nearly all an element costs does not
+ * depend on the direction -- its rows, offsets, control points, the geometry chain, the state's point values, the Dirichlet flags, JW --
+ * and is done once per element and chunk; the direction's forward pass, mat(), the way back and the scatter run per column, and the
+ * launch count drops from colours x nx to colours x ceil(nx / 16) (IGXGetLastTiming).  The contract of the single action holds per column:
+ * the Dirichlet rows; on several ranks every X_j holds its ghosts (IGXRefreshGhosts) and IGXReduceGhostRows(iga,NULL,Y_j) completes each
+ * result; every Y_j is zeroed first (a NaN-filled Y is harmless).  A column's result does not depend on its place in the block nor on
+ * its neighbours, bit for bit; entries of X may repeat.  A run-time struct (IGX_FORM_SOURCE) has no batched instantiation yet: its
+ * columns go through the single-column kernel one by one inside the call (correct, no faster, colours x nx launches) and
+ * IGXGetKernelName says "column by column".
+ * Refusals, each decided before the first HIP call, in this order:
+ *   1. a null iga, X or Y array, or a null state vector where the operator takes one: IGX_ERR_ARG_WRONG
+ *   2. nx outside [1, 48]: IGX_ERR_ARG_OUTOFRANGE
+ *   3. a null entry, or an entry (or state vector) of another IGX: IGX_ERR_ARG_WRONG
+ *   4. a Y_j that repeats, equals any X_i, or is U or V: IGX_ERR_ARG_WRONG
+ *   5. no form set: IGX_ERR_ARG_WRONGSTATE
+ *   6. whatever the single action refuses for the space: IGX_ERR_SUP with its reason under the block call's name ("the matrix action
+ *      on a block runs where the matrix action runs, and ..."); what it refuses for the form itself (order 3, a boundary branch) comes
+ *      under the same name from the launcher.
+ * IGXSetBatchedActions(stiff,1) makes IGXEigenSolve apply its operators through these calls: one block call on stiff and one on mass per
+ * block in place of m single actions each.  Default 0: the solve is bit for bit the one without the call.  info->actions counts
+ * columns either way; the kernel name carries the block action's name and the launch count the block calls' launches. */
+#define IGX_ACTION_MAXCOLS 16         /* columns per launch of the block actions; IGXEigenSolve's largest block */
+int IGXComputeMatrixActionBlock   (IGX iga,int nx,IGXVec X[],IGXVec Y[]);
+int IGXComputeJacobianActionBlock (IGX iga,IGXVec U,int nx,IGXVec X[],IGXVec Y[]);
+int IGXComputeIJacobianActionBlock(IGX iga,double a,IGXVec V,double t,IGXVec U,int nx,IGXVec X[],IGXVec Y[]);
+int IGXSetBatchedActions(IGX iga,int flag);   /* default 0 */
 /* Matrix-free diagonals (what MATOP_GET_DIAGONAL asks of a shell matrix: Jacobi, Chebyshev/Jacobi smoothing, diagonal scaling).
  * D = diag A with A exactly the operator the matching action applies, IGAElementFixJacobian included: a fixed dof holds the number
  * of local elements at its node, and a free field on a node whose other fields are fixed keeps its own entry.  Every mat() is
@@ -810,7 +837,8 @@ int IGXVecMAXPY(int ny,IGXVec Y[],int nx,IGXVec X[],const double C[] /* host [nx
  *   7. an entry of X that is null, of another IGX than stiff, or repeated: IGX_ERR_ARG_WRONG
  *   8. IGX_PC_FASTDIAG without IGXFastDiagSetUp on stiff: IGX_ERR_ORDER
  *   9. whatever the actions or the diagonals refuse, with their reason under the eigen solve's name.
- * Out of scope: a batched action on several columns per launch (the obvious next step: the 2 m actions dominate), locking of converged
+ * IGXSetBatchedActions(stiff,1) (above, with the block actions): steps 0 and 4 make one block call per operator in place of m single actions.
+ * Out of scope: the batched actions as the default, a batched action of a run-time struct, locking of converged
  * columns, interior or largest eigenvalues, Jacobian operators at a state, several ranks, the multigrid as T. */
 typedef enum { IGX_EIGEN_CONVERGED = 1, IGX_EIGEN_DIVERGED_ITS = -1, IGX_EIGEN_DIVERGED_BREAKDOWN = -2, IGX_EIGEN_DIVERGED_NAN = -3 } IGXEigenReason;
 typedef struct { int nev, block, pc; double rtol, atol; int maxit; } IGXEigenSpec;

@@ -175,6 +175,8 @@ def lib(build_if_needed=False):
         "IGXComputeIFunctionIJacobian": [V, C.c_double, V, C.c_double, V, V, V], "IGXComputeFunctionJacobian": [V, V, V, V],
         "IGXComputeMatrixAction": [V, V, V], "IGXComputeJacobianAction": [V, V, V, V],
         "IGXComputeIJacobianAction": [V, C.c_double, V, C.c_double, V, V, V],
+        "IGXComputeMatrixActionBlock": [V, C.c_int, C.POINTER(V), C.POINTER(V)], "IGXComputeJacobianActionBlock": [V, V, C.c_int, C.POINTER(V), C.POINTER(V)],
+        "IGXComputeIJacobianActionBlock": [V, C.c_double, V, C.c_double, V, C.c_int, C.POINTER(V), C.POINTER(V)], "IGXSetBatchedActions": [V, C.c_int],
         "IGXComputeMatrixDiagonal": [V, V], "IGXComputeJacobianDiagonal": [V, V, V],
         "IGXComputeIJacobianDiagonal": [V, C.c_double, V, C.c_double, V, V],
         "IGXComputeMatrixBlockDiagonal": [V, C.c_int, C.POINTER(V)], "IGXComputeJacobianBlockDiagonal": [V, V, C.c_int, C.POINTER(V)],
@@ -764,6 +766,18 @@ class IGX:
     def compute_matrix_action(self, X, Y): _ck(lib().IGXComputeMatrixAction(self.h, X.h, Y.h))
     def compute_jacobian_action(self, U, X, Y): _ck(lib().IGXComputeJacobianAction(self.h, U.h, X.h, Y.h))
     def compute_ijacobian_action(self, a, V, t, U, X, Y): _ck(lib().IGXComputeIJacobianAction(self.h, a, V.h, t, U.h, X.h, Y.h))
+    # the same actions on a block: X and Y are lists of Vecs of one length (1 .. 48), Y[j] = A X[j], IGX_ACTION_MAXCOLS = 16 columns per launch
+    @staticmethod
+    def _block(X, Y):
+        if len(X) != len(Y):
+            raise ValueError("the block action takes as many results as directions, got %d and %d" % (len(Y), len(X)))
+        return len(X), (C.c_void_p * max(len(X), 1))(*[x.h.value for x in X]), (C.c_void_p * max(len(Y), 1))(*[y.h.value for y in Y])
+    def compute_matrix_action_block(self, X, Y): _ck(lib().IGXComputeMatrixActionBlock(self.h, *self._block(X, Y)))
+    def compute_jacobian_action_block(self, U, X, Y): _ck(lib().IGXComputeJacobianActionBlock(self.h, U.h, *self._block(X, Y)))
+    def compute_ijacobian_action_block(self, a, V, t, U, X, Y): _ck(lib().IGXComputeIJacobianActionBlock(self.h, a, V.h, t, U.h, *self._block(X, Y)))
+    def set_batched_actions(self, flag):
+        """flag = 1: IGXEigenSolve on this IGX (as stiff) applies both operators through the block actions; 0 (the default): column by column"""
+        _ck(lib().IGXSetBatchedActions(self.h, int(flag)))
     # matrix-free diagonals: D = diag A of the operator the matching action applies (a fixed dof holds its element count)
     def compute_matrix_diagonal(self, D): _ck(lib().IGXComputeMatrixDiagonal(self.h, D.h))
     def compute_jacobian_diagonal(self, U, D): _ck(lib().IGXComputeJacobianDiagonal(self.h, U.h, D.h))

@@ -123,7 +123,9 @@ struct _p_IGX {
   std::shared_ptr<BlockVecState> blockvec;                          // IGXVecMDot / IGXVecMAXPY: the slab of partial tiles, the coefficient ring and the record (block_vec.hpp)
   std::shared_ptr<EigenState> eigen;                                // IGXEigenSolve's work vectors, kept between solves
   std::string self_timed;                                           // the value of last_kernel for which the call itself stored last_total_ms / last_kernel_ms (a solve loop; a probe of no points): IGXGetLastTiming keeps them
-  unsigned long long setup_gen = 0;                                 // counts IGXSetUp calls: a probe made before the last one is stale (IGXProbeCreate)
+  const ActionCols *action_cols = nullptr;                          // set while compute_matfree_block dispatches a chunk of columns: the action's launcher takes the BATCH instantiation of vec_sumfact
+  int batched_actions = 0;                                          // IGXSetBatchedActions: IGXEigenSolve applies this IGX's action to its blocks in one call
+  unsigned long long setup_gen = 0;                               // counts IGXSetUp calls: a probe made before the last one is stale (IGXProbeCreate)
 };
 
 struct _p_IGXMat {
@@ -805,7 +807,8 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
       if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);
       if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
       bool done = false;
-      if (int rc = try_vec_sumfact<Form, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
+      if (int rc = g->action_cols ? try_vec_sumfact<Form, true, false, false, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done, g->action_cols)
+                                  : try_vec_sumfact<Form, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
       return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix action it covers");
     } else
 #endif
@@ -1137,6 +1140,74 @@ static int action_args(IGX g, IGXVec X, IGXVec Y) {
 extern "C" int IGXComputeMatrixAction(IGX g, IGXVec X, IGXVec Y) { if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_MATRIX_ACTION, nullptr, nullptr, X, 1, &Y, 0, 0); }
 extern "C" int IGXComputeJacobianAction(IGX g, IGXVec U, IGXVec X, IGXVec Y) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_JACOBIAN_ACTION, U, nullptr, X, 1, &Y, 0, 0); }
 extern "C" int IGXComputeIJacobianAction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec X, IGXVec Y) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_IJACOBIAN_ACTION, U, V, X, 1, &Y, a, t); }
+
+// The actions on a block of vectors: Y_j = A X_j for nx columns, IGX_ACTION_MAXCOLS of them per launch (vec_sumfact, BATCH: what does not
+// depend on the direction is done once per element and chunk).  The nx results are zeroed, the colours are walked once
+// per chunk, last_launches = colours x ceil(nx / IGX_ACTION_MAXCOLS).  A run-time struct (IGX_FORM_SOURCE) has no batched instantiation yet:
+// its columns go through the single-column kernel one by one inside this call (colours x nx launches), and the kernel name says so.
+// Refusals: the single action's, under the block call's name.  The entries below and IGXEigenSolve check the arguments.
+constexpr int ACTION_BLOCK_MAX = 48;      // columns of a block call at the most (= BV_MAX: the block-vector limit, block_vec.hpp)
+static const char *const ACTION_BLOCK_WHERE = "the matrix action on a block runs where the matrix action runs, and ";
+static int compute_matfree_block(IGX g, int op, IGXVec U, IGXVec V, int nx, IGXVec *X, IGXVec *Y, double shift, double t) {
+  const Space &s = g->s;
+  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+  if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string(ACTION_BLOCK_WHERE) + why);
+  if (int rc = ensure_device(g)) return rc;
+  OutDev out; memset(&out, 0, sizeof(out));
+  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
+  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
+  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
+  for (int j = 0; j < nx; ++j) HIPCK(hipMemsetAsync(Y[j]->a.p, 0, Y[j]->a.bytes, g->stream));
+  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
+  const SpaceDev S = make_spacedev(g);
+  g->dom = DomInfo(); g->slab_valid = 0;
+  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
+  const bool bycolumn = s.form == IGX_FORM_SOURCE;
+  int launches = 0;
+  for (int j0 = 0; j0 < nx; j0 += bycolumn ? 1 : IGX_ACTION_MAXCOLS) {
+    int rc;
+    if (bycolumn) { out.X = X[j0]->a.as<double>(); out.vec = Y[j0]->a.as<double>(); rc = launch_generic_rtc(g, S, out); }
+    else {
+      ActionCols cols; memset(&cols, 0, sizeof(cols));
+      cols.nc = std::min(nx - j0, (int)IGX_ACTION_MAXCOLS);
+      for (int c = 0; c < cols.nc; ++c) { cols.X[c] = X[j0 + c]->a.as<double>(); cols.Y[c] = Y[j0 + c]->a.as<double>(); }
+      g->action_cols = &cols;
+      rc = dispatch_by_dim(g, S, out);
+      g->action_cols = nullptr;
+    }
+    if (rc) return rc == IGX_ERR_SUP ? fail(rc, ACTION_BLOCK_WHERE + std::string(g_err)) : rc;
+    launches += g->last_launches;
+  }
+  g->last_launches = launches;
+  if (bycolumn) {
+    const size_t at = g->last_kernel.find("matrix action:");
+    if (at != std::string::npos) g->last_kernel.replace(at, 14, "matrix action on a block, column by column:");
+  }
+  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
+  return 0;
+}
+// the pinned order of the block calls' refusals (include/petiga_amd.h), all ahead of the first HIP call
+static int action_block_args(IGX g, bool needU, IGXVec U, bool needV, IGXVec V, int nx, IGXVec *X, IGXVec *Y) {
+  NEEDIGA(g);
+  if (!X || !Y) return fail(IGX_ERR_ARG_WRONG, "null array of directions or results");
+  if ((needU && !U) || (needV && !V)) return fail(IGX_ERR_ARG_WRONG, "null state vector");
+  if (nx < 1 || nx > ACTION_BLOCK_MAX) return fail(IGX_ERR_ARG_OUTOFRANGE, "the matrix action on a block takes 1 to " + std::to_string(ACTION_BLOCK_MAX) + " columns, got " + std::to_string(nx));
+  for (int j = 0; j < nx; ++j) {
+    if (!X[j] || !Y[j]) return fail(IGX_ERR_ARG_WRONG, "null direction or result vector in the block");
+    if (X[j]->iga != g || Y[j]->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
+  }
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  for (int j = 0; j < nx; ++j) {
+    for (int k = 0; k < j; ++k) if (Y[k] == Y[j]) return fail(IGX_ERR_ARG_WRONG, "the same vector given for two results of the block");
+    for (int i = 0; i < nx; ++i) if (X[i] == Y[j]) return fail(IGX_ERR_ARG_WRONG, "a direction and a result of the block must be different vectors");
+    if ((U && U == Y[j]) || (V && V == Y[j])) return fail(IGX_ERR_ARG_WRONG, "a result must not be a state vector");
+  }
+  return 0;
+}
+extern "C" int IGXComputeMatrixActionBlock(IGX g, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, false, nullptr, false, nullptr, nx, X, Y)) return rc; return compute_matfree_block(g, OP_MATRIX_ACTION, nullptr, nullptr, nx, X, Y, 0, 0); }
+extern "C" int IGXComputeJacobianActionBlock(IGX g, IGXVec U, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, true, U, false, nullptr, nx, X, Y)) return rc; return compute_matfree_block(g, OP_JACOBIAN_ACTION, U, nullptr, nx, X, Y, 0, 0); }
+extern "C" int IGXComputeIJacobianActionBlock(IGX g, double a, IGXVec V, double t, IGXVec U, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, true, U, true, V, nx, X, Y)) return rc; return compute_matfree_block(g, OP_IJACOBIAN_ACTION, U, V, nx, X, Y, a, t); }
+extern "C" int IGXSetBatchedActions(IGX g, int flag) { NEEDIGA(g); g->batched_actions = flag ? 1 : 0; return 0; }
 
 // Matrix-free diagonals: D = diag A of the matrix the matching action applies (IGAElementFixJacobian included: a fixed dof holds the
 // number of local elements at its node): what a Jacobi or Chebyshev preconditioner of the shell matrix needs.

@@ -13,6 +13,7 @@ typedef long long int64_t;
 typedef int int32_t;
 typedef unsigned long size_t;
 #define IGX_ERR_USER 83
+#define IGX_ACTION_MAXCOLS 16
 #endif
 
 namespace igx {
@@ -254,6 +255,14 @@ struct OutDev {
                            // SystemVectorOf<Form>, a fixed row takes its value), 2 the form's vec() alone with the fixed rows left at 0 (block_pencil lifts itself)
   const double *X;         // OP_*_ACTION: the row-indexed direction (vec is Y), else null
   double *bcol[MAXBC];     // OP_*_BLOCK_DIAGONAL: the dof block columns, bcol[j][node * dof + i] = A_(node,i),(node,j) (vec is bcol[0]), else null
+};
+
+// The matrix-free action on a block of vectors (vec_sumfact, BATCH): the directions and results of one launch, a kernel argument of its
+// own beside OutDev (whose X and vec stay null).  nc columns, 1 .. IGX_ACTION_MAXCOLS; entries of X may repeat, those of Y may not.
+struct ActionCols {
+  const double *X[IGX_ACTION_MAXCOLS];
+  double *Y[IGX_ACTION_MAXCOLS];
+  int nc;
 };
 
 #ifndef IGX_RTC

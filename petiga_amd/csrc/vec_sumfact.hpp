@@ -194,9 +194,25 @@ template <int NS> struct vs_layout {
 // mat() returns holds them all.  Block row by block row: for a test field i the point stage keeps row i of every tile (DOF x 10
 // coefficients, as many as DIAGONAL holds -- all DOF^2 x 10 would be 320 registers for NS-VMS) and DOF ways back follow; the compiler
 // drops the rows of a call that are not kept.  An entry beside a fixed dof is 0, a fixed (i, i) the unit diagonal (IGAElementFixJacobian).
-template <class Form, bool GEO, int NS = 4, bool ACTION = false, bool DIAGONAL = false, bool BLOCK = false>
+// BATCH (with ACTION): the action on a block of nc <= IGX_ACTION_MAXCOLS vectors in one launch, Y_c = A X_c (the launcher below;
+// DESIGN.md 3.22).  What an element needs that does not depend on the direction -- rows, offsets, row map, control points, the geometry
+// chain, the state's point values, the Dirichlet flags, JW and G -- is done once; the direction's forward pass, the DOF calls of mat() per
+// test feature, the rational correction, the way back and the scatter run per column in ONE loop body that is not unrolled, so a column's
+// arithmetic does not depend on its place in the block.  nc is uniform over the launch: every thread of a workgroup reaches the barriers
+// of the helpers the same number of times.  The columns share buf; each helper opens with VS_SYNC() ahead of its first store, which is
+// the barrier between one column's way back and the next column's way forward.  No early load of the old result (PIPE, EF: it belongs
+// to one column): Y_c is read where it is added to, which the colour makes as safe as the early read.  Scalar forms fetch the next
+// column's nodal value while the current one computes (one register); the others load it at the top of the loop (no register to spare).
+// The block's table is a kernel argument of its own, behind the five every instantiation takes: the pack COLS is empty (the kernel's
+// signature is the one it always had, also for the run-time compiled instantiations that name it) or, with BATCH, ActionCols.
+__device__ __forceinline__ const ActionCols *vs_cols() { return nullptr; }
+__device__ __forceinline__ const ActionCols *vs_cols(const ActionCols &c) { return &c; }
+template <class Form, bool GEO, int NS = 4, bool ACTION = false, bool DIAGONAL = false, bool BLOCK = false, bool BATCH = false, class... COLS>
 __global__ void __launch_bounds__(vs_layout<NS>::THREADS, ((!vs_layout<NS>::WG && vs_pipe<Form, GEO>()) ? 4 : 2))      // (two waves per SIMD: the geometry variants of NS-VMS and Cahn-Hilliard need 290-350 VGPRs uncapped, one wave per SIMD)
-vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nelem) {
+vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nelem, COLS... colsarg) {
+  static_assert(sizeof...(COLS) == (BATCH ? 1 : 0), "BATCH takes the table of columns as its one further argument, the others none");
+  const ActionCols *cols = vs_cols(colsarg...);
+  static_assert(!BATCH || ACTION, "a block of columns is a variant of ACTION");
   constexpr int EPW = NS == 3 ? 2 : 1, NL = NS * NS * NS;               // elements per wavefront, lanes per element
   constexpr int DOF = Form::DOF;
   constexpr bool WG = vs_layout<NS>::WG;
@@ -295,8 +311,8 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
         if (readU) P.U[f] = out.U[P.row * DOF + f];
         if (useV) P.V[f] = out.V[P.row * DOF + f];
         if (S.fixtable) P.fx[f] = S.fixtable[P.row * DOF + f];
-        if constexpr (PIPE || EF) P.Fo[f] = out.vec[P.row * DOF + f];
-        if constexpr (ACTION) P.Xd[f] = out.X[P.row * DOF + f];
+        if constexpr ((PIPE || EF) && !BATCH) P.Fo[f] = out.vec[P.row * DOF + f];
+        if constexpr (ACTION && !BATCH) P.Xd[f] = out.X[P.row * DOF + f];
       }
     }
     if constexpr (PIPE) {      // (the geometry variants read these where they use them: no register to spare)
@@ -484,6 +500,23 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
       ut[f] = D[0] * iw;
     }
   }
+  // BATCH: the columns of the block go through the body below one after the other; everything above is done once for them all, and so
+  // are JW and G, at the first column (they stand where they always stood, behind the direction's forward pass).  Else the body runs
+  // once: no loop.  Xn: the next column's nodal value, on its way while this column computes.
+  constexpr bool XPRE = BATCH && DOF == 1;
+  double JW = 0.0, G[9], Xn = 0.0;
+  int col = 0;
+  if constexpr (XPRE) { if (isnode) Xn = cols->X[0][row]; }
+#pragma unroll 1
+  do {
+  if constexpr (BATCH) {
+    if constexpr (XPRE) { Xv[0] = Xn; if (isnode && col + 1 < cols->nc) Xn = cols->X[col + 1][row]; }
+    else {
+      const double *Xc = cols->X[col];
+#pragma unroll
+      for (int f = 0; f < DOF; ++f) Xv[f] = isnode ? Xc[row * DOF + f] : 0.0;
+    }
+  }
   // ACTION: the direction's point features, field by field, behind the state's (a fixed column takes no contribution: gathered as 0)
   double xv[ACTION ? DOF : 1], gx[ACTION ? DOF * 3 : 1], hx[ACTION && XORD == 2 ? DOF * 9 : 1];
   if constexpr (ACTION) {
@@ -497,7 +530,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   // the next element's loads go out here: its offsets have arrived, and the point stage and the way back lie ahead
   if (PIPE && more) stageB(unext, nxt);
   // ---- point: JW and the form's vec() on the unit test features
-  double JW = 0.0, G[9];
+  if (!BATCH || col == 0) {
   if (ispoint) {
     JW = detX;
     if constexpr (EF && !PIPE) JW *= cur.wq[0];
@@ -510,6 +543,7 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
   for (int a = 0; a < 3; ++a)
 #pragma unroll
     for (int i = 0; i < 3; ++i) G[a * 3 + i] = E1[a * 3 + i] / (PIPE ? cur.Jd[a] : S.ax[a].J[el[a]]);      // IGAPointFormInvGradGeomMap, src/petigapoint.c:269-294
+  }
   PtView p; p.x = x; p.u = u; p.ut = ut; p.gu = gu; p.hu = hu; p.G = G; p.prm = prm.v; p.shift = out.shift; p.t = out.t;
   p.normal = nullptr; p.atboundary = 0; p.boundary_id = -1;
   double Cq[DOF][10];
@@ -669,9 +703,12 @@ vec_sumfact(SpaceDev S, ParamsDev prm, OutDev out, ColorRange cr, long long nele
       else if (fixed[f] && sysvec) F = ufix[f];                  // IGAElementFixSystem: F_e[k] = v
       else if (fixed[f] && sysbody) F = 0.0;                     // (the band-row kernel that follows adds v per element itself)
       else if (fixed[f] && (op == OP_FUNCTION || op == OP_IFUNCTION)) F = Uv[f] - ufix[f];
+      if constexpr (BATCH) { if (F != 0.0) cols->Y[col][row * DOF + f] += F; }
+      else
       if (F != 0.0) { if constexpr (PIPE || EF) out.vec[row * DOF + f] = Fold[f] + F; else out.vec[row * DOF + f] += F; }
     }
   }
+  } while (BATCH && ++col < cols->nc);      // the block's next column
   if (!more) break;
   if (PIPE) cur = nxt;
   unit = unext;
@@ -698,12 +735,14 @@ static bool vec_sumfact_covers(const Space &s, const OutDev &out) {
   }
 }
 
-template <class Form, bool ACTION = false, bool DIAGONAL = false, bool BLOCK = false>
-static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &prm, const OutDev &out, hipStream_t stream, std::string &kname, int &launches, bool &done) {
+// BATCH (with ACTION): one launch per colour of the BATCH instantiation on the columns of cols (at most IGX_ACTION_MAXCOLS: the caller cuts the block)
+template <class Form, bool ACTION = false, bool DIAGONAL = false, bool BLOCK = false, bool BATCH = false>
+static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &prm, const OutDev &out, hipStream_t stream, std::string &kname, int &launches, bool &done, const ActionCols *cols = nullptr) {
   done = false;
   if constexpr (nscalar_of<Form>::v > 0 || has_boundary_of<Form>::v) return 0;
   else {
   if constexpr (!ACTION && !DIAGONAL) { if (!vec_sumfact_covers<Form>(s, out)) return 0; }      // (ACTION, DIAGONAL: the caller has asked vec_action_refusal)
+  if constexpr (BATCH) { if (!cols || cols->nc < 1 || cols->nc > IGX_ACTION_MAXCOLS) return IGX_ERR_PLIB; }
   launches = 0;
   color_sweeps(s, SweepSpec(), [&](const ColorRange &cr) -> int {
     const long long nelem = (long long)cr.count[0] * cr.count[1] * cr.count[2];
@@ -711,31 +750,29 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
     bool three = !s.env.no_vec_pairs;
     for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
     const bool g1 = s.nsd > 0 || s.rational;
+    // the instantiation of a layout (lanes per axis) on a mapped / rational geometry or on none
+    auto launch = [&](auto nsc, unsigned grid) {
+      constexpr int NS = decltype(nsc)::value;
+      if constexpr (BATCH) {
+        if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, NS, true, false, false, true, ActionCols>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem, *cols);
+        else hipLaunchKernelGGL((vec_sumfact<Form, false, NS, true, false, false, true, ActionCols>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem, *cols);
+      } else {
+        if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, NS, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem);
+        else hipLaunchKernelGGL((vec_sumfact<Form, false, NS, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem);
+      }
+    };
     if constexpr (ACTION || DIAGONAL) {      // more than four basis functions or points on an axis: one workgroup per element, 6 or 8 lanes per axis
       const int ns = vec_lanes_per_axis(s);
       if (ns > 4) {
-        const unsigned grid = (unsigned)nelem;
-        if (ns <= 6) {
-          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 6, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
-          else hipLaunchKernelGGL((vec_sumfact<Form, false, 6, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<6>::THREADS), 0, stream, S, prm, out, cr, nelem);
-        } else {
-          if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 8, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
-          else hipLaunchKernelGGL((vec_sumfact<Form, false, 8, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<8>::THREADS), 0, stream, S, prm, out, cr, nelem);
-        }
+        if (ns <= 6) launch(vs_int<6>(), (unsigned)nelem);
+        else launch(vs_int<8>(), (unsigned)nelem);
         launches++;
         return 0;
       }
     }
-    const bool onepass = true;      // (UNITS = 1 in the kernel)      // (one pass per wavefront: the launch has a wavefront per unit)
-    if (three) {
-      const unsigned grid = onepass ? (unsigned)((nelem + 7) / 8) : (unsigned)((nelem + 15) / 16);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 3, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 3, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-    } else {
-      const unsigned grid = onepass ? (unsigned)((nelem + 3) / 4) : (unsigned)((nelem + 7) / 8);
-      if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, 4, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-      else hipLaunchKernelGGL((vec_sumfact<Form, false, 4, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(256), 0, stream, S, prm, out, cr, nelem);
-    }
+    // (one pass per wavefront: the launch has a wavefront per unit -- UNITS = 1 in the kernel)
+    if (three) launch(vs_int<3>(), (unsigned)((nelem + 7) / 8));
+    else launch(vs_int<4>(), (unsigned)((nelem + 3) / 4));
     launches++;
     return 0;
   });
@@ -745,13 +782,15 @@ static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &p
     for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
     const int ns = vec_lanes_per_axis(s);
     if ((ACTION || DIAGONAL) && ns > 4)
-      kname = std::string(BLOCK ? "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, " : DIAGONAL ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, " : "vec_sumfact(matrix action: sum factorisation forward and backward, ")
+      kname = std::string(BLOCK ? "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, " : DIAGONAL ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, " : BATCH ? "vec_sumfact(matrix action on a block: sum factorisation forward and backward, " : "vec_sumfact(matrix action: sum factorisation forward and backward, ")
             + (ns <= 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : "one workgroup per element, 8 x 8 x 8 lanes)");
     else
     if constexpr (BLOCK) kname = three ? "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, two elements per wavefront)"
                                        : "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, one wavefront per element)";
     else if constexpr (DIAGONAL) kname = three ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, two elements per wavefront)"
                                           : "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, one wavefront per element)";
+    else if constexpr (BATCH) kname = three ? "vec_sumfact(matrix action on a block: sum factorisation forward and backward, two elements per wavefront)"
+                                       : "vec_sumfact(matrix action on a block: sum factorisation forward and backward, one wavefront per element)";
     else if constexpr (ACTION) kname = three ? "vec_sumfact(matrix action: sum factorisation forward and backward, two elements per wavefront)"
                                         : "vec_sumfact(matrix action: sum factorisation forward and backward, one wavefront per element)";
     else
