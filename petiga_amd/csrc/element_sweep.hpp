@@ -2,6 +2,7 @@
 // generic_kernel.hpp) and the feature-GEMM kernel (feature_assemble, feature_mfma.hpp), for built-in forms (engine.hip:
 // launch_generic, launch_feature_plan) and run-time forms (rtc.hpp: rtc_generic_launch, launch_feature_rtc) alike:
 //   FormFacts       what a launcher must know about a form, by name: from the traits of a built-in form, from igx_user_meta[16] of a module
+//   matfree_refusal where the matrix-free operators run, and why not: the one rule table of vec_sumfact's callers
 //   color_sweeps    the ColorRange of every non-empty colour combination of an interior sweep or a face pass (also vec_sumfact's sweeps)
 //   carve_generic / carve_feature      the kernels' LDS layouts (Carve, FCarve): a new region is added here, once
 //   sweep_generic / sweep_feature      the launch loops, templated on the callable that makes one launch (hipLaunchKernelGGL of an
@@ -65,6 +66,68 @@ struct FeatureFacts {
   int mfma_per_kstep = 0;       // executed MFMAs per k-step (fm_mfma_per_kstep)
 };
 inline FeatureFacts feature_facts_from_meta(const int meta[4]) { FeatureFacts f; f.wgs_per_cu = meta[0]; f.phi_in_lds = meta[1]; f.mfma_per_kstep = meta[2]; return f; }
+
+// ------------------------------------------------------------------ where the matrix-free operators run
+// The actions, the diagonals and the point-block diagonals run on vec_sumfact or not at all: the one table of why not.  The rules, and the
+// orders in which the callers ask them (the first that applies answers; include/petiga_amd.h and tests/test_gpu_matfree_routing.py pin them):
+//   the space   S1 a boundary-form face, S2 dim != 3, S3 a geometry with nsd != dim, S4 more than 8 functions or points on an axis,
+//               S5 IGX_VEC_SUMFACT=0, S6 IGXSetKernel != 0 -- worded for the action
+//   the form    F1 order 3 / the property array / the map's derivatives, F2 a boundary branch (a built-in form: "or functionals"),
+//               F3 second-order shape features (the diagonals alone)
+//   the fields  N a struct with NSCALAR; D dof != the form's DOF (IGX_ERR_ARG_WRONG, never under a prefix)
+//   MfCaller::FORM    a built-in form's launcher.  Actions: S1 S2 F1 F2 S3..S6 D (a form the action does not cover is not asked for the
+//                     kernel).  Diagonals: S1..S6 F1 F2 F3 D.
+//   MfCaller::STRUCT  a run-time struct's launcher: N D S1..S6 F1 F2 F3.
+//   MfCaller::CHECK   IGXCheckFormSource, no N and no D.  gram 7 (action): "needs dim 3", S1..S6.  gram 8 (diagonal): "needs dim 3", F1 F2 F3,
+//                     S1..S6.  gram 9 (block diagonal): S1..S6, F1 F2 F3.
+//   facts == nullptr  the struct's constants are not known (a module that is not loaded), or the caller asks before it has a form at hand
+//                     (a solve loop, the block action ahead of its first HIP call): the space's rules alone.
+// A diagonal gives a rule of the space under "the matrix diagonal runs where the matrix action runs, and "; the block diagonal and the
+// action on a block give every reason under their own such prefix (N excepted for the block diagonal, as ever).
+enum class MfCaller { FORM, STRUCT, CHECK };
+struct MfRefusal { int code = 0; std::string msg; explicit operator bool() const { return code != 0; } };
+inline const char *matfree_space_rule(const Space &s, int kernel_choice, int &rule) {
+  rule = 1;
+  for (int d = 0; d < s.dim; ++d) for (int sd = 0; sd < 2; ++sd) if (s.visit[d][sd]) return "the matrix action does not cover boundary-form passes (IGXSetBoundaryForm): it runs on vec_sumfact alone";
+  rule = 2;
+  if (s.dim != 3) return "the matrix action needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)";
+  rule = 3;
+  if (s.nsd != 0 && s.nsd != 3) return "the matrix action needs a geometry with nsd = dim";
+  if (vec_lanes_per_axis(s) > 8) return "the matrix action needs nen <= 8 and nqp <= 8 on every axis (degree <= 7)";
+  if (s.env.vec_sumfact == 0) return "the matrix action runs on vec_sumfact alone, and IGX_VEC_SUMFACT=0 switches that kernel off";
+  if (kernel_choice != 0) return "the matrix action runs on vec_sumfact alone: IGXSetKernel must leave the choice automatic (0)";
+  return nullptr;
+}
+inline MfRefusal matfree_refusal(const Space &s, int kernel_choice, VsMode mode, const FormFacts *f, MfCaller who) {
+  const VsTraits t = vs_traits(mode);
+  const std::string subject = t.diagonal ? "the matrix diagonal" : "the matrix action";
+  auto under = [&](std::string why) {      // ... the names of the calls that stand on another
+    if (t.block) why = "the matrix block diagonal runs where the matrix diagonal runs, and " + why;
+    if (t.batch) why = "the matrix action on a block runs where the matrix action runs, and " + why;
+    return MfRefusal{IGX_ERR_SUP, why};
+  };
+  int rule = 0;
+  const char *sp = matfree_space_rule(s, kernel_choice, rule);
+  auto space = [&]() { return under((t.diagonal ? "the matrix diagonal runs where the matrix action runs, and " : "") + std::string(sp)); };
+  auto form = [&]() -> MfRefusal {
+    if (!f) return {};
+    if (f->general_only()) return under(subject + " does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives");
+    if (f->has_boundary || (who == MfCaller::FORM && f->nscalar != 0)) return under(subject + " does not cover forms with a boundary branch" + (who == MfCaller::FORM ? " or functionals" : ""));
+    if (t.diagonal && f->shape_order >= 2) return under("the matrix diagonal does not cover forms with second-order shape features (Cahn-Hilliard's Laplacian): six product rows per axis and 55 coefficient slots per point are another kernel");
+    return {};
+  };
+  if (who == MfCaller::CHECK && !t.block && s.dim != 3) return {IGX_ERR_SUP, subject + " needs dim 3"};
+  if (who == MfCaller::STRUCT && f) {
+    if (f->nscalar > 0) return {IGX_ERR_SUP, std::string(t.batch ? "the matrix action on a block runs where the matrix action runs, and " : "") + "a struct with NSCALAR is a functional: IGXComputeScalarSource"};
+    if (s.dof != f->dof) return {IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)"};
+  }
+  const bool form_first = (who == MfCaller::FORM && !t.diagonal && rule > 2) || (who == MfCaller::CHECK && mode == VsMode::DIAGONAL);
+  if (sp && !form_first) return space();
+  if (const MfRefusal r = form()) return r;
+  if (sp) return space();
+  if (who == MfCaller::FORM && f && s.dof != f->dof) return {IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)"};
+  return {};
+}
 
 // ------------------------------------------------------------------ colour sweeps
 // colour c of an axis restricted to [lo,hi): arithmetic sequence (regular colours) or a single element

@@ -123,7 +123,6 @@ struct _p_IGX {
   std::shared_ptr<BlockVecState> blockvec;                          // IGXVecMDot / IGXVecMAXPY: the slab of partial tiles, the coefficient ring and the record (block_vec.hpp)
   std::shared_ptr<EigenState> eigen;                                // IGXEigenSolve's work vectors, kept between solves
   std::string self_timed;                                           // the value of last_kernel for which the call itself stored last_total_ms / last_kernel_ms (a solve loop; a probe of no points): IGXGetLastTiming keeps them
-  const ActionCols *action_cols = nullptr;                          // set while compute_matfree_block dispatches a chunk of columns: the action's launcher takes the BATCH instantiation of vec_sumfact
   int batched_actions = 0;                                          // IGXSetBatchedActions: IGXEigenSolve applies this IGX's action to its blocks in one call
   unsigned long long setup_gen = 0;                               // counts IGXSetUp calls: a probe made before the last one is stale (IGXProbeCreate)
 };
@@ -790,6 +789,31 @@ static int launch_feature(IGX g, const SpaceDev &S, const OutDev &out, bool &don
   }
 }
 
+// ------------------------------------------------------------------ matrix-free dispatch
+// The matrix-free operators of a built-in form (IGXCompute*Action, *ActionBlock, *Diagonal, *BlockDiagonal): vec_sumfact in the mode's
+// instantiation, or the refusal matfree_refusal names (element_sweep.hpp) -- no other kernel forms them.  cols: ACTION_BATCH's columns.
+template <class Form, int DIM>
+static int launch_matfree(IGX g, const SpaceDev &S, const OutDev &out, VsMode mode, const ActionCols *cols) {
+  const Space &s = g->s;
+  constexpr FormFacts facts = facts_of<Form>();
+  if (const MfRefusal r = matfree_refusal(s, g->kernel_choice, mode, &facts, MfCaller::FORM)) return fail(r.code, r.msg);
+#ifdef IGX_HAVE_VEC_SUMFACT
+  if constexpr (DIM == 3 && !general_only_of<Form>::v && nscalar_of<Form>::v == 0 && !has_boundary_of<Form>::v) {
+    const ParamsDev prm = params_of(s);
+    const VsTraits t = vs_traits(mode);
+    bool done = false;
+    auto run = [&](auto m) { return try_vec_sumfact<Form, decltype(m)::value>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done, cols); };
+    int rc = IGX_ERR_PLIB;
+    if (mode == VsMode::ACTION) rc = run(std::integral_constant<VsMode, VsMode::ACTION>());
+    else if (mode == VsMode::ACTION_BATCH) rc = run(std::integral_constant<VsMode, VsMode::ACTION_BATCH>());
+    else if constexpr (shape_order_of<Form>::v < 2) rc = t.block ? run(std::integral_constant<VsMode, VsMode::BLOCK_DIAGONAL>()) : run(std::integral_constant<VsMode, VsMode::DIAGONAL>());
+    if (rc) return fail(rc, "vec_sumfact kernel launch failed");
+    return done ? 0 : fail(IGX_ERR_PLIB, std::string("vec_sumfact did not take a ") + (t.block ? "matrix block diagonal" : t.diagonal ? "matrix diagonal" : "matrix action") + " it covers");
+  }
+#endif
+  return fail(IGX_ERR_PLIB, "matfree_refusal let a case pass that vec_sumfact does not hold");
+}
+
 // ------------------------------------------------------------------ generic kernel dispatch
 template <class Form, int DIM>
 static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
@@ -800,45 +824,6 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
   // third-order tabulation, the property array and the point's shape table exist in the general kernel only
   constexpr bool GENERAL = general_only_of<Form>::v;
   const ParamsDev prm = params_of(s);
-  // the matrix-free actions (IGXCompute*Action): vec_sumfact's ACTION instantiation or a refusal that names the reason -- no other kernel forms them
-  if (out.op == OP_MATRIX_ACTION || out.op == OP_JACOBIAN_ACTION || out.op == OP_IJACOBIAN_ACTION) {
-#ifdef IGX_HAVE_VEC_SUMFACT
-    if constexpr (DIM == 3 && !GENERAL && NS == 0 && !has_boundary_of<Form>::v) {
-      if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);
-      if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
-      bool done = false;
-      if (int rc = g->action_cols ? try_vec_sumfact<Form, true, false, false, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done, g->action_cols)
-                                  : try_vec_sumfact<Form, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
-      return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix action it covers");
-    } else
-#endif
-    {
-      for (int d = 0; d < s.dim; ++d) for (int sd = 0; sd < 2; ++sd) if (s.visit[d][sd]) return fail(IGX_ERR_SUP, "the matrix action does not cover boundary-form passes (IGXSetBoundaryForm): it runs on vec_sumfact alone");
-      if (DIM != 3) return fail(IGX_ERR_SUP, "the matrix action needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)");
-      if (GENERAL) return fail(IGX_ERR_SUP, "the matrix action does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives");
-      return fail(IGX_ERR_SUP, "the matrix action does not cover forms with a boundary branch or functionals");
-    }
-  }
-  // the matrix-free diagonals (IGXCompute*Diagonal) and point-block diagonals (IGXCompute*BlockDiagonal): vec_sumfact's DIAGONAL instantiation
-  // (with BLOCK) or a refusal, under the actions' conditions and first-order shape features; the block diagonal gives the diagonal's reasons under its own name
-  if (op_is_diagonal(out.op) || op_is_block_diagonal(out.op)) {
-    const bool blk = op_is_block_diagonal(out.op);
-    auto refuse = [&](const std::string &why) { return fail(IGX_ERR_SUP, blk ? vec_block_diagonal_reason(why) : why); };
-    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return refuse(why); }
-    if (GENERAL) return refuse(VEC_DIAGONAL_GENERAL);
-    if (NS != 0 || has_boundary_of<Form>::v) return refuse(VEC_DIAGONAL_BOUNDARY);
-    if (shape_order_of<Form>::v >= 2) return refuse(VEC_DIAGONAL_SECOND);
-#ifdef IGX_HAVE_VEC_SUMFACT
-    if constexpr (DIM == 3 && !GENERAL && NS == 0 && !has_boundary_of<Form>::v && shape_order_of<Form>::v < 2) {
-      if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
-      bool done = false;
-      if (int rc = blk ? try_vec_sumfact<Form, false, true, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)
-                       : try_vec_sumfact<Form, false, true>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
-      return done ? 0 : fail(IGX_ERR_PLIB, blk ? "vec_sumfact did not take a matrix block diagonal it covers" : "vec_sumfact did not take a matrix diagonal it covers");
-    }
-#endif
-    return refuse("the matrix diagonal needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)");
-  }
   if (GENERAL && g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a form of order 3 or one that reads the property array runs on the general kernel only");
   if ((Form::NEED & NEED_PROP) && !S.npd) return fail(IGX_ERR_ARG_WRONGSTATE, "No property set");      // src/petigaelem.c:300
   // a geometry of another dimension than the parametric one: tabulated by the general kernel only (no inverse map: src/petigaelem.c:966)
@@ -899,53 +884,55 @@ static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
 
 // GROUP < 0: every form; else only the forms of that group (0 scalar second-order-free forms, 1 multi-field
 // constant-coefficient forms, 2 the nonlinear demos), IGX_NOT_MINE for the others
-template <int DIM, int GROUP>
-static int dispatch_dim(IGX g, const SpaceDev &S, const OutDev &out) {
+// launch(form_tag<Form>()): the launcher of the entry -- the element kernels' (launch_generic) or the matrix-free operators' (launch_matfree)
+template <class Form> struct form_tag { using type = Form; };
+template <int DIM, int GROUP, class Launch>
+static int dispatch_dim(IGX g, Launch &&launch) {
   const Space &s = g->s;
-#define IGX_GROUP(gid, call) do { if constexpr (GROUP < 0 || GROUP == (gid)) return call; else return IGX_NOT_MINE; } while (0)
+#define IGX_GROUP(gid, ...) do { if constexpr (GROUP < 0 || GROUP == (gid)) return launch(form_tag<__VA_ARGS__>()); else return IGX_NOT_MINE; } while (0)
   switch (s.form) {
-  case IGX_FORM_POISSON:   IGX_GROUP(0, (launch_generic<FormPoisson<DIM>, DIM>(g, S, out)));
-  case IGX_FORM_POISSON_F: IGX_GROUP(0, (launch_generic<FormPoissonF<DIM>, DIM>(g, S, out)));
-  case IGX_FORM_L2PROJ_X2: IGX_GROUP(0, (launch_generic<FormL2ProjX2<DIM>, DIM>(g, S, out)));
-  case IGX_FORM_BOUNDARYINTEGRAL: IGX_GROUP(0, (launch_generic<FormBoundaryIntegral<DIM>, DIM>(g, S, out)));
-  case IGX_FORM_NITSCHE:          IGX_GROUP(0, (launch_generic<FormNitsche<DIM>, DIM>(g, S, out)));
-  case IGX_FORM_DER3:      IGX_GROUP(0, (launch_generic<FormDer3<DIM>, DIM>(g, S, out)));
-  case IGX_FORM_PROPERTY:  IGX_GROUP(0, (launch_generic<FormProperty<DIM>, DIM>(g, S, out)));
+  case IGX_FORM_POISSON:   IGX_GROUP(0, FormPoisson<DIM>);
+  case IGX_FORM_POISSON_F: IGX_GROUP(0, FormPoissonF<DIM>);
+  case IGX_FORM_L2PROJ_X2: IGX_GROUP(0, FormL2ProjX2<DIM>);
+  case IGX_FORM_BOUNDARYINTEGRAL: IGX_GROUP(0, FormBoundaryIntegral<DIM>);
+  case IGX_FORM_NITSCHE:          IGX_GROUP(0, FormNitsche<DIM>);
+  case IGX_FORM_DER3:      IGX_GROUP(0, FormDer3<DIM>);
+  case IGX_FORM_PROPERTY:  IGX_GROUP(0, FormProperty<DIM>);
   case IGX_FORM_SURFACE:
     if constexpr (GROUP < 0 || GROUP == 0) {
-      if constexpr (DIM <= 2) return launch_generic<FormSurface<DIM>, DIM>(g, S, out);
+      if constexpr (DIM <= 2) return launch(form_tag<FormSurface<DIM>>());
       else return fail(IGX_ERR_ARG_WRONG, "the surface form needs dim = 1 or 2 (a curve or a surface in space)");
     } else return IGX_NOT_MINE;
-  case IGX_FORM_ERRNORM:   IGX_GROUP(1, (launch_generic<FormErrNorm<DIM>, DIM>(g, S, out)));
+  case IGX_FORM_ERRNORM:   IGX_GROUP(1, FormErrNorm<DIM>);
   case IGX_FORM_MASS:
     if constexpr (GROUP < 0 || GROUP == 1) {
       switch (s.dof) {
-      case 1: return launch_generic<FormMass<DIM, 1>, DIM>(g, S, out);
-      case 2: return launch_generic<FormMass<DIM, 2>, DIM>(g, S, out);
-      case 3: return launch_generic<FormMass<DIM, 3>, DIM>(g, S, out);
-      case 4: return launch_generic<FormMass<DIM, 4>, DIM>(g, S, out);
+      case 1: return launch(form_tag<FormMass<DIM, 1>>());
+      case 2: return launch(form_tag<FormMass<DIM, 2>>());
+      case 3: return launch(form_tag<FormMass<DIM, 3>>());
+      case 4: return launch(form_tag<FormMass<DIM, 4>>());
       default: return fail(IGX_ERR_SUP, "mass form is instantiated for dof 1..4");
       }
     } else return IGX_NOT_MINE;
   case IGX_FORM_ELASTICITY:
     if constexpr (GROUP < 0 || GROUP == 1) {
-      if constexpr (DIM == 3) return launch_generic<FormElasticity, 3>(g, S, out);
+      if constexpr (DIM == 3) return launch(form_tag<FormElasticity>());
       else return fail(IGX_ERR_ARG_WRONG, "Elasticity3D form needs dim = 3");
     } else return IGX_NOT_MINE;
   case IGX_FORM_ELASTICITY_F:
     if constexpr (GROUP < 0 || GROUP == 1) {
-      if constexpr (DIM == 3) return launch_generic<FormElasticityF, 3>(g, S, out);
+      if constexpr (DIM == 3) return launch(form_tag<FormElasticityF>());
       else return fail(IGX_ERR_ARG_WRONG, "Elasticity3D form needs dim = 3");
     } else return IGX_NOT_MINE;
   case IGX_FORM_CAHNHILLIARD:
     if constexpr (GROUP < 0 || GROUP == 2) {
-      if constexpr (DIM >= 2) return launch_generic<FormCahnHilliard<DIM>, DIM>(g, S, out);
+      if constexpr (DIM >= 2) return launch(form_tag<FormCahnHilliard<DIM>>());
       else return fail(IGX_ERR_ARG_WRONG, "Cahn-Hilliard form needs dim = 2 or 3");
     } else return IGX_NOT_MINE;
-  case IGX_FORM_BRATU:     IGX_GROUP(2, (launch_generic<FormBratu<DIM>, DIM>(g, S, out)));
+  case IGX_FORM_BRATU:     IGX_GROUP(2, FormBratu<DIM>);
   case IGX_FORM_NSVMS:
     if constexpr (GROUP < 0 || GROUP == 2) {
-      if constexpr (DIM == 3) return launch_generic<FormNSVMS, 3>(g, S, out);
+      if constexpr (DIM == 3) return launch(form_tag<FormNSVMS>());
       else return fail(IGX_ERR_ARG_WRONG, "NavierStokesVMS form needs dim = 3");
     } else return IGX_NOT_MINE;
   default: return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");   // IGACheckFormOp, include/petiga.h:925-936
@@ -966,7 +953,10 @@ static int dispatch_scalar(IGX g, int kind, const SpaceDev &S, const OutDev &out
 
 // the entry points of this unit
 int igx_tu_dispatch(std::integral_constant<int, IGX_TU_DIM>, std::integral_constant<int, IGX_TU_GROUP>, IGX g, const SpaceDev &S, const OutDev &out) {
-  return dispatch_dim<IGX_TU_DIM, IGX_TU_GROUP>(g, S, out);
+  return dispatch_dim<IGX_TU_DIM, IGX_TU_GROUP>(g, [&](auto form) { return launch_generic<typename decltype(form)::type, IGX_TU_DIM>(g, S, out); });
+}
+int igx_tu_matfree(std::integral_constant<int, IGX_TU_DIM>, std::integral_constant<int, IGX_TU_GROUP>, IGX g, const SpaceDev &S, const OutDev &out, VsMode mode, const ActionCols *cols) {
+  return dispatch_dim<IGX_TU_DIM, IGX_TU_GROUP>(g, [&](auto form) { return launch_matfree<typename decltype(form)::type, IGX_TU_DIM>(g, S, out, mode, cols); });
 }
 #if IGX_TU_GROUP < 0 || IGX_TU_GROUP == 2
 int igx_tu_scalar(std::integral_constant<int, IGX_TU_DIM>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order) {
@@ -977,28 +967,32 @@ int igx_tu_scalar(std::integral_constant<int, IGX_TU_DIM>, IGX g, int kind, cons
 
 #ifndef IGX_TU_DISPATCH
 // kernel instantiations live in the dispatch units (one per dimension; three form groups for dim 3)
-int igx_tu_dispatch(std::integral_constant<int, 1>, std::integral_constant<int, -1>, IGX g, const SpaceDev &S, const OutDev &out);
-int igx_tu_dispatch(std::integral_constant<int, 2>, std::integral_constant<int, -1>, IGX g, const SpaceDev &S, const OutDev &out);
-int igx_tu_dispatch(std::integral_constant<int, 3>, std::integral_constant<int, 0>, IGX g, const SpaceDev &S, const OutDev &out);
-int igx_tu_dispatch(std::integral_constant<int, 3>, std::integral_constant<int, 1>, IGX g, const SpaceDev &S, const OutDev &out);
-int igx_tu_dispatch(std::integral_constant<int, 3>, std::integral_constant<int, 2>, IGX g, const SpaceDev &S, const OutDev &out);
+#define IGX_TU_ENTRIES(d, gr) \
+  int igx_tu_dispatch(std::integral_constant<int, d>, std::integral_constant<int, gr>, IGX g, const SpaceDev &S, const OutDev &out); \
+  int igx_tu_matfree(std::integral_constant<int, d>, std::integral_constant<int, gr>, IGX g, const SpaceDev &S, const OutDev &out, VsMode mode, const ActionCols *cols);
+IGX_TU_ENTRIES(1, -1) IGX_TU_ENTRIES(2, -1) IGX_TU_ENTRIES(3, 0) IGX_TU_ENTRIES(3, 1) IGX_TU_ENTRIES(3, 2)
+#undef IGX_TU_ENTRIES
 int igx_tu_scalar(std::integral_constant<int, 1>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order);
 int igx_tu_scalar(std::integral_constant<int, 2>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order);
 int igx_tu_scalar(std::integral_constant<int, 3>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order);
-static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out);
-static int dispatch_by_dim(IGX g, const SpaceDev &S, const OutDev &out) {
+static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out, VsMode mode = VsMode::VECTOR);
+// entry(dimension, form group) of the unit that holds the space's dimension (dim 3: the three form groups in turn)
+template <class Entry>
+static int unit_by_dim(IGX g, Entry &&entry) {
   using std::integral_constant;
   switch (g->s.dim) {
-  case 1: return igx_tu_dispatch(integral_constant<int, 1>(), integral_constant<int, -1>(), g, S, out);
-  case 2: return igx_tu_dispatch(integral_constant<int, 2>(), integral_constant<int, -1>(), g, S, out);
+  case 1: return entry(integral_constant<int, 1>(), integral_constant<int, -1>());
+  case 2: return entry(integral_constant<int, 2>(), integral_constant<int, -1>());
   default: {
-    int rc = igx_tu_dispatch(integral_constant<int, 3>(), integral_constant<int, 0>(), g, S, out);
-    if (rc == IGX_NOT_MINE) rc = igx_tu_dispatch(integral_constant<int, 3>(), integral_constant<int, 1>(), g, S, out);
-    if (rc == IGX_NOT_MINE) rc = igx_tu_dispatch(integral_constant<int, 3>(), integral_constant<int, 2>(), g, S, out);
+    int rc = entry(integral_constant<int, 3>(), integral_constant<int, 0>());
+    if (rc == IGX_NOT_MINE) rc = entry(integral_constant<int, 3>(), integral_constant<int, 1>());
+    if (rc == IGX_NOT_MINE) rc = entry(integral_constant<int, 3>(), integral_constant<int, 2>());
     return rc;
   }
   }
 }
+static int dispatch_by_dim(IGX g, const SpaceDev &S, const OutDev &out) { return unit_by_dim(g, [&](auto d, auto gr) { return igx_tu_dispatch(d, gr, g, S, out); }); }
+static int matfree_by_dim(IGX g, const SpaceDev &S, const OutDev &out, VsMode mode, const ActionCols *cols) { return unit_by_dim(g, [&](auto d, auto gr) { return igx_tu_matfree(d, gr, g, S, out, mode, cols); }); }
 
 // ------------------------------------------------------------------ the drivers
 // The overlap marks of an assembly with a communicator (IGX_OVERLAP): slab_done records "upper face of axis 2 assembled" on the engine
@@ -1100,21 +1094,29 @@ extern "C" int IGXComputeFunction(IGX g, IGXVec U, IGXVec F) { if (!U) return fa
 extern "C" int IGXComputeJacobian(IGX g, IGXVec U, IGXMat J) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_JACOBIAN, J, nullptr, U, nullptr, 0, 0); }
 extern "C" int IGXComputeIFunction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec F) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_IFUNCTION, nullptr, F, U, V, a, t); }
 extern "C" int IGXComputeIJacobian(IGX g, double a, IGXVec V, double t, IGXVec U, IGXMat J) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); return compute(g, OP_IJACOBIAN, J, nullptr, U, V, a, t); }
-// The matrix-free drivers: one pass of vec_sumfact (vec_sumfact.hpp) over the elements with the op's instantiation -- ACTION, DIAGONAL or
-// DIAGONAL + BLOCK -- or a refusal with IGX_ERR_SUP: there is no other kernel.  The nres result columns R are zeroed and assembled like
-// vectors; on several ranks X, U and V hold their ghosts and one IGXReduceGhostRows(iga, NULL, R[j]) per column completes the ghost rows.
-// The nine entries below check their own arguments; what they share is here, once.
-static int compute_matfree(IGX g, int op, IGXVec U, IGXVec V, IGXVec X, int nres, IGXVec *R, double shift, double t) {
-  const bool block = op_is_block_diagonal(op);
-  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
-  for (int j = 0; j < nres; ++j) if ((U && U == R[j]) || (V && V == R[j])) return fail(IGX_ERR_ARG_WRONG, block ? "a block column must not be a state vector" : "the result must not be a state vector");
-  if (int rc = ensure_device(g)) return rc;
+// The matrix-free drivers: passes of vec_sumfact (vec_sumfact.hpp) over the elements in the mode's instantiation of the operator igx_op
+// (IGX_OP_MATRIX / _JACOBIAN / _IJACOBIAN), or a refusal with IGX_ERR_SUP: there is no other kernel.  The nres result
+// columns R are zeroed and assembled like vectors; on several ranks X, U and V hold their ghosts and one IGXReduceGhostRows(iga, NULL, R[j])
+// per column completes the ghost rows.  ACTION: nx = nres = 1, one pass.  ACTION_BATCH: Y_j = A X_j for nx = nres columns,
+// IGX_ACTION_MAXCOLS of them per pass (what does not depend on the direction is done once per element and chunk), so
+// last_launches = colours x ceil(nx / IGX_ACTION_MAXCOLS); a run-time struct (IGX_FORM_SOURCE) has no batched instantiation yet: its columns
+// go through the single-column kernel one by one (colours x nx launches), and the kernel name says so.  The diagonals: nx = 0.
+// The entries below and the solve loops check their own arguments; what they share is here, once.
+static int compute_matfree(IGX g, VsMode mode, int igx_op, IGXVec U, IGXVec V, int nx, IGXVec *X, int nres, IGXVec *R, double shift, double t) {
+  const VsTraits tr = vs_traits(mode);
   const Space &s = g->s;
+  if ((U && U->iga != g) || (V && V->iga != g)) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  for (int j = 0; j < nres; ++j) if ((U && U == R[j]) || (V && V == R[j])) return fail(IGX_ERR_ARG_WRONG, tr.block ? "a block column must not be a state vector" : "the result must not be a state vector");
+  if (tr.batch) {      // (the block calls' pinned order, include/petiga_amd.h: the form and the space ahead of the first HIP call)
+    if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
+    if (const MfRefusal r = matfree_refusal(s, g->kernel_choice, mode, nullptr, MfCaller::FORM)) return fail(r.code, r.msg);
+  }
+  if (int rc = ensure_device(g)) return rc;
   if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
   OutDev out; memset(&out, 0, sizeof(out));
-  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
-  if (block) for (int j = 0; j < nres; ++j) out.bcol[j] = R[j]->a.as<double>();
-  out.vec = R[0]->a.as<double>(); out.X = X ? X->a.as<double>() : nullptr;
+  out.op = matfree_op(mode, igx_op); out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
+  if (tr.block) for (int j = 0; j < nres; ++j) out.bcol[j] = R[j]->a.as<double>();
+  if (!tr.batch) { out.vec = R[0]->a.as<double>(); out.X = nx ? X[0]->a.as<double>() : nullptr; }
   out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
   if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
   for (int j = 0; j < nres; ++j) HIPCK(hipMemsetAsync(R[j]->a.p, 0, R[j]->a.bytes, g->stream));
@@ -1122,8 +1124,23 @@ static int compute_matfree(IGX g, int op, IGXVec U, IGXVec V, IGXVec X, int nres
   const SpaceDev S = make_spacedev(g);
   g->dom = DomInfo(); g->slab_valid = 0;
   g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
-  const int rc = (s.form == IGX_FORM_SOURCE) ? launch_generic_rtc(g, S, out) : dispatch_by_dim(g, S, out);
-  if (rc) return rc;
+  const bool rtc = s.form == IGX_FORM_SOURCE;
+  int launches = 0;
+  for (int j0 = 0; j0 < (tr.batch ? nx : 1); j0 += rtc ? 1 : IGX_ACTION_MAXCOLS) {      // (one pass unless ACTION_BATCH: a chunk of columns, a struct's next column)
+    ActionCols cols; memset(&cols, 0, sizeof(cols));
+    if (tr.batch && rtc) { out.X = X[j0]->a.as<double>(); out.vec = R[j0]->a.as<double>(); }
+    else if (tr.batch) {
+      cols.nc = std::min(nx - j0, (int)IGX_ACTION_MAXCOLS);
+      for (int c = 0; c < cols.nc; ++c) { cols.X[c] = X[j0 + c]->a.as<double>(); cols.Y[c] = R[j0 + c]->a.as<double>(); }
+    }
+    if (int rc = rtc ? launch_generic_rtc(g, S, out, mode) : matfree_by_dim(g, S, out, mode, tr.batch ? &cols : nullptr)) return rc;
+    launches += g->last_launches;
+  }
+  g->last_launches = launches;
+  if (tr.batch && rtc) {
+    const size_t at = g->last_kernel.find("matrix action:");
+    if (at != std::string::npos) g->last_kernel.replace(at, 14, "matrix action on a block, column by column:");
+  }
   if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
   return 0;
 }
@@ -1137,55 +1154,12 @@ static int action_args(IGX g, IGXVec X, IGXVec Y) {
   if (X->iga != g || Y->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
   return 0;
 }
-extern "C" int IGXComputeMatrixAction(IGX g, IGXVec X, IGXVec Y) { if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_MATRIX_ACTION, nullptr, nullptr, X, 1, &Y, 0, 0); }
-extern "C" int IGXComputeJacobianAction(IGX g, IGXVec U, IGXVec X, IGXVec Y) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_JACOBIAN_ACTION, U, nullptr, X, 1, &Y, 0, 0); }
-extern "C" int IGXComputeIJacobianAction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec X, IGXVec Y) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, OP_IJACOBIAN_ACTION, U, V, X, 1, &Y, a, t); }
+extern "C" int IGXComputeMatrixAction(IGX g, IGXVec X, IGXVec Y) { if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, VsMode::ACTION, IGX_OP_MATRIX, nullptr, nullptr, 1, &X, 1, &Y, 0, 0); }
+extern "C" int IGXComputeJacobianAction(IGX g, IGXVec U, IGXVec X, IGXVec Y) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, VsMode::ACTION, IGX_OP_JACOBIAN, U, nullptr, 1, &X, 1, &Y, 0, 0); }
+extern "C" int IGXComputeIJacobianAction(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec X, IGXVec Y) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = action_args(g, X, Y)) return rc; return compute_matfree(g, VsMode::ACTION, IGX_OP_IJACOBIAN, U, V, 1, &X, 1, &Y, a, t); }
 
-// The actions on a block of vectors: Y_j = A X_j for nx columns, IGX_ACTION_MAXCOLS of them per launch (vec_sumfact, BATCH: what does not
-// depend on the direction is done once per element and chunk).  The nx results are zeroed, the colours are walked once
-// per chunk, last_launches = colours x ceil(nx / IGX_ACTION_MAXCOLS).  A run-time struct (IGX_FORM_SOURCE) has no batched instantiation yet:
-// its columns go through the single-column kernel one by one inside this call (colours x nx launches), and the kernel name says so.
-// Refusals: the single action's, under the block call's name.  The entries below and IGXEigenSolve check the arguments.
+// The actions on a block of vectors (compute_matfree, ACTION_BATCH).  Refusals: the single action's, under the block call's name.
 constexpr int ACTION_BLOCK_MAX = 48;      // columns of a block call at the most (= BV_MAX: the block-vector limit, block_vec.hpp)
-static const char *const ACTION_BLOCK_WHERE = "the matrix action on a block runs where the matrix action runs, and ";
-static int compute_matfree_block(IGX g, int op, IGXVec U, IGXVec V, int nx, IGXVec *X, IGXVec *Y, double shift, double t) {
-  const Space &s = g->s;
-  if (s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
-  if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string(ACTION_BLOCK_WHERE) + why);
-  if (int rc = ensure_device(g)) return rc;
-  OutDev out; memset(&out, 0, sizeof(out));
-  out.op = op; out.shift = shift; out.t = t; out.errflag = g->errflag.as<int>(); out.bid = -1;
-  out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
-  if (g->timing) HIPCK(hipEventRecord(g->ev[0], g->stream));
-  for (int j = 0; j < nx; ++j) HIPCK(hipMemsetAsync(Y[j]->a.p, 0, Y[j]->a.bytes, g->stream));
-  if (g->timing) HIPCK(hipEventRecord(g->ev[1], g->stream));
-  const SpaceDev S = make_spacedev(g);
-  g->dom = DomInfo(); g->slab_valid = 0;
-  g->zero_matrix = nullptr; g->slab_done = nullptr; g->face_done = nullptr;
-  const bool bycolumn = s.form == IGX_FORM_SOURCE;
-  int launches = 0;
-  for (int j0 = 0; j0 < nx; j0 += bycolumn ? 1 : IGX_ACTION_MAXCOLS) {
-    int rc;
-    if (bycolumn) { out.X = X[j0]->a.as<double>(); out.vec = Y[j0]->a.as<double>(); rc = launch_generic_rtc(g, S, out); }
-    else {
-      ActionCols cols; memset(&cols, 0, sizeof(cols));
-      cols.nc = std::min(nx - j0, (int)IGX_ACTION_MAXCOLS);
-      for (int c = 0; c < cols.nc; ++c) { cols.X[c] = X[j0 + c]->a.as<double>(); cols.Y[c] = Y[j0 + c]->a.as<double>(); }
-      g->action_cols = &cols;
-      rc = dispatch_by_dim(g, S, out);
-      g->action_cols = nullptr;
-    }
-    if (rc) return rc == IGX_ERR_SUP ? fail(rc, ACTION_BLOCK_WHERE + std::string(g_err)) : rc;
-    launches += g->last_launches;
-  }
-  g->last_launches = launches;
-  if (bycolumn) {
-    const size_t at = g->last_kernel.find("matrix action:");
-    if (at != std::string::npos) g->last_kernel.replace(at, 14, "matrix action on a block, column by column:");
-  }
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
-  return 0;
-}
 // the pinned order of the block calls' refusals (include/petiga_amd.h), all ahead of the first HIP call
 static int action_block_args(IGX g, bool needU, IGXVec U, bool needV, IGXVec V, int nx, IGXVec *X, IGXVec *Y) {
   NEEDIGA(g);
@@ -1204,9 +1178,9 @@ static int action_block_args(IGX g, bool needU, IGXVec U, bool needV, IGXVec V, 
   }
   return 0;
 }
-extern "C" int IGXComputeMatrixActionBlock(IGX g, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, false, nullptr, false, nullptr, nx, X, Y)) return rc; return compute_matfree_block(g, OP_MATRIX_ACTION, nullptr, nullptr, nx, X, Y, 0, 0); }
-extern "C" int IGXComputeJacobianActionBlock(IGX g, IGXVec U, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, true, U, false, nullptr, nx, X, Y)) return rc; return compute_matfree_block(g, OP_JACOBIAN_ACTION, U, nullptr, nx, X, Y, 0, 0); }
-extern "C" int IGXComputeIJacobianActionBlock(IGX g, double a, IGXVec V, double t, IGXVec U, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, true, U, true, V, nx, X, Y)) return rc; return compute_matfree_block(g, OP_IJACOBIAN_ACTION, U, V, nx, X, Y, a, t); }
+extern "C" int IGXComputeMatrixActionBlock(IGX g, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, false, nullptr, false, nullptr, nx, X, Y)) return rc; return compute_matfree(g, VsMode::ACTION_BATCH, IGX_OP_MATRIX, nullptr, nullptr, nx, X, nx, Y, 0, 0); }
+extern "C" int IGXComputeJacobianActionBlock(IGX g, IGXVec U, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, true, U, false, nullptr, nx, X, Y)) return rc; return compute_matfree(g, VsMode::ACTION_BATCH, IGX_OP_JACOBIAN, U, nullptr, nx, X, nx, Y, 0, 0); }
+extern "C" int IGXComputeIJacobianActionBlock(IGX g, double a, IGXVec V, double t, IGXVec U, int nx, IGXVec *X, IGXVec *Y) { if (int rc = action_block_args(g, true, U, true, V, nx, X, Y)) return rc; return compute_matfree(g, VsMode::ACTION_BATCH, IGX_OP_IJACOBIAN, U, V, nx, X, nx, Y, a, t); }
 extern "C" int IGXSetBatchedActions(IGX g, int flag) { NEEDIGA(g); g->batched_actions = flag ? 1 : 0; return 0; }
 
 // Matrix-free diagonals: D = diag A of the matrix the matching action applies (IGAElementFixJacobian included: a fixed dof holds the
@@ -1217,9 +1191,9 @@ static int diagonal_args(IGX g, IGXVec D) {
   if (D->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
   return 0;
 }
-extern "C" int IGXComputeMatrixDiagonal(IGX g, IGXVec D) { if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, OP_MATRIX_DIAGONAL, nullptr, nullptr, nullptr, 1, &D, 0, 0); }
-extern "C" int IGXComputeJacobianDiagonal(IGX g, IGXVec U, IGXVec D) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, OP_JACOBIAN_DIAGONAL, U, nullptr, nullptr, 1, &D, 0, 0); }
-extern "C" int IGXComputeIJacobianDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec D) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, OP_IJACOBIAN_DIAGONAL, U, V, nullptr, 1, &D, a, t); }
+extern "C" int IGXComputeMatrixDiagonal(IGX g, IGXVec D) { if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, VsMode::DIAGONAL, IGX_OP_MATRIX, nullptr, nullptr, 0, nullptr, 1, &D, 0, 0); }
+extern "C" int IGXComputeJacobianDiagonal(IGX g, IGXVec U, IGXVec D) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, VsMode::DIAGONAL, IGX_OP_JACOBIAN, U, nullptr, 0, nullptr, 1, &D, 0, 0); }
+extern "C" int IGXComputeIJacobianDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, IGXVec D) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); if (int rc = diagonal_args(g, D)) return rc; return compute_matfree(g, VsMode::DIAGONAL, IGX_OP_IJACOBIAN, U, V, 0, nullptr, 1, &D, a, t); }
 
 // Matrix-free point-block diagonals: the dof x dof blocks A_(a,i),(a,j) of every node a of the same operator (what PCPBJACOBI /
 // MatInvertBlockDiagonal ask of a shell matrix), in dof ordinary vectors, one per block column: B[j][node * dof + i] = A_(node,i),(node,j).
@@ -1234,9 +1208,9 @@ static int check_block_columns(IGX g, int nb, IGXVec *B) {
   }
   return 0;
 }
-extern "C" int IGXComputeMatrixBlockDiagonal(IGX g, int nb, IGXVec *B) { NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, OP_MATRIX_BLOCK_DIAGONAL, nullptr, nullptr, nullptr, nb, B, 0, 0); }
-extern "C" int IGXComputeJacobianBlockDiagonal(IGX g, IGXVec U, int nb, IGXVec *B) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, OP_JACOBIAN_BLOCK_DIAGONAL, U, nullptr, nullptr, nb, B, 0, 0); }
-extern "C" int IGXComputeIJacobianBlockDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, int nb, IGXVec *B) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, OP_IJACOBIAN_BLOCK_DIAGONAL, U, V, nullptr, nb, B, a, t); }
+extern "C" int IGXComputeMatrixBlockDiagonal(IGX g, int nb, IGXVec *B) { NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, VsMode::BLOCK_DIAGONAL, IGX_OP_MATRIX, nullptr, nullptr, 0, nullptr, nb, B, 0, 0); }
+extern "C" int IGXComputeJacobianBlockDiagonal(IGX g, IGXVec U, int nb, IGXVec *B) { if (!U) return fail(IGX_ERR_ARG_WRONG, "null state vector"); NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, VsMode::BLOCK_DIAGONAL, IGX_OP_JACOBIAN, U, nullptr, 0, nullptr, nb, B, 0, 0); }
+extern "C" int IGXComputeIJacobianBlockDiagonal(IGX g, double a, IGXVec V, double t, IGXVec U, int nb, IGXVec *B) { if (!U || !V) return fail(IGX_ERR_ARG_WRONG, "null state vector"); NEEDIGA(g); if (int rc = check_block_columns(g, nb, B)) return rc; return compute_matfree(g, VsMode::BLOCK_DIAGONAL, IGX_OP_IJACOBIAN, U, V, 0, nullptr, nb, B, a, t); }
 
 // The blocks as a preconditioner (block_diag.hpp): B <- B^-1 block by block in place (every local row; on several ranks after the
 // reduction and a refresh of each column), and Y_node = B_node X_node.  nsingular: the number of blocks with a zero or non-finite pivot,
@@ -1410,17 +1384,12 @@ extern "C" int IGXComputeFunctionJacobian(IGX g, IGXVec U, IGXVec F, IGXMat J) {
 }
 
 // ------------------------------------------------------------------ IGAComputeScalar (src/petigacomp.c:35-98)
-extern "C" int IGXComputeScalar(IGX g, IGXVec U, int kind, const double params[], int nparams, int n, double S[]) {
-  NEEDIGA(g);
-  if (int rc = ensure_device(g)) return rc;
+// What the built-in functionals and a user's (IGXComputeScalarSource, rtc.hpp) share: a row of ns partial sums per element, and one more per
+// element of a visited face; launch(Sd, out) fills them with the functional's parameters travelling like a form's; two stages of sums,
+// the read-back of S[ns], and the geometry's error flag.
+template <class Launch>
+static int reduce_scalars(IGX g, int ns, IGXVec U, const double params[], int nparams, Launch &&launch, double S[]) {
   Space &s = g->s;
-  if (U && U->iga != g) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
-  if (!S || n < 1) return fail(IGX_ERR_ARG_WRONG, "null result array");
-  const int ns = (kind == IGX_SCALAR_ERRNORM) ? 4 : (kind == IGX_SCALAR_VOLUME ? 2 : 1);
-  if (n != ns) return fail(IGX_ERR_ARG_WRONG, "this functional returns " + std::to_string(ns) + " scalars");
-  if (nparams < 0 || nparams > MAXPARAM || (nparams && !params)) return fail(IGX_ERR_ARG_OUTOFRANGE, "bad parameter list");
-  const int order = (kind == IGX_SCALAR_ERRNORM && nparams > 0) ? (int)params[0] : 0;
-  if (order < 0 || order > 2) return fail(IGX_ERR_ARG_OUTOFRANGE, "derivative order must be in range [0,2]");
   int64_t nel = (int64_t)s.elem_width[0] * s.elem_width[1] * s.elem_width[2];
   for (int a = 0; a < s.dim; ++a) for (int sd = 0; sd < 2; ++sd) {   // one more partial row per element of a visited face
     const int eface = sd ? s.elem_sizes[a] - 1 : 0;
@@ -1435,14 +1404,9 @@ extern "C" int IGXComputeScalar(IGX g, IGXVec U, int kind, const double params[]
   OutDev out; memset(&out, 0, sizeof(out));
   out.op = OP_SCALAR; out.bid = -1; out.errflag = g->errflag.as<int>(); out.vec = part; out.U = U ? U->a.as<double>() : nullptr;
   const SpaceDev Sd = make_spacedev(g);
-  const std::vector<double> keep = s.params;            // the functional's parameters travel like a form's
-  s.params.assign(params, params + nparams);
-  int rc;
-  switch (s.dim) {
-  case 1: rc = igx_tu_scalar(std::integral_constant<int, 1>(), g, kind, Sd, out, order); break;
-  case 2: rc = igx_tu_scalar(std::integral_constant<int, 2>(), g, kind, Sd, out, order); break;
-  default: rc = igx_tu_scalar(std::integral_constant<int, 3>(), g, kind, Sd, out, order); break;
-  }
+  const std::vector<double> keep = s.params;
+  s.params.assign(params, params + (params ? nparams : 0));
+  const int rc = launch(Sd, out);
   s.params = keep;
   if (rc) return rc;
   hipLaunchKernelGGL(k_sum_partials, dim3(nblk), dim3(256), 0, g->stream, part, nel, ns, stage, chunk);
@@ -1453,6 +1417,24 @@ extern "C" int IGXComputeScalar(IGX g, IGXVec U, int kind, const double params[]
   int flag = 0; HIPCK(hipMemcpy(&flag, g->errflag.p, sizeof(int), hipMemcpyDeviceToHost));
   if (flag) { HIPCK(hipMemset(g->errflag.p, 0, sizeof(int))); return fail(flag, "Non-positive det(Jacobian) of the geometry mapping"); }
   return 0;
+}
+extern "C" int IGXComputeScalar(IGX g, IGXVec U, int kind, const double params[], int nparams, int n, double S[]) {
+  NEEDIGA(g);
+  if (int rc = ensure_device(g)) return rc;
+  if (U && U->iga != g) return fail(IGX_ERR_ARG_WRONG, "state vector created by another IGX");
+  if (!S || n < 1) return fail(IGX_ERR_ARG_WRONG, "null result array");
+  const int ns = (kind == IGX_SCALAR_ERRNORM) ? 4 : (kind == IGX_SCALAR_VOLUME ? 2 : 1);
+  if (n != ns) return fail(IGX_ERR_ARG_WRONG, "this functional returns " + std::to_string(ns) + " scalars");
+  if (nparams < 0 || nparams > MAXPARAM || (nparams && !params)) return fail(IGX_ERR_ARG_OUTOFRANGE, "bad parameter list");
+  const int order = (kind == IGX_SCALAR_ERRNORM && nparams > 0) ? (int)params[0] : 0;
+  if (order < 0 || order > 2) return fail(IGX_ERR_ARG_OUTOFRANGE, "derivative order must be in range [0,2]");
+  return reduce_scalars(g, ns, U, params, nparams, [&](const SpaceDev &Sd, const OutDev &out) {
+    switch (g->s.dim) {
+    case 1: return igx_tu_scalar(std::integral_constant<int, 1>(), g, kind, Sd, out, order);
+    case 2: return igx_tu_scalar(std::integral_constant<int, 2>(), g, kind, Sd, out, order);
+    default: return igx_tu_scalar(std::integral_constant<int, 3>(), g, kind, Sd, out, order);
+    }
+  }, S);
 }
 
 // ------------------------------------------------------------------ checksums over the owned rows
@@ -2056,7 +2038,7 @@ extern "C" int IGXMultigridGetInfo(IGXMultigrid mg, int level, double *lambda, i
 static int mg_action(_p_IGXMultigrid *q, int k, IGXVec in, IGXVec out, LoopClock *clk) {
   MgLevel &l = q->lv[k]; const IGXMultigridSpec &sp = q->spec;
   const bool ij = sp.op == IGX_OP_IJACOBIAN;
-  if (int rc = compute_matfree(l.g, matfree_op(sp.op, MF_ACTION), sp.op == IGX_OP_MATRIX ? nullptr : l.U, ij ? l.V : nullptr, in, 1, &out, ij ? sp.a : 0.0, ij ? sp.t : 0.0)) return mg_refused(rc);
+  if (int rc = compute_matfree(l.g, VsMode::ACTION, sp.op, sp.op == IGX_OP_MATRIX ? nullptr : l.U, ij ? l.V : nullptr, 1, &in, 1, &out, ij ? sp.a : 0.0, ij ? sp.t : 0.0)) return mg_refused(rc);
   if (k == q->L - 1) q->action = l.g->last_kernel;
   return clk ? mg_driver(*clk, l.g) : 0;
 }
@@ -2089,7 +2071,7 @@ extern "C" int IGXMultigridSetUp(IGXMultigrid mg) {
       for (auto &v : l.dv) l.cols.push_back(v.get());
     }
     IGXVec U = sp.op == IGX_OP_MATRIX ? nullptr : l.U, V = ij ? l.V : nullptr;
-    if (int rc = compute_matfree(g, matfree_op(sp.op, pb ? MF_BLOCK_DIAGONAL : MF_DIAGONAL), U, V, nullptr, (int)l.cols.size(), l.cols.data(), ij ? sp.a : 0.0, ij ? sp.t : 0.0)) return mg_refused(rc);
+    if (int rc = compute_matfree(g, pb ? VsMode::BLOCK_DIAGONAL : VsMode::DIAGONAL, sp.op, U, V, 0, nullptr, (int)l.cols.size(), l.cols.data(), ij ? sp.a : 0.0, ij ? sp.t : 0.0)) return mg_refused(rc);
     if (pb) if (int rc = block_diagonal_run(g, g->s.dof, l.cols.data(), nullptr, nullptr, nullptr, true)) return mg_refused(rc);
     // lambda: power_its steps on D^-1 A from v_i = sin(1 + i); after each step lambda = |D^-1 A v| / |v|, and v <- D^-1 A v / |D^-1 A v|
     IGXVec v = l.work[MG_X].get(), w = l.work[MG_W].get(), z = l.work[MG_D].get();

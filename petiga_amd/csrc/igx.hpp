@@ -266,12 +266,34 @@ struct ActionCols {
 };
 
 #ifndef IGX_RTC
-// The matrix-free actions (OP_MATRIX_ACTION / OP_JACOBIAN_ACTION / OP_IJACOBIAN_ACTION) run on vec_sumfact (vec_sumfact.hpp, ACTION) or not at all: why not, or null.
-// Boundary loads do not enter a matrix and are ignored.
-inline bool op_is_action(int op) { return op == OP_MATRIX_ACTION || op == OP_JACOBIAN_ACTION || op == OP_IJACOBIAN_ACTION; }
 // the drivers that assemble a matrix / a vector (IGAComputeSystem does both)
 inline bool op_has_matrix(int op) { return op == OP_SYSTEM || op == OP_MATRIX || op == OP_JACOBIAN || op == OP_IJACOBIAN; }
 inline bool op_has_vector(int op) { return op == OP_SYSTEM || op == OP_VECTOR || op == OP_FUNCTION || op == OP_IFUNCTION; }
+
+// What one pass of vec_sumfact (vec_sumfact.hpp) forms: the vector of a vector-only driver, or one of the matrix-free operators -- Y = A X,
+// the same on a block of columns in one launch, D = diag A, the dof x dof point blocks -- which run on that kernel or not at all
+// (DESIGN.md 3.23).  The mode is named once, here; its traits are the only place that knows the kernel's four booleans.
+enum class VsMode { VECTOR, ACTION, ACTION_BATCH, DIAGONAL, BLOCK_DIAGONAL };
+struct VsTraits {
+  bool action, diagonal, block, batch;      // vec_sumfact's template parameters ACTION, DIAGONAL, BLOCK, BATCH
+  bool wide;                                // the layouts of one workgroup per element, 6 and 8 lanes per axis, exist (degrees 4 to 7)
+  const char *words;                        // the mode's part of the kernel name
+};
+constexpr VsTraits vs_traits(VsMode m) {
+  switch (m) {
+  case VsMode::ACTION:         return {true, false, false, false, true, "matrix action: sum factorisation forward and backward, "};
+  case VsMode::ACTION_BATCH:   return {true, false, false, true, true, "matrix action on a block: sum factorisation forward and backward, "};
+  case VsMode::DIAGONAL:       return {false, true, false, false, true, "matrix diagonal: sum factorisation forward, product rows backward, "};
+  case VsMode::BLOCK_DIAGONAL: return {false, true, true, false, true, "matrix block diagonal: sum factorisation forward, product rows backward per field pair, "};
+  default:                     return {false, false, false, false, false, "vector only: sum factorisation forward and backward, "};
+  }
+}
+// the mode of an op (ACTION_BATCH is the driver's choice for a block of columns), and the op of a mode for IGX_OP_MATRIX / _JACOBIAN / _IJACOBIAN
+inline VsMode vs_mode_of(int op) {
+  return op < OP_MATRIX_ACTION || op > OP_IJACOBIAN_BLOCK_DIAGONAL ? VsMode::VECTOR : op < OP_MATRIX_DIAGONAL ? VsMode::ACTION : op < OP_MATRIX_BLOCK_DIAGONAL ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL;
+}
+inline int matfree_op(VsMode m, int igx_op) { return (vs_traits(m).block ? OP_MATRIX_BLOCK_DIAGONAL : vs_traits(m).diagonal ? OP_MATRIX_DIAGONAL : OP_MATRIX_ACTION) + igx_op; }
+
 // basis functions and points of axis d: the basis' once the space is set up, before that what the axes and rules set so far will give (src/petigabasis.c:103)
 inline void vec_axis_sizes(const Space &s, int d, int &nen, int &nqp) {
   if (s.setup) { nen = s.basis[d].nen; nqp = s.basis[d].nqp; }
@@ -283,32 +305,25 @@ inline int vec_lanes_per_axis(const Space &s) {
   for (int d = 0; d < 3; ++d) { int nen, nqp; vec_axis_sizes(s, d, nen, nqp); m = nen > m ? nen : m; m = nqp > m ? nqp : m; }
   return m;
 }
-inline const char *vec_action_refusal(const Space &s, int kernel_choice) {
-  for (int d = 0; d < s.dim; ++d) for (int sd = 0; sd < 2; ++sd) if (s.visit[d][sd]) return "the matrix action does not cover boundary-form passes (IGXSetBoundaryForm): it runs on vec_sumfact alone";
-  if (s.dim != 3) return "the matrix action needs dim = 3 (vec_sumfact: sum factorisation in three dimensions)";
-  if (s.nsd != 0 && s.nsd != 3) return "the matrix action needs a geometry with nsd = dim";
-  if (vec_lanes_per_axis(s) > 8) return "the matrix action needs nen <= 8 and nqp <= 8 on every axis (degree <= 7)";
-  if (s.env.vec_sumfact == 0) return "the matrix action runs on vec_sumfact alone, and IGX_VEC_SUMFACT=0 switches that kernel off";
-  if (kernel_choice != 0) return "the matrix action runs on vec_sumfact alone: IGXSetKernel must leave the choice automatic (0)";
-  return nullptr;
+// The layout of a launch of vec_sumfact in a mode, for the built-in forms (try_vec_sumfact) and the run-time structs (launch_vecsf_rtc)
+// alike.  compile_only (IGXCheckFormSource): the space may not be set up, the degrees decide.
+struct VsLaunch {
+  int ns;                  // lanes per axis: 3 two elements per wavefront (p <= 2), 4 one; 6 and 8 one workgroup per element (wide modes)
+  unsigned threads;        // per workgroup (vs_layout<ns>::THREADS)
+  const char *tail;        // the layout's part of the kernel name
+  // (one pass per wavefront: the launch has a wavefront per unit -- UNITS = 1 in the kernel)
+  unsigned grid(long long nelem) const { return ns > 4 ? (unsigned)nelem : (unsigned)((nelem + (ns == 3 ? 7 : 3)) / (ns == 3 ? 8 : 4)); }
+};
+inline VsLaunch vs_launch_of(const Space &s, VsMode m, bool compile_only = false) {
+  const int lanes = vs_traits(m).wide ? vec_lanes_per_axis(s) : 4;      // (the vector-only drivers stay at 4 and below: vec_sumfact_covers)
+  if (lanes > 6) return {8, 512, "one workgroup per element, 8 x 8 x 8 lanes)"};
+  if (lanes > 4) return {6, 256, "one workgroup per element, 6 x 6 x 6 lanes)"};
+  // at most three basis functions and points per axis (p <= 2): two elements per wavefront (54 of 64 lanes instead of 27)
+  bool three = !s.env.no_vec_pairs;
+  for (int d = 0; d < 3; ++d) three = three && (compile_only ? s.axis[d].p >= 1 && s.axis[d].p <= 2 : s.basis[d].nen <= 3 && s.basis[d].nqp <= 3);
+  if (three) return {3, 256, "two elements per wavefront)"};
+  return {4, 256, "one wavefront per element)"};
 }
-// The matrix-free diagonals (OP_*_DIAGONAL) run where the actions run (vec_sumfact.hpp, DIAGONAL), first-order shape features only:
-// the same checks, asked through vec_action_refusal, under the diagonal's name.
-inline bool op_is_diagonal(int op) { return op == OP_MATRIX_DIAGONAL || op == OP_JACOBIAN_DIAGONAL || op == OP_IJACOBIAN_DIAGONAL; }
-inline std::string vec_diagonal_refusal(const Space &s, int kernel_choice) {
-  const char *why = vec_action_refusal(s, kernel_choice);
-  return why ? std::string("the matrix diagonal runs where the matrix action runs, and ") + why : std::string();
-}
-constexpr const char *VEC_DIAGONAL_SECOND = "the matrix diagonal does not cover forms with second-order shape features (Cahn-Hilliard's Laplacian): six product rows per axis and 55 coefficient slots per point are another kernel";
-constexpr const char *VEC_DIAGONAL_GENERAL = "the matrix diagonal does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives";
-constexpr const char *VEC_DIAGONAL_BOUNDARY = "the matrix diagonal does not cover forms with a boundary branch or functionals";
-// The point-block diagonals (OP_*_BLOCK_DIAGONAL) run where the diagonals run (vec_sumfact.hpp, DIAGONAL + BLOCK): the diagonal's checks and
-// reasons, asked through the functions and constants above, under the block diagonal's name.
-inline bool op_is_block_diagonal(int op) { return op == OP_MATRIX_BLOCK_DIAGONAL || op == OP_JACOBIAN_BLOCK_DIAGONAL || op == OP_IJACOBIAN_BLOCK_DIAGONAL; }
-inline std::string vec_block_diagonal_reason(const std::string &diagonal_reason) {
-  return diagonal_reason.empty() ? diagonal_reason : std::string("the matrix block diagonal runs where the matrix diagonal runs, and ") + diagonal_reason;
-}
-inline std::string vec_block_diagonal_refusal(const Space &s, int kernel_choice) { return vec_block_diagonal_reason(vec_diagonal_refusal(s, kernel_choice)); }
 #endif
 
 constexpr int MAXPARAM = 8;

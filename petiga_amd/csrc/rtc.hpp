@@ -81,7 +81,7 @@ struct RtcForm {
   hipModule_t module = nullptr; hipFunction_t func = nullptr;
   std::map<int, std::shared_ptr<RtcFeature>> feature;   // key: TA | NW << 4 | DOFI << 8 | HASM << 12
   std::map<int, std::shared_ptr<RtcFeature>> pencil;    // form_pencil instantiations; key: SYSTEM | P << 1 | IDENT << 4 | RAT << 5
-  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | two elements per wavefront << 1 | ACTION << 2 | DIAGONAL << 3 | 6 lanes << 4 | 8 lanes << 5 | BLOCK << 6 | one workgroup per element with 6 (8) lanes per axis << 4 (5)
+  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | lanes per axis << 1 | mode << 5 (launch_vecsf_rtc)
   std::map<int, std::shared_ptr<RtcFeature>> state;     // state_pencil instantiations; key: P (+ 10 + rational on a mapped geometry, + 100 packed tiles)
   std::map<int, std::shared_ptr<RtcFeature>> block;     // block_pencil instantiations; key: SYSTEM
   std::map<int, std::shared_ptr<RtcFeature>> band;      // band_points + band_pt instantiations; key: GEO | RAT << 1 | degree << 2
@@ -369,27 +369,24 @@ static bool rtc_vecsf_eligible(const Space &s, const RtcForm &F, const OutDev &o
   }
   return true;
 }
-// action: the ACTION instantiation (the matrix-free product of IGXCompute*Action); the caller has asked vec_action_refusal
-// diagonal: the DIAGONAL instantiation (IGXCompute*Diagonal), likewise; a struct of SHAPE_ORDER <= 1
-// block: DIAGONAL with BLOCK (IGXCompute*BlockDiagonal): the dof x dof point blocks into out.bcol
-static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done, bool compile_only = false, bool action = false, bool diagonal = false, bool block = false) {
+// mode: the instantiation of that mode (igx.hpp: VsMode), in the layout vs_launch_of gives; the matrix-free modes' caller has asked
+// matfree_refusal.  A struct has no ACTION_BATCH instantiation yet: its columns come one by one (compute_matfree)
+static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done, VsMode mode = VsMode::VECTOR, bool compile_only = false) {
   done = false;
-  if (block) diagonal = true;
   const Space &s = g->s;
-  if (!compile_only && !action && !diagonal && !rtc_vecsf_eligible(s, F, out)) return 0;
+  const VsTraits t = vs_traits(mode);
+  if (t.batch) return fail(IGX_ERR_PLIB, "a run-time struct has no instantiation of vec_sumfact on a block of columns");
+  if (!compile_only && mode == VsMode::VECTOR && !rtc_vecsf_eligible(s, F, out)) return 0;
   const bool geo = s.nsd > 0 || s.rational;
-  bool three = !s.env.no_vec_pairs;      // p <= 2: two elements per wavefront
-  for (int d = 0; d < 3; ++d) three = three && s.axis[d].p >= 1 && s.axis[d].p <= 2 && (compile_only || (s.basis[d].nen <= 3 && s.basis[d].nqp <= 3));
-  const int ns = (action || diagonal) ? vec_lanes_per_axis(s) : 4;      // above 4: one workgroup per element, 6 or 8 lanes per axis (the vector-only drivers stay below)
-  const int wg = ns > 6 ? 8 : (ns > 4 ? 6 : 0);
-  if (wg) three = false;
-  const int key = (geo ? 1 : 0) | (three ? 2 : 0) | (action ? 4 : 0) | (diagonal ? 8 : 0) | (wg == 6 ? 16 : 0) | (wg == 8 ? 32 : 0) | (block ? 64 : 0);
+  const VsLaunch L = vs_launch_of(s, mode, compile_only);
+  const int key = (geo ? 1 : 0) | L.ns << 1 | (int)mode << 5;
   std::shared_ptr<RtcFeature> K;
   auto it = F.vecsf.find(key);
   if (it != F.vecsf.end() && (it->second->module || compile_only)) K = it->second;
   else {
     K.reset(new RtcFeature());
-    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + (wg == 8 ? "8" : (wg == 6 ? "6" : (three ? "3" : "4"))) + (block ? ", false, true, true>" : (diagonal ? ", false, true>" : (action ? ", true>" : ">")));
+    // (the booleans up to the last that is set: the names the ABI tests instantiate)
+    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + std::to_string(L.ns) + (t.block ? ", false, true, true>" : (t.diagonal ? ", false, true>" : (t.action ? ", true>" : ">")));
     const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, long long);\n";
     if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, false, true)) return rc;
     if (!compile_only) {
@@ -406,13 +403,12 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
     args.cr = cr; args.nelem = (long long)cr.count[0] * cr.count[1] * cr.count[2];
     size_t asz = sizeof(args);
     void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    const unsigned want = wg ? (unsigned)args.nelem : (unsigned)((args.nelem + (three ? 7 : 3)) / (three ? 8 : 4));      // (a wavefront walks a sequence of elements: vec_sumfact.hpp, round 6)
-    HIPCK(hipModuleLaunchKernel(K->func[0], want, 1, 1, wg == 8 ? 512 : 256, 1, 1, 0, g->stream, nullptr, cfg));
+    HIPCK(hipModuleLaunchKernel(K->func[0], L.grid(args.nelem), 1, 1, L.threads, 1, 1, 0, g->stream, nullptr, cfg));
     launches++;
     return 0;
   })) return rc;
   g->last_launches = launches;
-  g->last_kernel = std::string("vec_sumfact<") + F.name + (block ? ">(hiprtc,matrix block diagonal: sum factorisation forward, product rows backward per field pair, " : diagonal ? ">(hiprtc,matrix diagonal: sum factorisation forward, product rows backward, " : (action ? ">(hiprtc,matrix action: sum factorisation forward and backward, " : ">(hiprtc,vector only: sum factorisation forward and backward, ")) + (wg == 8 ? "one workgroup per element, 8 x 8 x 8 lanes)" : (wg == 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : (three ? "two elements per wavefront)" : "one wavefront per element)")));
+  g->last_kernel = std::string("vec_sumfact<") + F.name + ">(hiprtc," + t.words + L.tail;
   done = true;
   return 0;
 }
@@ -603,15 +599,8 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
   return rc;
 }
 
-// what of the struct itself keeps it off the DIAGONAL instantiation (meta: rtc.hpp:79), or null
-static const char *rtc_diagonal_refusal(const RtcForm &F) {
-  if (F.facts.order >= 3 || (F.facts.need & (NEED_PROP | NEED_D3U | NEED_MAPX))) return VEC_DIAGONAL_GENERAL;
-  if (F.facts.has_boundary) return "the matrix diagonal does not cover forms with a boundary branch";
-  if (F.facts.shape_order >= 2) return VEC_DIAGONAL_SECOND;
-  return nullptr;
-}
-
-static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
+// mode: a matrix-free operator (compute_matfree), or VECTOR for the drivers that assemble
+static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out, VsMode mode) {
   Space &s = g->s;
   g->rtc_note.clear();
   if (!g->rtc || g->rtc->dim != s.dim) {
@@ -621,32 +610,15 @@ static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out) {
   }
   RtcForm &F = *g->rtc;
   if (int rc = rtc_load(g, F)) return rc;
-  const int DOF = F.facts.dof;
+  if (mode != VsMode::VECTOR) {      // the matrix-free operators: vec_sumfact's instantiation of the struct or a refusal, as for the built-in forms
+    if (const MfRefusal r = matfree_refusal(s, g->kernel_choice, mode, &F.facts, MfCaller::STRUCT)) return fail(r.code, r.msg);
+    const VsTraits t = vs_traits(mode);
+    bool done = false;
+    if (int rc = launch_vecsf_rtc(g, F, S, out, done, t.batch ? VsMode::ACTION : mode)) return rc;      // (a block's columns come one by one)
+    return done ? 0 : fail(IGX_ERR_PLIB, std::string("vec_sumfact did not take a ") + (t.block ? "matrix block diagonal" : t.diagonal ? "matrix diagonal" : "matrix action") + " it covers");
+  }
   if (F.facts.nscalar > 0) return fail(IGX_ERR_SUP, "a struct with NSCALAR is a functional: IGXComputeScalarSource");
-  if (s.dof != DOF) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
-  if (op_is_action(out.op)) {      // the matrix-free actions: vec_sumfact's ACTION instantiation of the struct or a refusal, as for the built-in forms
-    if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);
-    if (F.facts.order >= 3 || (F.facts.need & (NEED_PROP | NEED_D3U | NEED_MAPX))) return fail(IGX_ERR_SUP, "the matrix action does not cover forms of order 3 or forms that read the property array or the geometry map's derivatives");
-    if (F.facts.has_boundary) return fail(IGX_ERR_SUP, "the matrix action does not cover forms with a boundary branch");
-    bool done = false;
-    if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, true)) return rc;
-    return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix action it covers");
-  }
-  if (op_is_diagonal(out.op)) {    // the matrix-free diagonals: vec_sumfact's DIAGONAL instantiation of the struct or a refusal, as for the built-in forms
-    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
-    if (const char *why = rtc_diagonal_refusal(F)) return fail(IGX_ERR_SUP, why);
-    bool done = false;
-    if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, false, true)) return rc;
-    return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix diagonal it covers");
-  }
-  if (op_is_block_diagonal(out.op)) {    // the point-block diagonals: the DIAGONAL + BLOCK instantiation or the diagonal's refusal under the block diagonal's name
-    { const std::string why = vec_block_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
-    if (const char *why = rtc_diagonal_refusal(F)) return fail(IGX_ERR_SUP, vec_block_diagonal_reason(why));
-    if (s.dof != F.facts.dof) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
-    bool done = false;
-    if (int rc = launch_vecsf_rtc(g, F, S, out, done, false, false, true, true)) return rc;
-    return done ? 0 : fail(IGX_ERR_PLIB, "vec_sumfact did not take a matrix block diagonal it covers");
-  }
+  if (s.dof != F.facts.dof) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
   // a struct of ORDER 3, or one that reads the property array / the point's shape table / third derivatives of the state: the general kernel (as launch_generic)
   if (F.facts.order >= 3 || (F.facts.need & (NEED_PROP | NEED_D3U | NEED_MAPX)) || (s.nsd && s.nsd != s.dim)) {      // (... or a geometry with nsd != dim)
     if (g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a form of order 3 or one that reads the property array runs on the general kernel only");
@@ -751,33 +723,7 @@ extern "C" int IGXComputeScalarSource(IGX g, IGXVec U, const char *source, const
   if (n != ns) return fail(IGX_ERR_ARG_WRONG, "this functional returns " + std::to_string(ns) + " scalars");
   if (F.facts.dof != s.dof) return fail(IGX_ERR_ARG_WRONG, "functional does not match the number of fields (dof)");
   if ((F.facts.need & (NEED_U | NEED_GU | NEED_HU)) && !U) return fail(IGX_ERR_ARG_WRONG, "the functional reads the state: null vector");
-  int64_t nel = (int64_t)s.elem_width[0] * s.elem_width[1] * s.elem_width[2];
-  for (int a = 0; a < s.dim; ++a) for (int sd = 0; sd < 2; ++sd) {   // one more partial row per element of a visited face
-    const int eface = sd ? s.elem_sizes[a] - 1 : 0;
-    if (s.visit[a][sd] && eface >= s.elem_start[a] && eface < s.elem_start[a] + s.elem_width[a]) nel += (int64_t)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] / s.elem_width[a];
-  }
-  const int nblk = (int)std::min<int64_t>(1024, (nel + 255) / 256);
-  const int64_t chunk = (nel + nblk - 1) / nblk;
-  const size_t need = ((size_t)nel + nblk + 1) * ns * sizeof(double);
-  if (g->partials.bytes < need) { HIPCK(hipStreamSynchronize(g->stream)); if (g->partials.alloc(need)) return fail(IGX_ERR_MEM, "partial-sum buffer allocation failed"); }
-  double *part = g->partials.as<double>(), *stage = part + (size_t)nel * ns, *res = stage + (size_t)nblk * ns;
-  HIPCK(hipMemsetAsync(part, 0, (size_t)nel * ns * sizeof(double), g->stream));
-  OutDev out; memset(&out, 0, sizeof(out));
-  out.op = OP_SCALAR; out.bid = -1; out.errflag = g->errflag.as<int>(); out.vec = part; out.U = U ? U->a.as<double>() : nullptr;
-  const SpaceDev Sd = make_spacedev(g);
-  const std::vector<double> keep = s.params;
-  s.params.assign(params ? params : nullptr, params ? params + nparams : nullptr);
-  const int rc = rtc_generic_launch(g, F, Sd, out);
-  s.params = keep;
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_sum_partials, dim3(nblk), dim3(256), 0, g->stream, part, nel, ns, stage, chunk);
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, g->stream, stage, (int64_t)nblk, ns, res, (int64_t)nblk);
-  HIPCK(hipGetLastError());
-  HIPCK(hipMemcpyAsync(S, res, ns * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-  HIPCK(hipStreamSynchronize(g->stream));
-  int flag = 0; HIPCK(hipMemcpy(&flag, g->errflag.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (flag) { HIPCK(hipMemset(g->errflag.p, 0, sizeof(int))); return fail(flag, "Non-positive det(Jacobian) of the geometry mapping"); }
-  return 0;
+  return reduce_scalars(g, ns, U, params, nparams, [&](const SpaceDev &Sd, const OutDev &out) { return rtc_generic_launch(g, F, Sd, out); }, S);
 }
 
 // Compile-only check of a run-time form against the kernels the drivers would launch for the axes set so far (no GPU needed):
@@ -804,29 +750,18 @@ extern "C" int IGXCheckFormSource(IGX g, int with_matrix, int gram) {
     if (int rc = launch_state_rtc(g, *g->rtc, Sd, o, done, true)) return rc;
     return done ? 0 : fail(IGX_ERR_SUP, "state_pencil needs dim 3, dof 1, degree 2 or 3 (2 on a mapped geometry) and a struct with PENCIL_NFEAT / PENCIL_NC / pencil_coef / pencil_trial");
   }
-  if (gram == 7) {           // ... and its ACTION instantiation (IGXCompute*Action of the struct): compile only
-    if (s.dim != 3) return fail(IGX_ERR_SUP, "the matrix action needs dim 3");
-    if (const char *why = vec_action_refusal(s, g->kernel_choice)) return fail(IGX_ERR_SUP, why);      // (where the driver would refuse)
+  if (gram >= 7 && gram <= 9) {      // ... and its ACTION / DIAGONAL / DIAGONAL with BLOCK instantiation (IGXCompute*Action, *Diagonal, *BlockDiagonal of the struct) for the
+    // layout the driver would launch: compile only, refused where the driver would refuse.  (The struct's constants are read from the loaded
+    // module; without a GPU the kernel's static_assert names the cause.)
+    const VsMode mode = gram == 7 ? VsMode::ACTION : gram == 8 ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL;
+    if (const MfRefusal r = matfree_refusal(s, g->kernel_choice, mode, gram != 7 && g->rtc->func ? &g->rtc->facts : nullptr, MfCaller::CHECK)) return fail(r.code, r.msg);
     bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, true);
-  }
-  if (gram == 8) {           // ... and its DIAGONAL instantiation (IGXCompute*Diagonal of the struct): compile only
-    if (s.dim != 3) return fail(IGX_ERR_SUP, "the matrix diagonal needs dim 3");
-    if (g->rtc->func) { if (const char *why = rtc_diagonal_refusal(*g->rtc)) return fail(IGX_ERR_SUP, why); }      // (the struct's constants are read from the loaded module; without a GPU the kernel's static_assert names the cause)
-    { const std::string why = vec_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, false, true);
-  }
-  if (gram == 9) {           // ... and DIAGONAL with BLOCK (IGXCompute*BlockDiagonal of the struct) for the layout the driver would launch: compile only
-    { const std::string why = vec_block_diagonal_refusal(s, g->kernel_choice); if (!why.empty()) return fail(IGX_ERR_SUP, why); }
-    if (g->rtc->func) { if (const char *why = rtc_diagonal_refusal(*g->rtc)) return fail(IGX_ERR_SUP, vec_block_diagonal_reason(why)); }
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true, false, true, true);
+    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, mode, true);
   }
   if (gram == 3) {           // the sum-factorised vector kernel (vec_sumfact) of the struct, with and without a geometry: compile only
     if (s.dim != 3) return fail(IGX_ERR_SUP, "the sum-factorised vector kernel needs dim 3");
     bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, true);
+    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, VsMode::VECTOR, true);
   }
   if (gram == 2) {           // the pencil walk's instantiation (form_pencil) for the current degree / geometry: compile only
     if (s.dim != 3 || (s.axis[0].p != 2 && s.axis[0].p != 3)) return fail(IGX_ERR_SUP, "the pencil walk needs dim 3 and degree 2 or 3");

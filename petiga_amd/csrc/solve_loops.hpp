@@ -67,7 +67,7 @@ struct LoopClock {
 };
 
 // Each solver's words for the checks they share; the codes and the order are the same for all.  where: the prefix of "this solver runs where
-// ..., and <reason>", put before vec_action_refusal's reason and before an inner IGX_ERR_SUP.  inner: the stepper alone puts every inner
+// ..., and <reason>", put before the reason of matfree_refusal's space rules and before an inner IGX_ERR_SUP.  inner: the stepper alone puts every inner
 // refusal, of any code, under a prefix of its own.
 struct SolverWords { const char *call, *one_rank, *where, *inner; };
 static const SolverWords kKrylovWords = {"IGXSolve", "the Krylov solve needs one rank on every axis: the library has no sum across ranks (IGXVecDot gives each rank's part)",
@@ -87,20 +87,13 @@ static int solver_pc_ready(IGX g, const SolverWords &w, int pc) {
   return 0;
 }
 static int solver_runs_here(IGX g, const SolverWords &w) {
-  if (const char *why = vec_action_refusal(g->s, g->kernel_choice)) return fail(IGX_ERR_SUP, std::string(w.where) + why);
+  if (const MfRefusal r = matfree_refusal(g->s, g->kernel_choice, VsMode::ACTION, nullptr, MfCaller::FORM)) return fail(r.code, w.where + r.msg);
   return 0;
 }
 // what an operator or an inner loop refused, with its reason under the solver's own name
 static int solver_refused(const SolverWords &w, int rc) {
   if (w.inner) return fail(rc, w.inner + std::string(g_err));
   return rc == IGX_ERR_SUP ? fail(rc, w.where + std::string(g_err)) : rc;
-}
-
-enum { MF_ACTION = 0, MF_DIAGONAL, MF_BLOCK_DIAGONAL };
-static int matfree_op(int igx_op, int kind) {
-  static const int ops[3][3] = {{OP_MATRIX_ACTION, OP_JACOBIAN_ACTION, OP_IJACOBIAN_ACTION}, {OP_MATRIX_DIAGONAL, OP_JACOBIAN_DIAGONAL, OP_IJACOBIAN_DIAGONAL},
-                                {OP_MATRIX_BLOCK_DIAGONAL, OP_JACOBIAN_BLOCK_DIAGONAL, OP_IJACOBIAN_BLOCK_DIAGONAL}};
-  return ops[kind][igx_op];
 }
 
 // ------------------------------------------------------------------ vector algebra on IGXVec and the Krylov loop (krylov.hpp)
@@ -447,13 +440,13 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
   if (int rc = clk.begin(g)) return rc;
   std::string opname;
   auto A = [&](IGXVec in, IGXVec out) -> int {
-    if (int rc = compute_matfree(g, matfree_op(sp->op, MF_ACTION), U, V, in, 1, &out, shift, t)) return solver_refused(words, rc);
+    if (int rc = compute_matfree(g, VsMode::ACTION, sp->op, U, V, 1, &in, 1, &out, shift, t)) return solver_refused(words, rc);
     if (opname.empty()) opname = g->last_kernel;
     return clk.driver(g);
   };
   std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
   if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
-    if (int rc = compute_matfree(g, matfree_op(sp->op, pc == IGX_PC_JACOBI ? MF_DIAGONAL : MF_BLOCK_DIAGONAL), U, V, nullptr, (int)cols.size(), cols.data(), shift, t)) return solver_refused(words, rc);
+    if (int rc = compute_matfree(g, pc == IGX_PC_JACOBI ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL, sp->op, U, V, 0, nullptr, (int)cols.size(), cols.data(), shift, t)) return solver_refused(words, rc);
     if (int rc = clk.driver(g)) return rc;
   }
   if (pc == IGX_PC_PBJACOBI) {
@@ -839,29 +832,29 @@ extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IG
   std::string opname;
   int actions = 0;
   auto actA = [&](IGXVec in, IGXVec out) -> int {
-    if (int rc = compute_matfree(g, OP_MATRIX_ACTION, nullptr, nullptr, in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
+    if (int rc = compute_matfree(g, VsMode::ACTION, IGX_OP_MATRIX, nullptr, nullptr, 1, &in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
     if (opname.empty()) opname = g->last_kernel;
     ++actions;
     return clk.driver(g);
   };
   auto actB = [&](IGXVec in, IGXVec out) -> int {      // the mass IGX's figures: its own launches and, where it is timed too, its own events
-    if (int rc = compute_matfree(mass, OP_MATRIX_ACTION, nullptr, nullptr, in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
+    if (int rc = compute_matfree(mass, VsMode::ACTION, IGX_OP_MATRIX, nullptr, nullptr, 1, &in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
     ++actions;
     clk.launches += mass->last_launches;
     if (clk.timing && mass->timing) { float ms = 0; HIPCK(hipEventSynchronize(mass->ev[2])); HIPCK(hipEventElapsedTime(&ms, mass->ev[1], mass->ev[2])); clk.op_ms += ms; }
     return 0;
   };
-  // IGXSetBatchedActions(stiff, 1): one call of the action on a block per operator (compute_matfree_block) in place of m single actions;
+  // IGXSetBatchedActions(stiff, 1): one call of the action on a block per operator (compute_matfree, ACTION_BATCH) in place of m single actions;
   // the figures are taken as above, the block call's in place of the m calls'
   static_assert(BV_EIG_MAX <= IGX_ACTION_MAXCOLS && ACTION_BLOCK_MAX == BV_MAX, "the eigen solve's block is one chunk of the block action; a block call takes a block vector");
   auto act_block = [&](const Block &in, const Block &aout, const Block &bout) -> int {
     if (g->batched_actions) {
-      if (int rc = compute_matfree_block(g, OP_MATRIX_ACTION, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), const_cast<IGXVec *>(aout.data()), 0.0, 0.0)) return solver_refused(words, rc);
+      if (int rc = compute_matfree(g, VsMode::ACTION_BATCH, IGX_OP_MATRIX, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), m, const_cast<IGXVec *>(aout.data()), 0.0, 0.0)) return solver_refused(words, rc);
       if (opname.empty()) opname = g->last_kernel;
       actions += m;
       if (int rc = clk.driver(g)) return rc;
       if (!mass) return 0;
-      if (int rc = compute_matfree_block(mass, OP_MATRIX_ACTION, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), const_cast<IGXVec *>(bout.data()), 0.0, 0.0)) return solver_refused(words, rc);
+      if (int rc = compute_matfree(mass, VsMode::ACTION_BATCH, IGX_OP_MATRIX, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), m, const_cast<IGXVec *>(bout.data()), 0.0, 0.0)) return solver_refused(words, rc);
       actions += m;
       clk.launches += mass->last_launches;
       if (clk.timing && mass->timing) { float ms = 0; HIPCK(hipEventSynchronize(mass->ev[2])); HIPCK(hipEventElapsedTime(&ms, mass->ev[1], mass->ev[2])); clk.op_ms += ms; }
@@ -897,7 +890,7 @@ extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IG
   // the preconditioner T of stiff: its diagonal, or its inverted point blocks
   std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
   if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
-    if (int rc = compute_matfree(g, pc == IGX_PC_JACOBI ? OP_MATRIX_DIAGONAL : OP_MATRIX_BLOCK_DIAGONAL, nullptr, nullptr, nullptr, (int)cols.size(), cols.data(), 0.0, 0.0)) return solver_refused(words, rc);
+    if (int rc = compute_matfree(g, pc == IGX_PC_JACOBI ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL, IGX_OP_MATRIX, nullptr, nullptr, 0, nullptr, (int)cols.size(), cols.data(), 0.0, 0.0)) return solver_refused(words, rc);
     if (int rc = clk.driver(g)) return rc;
   }
   if (pc == IGX_PC_PBJACOBI) {

@@ -735,68 +735,44 @@ static bool vec_sumfact_covers(const Space &s, const OutDev &out) {
   }
 }
 
-// BATCH (with ACTION): one launch per colour of the BATCH instantiation on the columns of cols (at most IGX_ACTION_MAXCOLS: the caller cuts the block)
-template <class Form, bool ACTION = false, bool DIAGONAL = false, bool BLOCK = false, bool BATCH = false>
+// One launch per colour of the mode's instantiation (igx.hpp: VsMode, vs_traits) in the layout of the space (vs_launch_of).
+// ACTION_BATCH: on the columns of cols (at most IGX_ACTION_MAXCOLS: the caller cuts the block).  The matrix-free modes: the caller has asked matfree_refusal.
+template <class Form, VsMode M = VsMode::VECTOR>
 static int try_vec_sumfact(const Space &s, const SpaceDev &S, const ParamsDev &prm, const OutDev &out, hipStream_t stream, std::string &kname, int &launches, bool &done, const ActionCols *cols = nullptr) {
   done = false;
+  constexpr VsTraits T = vs_traits(M);
   if constexpr (nscalar_of<Form>::v > 0 || has_boundary_of<Form>::v) return 0;
   else {
-  if constexpr (!ACTION && !DIAGONAL) { if (!vec_sumfact_covers<Form>(s, out)) return 0; }      // (ACTION, DIAGONAL: the caller has asked vec_action_refusal)
-  if constexpr (BATCH) { if (!cols || cols->nc < 1 || cols->nc > IGX_ACTION_MAXCOLS) return IGX_ERR_PLIB; }
+  if constexpr (M == VsMode::VECTOR) { if (!vec_sumfact_covers<Form>(s, out)) return 0; }
+  if constexpr (T.batch) { if (!cols || cols->nc < 1 || cols->nc > IGX_ACTION_MAXCOLS) return IGX_ERR_PLIB; }
+  const VsLaunch L = vs_launch_of(s, M);
+  const bool g1 = s.nsd > 0 || s.rational;
   launches = 0;
   color_sweeps(s, SweepSpec(), [&](const ColorRange &cr) -> int {
     const long long nelem = (long long)cr.count[0] * cr.count[1] * cr.count[2];
-    // at most three basis functions and points per axis (p <= 2): two elements per wavefront (54 of 64 lanes instead of 27)
-    bool three = !s.env.no_vec_pairs;
-    for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
-    const bool g1 = s.nsd > 0 || s.rational;
     // the instantiation of a layout (lanes per axis) on a mapped / rational geometry or on none
-    auto launch = [&](auto nsc, unsigned grid) {
+    auto launch = [&](auto nsc) {
       constexpr int NS = decltype(nsc)::value;
-      if constexpr (BATCH) {
-        if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, NS, true, false, false, true, ActionCols>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem, *cols);
-        else hipLaunchKernelGGL((vec_sumfact<Form, false, NS, true, false, false, true, ActionCols>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem, *cols);
+      const dim3 grid(L.grid(nelem)), threads(vs_layout<NS>::THREADS);
+      if constexpr (T.batch) {
+        if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, NS, T.action, T.diagonal, T.block, true, ActionCols>), grid, threads, 0, stream, S, prm, out, cr, nelem, *cols);
+        else hipLaunchKernelGGL((vec_sumfact<Form, false, NS, T.action, T.diagonal, T.block, true, ActionCols>), grid, threads, 0, stream, S, prm, out, cr, nelem, *cols);
       } else {
-        if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, NS, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem);
-        else hipLaunchKernelGGL((vec_sumfact<Form, false, NS, ACTION, DIAGONAL, BLOCK>), dim3(grid), dim3(vs_layout<NS>::THREADS), 0, stream, S, prm, out, cr, nelem);
+        if (g1) hipLaunchKernelGGL((vec_sumfact<Form, true, NS, T.action, T.diagonal, T.block>), grid, threads, 0, stream, S, prm, out, cr, nelem);
+        else hipLaunchKernelGGL((vec_sumfact<Form, false, NS, T.action, T.diagonal, T.block>), grid, threads, 0, stream, S, prm, out, cr, nelem);
       }
     };
-    if constexpr (ACTION || DIAGONAL) {      // more than four basis functions or points on an axis: one workgroup per element, 6 or 8 lanes per axis
-      const int ns = vec_lanes_per_axis(s);
-      if (ns > 4) {
-        if (ns <= 6) launch(vs_int<6>(), (unsigned)nelem);
-        else launch(vs_int<8>(), (unsigned)nelem);
-        launches++;
-        return 0;
-      }
+    switch (L.ns) {
+    case 3: launch(vs_int<3>()); break;
+    case 4: launch(vs_int<4>()); break;
+    case 6: if constexpr (T.wide) launch(vs_int<6>()); break;      // more than four basis functions or points on an axis: one workgroup per element
+    default: if constexpr (T.wide) launch(vs_int<8>()); break;
     }
-    // (one pass per wavefront: the launch has a wavefront per unit -- UNITS = 1 in the kernel)
-    if (three) launch(vs_int<3>(), (unsigned)((nelem + 7) / 8));
-    else launch(vs_int<4>(), (unsigned)((nelem + 3) / 4));
     launches++;
     return 0;
   });
   if (hipGetLastError() != hipSuccess) return IGX_ERR_LIB;
-  {
-    bool three = !s.env.no_vec_pairs;
-    for (int d = 0; d < 3; ++d) three = three && s.basis[d].nen <= 3 && s.basis[d].nqp <= 3;
-    const int ns = vec_lanes_per_axis(s);
-    if ((ACTION || DIAGONAL) && ns > 4)
-      kname = std::string(BLOCK ? "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, " : DIAGONAL ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, " : BATCH ? "vec_sumfact(matrix action on a block: sum factorisation forward and backward, " : "vec_sumfact(matrix action: sum factorisation forward and backward, ")
-            + (ns <= 6 ? "one workgroup per element, 6 x 6 x 6 lanes)" : "one workgroup per element, 8 x 8 x 8 lanes)");
-    else
-    if constexpr (BLOCK) kname = three ? "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, two elements per wavefront)"
-                                       : "vec_sumfact(matrix block diagonal: sum factorisation forward, product rows backward per field pair, one wavefront per element)";
-    else if constexpr (DIAGONAL) kname = three ? "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, two elements per wavefront)"
-                                          : "vec_sumfact(matrix diagonal: sum factorisation forward, product rows backward, one wavefront per element)";
-    else if constexpr (BATCH) kname = three ? "vec_sumfact(matrix action on a block: sum factorisation forward and backward, two elements per wavefront)"
-                                       : "vec_sumfact(matrix action on a block: sum factorisation forward and backward, one wavefront per element)";
-    else if constexpr (ACTION) kname = three ? "vec_sumfact(matrix action: sum factorisation forward and backward, two elements per wavefront)"
-                                        : "vec_sumfact(matrix action: sum factorisation forward and backward, one wavefront per element)";
-    else
-    kname = three ? "vec_sumfact(vector only: sum factorisation forward and backward, two elements per wavefront)"
-                  : "vec_sumfact(vector only: sum factorisation forward and backward, one wavefront per element)";
-  }
+  kname = std::string("vec_sumfact(") + T.words + L.tail;
   done = true;
   return 0;
   }

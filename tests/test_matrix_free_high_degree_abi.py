@@ -39,7 +39,7 @@ def test_more_than_eight_points_per_axis_is_refused_as_the_driver_refuses_it(gra
 def test_degree_8_is_refused(gram):
     """p = 8 (nen = 9) answers IGX_ERR_SUP (56).  The library as a whole stops at degree 7: IGXAxisSetDegree refuses 8 with "degree > 7
     not supported" before a form or a driver is reached, so that is the text seen here; a space that could hold nen = 9 would get the
-    matrix-free drivers' own "nen <= 8" (vec_action_refusal), which the nine-point case above reaches through nqp."""
+    matrix-free drivers' own "nen <= 8" (matfree_refusal), which the nine-point case above reaches through nqp."""
     import petiga_amd as P
     with pytest.raises(P.IGXError) as e:
         g = P.IGX(3, 1)
