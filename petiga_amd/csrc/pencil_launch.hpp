@@ -19,6 +19,7 @@
 #include "gram_patch3.hpp"
 #include "boundary_loads.hpp"
 #include "pencil_stamps.hpp"
+#include "module_launch.hpp"
 
 namespace igx {
 
@@ -267,9 +268,7 @@ static void launch_pencils(const Space &s, const SpaceDev &S, const OutDev &out,
       struct { SpaceDev S; OutDev out; PencilArgs pa; ParamsDev prm; } args;
       memset(&args, 0, sizeof(args));
       args.S = S; args.out = out; args.pa = pa; args.prm = mod->prm;
-      size_t asz = sizeof(args);
-      void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-      if (hipModuleLaunchKernel(mod->fn, pl.grid, 1, 1, pl.block, 1, 1, (unsigned)pl.lds, stream, nullptr, cfg) != hipSuccess) { pencil_launch_error() = "launch of the run-time instantiation of the pencil walk failed"; return false; }
+      if (module_launch(mod->fn, pl.grid, pl.block, pl.lds, stream, args) != hipSuccess) { pencil_launch_error() = "launch of the run-time instantiation of the pencil walk failed"; return false; }
     } else {
       const GramKernel kern = w.pick(pl);
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);

@@ -13,6 +13,7 @@
 #include <unistd.h>
 #include <map>
 #include "rtc_sources.inc"
+#include "module_launch.hpp"
 
 namespace {
 
@@ -60,16 +61,16 @@ static int load_hiprtc(std::string &err) {
 
 }  // namespace
 
-// feature_assemble<UserForm, dim, TA, NW, I0, DOFI, HASM> for one wave layout: one function per group of row fields
-struct RtcFeature {
-  bool guard_known = false, guard_ok = true; std::vector<double> guard_prm;     // band_pt: the struct's band_params_ok at the parameters it was last asked about
+// one program of a struct beyond the point-form kernel: the instantiations one family launches together (the groups of row fields of
+// feature_assemble, one form_pencil / vec_sumfact / state_pencil / block_pencil, band_points + band_pt), built and loaded by rtc_instance
+struct RtcInstance {
   std::vector<char> code;
   std::vector<std::string> lowered;
-  hipModule_t module = nullptr; std::vector<hipFunction_t> func;
-  FeatureFacts facts;                  // feature_assemble: igx_feature_meta[4] by name (element_sweep.hpp)
-  int band_rec = 0, band_products = 0; bool band_guard = false;      // band_pt: igx_band_meta[4] (bpt_rec, bpt_products, the struct has its own band_params_ok)
+  hipModule_t module = nullptr; std::vector<hipFunction_t> func;      // (code without a module: compiled for IGXCheckFormSource, not yet launched)
+  int meta[4] = {0, 0, 0, 0};          // the int[4] global the family asked to be read back (igx_feature_meta, igx_band_meta)
+  bool guard_known = false, guard_ok = true; std::vector<double> guard_prm;     // band_pt: the struct's band_params_ok at the parameters it was last asked about
   bool failed = false; std::string why;     // band_pt under the automatic choice: the instantiation did not compile; the form stays on the feature kernel
-  ~RtcFeature() { if (module) (void)hipModuleUnload(module); }
+  ~RtcInstance() { if (module) (void)hipModuleUnload(module); }
 };
 
 // one compiled user form for one dimension: code object + what the host-side launcher must know about the struct
@@ -79,12 +80,7 @@ struct RtcForm {
   std::vector<char> code;
   FormFacts facts;      // igx_user_meta[16] of the module by name (element_sweep.hpp); read by rtc_load
   hipModule_t module = nullptr; hipFunction_t func = nullptr;
-  std::map<int, std::shared_ptr<RtcFeature>> feature;   // key: TA | NW << 4 | DOFI << 8 | HASM << 12
-  std::map<int, std::shared_ptr<RtcFeature>> pencil;    // form_pencil instantiations; key: SYSTEM | P << 1 | IDENT << 4 | RAT << 5
-  std::map<int, std::shared_ptr<RtcFeature>> vecsf;     // vec_sumfact instantiations; key: GEO | lanes per axis << 1 | mode << 5 (launch_vecsf_rtc)
-  std::map<int, std::shared_ptr<RtcFeature>> state;     // state_pencil instantiations; key: P (+ 10 + rational on a mapped geometry, + 100 packed tiles)
-  std::map<int, std::shared_ptr<RtcFeature>> block;     // block_pencil instantiations; key: SYSTEM
-  std::map<int, std::shared_ptr<RtcFeature>> band;      // band_points + band_pt instantiations; key: GEO | RAT << 1 | degree << 2
+  std::map<std::string, std::shared_ptr<RtcInstance>> instances;      // every family's, by the program's name expressions (rtc_key; the disk cache hashes the same text)
   ~RtcForm() { if (module) (void)hipModuleUnload(module); }
 };
 
@@ -147,18 +143,20 @@ static void rtc_cache_store(const std::string &path, const std::vector<char> &co
   if (!ok || rename(tmp.c_str(), path.c_str()) != 0) (void)remove(tmp.c_str());     // (rename: concurrent ranks write the same object)
 }
 
+// the embedded headers a program needs beyond igx, forms, generic_kernel and feature_mfma, which every program has
+enum RtcHeaders : unsigned { RTC_BASE = 0, RTC_GRAM = 1, RTC_VECSF = 2, RTC_BLOCK = 4, RTC_BAND = 8 };      // (band_pt.hpp builds on block_pencil.hpp)
+
 // compiles `tail` behind the library headers and the user's source; returns the code object and the lowered names of `exprs`
-static int rtc_build(const std::string &source, bool with_feature, const std::string &tail, const std::vector<std::string> &exprs,
-                     std::vector<char> &code, std::vector<std::string> &lowered, bool with_pencil = false, bool with_vecsf = false, bool with_block = false, bool with_band = false) {
+static int rtc_build(const std::string &source, unsigned headers, const std::string &tail, const std::vector<std::string> &exprs,
+                     std::vector<char> &code, std::vector<std::string> &lowered) {
   std::string src;
   src.reserve(source.size() + 400000);
   src += "#define IGX_RTC 1\n";
-  src += kRtcSrc_igx; src += "\n"; src += kRtcSrc_forms; src += "\n"; src += kRtcSrc_generic; src += "\n";
-  if (with_feature) { src += kRtcSrc_feature; src += "\n"; }
-  if (with_pencil) { src += kRtcSrc_pencil; src += "\n"; src += kRtcSrc_gram; src += "\n"; }
-  if (with_vecsf) { src += kRtcSrc_vecsf; src += "\n"; }
-  if (with_block || with_band) { src += kRtcSrc_pencil; src += "\n"; src += kRtcSrc_block; src += "\n"; }
-  if (with_band) { src += kRtcSrc_band; src += "\n"; }
+  src += kRtcSrc_igx; src += "\n"; src += kRtcSrc_forms; src += "\n"; src += kRtcSrc_generic; src += "\n"; src += kRtcSrc_feature; src += "\n";
+  if (headers & RTC_GRAM) { src += kRtcSrc_pencil; src += "\n"; src += kRtcSrc_gram; src += "\n"; }
+  if (headers & RTC_VECSF) { src += kRtcSrc_vecsf; src += "\n"; }
+  if (headers & (RTC_BLOCK | RTC_BAND)) { src += kRtcSrc_pencil; src += "\n"; src += kRtcSrc_block; src += "\n"; }
+  if (headers & RTC_BAND) { src += kRtcSrc_band; src += "\n"; }
   src += "using namespace igx;\n#line 1 \"user_form.hip\"\n";
   src += source;
   src += "\n";
@@ -200,7 +198,7 @@ static int rtc_compile(IGX g, const std::string &source, const std::string &name
   tail += "template __global__ void " + expr + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, igx::Carve, double *, size_t);\n";
   std::shared_ptr<RtcForm> f(new RtcForm());
   std::vector<std::string> low;
-  if (int rc = rtc_build(source, true, tail, {expr}, f->code, low)) return rc;
+  if (int rc = rtc_build(source, RTC_BASE, tail, {expr}, f->code, low)) return rc;
   f->lowered = low[0];
   f->name = name; f->source = source; f->dim = dim;
   out = f;
@@ -220,6 +218,52 @@ static int rtc_load(IGX g, RtcForm &f) {
   return 0;
 }
 
+// ---- the store of a struct's instantiations and the one way into it.  A family says what its program is; rtc_instance finds it in
+// F.instances or builds it (rtc_build: the disk cache or hiprtc), loads it when a driver is about to launch it, and keeps it.
+// The program text is: the headers, the struct's source, `before`, one `template __global__ void X(sig);` per name expression, `after`.
+struct RtcProgram {
+  unsigned headers = RTC_BASE;
+  std::vector<std::string> exprs; const char *sig = "";
+  std::string before, after;        // the meta globals, static_assert and guard kernel of a family, on the side of the instantiations it has them
+  const char *meta = nullptr;       // an int[4] global to read into RtcInstance::meta at the load
+};
+
+static const char *bool_name(bool b) { return b ? "true" : "false"; }
+
+static int rtc_load_instance(RtcInstance &K, const char *meta_name) {
+  HIPCK(hipModuleLoadData(&K.module, K.code.data()));
+  for (const std::string &l : K.lowered) { hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, K.module, l.c_str())); K.func.push_back(fn); }
+  if (!meta_name) return 0;
+  hipDeviceptr_t p = nullptr; size_t n = 0;
+  HIPCK(hipModuleGetGlobal(&p, &n, K.module, meta_name));
+  if (n != sizeof(K.meta)) return fail(IGX_ERR_LIB, std::string("unexpected ") + meta_name + " size");
+  HIPCK(hipMemcpy(K.meta, p, sizeof(K.meta), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// the key of a program in the store: its name expressions (band_points<F, degree> alone would not tell band_pt's geometries apart)
+static std::string rtc_key(const RtcProgram &P) { std::string k; for (const std::string &x : P.exprs) { k += x; k += ';'; } return k; }
+// load = false: the compile-only check (no GPU needed).  An entry that holds code is not built again: a driver loads what the check compiled.
+static int rtc_instance(RtcForm &F, const RtcProgram &P, bool load, std::shared_ptr<RtcInstance> &K) {
+  auto it = F.instances.find(rtc_key(P));
+  if (it != F.instances.end() && !it->second->code.empty()) K = it->second;
+  else {
+    K.reset(new RtcInstance());
+    std::string tail = P.before;
+    for (const std::string &x : P.exprs) tail += "template __global__ void " + x + "(" + P.sig + ");\n";
+    tail += P.after;
+    if (int rc = rtc_build(F.source, P.headers, tail, P.exprs, K->code, K->lowered)) return rc;
+    F.instances[rtc_key(P)] = K;
+  }
+  if (!load || K->module) return 0;
+  const int rc = rtc_load_instance(*K, P.meta);
+  if (rc) { if (K->module) (void)hipModuleUnload(K->module); K->module = nullptr; K->func.clear(); }      // (the next call loads again)
+  return rc;
+}
+
+// MatZeroEntries of the running IGXCompute*, for the launchers that take it as a function (try_gram_mfma, block_pencil_run, band_pt_run)
+static std::function<void()> zero_matrix_of(IGX g) { return g->zero_matrix ? g->zero_matrix : std::function<void()>([] {}); }
+
 // the kernel arguments of generic_assemble, laid out as the kernarg segment is (natural alignment, in order)
 struct RtcArgs { SpaceDev S; ParamsDev prm; OutDev out; ColorRange cr; Carve cv; double *phi_global; size_t phi_stride; };
 
@@ -228,36 +272,18 @@ struct RtcArgs { SpaceDev S; ParamsDev prm; OutDev out; ColorRange cr; Carve cv;
 // engine.hip with the form's constants read from the module.  Element mode only (no pencil walk), matrix / vector drivers.
 struct RtcFeatArgs { SpaceDev S; ParamsDev prm; OutDev out; ColorRange cr; FCarve cv; };
 
+// feature_assemble<UserForm, dim, TA, NW, I0, DOFI, HASM> for one wave layout: one function per group of row fields
 // (DOF is passed in: it is read from the module on a GPU, and given by the caller for the compile-only check)
-static int rtc_feature_module(IGX g, RtcForm &F, int DIM, int DOF, int TA, int NW, int DOFI, bool HASM, bool load, std::shared_ptr<RtcFeature> &out) {
-  const int key = TA | (NW << 4) | (DOFI << 8) | ((HASM ? 1 : 0) << 12);
-  auto it = F.feature.find(key);
-  if (it != F.feature.end() && (it->second->module || !load)) { out = it->second; return 0; }
-  std::shared_ptr<RtcFeature> f(new RtcFeature());
-  std::vector<std::string> exprs;
+static int rtc_feature_module(RtcForm &F, int DIM, int DOF, int TA, int NW, int DOFI, bool HASM, bool load, std::shared_ptr<RtcInstance> &out) {
+  RtcProgram P; P.sig = "igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, igx::FCarve"; P.meta = "igx_feature_meta";
   const std::string common = F.name + ", " + std::to_string(DIM) + ", " + std::to_string(TA) + ", " + std::to_string(NW) + ", ";
-  std::string tail;
   const bool fuse = HASM && DOFI < DOF;   // all groups of row fields in one launch (feature_mfma.hpp, FUSE)
-  for (int I0 = 0; I0 < ((HASM && !fuse) ? DOF : 1); I0 += DOFI) {
-    const std::string x = "igx::feature_assemble<" + common + std::to_string(I0) + ", " + std::to_string(DOFI) + ", " + (HASM ? "true" : "false") + ", false, " + (fuse ? "true" : "false") + ">";
-    exprs.push_back(x);
-    tail += "template __global__ void " + x + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, igx::FCarve);\n";
-  }
+  for (int I0 = 0; I0 < ((HASM && !fuse) ? DOF : 1); I0 += DOFI)
+    P.exprs.push_back("igx::feature_assemble<" + common + std::to_string(I0) + ", " + std::to_string(DOFI) + ", " + bool_name(HASM) + ", false, " + bool_name(fuse) + ">");
   const std::string nfs = "((igx::shape_order_of<" + F.name + ">::v >= 2) ? 1 + " + std::to_string(DIM) + " + " + std::to_string(DIM * DIM) + " : 1 + " + std::to_string(DIM) + ")";
-  tail += "__device__ int igx_feature_meta[4] = {igx::fm_min_waves<" + F.name + ", " + std::to_string(TA) + ", " + std::to_string(NW) + ", " + std::to_string(DOFI) + ", " + (HASM ? "true" : "false") +
-          ", false>(), igx::fm_popcount((unsigned long long)(igx::phi_mask_of<" + F.name + ">::v & ((1u << " + nfs + ") - 1u))), igx::fm_mfma_per_kstep<" + F.name + ">(" + nfs + "), 0};\n";
-  if (int rc = rtc_build(F.source, true, tail, exprs, f->code, f->lowered)) return rc;
-  if (!load) { F.feature[key] = f; out = f; return 0; }
-  HIPCK(hipModuleLoadData(&f->module, f->code.data()));
-  for (const std::string &l : f->lowered) { hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, f->module, l.c_str())); f->func.push_back(fn); }
-  hipDeviceptr_t p = nullptr; size_t n = 0;
-  HIPCK(hipModuleGetGlobal(&p, &n, f->module, "igx_feature_meta"));
-  int meta[4];
-  if (n != sizeof(meta)) return fail(IGX_ERR_LIB, "unexpected igx_feature_meta size");
-  HIPCK(hipMemcpy(meta, p, sizeof(meta), hipMemcpyDeviceToHost));
-  f->facts = feature_facts_from_meta(meta);
-  F.feature[key] = f; out = f;
-  return 0;
+  P.after = "__device__ int igx_feature_meta[4] = {igx::fm_min_waves<" + F.name + ", " + std::to_string(TA) + ", " + std::to_string(NW) + ", " + std::to_string(DOFI) + ", " + bool_name(HASM) +
+            ", false>(), igx::fm_popcount((unsigned long long)(igx::phi_mask_of<" + F.name + ">::v & ((1u << " + nfs + ") - 1u))), igx::fm_mfma_per_kstep<" + F.name + ">(" + nfs + "), 0};\n";
+  return rtc_instance(F, P, load, out);
 }
 
 // wave layouts of launch_feature_ta (engine.hip): 8 waves at 4x4 tiles, except scalar matrix forms (4 waves with 4 tiles each);
@@ -283,9 +309,10 @@ static int launch_feature_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev
   const bool HASM = op_has_matrix(out.op);
   if (HASM && out.op == OP_SYSTEM && SECOND && !SECOND_S && (F.facts.need & NEED_HU) && !(F.facts.mat_need & NEED_HU)) return 0;   // (HU_HERE, feature_mfma.hpp)
   int TA, NW, DOFI; rtc_feature_layout(NE, DOF, GRAM, HASM, TA, NW, DOFI);
-  std::shared_ptr<RtcFeature> K;
-  if (int rc = rtc_feature_module(g, F, DIM, DOF, TA, NW, DOFI, HASM, true, K)) return rc;
-  const FeatureCarve fc = carve_feature(F.facts, s, out.op, TA, NW, HASM, std::max(K->facts.wgs_per_cu, 1), K->facts.phi_in_lds, 0);
+  std::shared_ptr<RtcInstance> K;
+  if (int rc = rtc_feature_module(F, DIM, DOF, TA, NW, DOFI, HASM, true, K)) return rc;
+  const FeatureFacts kf = feature_facts_from_meta(K->meta);      // igx_feature_meta[4] by name (element_sweep.hpp)
+  const FeatureCarve fc = carve_feature(F.facts, s, out.op, TA, NW, HASM, std::max(kf.wgs_per_cu, 1), kf.phi_in_lds, 0);
   if (!fc.fits) return 0;   // the generic kernel takes it
   const FCarve &cv = fc.cv;
   RtcFeatArgs args; memset(&args, 0, sizeof(args));
@@ -293,13 +320,11 @@ static int launch_feature_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev
   // (no functionals, no second pass over axis 2, no pencil mode: element mode, one or several functions per colour)
   FeatureSweep fs;
   fs.HASM = HASM; fs.dom_name = "feature_assemble<element, hiprtc>";
-  fs.flop_per_element = HASM ? 2048.0 * K->facts.mfma_per_kstep * TA * TA * (cv.QC * cv.nchunk / 4) : 0.0;
+  fs.flop_per_element = HASM ? 2048.0 * kf.mfma_per_kstep * TA * TA * (cv.QC * cv.nchunk / 4) : 0.0;
   if (int rc = sweep_feature(g, out, fs, [&](const OutDev &o, const ColorRange &cr, size_t nblocks, bool, int &launches) -> int {
         args.out = o; args.cr = cr;
         for (hipFunction_t fn : K->func) {
-          size_t asz = sizeof(args);
-          void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-          HIPCK(hipModuleLaunchKernel(fn, (unsigned)nblocks, 1, 1, (unsigned)(64 * NW), 1, 1, (unsigned)fc.lds_bytes, g->stream, nullptr, cfg));
+          HIPCK(module_launch(fn, (unsigned)nblocks, (unsigned)(64 * NW), fc.lds_bytes, g->stream, args));
           launches++;
         }
         return 0;
@@ -328,32 +353,21 @@ static bool rtc_pencil_eligible(const Space &s, const RtcForm &F, const OutDev &
   return true;
 }
 
+static const char *kPencilSig = "igx::SpaceDev, igx::OutDev, igx::PencilArgs, igx::ParamsDev";      // form_pencil and the state_pencil kernels
 static int launch_pencil_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out, bool &done, bool compile_only = false, int sys_only = -1) {
   done = false;
   const Space &s = g->s;
   if (!compile_only && !rtc_pencil_eligible(s, F, out)) return 0;
   const int deg = s.axis[0].p;
   const bool sys = compile_only ? sys_only != 0 : out.op == OP_SYSTEM, ident = s.nsd == 0, rat = s.rational != 0;
-  const int key = (sys ? 1 : 0) | (deg << 1) | ((ident ? 1 : 0) << 4) | ((rat ? 1 : 0) << 5);
-  std::shared_ptr<RtcFeature> K;
-  auto it = F.pencil.find(key);
-  if (it != F.pencil.end() && (it->second->module || compile_only)) K = it->second;
-  else {
-    K.reset(new RtcFeature());
-    const std::string x = std::string("igx::form_pencil<") + (sys ? "true" : "false") + ", " + std::to_string(deg) + ", " + (ident ? "true" : "false") + ", " + (rat ? "true" : "false") + ", " + F.name + ">";
-    const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::OutDev, igx::PencilArgs, igx::ParamsDev);\n";
-    if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, true)) return rc;
-    if (!compile_only) {
-      HIPCK(hipModuleLoadData(&K->module, K->code.data()));
-      hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, K->module, K->lowered[0].c_str())); K->func.push_back(fn);
-    }
-    F.pencil[key] = K;
-  }
+  RtcProgram P; P.headers = RTC_GRAM; P.sig = kPencilSig;
+  P.exprs = {std::string("igx::form_pencil<") + bool_name(sys) + ", " + std::to_string(deg) + ", " + bool_name(ident) + ", " + bool_name(rat) + ", " + F.name + ">"};
+  std::shared_ptr<RtcInstance> K;
+  if (int rc = rtc_instance(F, P, !compile_only, K)) return rc;
   if (compile_only) { done = true; return 0; }
   PencilModule mod; mod.prm = params_of(s);
   mod.fn = K->func[0]; mod.name = F.name;
-  std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
-  return try_gram_mfma(s, S, out, g->stream, false, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, &mod, g->face_done);
+  return try_gram_mfma(s, S, out, g->stream, false, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix_of(g), g->slab_done, &mod, g->face_done);
 }
 
 // ---- the sum-factorised vector kernel (vec_sumfact.hpp) for a run-time form: Vector / Function / IFunction in 3-D at nen, nqp <= 4
@@ -379,31 +393,18 @@ static int launch_vecsf_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   if (!compile_only && mode == VsMode::VECTOR && !rtc_vecsf_eligible(s, F, out)) return 0;
   const bool geo = s.nsd > 0 || s.rational;
   const VsLaunch L = vs_launch_of(s, mode, compile_only);
-  const int key = (geo ? 1 : 0) | L.ns << 1 | (int)mode << 5;
-  std::shared_ptr<RtcFeature> K;
-  auto it = F.vecsf.find(key);
-  if (it != F.vecsf.end() && (it->second->module || compile_only)) K = it->second;
-  else {
-    K.reset(new RtcFeature());
-    // (the booleans up to the last that is set: the names the ABI tests instantiate)
-    const std::string x = std::string("igx::vec_sumfact<") + F.name + ", " + (geo ? "true" : "false") + ", " + std::to_string(L.ns) + (t.block ? ", false, true, true>" : (t.diagonal ? ", false, true>" : (t.action ? ", true>" : ">")));
-    const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, long long);\n";
-    if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, false, true)) return rc;
-    if (!compile_only) {
-      HIPCK(hipModuleLoadData(&K->module, K->code.data()));
-      hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, K->module, K->lowered[0].c_str())); K->func.push_back(fn);
-    }
-    F.vecsf[key] = K;
-  }
+  RtcProgram P; P.headers = RTC_VECSF; P.sig = "igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::ColorRange, long long";
+  // (the booleans up to the last that is set: the names the ABI tests instantiate)
+  P.exprs = {std::string("igx::vec_sumfact<") + F.name + ", " + bool_name(geo) + ", " + std::to_string(L.ns) + (t.block ? ", false, true, true>" : (t.diagonal ? ", false, true>" : (t.action ? ", true>" : ">")))};
+  std::shared_ptr<RtcInstance> K;
+  if (int rc = rtc_instance(F, P, !compile_only, K)) return rc;
   if (compile_only) { done = true; return 0; }
   RtcVecArgs args; memset(&args, 0, sizeof(args));
   args.S = S; args.out = out; args.prm = params_of(s);
   int launches = 0;
   if (int rc = color_sweeps(s, SweepSpec(), [&](const ColorRange &cr) -> int {
     args.cr = cr; args.nelem = (long long)cr.count[0] * cr.count[1] * cr.count[2];
-    size_t asz = sizeof(args);
-    void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-    HIPCK(hipModuleLaunchKernel(K->func[0], L.grid(args.nelem), 1, 1, L.threads, 1, 1, 0, g->stream, nullptr, cfg));
+    HIPCK(module_launch(K->func[0], L.grid(args.nelem), L.threads, 0, g->stream, args));
     launches++;
     return 0;
   })) return rc;
@@ -427,33 +428,21 @@ static int launch_state_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
   const bool geo = s.nsd != 0;
   if (geo && (s.nsd != 3 || deg != 2)) return 0;
   const bool pack = deg == 2 && s.env.p2_pack != 0;
-  const int key = deg + (geo ? 10 + (s.rational ? 1 : 0) : 0) + (pack ? 100 : 0);      // (12: p = 2 on a polynomial map, 13: on a NURBS map; + 100: packed tiles)
-  std::shared_ptr<RtcFeature> K;
-  auto it = F.state.find(key);
-  if (it != F.state.end() && (it->second->module || compile_only)) K = it->second;
-  else {
-    K.reset(new RtcFeature());
-    // p = 2: the packed-tile kernels, as for the built-in forms (IGX_P2_PACK=0: the layer-pair tiles; the key below tells them apart)
-    const std::string x = (deg == 2 && pack) ? (geo ? std::string("igx::state_pencil_geo_k<") + (s.rational ? "true, " : "false, ") + F.name + ">"
-                                                    : std::string("igx::state_pencil_k<") + F.name + ">")
-                        : geo ? std::string("igx::state_pencil_geo<2, ") + (s.rational ? "true, " : "false, ") + F.name + ">"
-                              : std::string("igx::state_pencil<") + std::to_string(deg) + ", " + F.name + ">";
-    const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::OutDev, igx::PencilArgs, igx::ParamsDev);\n";
-    if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, true)) return rc;
-    if (!compile_only) {
-      HIPCK(hipModuleLoadData(&K->module, K->code.data()));
-      hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, K->module, K->lowered[0].c_str())); K->func.push_back(fn);
-    }
-    F.state[key] = K;
-  }
+  RtcProgram P; P.headers = RTC_GRAM; P.sig = kPencilSig;
+  // p = 2: the packed-tile kernels, as for the built-in forms (IGX_P2_PACK=0: the layer-pair tiles, under another name)
+  P.exprs = {pack ? (geo ? std::string("igx::state_pencil_geo_k<") + bool_name(s.rational) + ", " + F.name + ">"
+                         : std::string("igx::state_pencil_k<") + F.name + ">")
+                  : geo ? std::string("igx::state_pencil_geo<2, ") + bool_name(s.rational) + ", " + F.name + ">"
+                        : std::string("igx::state_pencil<") + std::to_string(deg) + ", " + F.name + ">"};
+  std::shared_ptr<RtcInstance> K;
+  if (int rc = rtc_instance(F, P, !compile_only, K)) return rc;
   if (compile_only) { done = true; return 0; }
   PencilModule mod; mod.prm = params_of(s);
   mod.fn = K->func[0]; mod.name = F.name + ",hiprtc"; mod.state = true; mod.state_geo = geo;
   mod.extra_lds = pencil_state_bytes() + (geo ? pencil_sgeo_bytes() - pencil_geo_bytes() : 0);
   mod.pack = pack ? (geo ? 2 : 1) : 0;
   mod.flop_per_element = 2048.0 * F.facts.pencil_nfeat * (deg == 2 ? 7 * (pack ? 4 : 9) : 16 * 16);
-  std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
-  return try_gram_mfma(s, S, out, g->stream, false, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, &mod, g->face_done);
+  return try_gram_mfma(s, S, out, g->stream, false, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix_of(g), g->slab_done, &mod, g->face_done);
 }
 
 // ---- band rows by node layer (block_pencil.hpp) for a run-time struct: constant-coefficient multi-field forms (MAT_PAIR_MASK, 2 or 3
@@ -470,35 +459,19 @@ static int launch_block_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
     if (!block_pencil_covers_space(s, S, out, DOF)) return 0;
   }
   const bool sysk = compile_only ? sys_only != 0 : out.op == OP_SYSTEM;
-  auto module_of = [&](bool sys, std::shared_ptr<RtcFeature> &K) -> int {
-    auto it = F.block.find(sys ? 1 : 0);
-    if (it != F.block.end() && (it->second->module || compile_only)) { K = it->second; return 0; }
-    K.reset(new RtcFeature());
-    const std::string x = std::string("igx::block_pencil<") + F.name + ", 3, " + (sys ? "true" : "false") + ">";
-    const std::string tail = "template __global__ void " + x + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::BlockPencilArgs);\n";
-    if (int rc = rtc_build(F.source, true, tail, {x}, K->code, K->lowered, false, false, true)) return rc;
-    if (!compile_only) {
-      HIPCK(hipModuleLoadData(&K->module, K->code.data()));
-      hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, K->module, K->lowered[0].c_str())); K->func.push_back(fn);
-    }
-    F.block[sys ? 1 : 0] = K;
-    return 0;
-  };
-  std::shared_ptr<RtcFeature> K;
-  if (int rc = module_of(sysk, K)) return rc;
+  RtcProgram P; P.headers = RTC_BLOCK; P.sig = "igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::BlockPencilArgs";
+  P.exprs = {std::string("igx::block_pencil<") + F.name + ", 3, " + bool_name(sysk) + ">"};
+  std::shared_ptr<RtcInstance> K;
+  if (int rc = rtc_instance(F, P, !compile_only, K)) return rc;
   if (compile_only) { done = true; return 0; }
   const ParamsDev prm = params_of(s);
-  hipFunction_t fn = K->func[0];
   hipStream_t stream = g->stream;
-  std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
   int lrc = 0;
-  const int rc = block_pencil_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, F.facts.dof, F.facts.npairs,
+  const int rc = block_pencil_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix_of(g), g->slab_done, F.facts.dof, F.facts.npairs,
                                   [&](bool, unsigned grid, size_t lds, const BlockPencilArgs &pa) {
                                     RtcBlockArgs a; memset(&a, 0, sizeof(a));
                                     a.S = S; a.prm = prm; a.out = out; a.pa = pa;
-                                    size_t asz = sizeof(a);
-                                    void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-                                    if (lds > (size_t)160 * 1024 || hipModuleLaunchKernel(fn, grid, 1, 1, 512, 1, 1, (unsigned)lds, stream, nullptr, cfg) != hipSuccess) lrc = IGX_ERR_LIB;
+                                    if (lds > (size_t)160 * 1024 || module_launch(K->func[0], grid, 512, lds, stream, a) != hipSuccess) lrc = IGX_ERR_LIB;
                                   });
   if (rc == 0 && lrc) return fail(lrc, "block_pencil: launch of the run-time instantiation failed");
   if (rc == 0 && done) g->last_kernel = std::string("block_pencil<") + F.name + ">(hiprtc,mfma_f64_16x16x4,p=3,dof=" + char('0' + F.facts.dof) + ",band rows by node layer)";
@@ -523,44 +496,27 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
   const bool geo = compile_only ? (geo_only & 1) != 0 : s.nsd != 0, rat = compile_only ? (geo_only & 2) != 0 : s.rational != 0;
   const int deg = s.axis[0].p;
   if (deg != 2 && deg != 3) { if (compile_only) return fail(IGX_ERR_SUP, "band_pt needs degree 2 or 3"); return 0; }
-  const int key = (geo ? 1 : 0) | (rat ? 2 : 0) | (deg << 2);
-  std::shared_ptr<RtcFeature> K;
-  auto it = F.band.find(key);
-  if (it != F.band.end() && it->second->failed && !compile_only && g->kernel_choice == 0) { g->rtc_note = it->second->why; return 0; }
-  if (it != F.band.end() && (it->second->module || compile_only)) K = it->second;
-  else {
-    K.reset(new RtcFeature());
-    const std::string xp = std::string("igx::band_points<") + F.name + ", " + std::to_string(deg) + ">";
-    const std::string xb = std::string("igx::band_pt<") + F.name + ", " + (geo ? "true" : "false") + ", " + (rat ? "true" : "false") + ", " + std::to_string(deg) + ">";
-    const std::string tail = "static_assert(igx::bpt_form_ok<" + F.name + ">(), \"band_pt: four fields, first order, NCOEF / point_coef / mat_c, no atboundary branch\");\n"
-                             "__device__ int igx_band_meta[4] = {igx::bpt_rec<" + F.name + ">(), igx::bpt_products<" + F.name + ">(), igx::band_nacc_of<" + F.name + ">::own ? 1 : 0, 0};\n"
-                             // the struct's own guard on the parameters (a struct with BAND_NACC hooks declares band_params_ok __host__ __device__)
-                             "__device__ double igx_band_prm[igx::MAXPARAM]; __device__ int igx_band_ok;\n"
-                             "template <class F> __device__ int igx_band_guard_of(const double *prm) { if constexpr (igx::band_nacc_of<F>::own) return F::band_params_ok(prm) ? 1 : 0; else return 1; }\n"
-                             "extern \"C\" __global__ void igx_band_guard() { igx_band_ok = igx_band_guard_of<" + F.name + ">(igx_band_prm); }\n"
-                             "template __global__ void " + xp + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::BandArgs);\n"
-                             "template __global__ void " + xb + "(igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::BandArgs);\n";
-    if (int rc = rtc_build(F.source, true, tail, {xp, xb}, K->code, K->lowered, false, false, false, true)) {
-      // Under the automatic choice a struct whose band-row instantiation does not compile (the usual reason: a band_params_ok
-      // that is not __host__ __device__, include/petiga_amd.h) is a struct the band-row kernel does not cover: the feature kernel
-      // takes the assembly and the kernel name carries the reason.  Asked for by name (IGXSetKernel(4), IGXCheckFormSource) it fails.
-      if (compile_only || g->kernel_choice != 0) return rc;
-      K->failed = true;
-      K->why = "band_pt<" + F.name + "> did not compile (is band_params_ok declared __host__ __device__?): " + g_err.substr(0, 400);
-      F.band[key] = K; g->rtc_note = K->why;
-      return 0;
-    }
-    if (!compile_only) {
-      HIPCK(hipModuleLoadData(&K->module, K->code.data()));
-      for (int k = 0; k < 2; ++k) { hipFunction_t fn = nullptr; HIPCK(hipModuleGetFunction(&fn, K->module, K->lowered[k].c_str())); K->func.push_back(fn); }
-      hipDeviceptr_t p = nullptr; size_t n = 0;
-      HIPCK(hipModuleGetGlobal(&p, &n, K->module, "igx_band_meta"));
-      int meta[4];
-      if (n != sizeof(meta)) return fail(IGX_ERR_LIB, "unexpected igx_band_meta size");
-      HIPCK(hipMemcpy(meta, p, sizeof(meta), hipMemcpyDeviceToHost));
-      K->band_rec = meta[0]; K->band_products = meta[1]; K->band_guard = meta[2] != 0;
-    }
-    F.band[key] = K;
+  RtcProgram P; P.headers = RTC_BAND; P.sig = "igx::SpaceDev, igx::ParamsDev, igx::OutDev, igx::BandArgs"; P.meta = "igx_band_meta";      // (bpt_rec, bpt_products, the struct has its own band_params_ok)
+  P.exprs = {std::string("igx::band_points<") + F.name + ", " + std::to_string(deg) + ">", std::string("igx::band_pt<") + F.name + ", " + bool_name(geo) + ", " + bool_name(rat) + ", " + std::to_string(deg) + ">"};
+  P.before = "static_assert(igx::bpt_form_ok<" + F.name + ">(), \"band_pt: four fields, first order, NCOEF / point_coef / mat_c, no atboundary branch\");\n"
+             "__device__ int igx_band_meta[4] = {igx::bpt_rec<" + F.name + ">(), igx::bpt_products<" + F.name + ">(), igx::band_nacc_of<" + F.name + ">::own ? 1 : 0, 0};\n"
+             // the struct's own guard on the parameters (a struct with BAND_NACC hooks declares band_params_ok __host__ __device__)
+             "__device__ double igx_band_prm[igx::MAXPARAM]; __device__ int igx_band_ok;\n"
+             "template <class F> __device__ int igx_band_guard_of(const double *prm) { if constexpr (igx::band_nacc_of<F>::own) return F::band_params_ok(prm) ? 1 : 0; else return 1; }\n"
+             "extern \"C\" __global__ void igx_band_guard() { igx_band_ok = igx_band_guard_of<" + F.name + ">(igx_band_prm); }\n";
+  auto it = F.instances.find(rtc_key(P));
+  if (it != F.instances.end() && it->second->failed && !compile_only && g->kernel_choice == 0) { g->rtc_note = it->second->why; return 0; }
+  std::shared_ptr<RtcInstance> K;
+  if (int rc = rtc_instance(F, P, !compile_only, K)) {
+    // Under the automatic choice a struct whose band-row instantiation does not compile (the usual reason: a band_params_ok
+    // that is not __host__ __device__, include/petiga_amd.h) is a struct the band-row kernel does not cover: the feature kernel
+    // takes the assembly and the kernel name carries the reason.  Asked for by name (IGXSetKernel(4), IGXCheckFormSource) it fails.
+    // (An entry with code is one that compiled and did not load: an error under every choice.)
+    if (!K->code.empty() || compile_only || g->kernel_choice != 0) return rc;
+    K->failed = true;
+    K->why = "band_pt<" + F.name + "> did not compile (is band_params_ok declared __host__ __device__?): " + g_err.substr(0, 400);
+    F.instances[rtc_key(P)] = K; g->rtc_note = K->why;
+    return 0;
   }
   if (compile_only) { done = true; return 0; }
   const ParamsDev prm = params_of(s);
@@ -568,7 +524,7 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
   // The struct's guard on its parameters, as the built-in path has it (band_pt.hpp: Form::band_params_ok): band_coef / band_finish
   // may divide by a parameter (FormNSVMS: 1 / nu), and a struct that says no stays on the feature kernel.  Evaluated by the
   // module's one-lane kernel whenever the parameters differ from the ones it was last asked about.
-  if (K->band_guard) {
+  if (K->meta[2] != 0) {
     const std::vector<double> now(prm.v, prm.v + MAXPARAM);
     if (!K->guard_known || now != K->guard_prm) {
       hipFunction_t gf = nullptr; hipDeviceptr_t pp = nullptr, po = nullptr; size_t n = 0; int ok = 0;
@@ -585,14 +541,11 @@ static int launch_band_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &o
     if (!K->guard_ok) return 0;       // done stays false: the caller goes on to the feature kernel
   }
   int lrc = 0;
-  std::function<void()> zero = g->zero_matrix ? g->zero_matrix : std::function<void()>([] {});
-  const int rc = band_pt_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero, g->slab_done, K->band_rec, K->band_products,
+  const int rc = band_pt_run(s, S, out, stream, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix_of(g), g->slab_done, K->meta[0], K->meta[1],
                              [&](bool points, unsigned grid, size_t lds, bool, bool, int, const BandArgs &pa) {
                                RtcBandArgs a; memset(&a, 0, sizeof(a));
                                a.S = S; a.prm = prm; a.out = out; a.pa = pa;
-                               size_t asz = sizeof(a);
-                               void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-                               if (hipModuleLaunchKernel(K->func[points ? 0 : 1], grid, 1, 1, 256, 1, 1, (unsigned)lds, stream, nullptr, cfg) != hipSuccess) lrc = IGX_ERR_LIB;
+                               if (module_launch(K->func[points ? 0 : 1], grid, 256, lds, stream, a) != hipSuccess) lrc = IGX_ERR_LIB;
                              });
   if (rc == 0 && lrc) return fail(lrc, "band_pt: launch of the run-time instantiation failed");
   if (rc == 0 && done) g->last_kernel = std::string("band_pt<") + F.name + ">(hiprtc,mfma_f64_16x16x4,p=" + std::to_string(deg) + ",dof=4,band rows by node layer,point records)";
@@ -678,9 +631,7 @@ static int rtc_generic_launch(IGX g, RtcForm &F, const SpaceDev &S, const OutDev
   // (HAS_BOUNDARY), any other is integrated over the face
   if (int rc = sweep_generic(g, g_err, gc, F.facts.nscalar > 0, [&](const ColorRange &cr, int bid, int64_t elem_base, size_t nblocks) -> int {
         args.cr = cr; args.phi_global = g->scratch.as<double>(); args.out.bid = bid; args.out.elem_base = elem_base;
-        size_t asz = sizeof(args);
-        void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &asz, HIP_LAUNCH_PARAM_END};
-        HIPCK(hipModuleLaunchKernel(F.func, (unsigned)nblocks, 1, 1, 256, 1, 1, (unsigned)gc.lds_bytes, g->stream, nullptr, cfg));
+        HIPCK(module_launch(F.func, (unsigned)nblocks, 256, gc.lds_bytes, g->stream, args));
         return 0;
       })) return rc;
   g->last_kernel = std::string("generic_assemble<") + F.name + "> (hiprtc," + (gc.phi_in_lds ? "phi=LDS" : "phi=HBM") + ")";
@@ -726,6 +677,9 @@ extern "C" int IGXComputeScalarSource(IGX g, IGXVec U, const char *source, const
   return reduce_scalars(g, ns, U, params, nparams, [&](const SpaceDev &Sd, const OutDev &out) { return rtc_generic_launch(g, F, Sd, out); }, S);
 }
 
+// the values of `gram` beyond 0 / 1 (the feature kernel without / with the Gram path), as include/petiga_amd.h documents them
+enum RtcCheckKind { CHECK_PENCIL = 2, CHECK_VECSF = 3, CHECK_STATE = 4, CHECK_BLOCK = 5, CHECK_BAND = 6, CHECK_ACTION = 7, CHECK_DIAGONAL = 8, CHECK_BLOCK_DIAGONAL = 9 };
+
 // Compile-only check of a run-time form against the kernels the drivers would launch for the axes set so far (no GPU needed):
 // the point-form kernel was compiled by IGXSetFormSource; this adds the matrix-core kernel (feature_mfma.hpp) in the wave
 // layout of the current degree, for the matrix drivers (with_matrix != 0) or the vector-only ones.
@@ -733,48 +687,43 @@ extern "C" int IGXCheckFormSource(IGX g, int with_matrix, int gram) {
   NEEDIGA(g);
   if (g->s.form != IGX_FORM_SOURCE || !g->rtc) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGXSetFormSource() first");
   const Space &s = g->s;
-  if (gram == 6) {           // band_points + band_pt of a four-field struct with separated point coefficients: compile only (no geometry and NURBS)
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    if (int rc = launch_band_rtc(g, *g->rtc, Sd, o, done, true, 0)) return rc;
+  RtcForm &F = *g->rtc;
+  bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));      // (compile only: the launchers read neither)
+  if (gram == CHECK_BAND) {           // band_points + band_pt of a four-field struct with separated point coefficients: compile only (no geometry and NURBS)
+    if (int rc = launch_band_rtc(g, F, Sd, o, done, true, 0)) return rc;
     if (!done) return fail(IGX_ERR_SUP, "band_pt needs dim 3");
-    return launch_band_rtc(g, *g->rtc, Sd, o, done, true, 3);
+    return launch_band_rtc(g, F, Sd, o, done, true, 3);
   }
-  if (gram == 5) {           // block_pencil of a constant-coefficient multi-field struct (System and Matrix driver): compile only
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    if (int rc = launch_block_rtc(g, *g->rtc, Sd, o, done, true, 1)) return rc;
+  if (gram == CHECK_BLOCK) {           // block_pencil of a constant-coefficient multi-field struct (System and Matrix driver): compile only
+    if (int rc = launch_block_rtc(g, F, Sd, o, done, true, 1)) return rc;
     if (!done) return fail(IGX_ERR_SUP, "block_pencil needs dim 3");
-    return launch_block_rtc(g, *g->rtc, Sd, o, done, true, 0);
+    return launch_block_rtc(g, F, Sd, o, done, true, 0);
   }
-  if (gram == 4) {           // state_pencil of a struct with the PENCIL_* hooks, for the current degree: compile only
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    if (int rc = launch_state_rtc(g, *g->rtc, Sd, o, done, true)) return rc;
+  if (gram == CHECK_STATE) {           // state_pencil of a struct with the PENCIL_* hooks, for the current degree: compile only
+    if (int rc = launch_state_rtc(g, F, Sd, o, done, true)) return rc;
     return done ? 0 : fail(IGX_ERR_SUP, "state_pencil needs dim 3, dof 1, degree 2 or 3 (2 on a mapped geometry) and a struct with PENCIL_NFEAT / PENCIL_NC / pencil_coef / pencil_trial");
   }
-  if (gram >= 7 && gram <= 9) {      // ... and its ACTION / DIAGONAL / DIAGONAL with BLOCK instantiation (IGXCompute*Action, *Diagonal, *BlockDiagonal of the struct) for the
+  if (gram >= CHECK_ACTION && gram <= CHECK_BLOCK_DIAGONAL) {      // ... and its ACTION / DIAGONAL / DIAGONAL with BLOCK instantiation (IGXCompute*Action, *Diagonal, *BlockDiagonal of the struct) for the
     // layout the driver would launch: compile only, refused where the driver would refuse.  (The struct's constants are read from the loaded
     // module; without a GPU the kernel's static_assert names the cause.)
-    const VsMode mode = gram == 7 ? VsMode::ACTION : gram == 8 ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL;
-    if (const MfRefusal r = matfree_refusal(s, g->kernel_choice, mode, gram != 7 && g->rtc->func ? &g->rtc->facts : nullptr, MfCaller::CHECK)) return fail(r.code, r.msg);
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, mode, true);
+    const VsMode mode = gram == CHECK_ACTION ? VsMode::ACTION : gram == CHECK_DIAGONAL ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL;
+    if (const MfRefusal r = matfree_refusal(s, g->kernel_choice, mode, gram != CHECK_ACTION && F.func ? &F.facts : nullptr, MfCaller::CHECK)) return fail(r.code, r.msg);
+    return launch_vecsf_rtc(g, F, Sd, o, done, mode, true);
   }
-  if (gram == 3) {           // the sum-factorised vector kernel (vec_sumfact) of the struct, with and without a geometry: compile only
+  if (gram == CHECK_VECSF) {           // the sum-factorised vector kernel (vec_sumfact) of the struct, with and without a geometry: compile only
     if (s.dim != 3) return fail(IGX_ERR_SUP, "the sum-factorised vector kernel needs dim 3");
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o)); SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    return launch_vecsf_rtc(g, *g->rtc, Sd, o, done, VsMode::VECTOR, true);
+    return launch_vecsf_rtc(g, F, Sd, o, done, VsMode::VECTOR, true);
   }
-  if (gram == 2) {           // the pencil walk's instantiation (form_pencil) for the current degree / geometry: compile only
+  if (gram == CHECK_PENCIL) {           // the pencil walk's instantiation (form_pencil) for the current degree / geometry: compile only
     if (s.dim != 3 || (s.axis[0].p != 2 && s.axis[0].p != 3)) return fail(IGX_ERR_SUP, "the pencil walk needs dim 3 and degree 2 or 3");
-    bool done = false; OutDev o; memset(&o, 0, sizeof(o));
-    SpaceDev Sd; memset(&Sd, 0, sizeof(Sd));
-    if (int rc = launch_pencil_rtc(g, *g->rtc, Sd, o, done, true, 1)) return rc;      // System driver
-    return launch_pencil_rtc(g, *g->rtc, Sd, o, done, true, 0);                        // Matrix driver
+    if (int rc = launch_pencil_rtc(g, F, Sd, o, done, true, 1)) return rc;      // System driver
+    return launch_pencil_rtc(g, F, Sd, o, done, true, 0);                        // Matrix driver
   }
   if (s.dim < 2) return 0;   // dim 1: the point-form kernel only
   int NE = 1;
   for (int d = 0; d < s.dim; ++d) { if (s.axis[d].p < 1) return fail(IGX_ERR_ARG_WRONGSTATE, "set the axes (degrees) first"); NE *= s.axis[d].p + 1; }
   if (NE > 256 || (NE > 64 && (s.dim != 3 || gram || s.dof > 2)) || (NE > 128 && s.dof > 1)) return 0;
   int TA, NW, DOFI; rtc_feature_layout(NE, s.dof, gram != 0, with_matrix != 0, TA, NW, DOFI);
-  std::shared_ptr<RtcFeature> K;
-  return rtc_feature_module(g, *g->rtc, s.dim, s.dof, TA, NW, DOFI, with_matrix != 0, false, K);
+  std::shared_ptr<RtcInstance> K;
+  return rtc_feature_module(F, s.dim, s.dof, TA, NW, DOFI, with_matrix != 0, false, K);
 }

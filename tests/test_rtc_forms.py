@@ -252,6 +252,32 @@ def test_code_object_cache_on_disk(tmp_path, monkeypatch):
     assert victim.stat().st_size > 1000
 
 
+def test_the_families_of_one_struct_share_a_store(tmp_path, monkeypatch):
+    """One IGX, two families, then the first again: form_pencil (System and Matrix) and vec_sumfact each write their code objects once,
+    and the second check of form_pencil compiles and writes nothing -- the families keep their instantiations side by side."""
+    import petiga_amd as P
+    monkeypatch.setenv("IGX_RTC_CACHE_DIR", str(tmp_path))
+    files = lambda: sorted(p.name for p in tmp_path.iterdir())
+    stamps = lambda: {p.name: p.stat().st_mtime_ns for p in tmp_path.iterdir()}
+    g = P.IGX(3, 1)
+    for i in range(3):
+        g.axis_uniform(i, 2, 4)
+    g.set_form_source(USER_POISSON, "UserPoisson", (1.0,))
+    point_form = files()
+    assert len(point_form) == 1
+    g.check_form_source(True, 2)
+    pencil = [f for f in files() if f not in point_form]
+    assert len(pencil) == 2                                   # form_pencil<System> and form_pencil<Matrix>
+    g.check_form_source(False, 3)
+    vecsf = [f for f in files() if f not in point_form + pencil]
+    assert len(vecsf) == 1                                    # vec_sumfact
+    before = stamps()
+    for f in pencil:                                          # (a second build would read these: without them it would have to compile, and write them again)
+        (tmp_path / f).unlink()
+    g.check_form_source(True, 2)
+    assert files() == sorted(point_form + vecsf) and all(stamps()[f] == before[f] for f in point_form + vecsf)
+
+
 # ---- run-time scalar forms on the pencil walk (form_pencil, gram_mfma.hpp): the enum gate is off the headline path
 USER_POISSON = r"""
 // demo/Poisson3D.c:3-23 (System) as a user struct; params = {forcing}.  The three optional declarations tell the library what the
