@@ -423,7 +423,7 @@ int IGXFastDiagGetAxis(IGX iga,int axis,int field,int *first,int *m,double lambd
  * Sweeps of 16-byte accesses with a scalar tail over a capped grid (krylov.hpp).  IGXVecAXPBY with b = 0 gives y = a x whatever y held.
  * IGXVecPointwiseDivide gives the correctly rounded quotients.  IGXVecDot and IGXVecNorm2 sum over the rows this rank OWNS (IGXChecksum's
  * rule; on one rank every row) and hand the number back, so they synchronise the stream; on several ranks the caller adds the parts, as
- * for IGXComputeScalar (for the norm: the squares).  The sums use no atomics: each workgroup adds its lanes in a fixed tree and stores one
+ * for IGXComputeScalar (for the norm: the squares), with IGXCommAllSum where it has no sum of its own.  The sums use no atomics: each workgroup adds its lanes in a fixed tree and stores one
  * partial, the partials are added in index order by a one-workgroup kernel: bitwise repeatable. */
 int IGXVecSet  (IGXVec y,double value);
 int IGXVecCopy (IGXVec x,IGXVec y);                       /* y = x */
@@ -449,7 +449,31 @@ int IGXVecNorm2(IGXVec x,double *s);
  * first solve and kept with the IGX while the method and the preconditioner need the same set; IGXSetUp drops them, IGXDestroy frees them.
  * Bitwise repeatable.  IGXSetTiming / IGXGetLastTiming cover the whole solve (total time, the operators' and preconditioners' own kernel
  * time, launches); IGXGetKernelName gives "krylov(<method>, pc=<..>, <the action's kernel name>, <k> iterations)".
- * IGX_ERR_SUP with a reason that names the Krylov solve: more than one rank on an axis (the library has no sum across ranks), and
+ * On a partition (more than one rank, after IGXCommInitRCCL / IGXCommInitTransport) the same loop runs on every rank, collectively:
+ *   contract   b is complete on the rows the rank owns (IGXComputeSystem, then IGXReduceGhostRows); U and V carry their ghosts, as for the
+ *              actions.  Of b and of the guess in x only the owned rows are read: every sweep of the loop visits the owned entries alone
+ *              (runs of contiguous doubles at a constant stride, krylov.hpp), so a ghost row is never summed and never written by a sweep.
+ *   A(in,out)  IGXRefreshGhosts(in); the action; IGXReduceGhostRows(NULL,out): out is complete on the owned rows.
+ *   Jacobi     the diagonal, IGXReduceGhostRows, IGXRefreshGhosts, once per solve: no local row holds a partial value.
+ *   PBJacobi   every block column, IGXReduceGhostRows and IGXRefreshGhosts per column, then the invert and apply kernels as on one rank.
+ *   rank sums  every group of partial sums is added across the ranks before anything reads it: each rank adds its slab in index order,
+ *              one group of messages gathers the ranks' sums, and the slab is rewritten to hold rank r's sum in entry r (0 behind the last
+ *              rank), so that the kernels that consume it add ((s_0 + s_1) + s_2) + ... -- the same bits on every rank.  alpha, beta,
+ *              omega, the record and with them every decision of the host (stop, breakdown, NaN, b = 0) are bit-identical on all ranks.
+ *   start      r = b - A(x); one rank sum of {r.r, b.b, the first r.z (CG) or rho (BiCGStab)}.
+ *   CG step    p = z + beta p; A(p,Ap); p.Ap, rank sum; x += alpha p, r -= alpha Ap, r.r; z = M r with r.z; rank sum of {r.r, r.z}; the record.
+ *   BiCGStab   p; y = M p; A(y,v); rhat.v, rank sum; s; z = M s; A(z,t); {t.s, t.t}, rank sum; x, r with {r.r, the next rho}, rank sum; the record.
+ *   end        one IGXRefreshGhosts(x): x holds the solution on the owned rows and their values in its ghosts.
+ * info and history are the same bits on every rank, and a second solve gives the same bits.  IGXGetKernelName then ends in
+ * "<k> iterations, <R> ranks)".  IGXGetLastTiming's launches then count the sweeps, the operators' and preconditioners' kernels and the two
+ * kernels of every rank sum; the pack and unpack kernels of IGXRefreshGhosts / IGXReduceGhostRows and the transport's own are not counted.
+ * What the two exchanges refuse in the loop comes back under the solve's name like any operator's refusal.  The exchanges and the rank sums are stream-ordered on the exchange stream; nothing hides them under the
+ * sweeps, and there is no pipelined or s-step variant.  A failure on one rank in the middle of the loop (a failed launch) leaves its
+ * peers to the transport's timeout.  IGXSolveNonlinear, IGXTimeStep, IGXMultigrid, IGXEigenSolve and the block-vector calls still need one
+ * rank on every axis, and so does IGX_PC_FASTDIAG (its solves run along whole axes).
+ * IGX_ERR_SUP with a reason that names the Krylov solve: more than one rank on an axis without a communicator (the library has no sum
+ * across ranks then), what the ghost-row exchange refuses (a periodic ghost layer that wraps onto its own rank), IGX_PC_FASTDIAG or more
+ * than 256 ranks on a partition -- all decided before the first message from what every rank knows alike -- and
  * whatever the action, the diagonal, the block diagonal or fast diagonalisation refuse, with their reason.  x == b, null or foreign
  * vectors, U / V missing where op needs them, x a state vector: IGX_ERR_ARG_WRONG; maxit < 0, a negative tolerance, an unknown method,
  * operator or preconditioner: IGX_ERR_ARG_OUTOFRANGE; before IGXSetUp: IGX_ERR_ORDER; no form set: IGX_ERR_ARG_WRONGSTATE. */
@@ -460,6 +484,14 @@ typedef enum { IGX_CONVERGED_RTOL = 1, IGX_CONVERGED_ATOL = 2, IGX_DIVERGED_ITS 
 typedef struct { int method, op, pc; double a, t; IGXVec V, U; double rtol, atol; int maxit; } IGXSolveSpec;
 typedef struct { int iterations, reason; double rnorm0, rnorm, bnorm; } IGXSolveInfo;
 int IGXSolve(IGX iga,const IGXSolveSpec *spec,IGXVec b,IGXVec x,IGXSolveInfo *info,double *history /* NULL or [maxit+1]: |r_k|_2 */);
+/* EXPERIMENTAL, for measurements only (scripts/solve_ranks_rate.py; like IGXCommLoopbackTest no part of the interface a caller builds on, and
+ * free to change or go): the mean time in ms of reps launches of one fused sweep of IGXSolve's loops on vectors
+ * of its own, after 3 untimed launches.  runs = 1: the sweep over the owned rows of this IGX's partition (runs of contiguous doubles; needs
+ * IGXSetComm and IGXSetUp, no communicator); runs = 0: its contiguous sibling over the same number of entries.  It synchronises.  An
+ * unknown sweep or form, reps < 1: IGX_ERR_ARG_OUTOFRANGE; before IGXSetUp: IGX_ERR_ORDER. */
+typedef enum { IGX_SWEEP_RESID0 = 0, IGX_SWEEP_DOT, IGX_SWEEP_DOT2, IGX_SWEEP_JACOBI_RZ, IGX_SWEEP_CG_UPDATE, IGX_SWEEP_BICG_XR, IGX_SWEEP_CG_P,
+               IGX_SWEEP_BICG_P, IGX_SWEEP_BICG_S, IGX_SWEEP_PDIV, IGX_SWEEP_SET, IGX_SWEEP_COUNT } IGXKrylovSweep;
+int IGXKrylovSweepTime(IGX iga,int sweep,int runs,int reps,double *ms);
 
 /* The Newton loop on the matrix-free operators, resident on the device: G(x) = 0 from the guess x holds on entry, for the nonlinear forms
  * (Bratu, Cahn-Hilliard, NS-VMS, Bratu as IFunction).  op = IGX_OP_JACOBIAN: G(U) = IGXComputeFunction(U), dG/dU the Jacobian at U.
@@ -932,6 +964,15 @@ int IGXCommDestroy(IGX iga);
 int IGXReduceGhostRows(IGX iga,IGXMat A,IGXVec b);        /* A or b may be NULL */
 int IGXRefreshGhosts(IGX iga,IGXVec v);
 int IGXCommGetLastBytes(IGX iga,int64_t *bytes_sent);      /* of the last exchange */
+/* The sum across ranks, ordered by rank: vals[i] becomes ((v_0[i] + v_1[i]) + v_2[i]) + ... with v_r the values rank r passed, in place,
+ * for 1 <= n <= 64 doubles.  Every rank's values travel to every other rank in ONE group of ncclRecv / ncclSend on the exchange stream (one
+ * call of the host transport with every other rank as peer), and every rank adds them in rank order on the host: all ranks get the same
+ * bits.  Collective over the communicator and blocking: it is what finishes IGXVecDot, IGXVecNorm2 (the squares) and IGXChecksum on a
+ * partition.  IGXSolve adds its inner products by the same rule through the same gather, without leaving the device (below).
+ * Refusals, in this order: null iga or vals: IGX_ERR_ARG_WRONG; n outside [1, 64]: IGX_ERR_ARG_OUTOFRANGE; before IGXSetUp: IGX_ERR_ORDER;
+ * more than one rank and no communicator: IGX_ERR_ARG_WRONGSTATE; more than 256 ranks: IGX_ERR_SUP.  On one rank it returns 0, leaves
+ * vals as they are and touches no device. */
+int IGXCommAllSum(IGX iga,int n,double vals[]);
 /* The rate (GB/s per direction) a face message of the ghost-row reduction travels at, as the face-first decision of the pencil
  * walks uses it: IGXCommInitRCCL times one grouped ncclSend / ncclRecv of IGX_LINK_PROBE_MB (default 64) MB with
  * every face neighbour, all faces at once, after an untimed one that pays the connection set-up; $IGX_LINK_GBS overrides it.

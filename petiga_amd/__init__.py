@@ -90,6 +90,7 @@ class IGXTimeStepInfo(C.Structure):
 SOLVE_METHODS = dict(cg=0, bicgstab=1)
 SOLVE_OPERATORS = dict(matrix=0, jacobian=1, ijacobian=2)
 SOLVE_PCS = dict(none=0, jacobi=1, pbjacobi=2, fastdiag=3)
+KRYLOV_SWEEPS = ("resid0", "dot", "dot2", "jacobi_rz", "cg_update", "bicg_xr", "cg_p", "bicg_p", "bicg_s", "pdiv", "set")      # IGXKrylovSweep, in the header's order
 SOLVE_REASONS = {1: "converged_rtol", 2: "converged_atol", -1: "diverged_its", -2: "diverged_breakdown", -3: "diverged_nan"}
 EIGEN_REASONS = {1: "converged", -1: "diverged_its", -2: "diverged_breakdown", -3: "diverged_nan", 0: "iterating"}
 NEWTON_LINESEARCHES = dict(basic=0, bt=1)
@@ -213,7 +214,8 @@ def lib(build_if_needed=False):
         "IGXCommGetUniqueId": [C.c_void_p, C.c_char_p], "IGXCommInitRCCL": [V, C.c_void_p, C.c_char_p], "IGXCommInitTransport": [V, TRANSPORT_FN, C.c_void_p],
         "IGXCommDestroy": [V], "IGXReduceGhostRows": [V, V, V], "IGXRefreshGhosts": [V, V], "IGXCommGetLastBytes": [V, C.POINTER(C.c_int64)],
         "IGXCommLoopbackTest": [V, C.c_int64, _dp], "IGXCommGetRanks": [V, C.POINTER(C.c_int), C.POINTER(C.c_int)], "IGXCommGetEarlyPhases": [V, C.POINTER(C.c_int)],
-        "IGXCommGetLinkRate": [V, _dp, _ip, _dp, _ip], "IGXGetFacePasses": [V, _ip],
+        "IGXCommGetLinkRate": [V, _dp, _ip, _dp, _ip], "IGXGetFacePasses": [V, _ip], "IGXCommAllSum": [V, C.c_int, _dp],
+        "IGXKrylovSweepTime": [V, C.c_int, C.c_int, C.c_int, _dp],
         "IGXGetDeviceInfo": [C.c_char_p, C.c_int], "IGXCreateFromTables": [V, C.POINTER(V)],
     }
     missing = []
@@ -811,7 +813,10 @@ class IGX:
 
     def solve(self, b, x, method="cg", op="matrix", pc="none", rtol=1e-10, atol=0.0, maxit=1000, a=0.0, t=0.0, V=None, U=None, history=False):
         """IGXSolve: A x = b on the device with A the action `op` names at the state (a, V, t, U), from the guess x holds.  Returns a dict of
-        the info fields (iterations, reason, reason_name, rnorm0, rnorm, bnorm) and, with history=True, |r_k| for k = 0 .. iterations."""
+        the info fields (iterations, reason, reason_name, rnorm0, rnorm, bnorm) and, with history=True, |r_k| for k = 0 .. iterations.
+        On a partition (set_comm and a communicator) every rank calls it: b complete on the owned rows (reduce_ghost_rows), U and V with their
+        ghosts; only the owned rows of b and x are read, x returns with its ghosts refreshed, and the info and the history are the same bits on
+        every rank (the inner products are added across the ranks in rank order).  pc="fastdiag" needs one rank on every axis."""
         code = lambda table, v: table[v] if isinstance(v, str) else int(v)
         spec = IGXSolveSpec(code(SOLVE_METHODS, method), code(SOLVE_OPERATORS, op), code(SOLVE_PCS, pc), float(a), float(t),
                             V.h if V is not None else None, U.h if U is not None else None, float(rtol), float(atol), int(maxit))
@@ -824,6 +829,13 @@ class IGX:
         if history:
             out["history"] = hist[:info.iterations + 1].copy()
         return out
+
+    def krylov_sweep_time(self, sweep, runs, reps=20):
+        """IGXKrylovSweepTime: the mean time in ms of `reps` launches of the fused sweep `sweep` (a name of KRYLOV_SWEEPS or its index), over the
+        owned rows of this IGX's partition (runs=True) or as the contiguous kernel over as many entries (runs=False)."""
+        ms = C.c_double(0.0)
+        _ck(lib().IGXKrylovSweepTime(self.h, KRYLOV_SWEEPS.index(sweep) if isinstance(sweep, str) else int(sweep), int(bool(runs)), int(reps), C.byref(ms)))
+        return ms.value
 
     def eigen(self, nev, mass=None, block=None, pc="none", rtol=1e-8, atol=0.0, maxit=200, X=None, history=False):
         """IGXEigenSolve: the nev lowest eigenpairs of A x = lambda B x by LOBPCG on the device, A this IGX's matrix action, B that of the
@@ -970,6 +982,13 @@ class IGX:
     def comm_destroy(self): _ck(lib().IGXCommDestroy(self.h))
     def reduce_ghost_rows(self, A=None, b=None): _ck(lib().IGXReduceGhostRows(self.h, A.h if A is not None else None, b.h if b is not None else None))
     def refresh_ghosts(self, v): _ck(lib().IGXRefreshGhosts(self.h, v.h))
+
+    def comm_all_sum(self, values):
+        """IGXCommAllSum: the sum of `values` (1 to 64 numbers) over all ranks, added in rank order -- the same bits on every rank.  Collective
+        and blocking; on one rank the values come back as they are.  It finishes Vec.dot, Vec.norm (the squares) and checksum on a partition."""
+        v = np.array(values, dtype=np.float64).ravel()
+        _ck(lib().IGXCommAllSum(self.h, int(v.size), v.ctypes.data_as(_dp)))
+        return v
 
     def comm_last_bytes(self):
         n = C.c_int64()

@@ -10,7 +10,12 @@
 // RCCL is bound at run time (dlopen): the library has no link-time dependency on it, a copy that is already loaded in the
 // process (e.g. the one PyTorch ships) is reused.  A second transport takes a host callback that is handed the packed device
 // buffers: the test transport (gloo in tests / bench.py with ranks sharing one GPU) and the hook for an MPI-based caller.
+//
+// The sum across ranks (the end of this file) travels the same way: every rank's part goes to every other rank in one group on the
+// exchange stream, and every rank adds the parts in rank order, so all ranks hold the same bits.  comm_rank_sum is the device form the
+// solve loops call between their sweeps (krylov.hpp's slabs in, the same slabs out), IGXCommAllSum the host form.
 #include <dlfcn.h>
+#include "krylov.hpp"      // (KR_G, KR_NREC, kr_slab_sum: the slabs the device form of the rank sum works on)
 
 namespace {
 
@@ -87,12 +92,16 @@ struct IgxComm {
   int early_phases = 0;               // phases of the last reduction that started on a face mark of the assembly (IGXCommGetEarlyPhases)
   double link_gbs = 0; int link_source = 0;      // IGXCommGetLinkRate: GB/s per direction of a face message; 0 assumed constant, 1 measured at init, 2 $IGX_LINK_GBS
   double link_probe_ms = 0; int link_faces = 0;
+  DevBuf gather;                      // the rank sum: [world][KR_ALLSUM_MAX] doubles, row r holds rank r's parts
+  hipEvent_t sum_ready = nullptr, sum_done = nullptr;
   ~IgxComm() {
     if (xs) (void)hipStreamSynchronize(xs);      // nothing of this communicator is in flight when it goes
     if (nccl && rccl_api().CommDestroy) (void)rccl_api().CommDestroy(nccl);
     if (ready) (void)hipEventDestroy(ready);
     if (done) (void)hipEventDestroy(done);
     if (packed1) (void)hipEventDestroy(packed1);
+    if (sum_ready) (void)hipEventDestroy(sum_ready);
+    if (sum_done) (void)hipEventDestroy(sum_done);
     if (xs) (void)hipStreamDestroy(xs);
   }
 };
@@ -355,5 +364,98 @@ extern "C" int IGXCommLoopbackTest(IGX g, int64_t n, double *maxdiff) {
   HIPCK(hipMemcpy(back.data(), r.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   double d = 0; for (int64_t i = 0; i < n; ++i) d = std::max(d, std::fabs(back[(size_t)i] - h[(size_t)i]));
   *maxdiff = d;
+  return 0;
+}
+
+// ------------------------------------------------------------------ the sum across ranks, ordered by rank
+// Every rank's m <= KR_ALLSUM_MAX parts go into row `rank` of the gather buffer, one group of messages carries each row to every other
+// rank, and every rank adds column j over the rows 0, 1, ... in that order: ((s_0 + s_1) + s_2) + ..., the same bits everywhere.  The
+// device form keeps the addition where it already is: the slab of a sum is rewritten to hold rank r's part in entry r and 0 behind the
+// last rank, and kr_slab_sum of whoever consumes it (kr_cg_update ..., kr_record) adds in index order as before.
+constexpr int KR_ALLSUM_MAX = 64;      // parts per call, and the row length of the gather buffer
+struct KrRankSlabs { double *s[KR_NREC]; int m; };
+// step 1, one workgroup: row[j] = the index-order sum of slab j
+__global__ void __launch_bounds__(64) kr_rank_own(const KrRankSlabs a, double *row) {
+  if ((int)threadIdx.x < a.m) row[threadIdx.x] = kr_slab_sum(a.s[threadIdx.x]);
+}
+// step 3, workgroup j of KR_G threads: slab j = (rank 0's sum, rank 1's sum, ..., 0, ...)
+__global__ void __launch_bounds__(KR_G) kr_rank_spread(const KrRankSlabs a, const double *gather, int world) {
+  a.s[blockIdx.x][threadIdx.x] = (int)threadIdx.x < world ? gather[(size_t)threadIdx.x * KR_ALLSUM_MAX + blockIdx.x] : 0.0;
+}
+// what a rank sum needs, allocated before the first message: the gather buffer and the two events.  World sizes past KR_G do not fit a slab.
+static int comm_rank_sum_ready(IGX g) {
+  if (!g->comm) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGXCommInitRCCL() / IGXCommInitTransport() first");
+  if (g->s.comm_size > KR_G) return fail(IGX_ERR_SUP, "the sum across ranks holds one entry of a slab per rank: " + std::to_string(KR_G) + " ranks at the most, got " + std::to_string(g->s.comm_size));
+  if (int rc = ensure_device(g)) return rc;
+  IgxComm &c = *g->comm;
+  const size_t bytes = (size_t)g->s.comm_size * KR_ALLSUM_MAX * sizeof(double);
+  if (c.gather.bytes != bytes) {
+    HIPCK(hipStreamSynchronize(c.xs));
+    if (c.gather.alloc(bytes)) return fail(IGX_ERR_MEM, "device allocation of the rank sum's gather buffer failed");
+    HIPCK(hipMemset(c.gather.p, 0, bytes));
+  }
+  if (!c.sum_ready) HIPCK(hipEventCreateWithFlags(&c.sum_ready, hipEventDisableTiming));
+  if (!c.sum_done) HIPCK(hipEventCreateWithFlags(&c.sum_done, hipEventDisableTiming));
+  return 0;
+}
+// step 2 on the exchange stream: the first m doubles of this rank's row to every other rank, theirs into their rows -- ONE group of
+// ncclRecv / ncclSend, or one call of the host transport with every other rank as peer
+static int comm_gather(IGX g, int m) {
+  IgxComm &c = *g->comm;
+  const int world = g->s.comm_size, me = g->s.comm_rank;
+  double *buf = c.gather.as<double>();
+  if (c.kind == 1) {
+    NCCLCK(rccl_api().GroupStart());
+    int rc_ = 0;      // (an error inside the group still closes it)
+    for (int r = 0; r < world && !rc_; ++r) if (r != me) rc_ = rccl_api().Recv(buf + (size_t)r * KR_ALLSUM_MAX, (size_t)m, kNcclDouble, r, c.nccl, c.xs);
+    for (int r = 0; r < world && !rc_; ++r) if (r != me) rc_ = rccl_api().Send(buf + (size_t)me * KR_ALLSUM_MAX, (size_t)m, kNcclDouble, r, c.nccl, c.xs);
+    const int re_ = rccl_api().GroupEnd();
+    NCCLCK(rc_);
+    NCCLCK(re_);
+    return 0;
+  }
+  std::vector<int> peers; std::vector<double *> sb, rb; std::vector<int64_t> cnt;
+  for (int r = 0; r < world; ++r) if (r != me) { peers.push_back(r); sb.push_back(buf + (size_t)me * KR_ALLSUM_MAX); rb.push_back(buf + (size_t)r * KR_ALLSUM_MAX); cnt.push_back(m); }
+  HIPCK(hipStreamSynchronize(c.xs));      // a host transport reads this rank's row
+  if (int rc = c.fn(c.fnctx, (int)peers.size(), peers.data(), sb.data(), cnt.data(), (int)peers.size(), peers.data(), rb.data(), cnt.data())) return fail(IGX_ERR_LIB, "transport callback failed with code " + std::to_string(rc));
+  return 0;
+}
+// The device form: the m <= KR_NREC slabs leave with rank r's sum in entry r.  Stream-ordered like comm_exchange: an event from the
+// engine stream, the three steps on the exchange stream, an event back; on RCCL the host never waits.  comm_rank_sum_ready has run.
+static int comm_rank_sum(IGX g, double *const slabs[], int m) {
+  IgxComm &c = *g->comm;
+  KrRankSlabs a; memset(&a, 0, sizeof(a));
+  for (int j = 0; j < m; ++j) a.s[j] = slabs[j];
+  a.m = m;
+  HIPCK(hipEventRecord(c.sum_ready, g->stream));
+  HIPCK(hipStreamWaitEvent(c.xs, c.sum_ready, 0));
+  hipLaunchKernelGGL(kr_rank_own, dim3(1), dim3(64), 0, c.xs, a, c.gather.as<double>() + (size_t)g->s.comm_rank * KR_ALLSUM_MAX);
+  if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "kr_rank_own: kernel launch failed");
+  if (int rc = comm_gather(g, m)) return rc;
+  hipLaunchKernelGGL(kr_rank_spread, dim3(m), dim3(KR_G), 0, c.xs, a, c.gather.as<double>(), g->s.comm_size);
+  if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "kr_rank_spread: kernel launch failed");
+  HIPCK(hipEventRecord(c.sum_done, c.xs));
+  HIPCK(hipStreamWaitEvent(g->stream, c.sum_done, 0));
+  return 0;
+}
+// The host form: vals[i] = the rank-ordered sum of every rank's vals[i], through the same gather.  Blocks until the sums are there.
+extern "C" int IGXCommAllSum(IGX g, int n, double vals[]) {
+  if (!g || !vals) return fail(IGX_ERR_ARG_WRONG, "IGXCommAllSum: null IGX or null values");
+  if (n < 1 || n > KR_ALLSUM_MAX) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXCommAllSum: 1 to " + std::to_string(KR_ALLSUM_MAX) + " values a call, got " + std::to_string(n));
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXCommAllSum()");
+  if (g->s.comm_size <= 1) return 0;
+  if (int rc = comm_rank_sum_ready(g)) return rc;
+  IgxComm &c = *g->comm;
+  const int world = g->s.comm_size;
+  HIPCK(hipMemcpyAsync(c.gather.as<double>() + (size_t)g->s.comm_rank * KR_ALLSUM_MAX, vals, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c.xs));
+  if (int rc = comm_gather(g, n)) return rc;
+  std::vector<double> rows((size_t)world * KR_ALLSUM_MAX);
+  HIPCK(hipMemcpyAsync(rows.data(), c.gather.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, c.xs));
+  HIPCK(hipStreamSynchronize(c.xs));
+  for (int i = 0; i < n; ++i) {
+    double a = 0.0;
+    for (int r = 0; r < world; ++r) a += rows[(size_t)r * KR_ALLSUM_MAX + i];
+    vals[i] = a;
+  }
   return 0;
 }

@@ -3,3 +3,4 @@
 #undef KR_TAIL
 #undef KR_V2
 #undef KR_C2
+#undef KR_RUN_SWEEP

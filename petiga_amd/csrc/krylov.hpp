@@ -2,7 +2,8 @@
 // BiCGStab over IGXCompute*Action and the diagonal / point-block / fast-diagonalisation preconditioners).  Included by the main unit only,
 // after the drivers it calls.  The sweep macros (KR_PAIRS ... KR_C2) live between kr_sweep_begin.hpp and kr_sweep_end.hpp, here and in newton.hpp.
 // Sweeps: KR_T threads per workgroup, a grid-stride loop over a grid capped at KR_G workgroups, 16-byte accesses (every IGXVec starts at its
-// allocation, so the pairs are aligned) and a scalar tail of n & 1 entries in thread 0 of workgroup 0.
+// allocation, so the pairs are aligned) and a scalar tail of n & 1 entries in thread 0 of workgroup 0.  On a partition the sweeps of the two
+// loops run over the rows the rank owns instead: runs of contiguous doubles at a constant stride (KrRuns, KR_RUN_SWEEP; the end of this file).
 // Reductions: a kernel that emits a sum always runs KR_G workgroups; each adds its lanes in a fixed tree (wavefront shuffles, then LDS in wave
 // order) and stores ONE partial into a slab of KR_G doubles (an idle workgroup stores 0).  The slab is added in index order at the launch
 // boundary: by the prologue of the kernel that consumes the scalar (every thread adds the KR_G partials itself: uniform addresses, one chain
@@ -197,6 +198,130 @@ __global__ void __launch_bounds__(64) kr_bicg_record(const double *slab_rr, cons
   const double alpha = skip ? 0.0 : rho1 / rhatv, omega = skip ? 0.0 : ts / tt;
   rec[0] = kr_slab_sum(slab_rr); rec[1] = rhatv; rec[2] = tt; rec[3] = ts; rec[4] = kr_slab_sum(slab_rho_next); rec[5] = alpha; rec[6] = omega;
   sc[0] = rho1; sc[1] = alpha; sc[2] = omega;
+}
+
+// ------------------------------------------------------------------ the sweeps of the two loops over the owned rows of a rank with ghosts
+// The rows a rank owns are a prefix box (nown0, nown1, nown2) of its row box (nrow0, nrow1, .): with the leading axes the rank holds whole
+// collapsed, the owned entries are runs of len contiguous doubles -- one run when only axis 2 is cut, runs of bs nrow0 nown1 when axis 1
+// is cut too, runs of bs nown0 when axis 0 is.  KR_RUN_SWEEP (kr_sweep_begin.hpp) walks them; a kernel below states its arithmetic once, as
+// a lambda over the width of the access (an aligned pair inside a run, one entry at its ends), and has the name and the prologue of its
+// contiguous sibling above.  A one-rank solve launches the siblings; a partitioned one these, on every rank, the top one with its one run.
+struct KrRuns { long long len, s1, s2; int n1, n2; };
+inline KrRuns kr_runs(const int nown[3], int nrow0, int nrow1, int bs) {
+  KrRuns r;
+  if (nown[0] == nrow0 && nown[1] == nrow1) r = KrRuns{(long long)bs * nrow0 * nrow1 * nown[2], 0, 0, 1, 1};
+  else if (nown[0] == nrow0) r = KrRuns{(long long)bs * nrow0 * nown[1], (long long)bs * nrow0 * nrow1, 0, nown[2], 1};
+  else r = KrRuns{(long long)bs * nown[0], (long long)bs * nrow0, (long long)bs * nrow0 * nrow1, nown[1], nown[2]};
+  if (r.len <= 0 || r.n1 <= 0) { r.len = 0; r.n1 = 1; r.n2 = 0; }      // a rank that owns nothing: no run
+  return r;
+}
+// workgroups of a run sweep that emits no sum: one pass of its (run, chunk) items, KR_G at the most
+inline unsigned kr_run_grid(const KrRuns &r) {
+  const long long half = r.len >> 1, items = (half > 0 ? (half + 63) >> 6 : 1) * r.n1 * r.n2, w = (items + KR_T / 64 - 1) / (KR_T / 64);
+  return (unsigned)(w < 1 ? 1 : (w > KR_G ? KR_G : w));
+}
+template <class T> __device__ inline T kr_ld(const double *p, long long e) { return *reinterpret_cast<const T *>(p + e); }
+template <class T> __device__ inline void kr_st(double *p, long long e, T v) { *reinterpret_cast<T *>(p + e) = v; }
+__device__ inline void kr_acc(double &s, double u, double v) { s += u * v; }
+__device__ inline void kr_acc(double &s, kr_d2 u, kr_d2 v) { s += u.x * v.x; s += u.y * v.y; }
+__device__ inline double kr_fill(double, double v) { return v; }      // v in the width of the first argument, bit for bit (-0.0 stays -0.0)
+__device__ inline kr_d2 kr_fill(kr_d2, double v) { return kr_d2{v, v}; }
+// Every kernel below restates the prologue (the skip conditions, alpha, beta, omega) and the arithmetic of the contiguous kernel of the same
+// name above, which keeps its own text so that a one-rank solve stays bit for bit what it was: a change to one of a pair is a change to both.
+
+__global__ void __launch_bounds__(KR_T) kr_set_runs(const KrRuns rn, double *y, double v) {
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; kr_st<T>(y, e, kr_fill(w, v)); };
+  KR_RUN_SWEEP(rn, body);
+}
+__global__ void __launch_bounds__(KR_T) kr_pdiv_runs(const KrRuns rn, double *z, const double *x, const double *d) {
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; kr_st<T>(z, e, kr_ld<T>(x, e) / kr_ld<T>(d, e)); };
+  KR_RUN_SWEEP(rn, body);
+}
+__global__ void __launch_bounds__(KR_T) kr_dot_runs(const KrRuns rn, const double *x, const double *y, double *slab) {
+  __shared__ double red[KR_T / 64];
+  double s = 0.0;
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; kr_acc(s, kr_ld<T>(x, e), kr_ld<T>(y, e)); };
+  KR_RUN_SWEEP(rn, body);
+  s = kr_block_sum(s, red);
+  if (threadIdx.x == 0) slab[blockIdx.x] = s;
+}
+__global__ void __launch_bounds__(KR_T) kr_dot2_runs(const KrRuns rn, const double *t, const double *s, double *slab_a, double *slab_b) {
+  __shared__ double red[KR_T / 64];
+  double a = 0.0, b = 0.0;
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; const T u = kr_ld<T>(t, e); kr_acc(a, u, kr_ld<T>(s, e)); kr_acc(b, u, u); };
+  KR_RUN_SWEEP(rn, body);
+  a = kr_block_sum(a, red); b = kr_block_sum(b, red);
+  if (threadIdx.x == 0) { slab_a[blockIdx.x] = a; slab_b[blockIdx.x] = b; }
+}
+__global__ void __launch_bounds__(KR_T) kr_resid0_runs(const KrRuns rn, double *r, const double *b, const double *w_, double *slab_rr, double *slab_bb) {
+  __shared__ double red[KR_T / 64];
+  double rr = 0.0, bb = 0.0;
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; const T u = kr_ld<T>(b, e), q = u - kr_ld<T>(w_, e); kr_st<T>(r, e, q); kr_acc(rr, q, q); kr_acc(bb, u, u); };
+  KR_RUN_SWEEP(rn, body);
+  rr = kr_block_sum(rr, red); bb = kr_block_sum(bb, red);
+  if (threadIdx.x == 0) { slab_rr[blockIdx.x] = rr; slab_bb[blockIdx.x] = bb; }
+}
+__global__ void __launch_bounds__(KR_T) kr_cg_update_runs(const KrRuns rn, double *x, double *r, const double *p, const double *Ap, const double *slab_pAp, const double *slab_rz, double *slab_rr) {
+  __shared__ double red[KR_T / 64];
+  const double pAp = kr_slab_sum(slab_pAp), rz = kr_slab_sum(slab_rz);
+  const bool skip = !(pAp > 0.0) || kr_bad(pAp) || kr_bad(rz);
+  const double alpha = skip ? 0.0 : rz / pAp;
+  double rr = 0.0;
+  auto body = [&](auto w, long long e) {
+    typedef decltype(w) T;
+    T q = kr_ld<T>(r, e);
+    if (!skip) { kr_st<T>(x, e, kr_ld<T>(x, e) + alpha * kr_ld<T>(p, e)); q -= alpha * kr_ld<T>(Ap, e); kr_st<T>(r, e, q); }
+    kr_acc(rr, q, q);
+  };
+  KR_RUN_SWEEP(rn, body);
+  rr = kr_block_sum(rr, red);
+  if (threadIdx.x == 0) slab_rr[blockIdx.x] = rr;
+}
+__global__ void __launch_bounds__(KR_T) kr_jacobi_rz_runs(const KrRuns rn, double *z, const double *r, const double *D, double *slab_rz) {
+  __shared__ double red[KR_T / 64];
+  double s = 0.0;
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; const T u = kr_ld<T>(r, e), q = u / kr_ld<T>(D, e); kr_st<T>(z, e, q); kr_acc(s, u, q); };
+  KR_RUN_SWEEP(rn, body);
+  s = kr_block_sum(s, red);
+  if (threadIdx.x == 0) slab_rz[blockIdx.x] = s;
+}
+__global__ void __launch_bounds__(KR_T) kr_cg_p_runs(const KrRuns rn, double *p, const double *z, const double *slab_new, const double *slab_old) {
+  const double beta = kr_slab_sum(slab_new) / kr_slab_sum(slab_old);
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; kr_st<T>(p, e, kr_ld<T>(z, e) + beta * kr_ld<T>(p, e)); };
+  KR_RUN_SWEEP(rn, body);
+}
+__global__ void __launch_bounds__(KR_T) kr_bicg_p_runs(const KrRuns rn, double *p, const double *r, const double *v, const double *slab_rho, const double *sc) {
+  const double rho1 = kr_slab_sum(slab_rho), omega = sc[2];
+  const double beta = (rho1 / sc[0]) * (sc[1] / omega);
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; kr_st<T>(p, e, kr_ld<T>(r, e) + beta * (kr_ld<T>(p, e) - omega * kr_ld<T>(v, e))); };
+  KR_RUN_SWEEP(rn, body);
+}
+__global__ void __launch_bounds__(KR_T) kr_bicg_s_runs(const KrRuns rn, double *s, const double *r, const double *v, const double *slab_rho, const double *slab_rhatv) {
+  const double alpha = kr_slab_sum(slab_rho) / kr_slab_sum(slab_rhatv);
+  auto body = [&](auto w, long long e) { typedef decltype(w) T; kr_st<T>(s, e, kr_ld<T>(r, e) - alpha * kr_ld<T>(v, e)); };
+  KR_RUN_SWEEP(rn, body);
+}
+__global__ void __launch_bounds__(KR_T) kr_bicg_xr_runs(const KrRuns rn, double *x, double *r, const double *y, const double *z, const double *s, const double *t, const double *rhat,
+                                                        const double *slab_rho, const double *slab_rhatv, const double *slab_ts, const double *slab_tt, double *slab_rr, double *slab_rho_next) {
+  __shared__ double red[KR_T / 64];
+  const double rhatv = kr_slab_sum(slab_rhatv), tt = kr_slab_sum(slab_tt);
+  const bool skip = kr_bad(rhatv) || kr_bad(tt);
+  const double alpha = skip ? 0.0 : kr_slab_sum(slab_rho) / rhatv, omega = skip ? 0.0 : kr_slab_sum(slab_ts) / tt;
+  double rr = 0.0, rh = 0.0;
+  auto body = [&](auto w, long long e) {
+    typedef decltype(w) T;
+    T q;
+    if (skip) q = kr_ld<T>(r, e);
+    else {
+      kr_st<T>(x, e, kr_ld<T>(x, e) + (alpha * kr_ld<T>(y, e) + omega * kr_ld<T>(z, e)));
+      q = kr_ld<T>(s, e) - omega * kr_ld<T>(t, e);
+      kr_st<T>(r, e, q);
+    }
+    kr_acc(rr, q, q); kr_acc(rh, kr_ld<T>(rhat, e), q);
+  };
+  KR_RUN_SWEEP(rn, body);
+  rr = kr_block_sum(rr, red); rh = kr_block_sum(rh, red);
+  if (threadIdx.x == 0) { slab_rr[blockIdx.x] = rr; slab_rho_next[blockIdx.x] = rh; }
 }
 
 #include "kr_sweep_end.hpp"

@@ -76,9 +76,10 @@ static const SolverWords kNewtonWords = {"IGXSolveNonlinear", "the Newton solve 
                                          "the Newton solve runs where its residual and its linear solve run, and ", nullptr};
 static const SolverWords kTimeStepWords = {"IGXTimeStep", "the time stepper needs one rank on every axis: its norms and its Newton solve have no sum across ranks",
                                            "the time stepper runs where its Newton solve runs, and ", "IGXTimeStep: the time stepper takes its stages with IGXSolveNonlinear, and "};
-static int solver_ready(IGX g, const SolverWords &w) {
+// on_ranks: the solver runs on a partition once a communicator is there (IGXSolve); without one, and for every other solver, today's refusal
+static int solver_ready(IGX g, const SolverWords &w, bool on_ranks = false) {
   if (!g->s.setup) return fail(IGX_ERR_ORDER, std::string("Must call IGXSetUp() before ") + w.call + "()");
-  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, w.one_rank);
+  for (int d = 0; d < g->s.dim; ++d) if (g->s.proc_sizes[d] != 1 && !(on_ranks && g->comm)) return fail(IGX_ERR_SUP, w.one_rank);
   if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");
   return 0;
 }
@@ -99,7 +100,7 @@ static int solver_refused(const SolverWords &w, int rc) {
 // ------------------------------------------------------------------ vector algebra on IGXVec and the Krylov loop (krylov.hpp)
 #include "krylov.hpp"
 // Everything is enqueued on the engine's stream; IGXVecDot / IGXVecNorm2 read their result back and so synchronise.  The sums run over the
-// rows this rank owns (a prefix of the row box on every axis, as in IGXChecksum): on several ranks the caller adds the parts.
+// rows this rank owns (a prefix of the row box on every axis, as in IGXChecksum): on several ranks the caller adds the parts (IGXCommAllSum).
 static int kr_scalars(IGX g) {
   if (g->krscal.p) return 0;
   if (g->krscal.alloc(KR_SCAL_DOUBLES * sizeof(double))) return fail(IGX_ERR_MEM, "device allocation of the partial-sum slabs failed");
@@ -287,7 +288,10 @@ extern "C" int IGXVecMAXPY(int ny, IGXVec Y[], int nx, IGXVec X[], const double 
 // account their own launches on clk.  IGXSolve passes the matrix-free action and its four preconditioners, IGXMultigridSolve the V-cycle.
 // st.work: r z p Ap (CG), r rhat p v s t y z (BiCGStab), of length st.n on g.
 static bool kr_bad_host(double d) { return !(std::fabs(d) > 0.0) || !std::isfinite(d); }
-struct KrylovPlan { int method; double rtol, atol; int maxit; bool pc_none; const double *jacobi; };
+// On a partition the plan also carries the owned box as runs (krylov.hpp: every sweep then visits the owned entries only) and the number of
+// ranks: each group of sums is then added across the ranks in rank order (comm_rank_sum) before anything reads it.  runs == nullptr is one
+// rank: every launch, argument and bit as it was before the loop knew of ranks.
+struct KrylovPlan { int method; double rtol, atol; int maxit; bool pc_none; const double *jacobi; const KrRuns *runs = nullptr; int ranks = 1; };
 template <class FA, class FM>
 static int krylov_loop(IGX g, KrylovState &st, LoopClock &clk, const KrylovPlan &kp, FA &&A, FM &&M, IGXVec b, IGXVec x, IGXSolveInfo *info, int *iterations, double *history) {
   const long long n = (long long)st.n;
@@ -295,13 +299,28 @@ static int krylov_loop(IGX g, KrylovState &st, LoopClock &clk, const KrylovPlan 
   double *drec = kr_rec(g), *dsc = drec + KR_NREC;
   auto record = [&](std::initializer_list<int> slabs) -> int { clk.own(1); return read_sums(g, slabs, rec); };
   auto D = [&](int k) { return st.work[k]->a.as<double>(); };
+  auto S = [&](int k) { return kr_slab(g, k); };
+  const KrRuns *const rn = kp.runs;
+  // the slabs given hold the sum over all ranks afterwards (one rank: nothing to do)
+  auto rank_sum = [&](std::initializer_list<int> slabs) -> int {
+    if (kp.ranks <= 1) return 0;
+    double *sl[KR_NREC]; int m = 0;
+    for (int k : slabs) sl[m++] = S(k);
+    clk.own(2);
+    return comm_rank_sum(g, sl, m);
+  };
+  // the sweeps: the contiguous kernel over all n entries, or its sibling over the runs of the owned box
+  auto k_dot = [&](const double *a, const double *c, int slab) -> int {
+    if (rn) KR_LAUNCH(kr_dot_runs, KR_G, KR_T, g, *rn, a, c, S(slab)); else KR_LAUNCH(kr_dot, KR_G, KR_T, g, a, c, n, S(slab));
+    return 0;
+  };
   double *xd = x->a.as<double>(); const double *bd = b->a.as<double>();
   g->slab_valid = 0;
   int its = 0, reason = 0;
   double bnorm = 0, rnorm = 0, rnorm0 = 0, thr = 0;
   // r = b - A x with |r| and |b|, shared by both methods: the product goes to work vector 3 (Ap / v), r is work vector 0
   if (int rc = A(x, st.work[3].get())) return rc;
-  KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), bd, D(3), n, kr_slab(g, KS_RR), kr_slab(g, KS_BB));
+  if (rn) KR_LAUNCH(kr_resid0_runs, KR_G, KR_T, g, *rn, D(0), bd, D(3), S(KS_RR), S(KS_BB)); else KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), bd, D(3), n, kr_slab(g, KS_RR), kr_slab(g, KS_BB));
   clk.own(1);
   auto stop = [&]() {      // the test of the recurrence residual, 0 to go on
     if (std::isnan(rnorm)) return (int)IGX_DIVERGED_NAN;
@@ -321,26 +340,37 @@ static int krylov_loop(IGX g, KrylovState &st, LoopClock &clk, const KrylovPlan 
     IGXVec r = st.work[0].get(), z = kp.pc_none ? r : st.work[1].get(), p = st.work[2].get(), Ap = st.work[3].get();
     int cur = 0;      // KS_A + cur holds the newest r.z, KS_A + 1 - cur the one before; KS_C holds p.Ap
     auto precondition = [&](int slab) -> int {
-      if (kp.jacobi) { KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, z->a.as<double>(), r->a.as<double>(), kp.jacobi, n, kr_slab(g, slab)); clk.own(1); return 0; }
+      if (kp.jacobi) {
+        if (rn) KR_LAUNCH(kr_jacobi_rz_runs, KR_G, KR_T, g, *rn, z->a.as<double>(), r->a.as<double>(), kp.jacobi, S(slab)); else KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, z->a.as<double>(), r->a.as<double>(), kp.jacobi, n, kr_slab(g, slab));
+        clk.own(1); return 0;
+      }
       if (int rc = M(r, z)) return rc;
-      KR_LAUNCH(kr_dot, KR_G, KR_T, g, r->a.as<double>(), z->a.as<double>(), n, kr_slab(g, slab));
+      if (int rc = k_dot(r->a.as<double>(), z->a.as<double>(), slab)) return rc;
       clk.own(1);
       return 0;
     };
     if (int rc = precondition(KS_A)) return rc;
+    if (int rc = rank_sum({KS_RR, KS_BB, KS_A})) return rc;
     if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
     double rz = rec[2];
     if (start()) {
       HIPCK(hipMemcpyAsync(p->a.p, z->a.p, z->a.bytes, hipMemcpyDeviceToDevice, g->stream));
       while (!(reason = stop())) {
         if (kr_bad_host(rz)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
-        if (its > 0) { KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, p->a.as<double>(), z->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_A + 1 - cur)); clk.own(1); }
+        if (its > 0) {
+          if (rn) KR_LAUNCH(kr_cg_p_runs, kr_run_grid(*rn), KR_T, g, *rn, p->a.as<double>(), z->a.as<double>(), S(KS_A + cur), S(KS_A + 1 - cur));
+          else KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, p->a.as<double>(), z->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_A + 1 - cur));
+          clk.own(1);
+        }
         if (int rc = A(p, Ap)) return rc;
-        KR_LAUNCH(kr_dot, KR_G, KR_T, g, p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C));
-        KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C), kr_slab(g, KS_A + cur), kr_slab(g, KS_RR));
+        if (int rc = k_dot(p->a.as<double>(), Ap->a.as<double>(), KS_C)) return rc;
+        if (int rc = rank_sum({KS_C})) return rc;
+        if (rn) KR_LAUNCH(kr_cg_update_runs, KR_G, KR_T, g, *rn, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), S(KS_C), S(KS_A + cur), S(KS_RR));
+        else KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, xd, r->a.as<double>(), p->a.as<double>(), Ap->a.as<double>(), n, kr_slab(g, KS_C), kr_slab(g, KS_A + cur), kr_slab(g, KS_RR));
         clk.own(2);
         cur ^= 1;
         if (int rc = precondition(KS_A + cur)) return rc;
+        if (int rc = rank_sum({KS_RR, KS_A + cur})) return rc;
         if (int rc = record({KS_RR, KS_C, KS_A + cur})) return rc;
         if (!(rec[1] > 0.0) || !std::isfinite(rec[1])) { reason = IGX_DIVERGED_BREAKDOWN; break; }      // p.Ap <= 0: the update kernel left x and r alone
         ++its; rnorm = std::sqrt(rec[0]); rz = rec[2];
@@ -353,8 +383,9 @@ static int krylov_loop(IGX g, KrylovState &st, LoopClock &clk, const KrylovPlan 
     int cur = 0;      // KS_A + cur holds rho' = rhat.r of the iteration at hand; KS_C rhat.v, KS_D t.s, KS_E t.t
     static const double one3[3] = {1.0, 1.0, 1.0};
     HIPCK(hipMemcpyAsync(rhat->a.p, r->a.p, r->a.bytes, hipMemcpyDeviceToDevice, g->stream));
-    KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), r->a.as<double>(), n, kr_slab(g, KS_A));
+    if (int rc = k_dot(rhat->a.as<double>(), r->a.as<double>(), KS_A)) return rc;
     clk.own(1);
+    if (int rc = rank_sum({KS_RR, KS_BB, KS_A})) return rc;
     if (int rc = record({KS_RR, KS_BB, KS_A})) return rc;
     double rho_next = rec[2], omega = 1.0;
     if (start()) {
@@ -363,18 +394,25 @@ static int krylov_loop(IGX g, KrylovState &st, LoopClock &clk, const KrylovPlan 
       HIPCK(hipMemcpyAsync(dsc, one3, sizeof(one3), hipMemcpyHostToDevice, g->stream));
       while (!(reason = stop())) {
         if (kr_bad_host(rho_next) || kr_bad_host(omega)) { reason = IGX_DIVERGED_BREAKDOWN; break; }
-        KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), dsc);
+        if (rn) KR_LAUNCH(kr_bicg_p_runs, kr_run_grid(*rn), KR_T, g, *rn, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), S(KS_A + cur), dsc);
+        else KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, p->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), dsc);
         clk.own(1);
         if (int rc = M(p, y)) return rc;
         if (int rc = A(y, v)) return rc;
-        KR_LAUNCH(kr_dot, KR_G, KR_T, g, rhat->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_C));
-        KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_C));
+        if (int rc = k_dot(rhat->a.as<double>(), v->a.as<double>(), KS_C)) return rc;
+        if (int rc = rank_sum({KS_C})) return rc;
+        if (rn) KR_LAUNCH(kr_bicg_s_runs, kr_run_grid(*rn), KR_T, g, *rn, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), S(KS_A + cur), S(KS_C));
+        else KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, s->a.as<double>(), r->a.as<double>(), v->a.as<double>(), n, kr_slab(g, KS_A + cur), kr_slab(g, KS_C));
         clk.own(2);
         if (int rc = M(s, z)) return rc;
         if (int rc = A(z, tv)) return rc;
-        KR_LAUNCH(kr_dot2, KR_G, KR_T, g, tv->a.as<double>(), s->a.as<double>(), n, kr_slab(g, KS_D), kr_slab(g, KS_E));
-        KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(), n,
+        if (rn) KR_LAUNCH(kr_dot2_runs, KR_G, KR_T, g, *rn, tv->a.as<double>(), s->a.as<double>(), S(KS_D), S(KS_E)); else KR_LAUNCH(kr_dot2, KR_G, KR_T, g, tv->a.as<double>(), s->a.as<double>(), n, kr_slab(g, KS_D), kr_slab(g, KS_E));
+        if (int rc = rank_sum({KS_D, KS_E})) return rc;
+        if (rn) KR_LAUNCH(kr_bicg_xr_runs, KR_G, KR_T, g, *rn, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(),
+                          S(KS_A + cur), S(KS_C), S(KS_D), S(KS_E), S(KS_RR), S(KS_A + 1 - cur));
+        else KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, xd, r->a.as<double>(), y->a.as<double>(), z->a.as<double>(), s->a.as<double>(), tv->a.as<double>(), rhat->a.as<double>(), n,
                   kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_RR), kr_slab(g, KS_A + 1 - cur));
+        if (int rc = rank_sum({KS_RR, KS_A + 1 - cur})) return rc;
         KR_LAUNCH(kr_bicg_record, 1, 64, g, kr_slab(g, KS_RR), kr_slab(g, KS_A + cur), kr_slab(g, KS_C), kr_slab(g, KS_D), kr_slab(g, KS_E), kr_slab(g, KS_A + 1 - cur), drec, dsc);
         clk.own(3);
         if (int rc = read_record(g, rec, 7)) return rc;
@@ -385,8 +423,8 @@ static int krylov_loop(IGX g, KrylovState &st, LoopClock &clk, const KrylovPlan 
       }
     }
   }
-  if (reason == IGX_CONVERGED_ATOL && bnorm == 0.0) {      // b = 0: the solution is 0
-    KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, xd, 0.0, n);
+  if (reason == IGX_CONVERGED_ATOL && bnorm == 0.0) {      // b = 0: the solution is 0 (on a partition: on the owned rows; the caller's refresh carries it to the ghosts)
+    if (rn) KR_LAUNCH(kr_set_runs, kr_run_grid(*rn), KR_T, g, *rn, xd, 0.0); else KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, xd, 0.0, n);
     clk.own(1);
     rnorm0 = rnorm = 0.0; if (history) history[0] = 0.0;
     HIPCK(hipStreamSynchronize(g->stream));
@@ -408,7 +446,15 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
   if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: unknown preconditioner");
   if (sp->maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: maxit must not be negative");
   if (!(sp->rtol >= 0) || !(sp->atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXSolve: the tolerances must not be negative");
-  if (int rc = solver_ready(g, words)) return rc;
+  if (int rc = solver_ready(g, words, true)) return rc;
+  // A partition: whatever is refused is refused from what every rank knows alike, before the first message
+  const int ranks = g->s.comm_size;
+  if (ranks > 1) {
+    std::string e;
+    if (int rc = exchange_supported(g->s, e)) return fail(rc, words.where + e);
+    if (sp->pc == IGX_PC_FASTDIAG) return fail(IGX_ERR_SUP, std::string(words.where) + "fast diagonalisation solves along whole axes and needs one rank on every axis");
+    if (ranks > KR_G) return fail(IGX_ERR_SUP, std::string(words.where) + "the sum across ranks holds " + std::to_string(KR_G) + " ranks at the most");
+  }
   if (!b || !x) return fail(IGX_ERR_ARG_WRONG, "null right-hand side or solution vector");
   if (b->iga != g || x->iga != g) return fail(IGX_ERR_ARG_WRONG, "vector created by another IGX");
   if (x == b) return fail(IGX_ERR_ARG_WRONG, "the solution and the right-hand side must be different vectors");
@@ -423,6 +469,17 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
   const long long n = (long long)g->nbrows * g->s.dof;
   if (b->n != n || x->n != n) return fail(IGX_ERR_ARG_WRONG, "vector of another size than the space's");
   if (int rc = kr_scalars(g)) return rc;
+  // the owned box as runs, and the rank sum's buffers
+  KrRuns runs = {0, 0, 0, 1, 0};
+  if (ranks > 1) {
+    int nown[3];
+    for (int d = 0; d < 3; ++d) {
+      const AxisLayout &L = g->s.lay[d]; nown[d] = 0;
+      for (int r = 0; r < L.nrow; ++r) if (L.owned[r]) { if (nown[d] != r) return fail(IGX_ERR_PLIB, "owned rows are not a prefix of the row box"); nown[d]++; }
+    }
+    runs = kr_runs(nown, g->s.lay[0].nrow, g->s.lay[1].nrow, g->s.dof);
+    if (int rc = comm_rank_sum_ready(g)) return rc;
+  }
   const bool cg = sp->method == IGX_SOLVE_CG;
   const int dof = g->s.dof, pc = sp->pc;
   const double shift = sp->op == IGX_OP_IJACOBIAN ? sp->a : 0.0, t = sp->op == IGX_OP_IJACOBIAN ? sp->t : 0.0;
@@ -439,15 +496,21 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
   LoopClock clk(g, st);
   if (int rc = clk.begin(g)) return rc;
   std::string opname;
+  // on a partition: the ghosts of the input from their owners, the action, the ghost rows of the product to their owners
   auto A = [&](IGXVec in, IGXVec out) -> int {
+    if (ranks > 1) if (int rc = IGXRefreshGhosts(g, in)) return solver_refused(words, rc);
     if (int rc = compute_matfree(g, VsMode::ACTION, sp->op, U, V, 1, &in, 1, &out, shift, t)) return solver_refused(words, rc);
     if (opname.empty()) opname = g->last_kernel;
-    return clk.driver(g);
+    if (int rc = clk.driver(g)) return rc;
+    if (ranks > 1) if (int rc = IGXReduceGhostRows(g, nullptr, out)) return solver_refused(words, rc);
+    return 0;
   };
   std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
   if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
     if (int rc = compute_matfree(g, pc == IGX_PC_JACOBI ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL, sp->op, U, V, 0, nullptr, (int)cols.size(), cols.data(), shift, t)) return solver_refused(words, rc);
     if (int rc = clk.driver(g)) return rc;
+    // on a partition every column is completed on its owner and handed back, so that no local row holds a partial value
+    if (ranks > 1) for (IGXVec c : cols) { if (int rc = IGXReduceGhostRows(g, nullptr, c)) return solver_refused(words, rc); if (int rc = IGXRefreshGhosts(g, c)) return solver_refused(words, rc); }
   }
   if (pc == IGX_PC_PBJACOBI) {
     if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return solver_refused(words, rc);
@@ -456,15 +519,84 @@ extern "C" int IGXSolve(IGX g, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSo
   // out = M^-1 in (IGX_PC_NONE: the caller aliases the two)
   auto M = [&](IGXVec in, IGXVec out) -> int {
     if (pc == IGX_PC_NONE) return 0;
-    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); clk.own(1); return 0; }
+    if (pc == IGX_PC_JACOBI) {
+      if (ranks > 1) KR_LAUNCH(kr_pdiv_runs, kr_run_grid(runs), KR_T, g, runs, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>());
+      else KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n);
+      clk.own(1); return 0;
+    }
     if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return solver_refused(words, rc);
     return clk.driver(g);
   };
-  const KrylovPlan kp = {sp->method, sp->rtol, sp->atol, sp->maxit, pc == IGX_PC_NONE, pc == IGX_PC_JACOBI ? cols[0]->a.as<double>() : nullptr};
+  KrylovPlan kp = {sp->method, sp->rtol, sp->atol, sp->maxit, pc == IGX_PC_NONE, pc == IGX_PC_JACOBI ? cols[0]->a.as<double>() : nullptr};
+  if (ranks > 1) { kp.runs = &runs; kp.ranks = ranks; }
   int its = 0;
   if (int rc = krylov_loop(g, st, clk, kp, A, M, b, x, info, &its, history)) return rc;
+  if (ranks > 1) if (int rc = IGXRefreshGhosts(g, x)) return solver_refused(words, rc);      // x leaves with its ghosts, as the actions take it
   static const char *const methods[2] = {"cg", "bicgstab"}, *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
-  return clk.finish(g, std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)");
+  return clk.finish(g, std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations" + (ranks > 1 ? ", " + std::to_string(ranks) + " ranks)" : ")"));
+}
+
+// The measurement hook of scripts/solve_ranks_rate.py: the mean time in ms of `reps` launches of one sweep of the two loops, after 3 untimed
+// ones, by two events on the engine stream.  runs = 1: the run form over the owned box of this IGX's partition (no communicator needed);
+// runs = 0: the contiguous sibling over the same NUMBER of entries.  The vectors are the call's own (ones), the slabs are set so that no
+// kernel takes its skip path and every coefficient is 1; the slabs are zeroed again before the call returns.
+extern "C" int IGXKrylovSweepTime(IGX g, int sweep, int runs, int reps, double *ms) {
+  NEEDIGA(g);
+  if (!ms) return fail(IGX_ERR_ARG_WRONG, "IGXKrylovSweepTime: null result");
+  if (sweep < 0 || sweep >= IGX_SWEEP_COUNT || reps < 1 || (runs != 0 && runs != 1)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXKrylovSweepTime: unknown sweep or form, or reps < 1");
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXKrylovSweepTime()");
+  if (int rc = ensure_device(g)) return rc;
+  if (int rc = kr_scalars(g)) return rc;
+  int nown[3];
+  for (int d = 0; d < 3; ++d) { const AxisLayout &L = g->s.lay[d]; nown[d] = 0; for (int r = 0; r < L.nrow; ++r) if (L.owned[r]) nown[d]++; }
+  const KrRuns rn = kr_runs(nown, g->s.lay[0].nrow, g->s.lay[1].nrow, g->s.dof);
+  const long long n = rn.len * rn.n1 * rn.n2, nall = (long long)g->nbrows * g->s.dof;      // the owned entries; the local vector
+  std::vector<std::unique_ptr<_p_IGXVec>> v;
+  if (int rc = add_vecs(g, nall, 7, v, "device allocation of the sweep probe's vectors failed")) return rc;
+  auto D = [&](int k) { return v[k]->a.as<double>(); };
+  auto S = [&](int k) { return kr_slab(g, k); };
+  for (int k = 0; k < 7; ++k) KR_LAUNCH(kr_set, kr_grid(nall), KR_T, g, D(k), 1.0, nall);
+  double *sc = kr_rec(g) + KR_NREC;
+  static const double scal[3] = {(double)KR_G, 1.0, 1.0};      // rho of the iteration before = the slab sum of rho': beta = 1
+  auto launch = [&]() -> int {
+    switch (sweep) {
+      case IGX_SWEEP_RESID0: if (runs) KR_LAUNCH(kr_resid0_runs, KR_G, KR_T, g, rn, D(0), D(1), D(2), S(KS_RR), S(KS_BB)); else KR_LAUNCH(kr_resid0, KR_G, KR_T, g, D(0), D(1), D(2), n, S(KS_RR), S(KS_BB)); break;
+      case IGX_SWEEP_DOT: if (runs) KR_LAUNCH(kr_dot_runs, KR_G, KR_T, g, rn, D(0), D(1), S(KS_USER)); else KR_LAUNCH(kr_dot, KR_G, KR_T, g, D(0), D(1), n, S(KS_USER)); break;
+      case IGX_SWEEP_DOT2: if (runs) KR_LAUNCH(kr_dot2_runs, KR_G, KR_T, g, rn, D(0), D(1), S(KS_USER), S(KS_BB)); else KR_LAUNCH(kr_dot2, KR_G, KR_T, g, D(0), D(1), n, S(KS_USER), S(KS_BB)); break;
+      case IGX_SWEEP_JACOBI_RZ: if (runs) KR_LAUNCH(kr_jacobi_rz_runs, KR_G, KR_T, g, rn, D(0), D(1), D(2), S(KS_USER)); else KR_LAUNCH(kr_jacobi_rz, KR_G, KR_T, g, D(0), D(1), D(2), n, S(KS_USER)); break;
+      case IGX_SWEEP_CG_UPDATE: if (runs) KR_LAUNCH(kr_cg_update_runs, KR_G, KR_T, g, rn, D(0), D(1), D(2), D(3), S(KS_C), S(KS_A), S(KS_RR)); else KR_LAUNCH(kr_cg_update, KR_G, KR_T, g, D(0), D(1), D(2), D(3), n, S(KS_C), S(KS_A), S(KS_RR)); break;
+      case IGX_SWEEP_BICG_XR:
+        if (runs) KR_LAUNCH(kr_bicg_xr_runs, KR_G, KR_T, g, rn, D(0), D(1), D(2), D(3), D(4), D(5), D(6), S(KS_A), S(KS_C), S(KS_D), S(KS_E), S(KS_RR), S(KS_BB));
+        else KR_LAUNCH(kr_bicg_xr, KR_G, KR_T, g, D(0), D(1), D(2), D(3), D(4), D(5), D(6), n, S(KS_A), S(KS_C), S(KS_D), S(KS_E), S(KS_RR), S(KS_BB));
+        break;
+      case IGX_SWEEP_CG_P: if (runs) KR_LAUNCH(kr_cg_p_runs, kr_run_grid(rn), KR_T, g, rn, D(0), D(1), S(KS_A), S(KS_C)); else KR_LAUNCH(kr_cg_p, kr_grid(n), KR_T, g, D(0), D(1), n, S(KS_A), S(KS_C)); break;
+      case IGX_SWEEP_BICG_P: if (runs) KR_LAUNCH(kr_bicg_p_runs, kr_run_grid(rn), KR_T, g, rn, D(0), D(1), D(2), S(KS_A), sc); else KR_LAUNCH(kr_bicg_p, kr_grid(n), KR_T, g, D(0), D(1), D(2), n, S(KS_A), sc); break;
+      case IGX_SWEEP_BICG_S: if (runs) KR_LAUNCH(kr_bicg_s_runs, kr_run_grid(rn), KR_T, g, rn, D(0), D(1), D(2), S(KS_A), S(KS_C)); else KR_LAUNCH(kr_bicg_s, kr_grid(n), KR_T, g, D(0), D(1), D(2), n, S(KS_A), S(KS_C)); break;
+      case IGX_SWEEP_PDIV: if (runs) KR_LAUNCH(kr_pdiv_runs, kr_run_grid(rn), KR_T, g, rn, D(0), D(1), D(2)); else KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, D(0), D(1), D(2), n); break;
+      default: if (runs) KR_LAUNCH(kr_set_runs, kr_run_grid(rn), KR_T, g, rn, D(0), 1.0); else KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, D(0), 1.0, n); break;
+    }
+    return 0;
+  };
+  struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (auto &x : e) if (x) (void)hipEventDestroy(x); } } ev;      // (freed on every way out)
+  for (auto &x : ev.e) HIPCK(hipEventCreate(&x));
+  const hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
+  int rc = 0; float t = 0;
+  for (int k = -3; k < reps && !rc; ++k) {
+    // the slabs a sweep reads hold 1 in every entry again (a sweep before may have written some of them)
+    if (k <= 0) {
+      hipLaunchKernelGGL(kr_set, dim3(kr_grid((long long)KR_NSLAB * KR_G)), dim3(KR_T), 0, g->stream, g->krscal.as<double>(), 1.0, (long long)KR_NSLAB * KR_G);
+      if (hipGetLastError() != hipSuccess) { rc = fail(IGX_ERR_LIB, "kr_set: kernel launch failed"); break; }
+      if (hipMemcpyAsync(sc, scal, sizeof(scal), hipMemcpyHostToDevice, g->stream) != hipSuccess) { rc = fail(IGX_ERR_LIB, "IGXKrylovSweepTime: copy of the scalars failed"); break; }
+      if (k == 0 && hipEventRecord(e0, g->stream) != hipSuccess) { rc = fail(IGX_ERR_LIB, "IGXKrylovSweepTime: hipEventRecord failed"); break; }
+    }
+    rc = launch();
+  }
+  if (!rc && (hipEventRecord(e1, g->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&t, e0, e1) != hipSuccess)) rc = fail(IGX_ERR_LIB, "IGXKrylovSweepTime: the timed launches failed");
+  (void)hipMemsetAsync(g->krscal.p, 0, g->krscal.bytes, g->stream);
+  (void)hipStreamSynchronize(g->stream);
+  if (rc) return rc;
+  *ms = (double)t / reps;
+  return 0;
 }
 
 // ------------------------------------------------------------------ the Newton loop (newton.hpp)
