@@ -493,6 +493,40 @@ typedef enum { IGX_SWEEP_RESID0 = 0, IGX_SWEEP_DOT, IGX_SWEEP_DOT2, IGX_SWEEP_JA
                IGX_SWEEP_BICG_P, IGX_SWEEP_BICG_S, IGX_SWEEP_PDIV, IGX_SWEEP_SET, IGX_SWEEP_COUNT } IGXKrylovSweep;
 int IGXKrylovSweepTime(IGX iga,int sweep,int runs,int reps,double *ms);
 
+/* The assembled matrix as an operator, for a caller without PETSc's Mat: the product, the diagonals and the Krylov loop on an IGXMat, however
+ * its values got there (any IGXCompute* driver that assembles, any form, dimension, degree or boundary pass: the product only reads them).
+ * One rank on every axis: a column node index is then a row index of x (a periodic axis wrapped inside the rank included).  Everything is
+ * enqueued on the engine's stream; nothing here synchronises but IGXMatSolve's record reads.
+ * IGXMatMult: y = A x, y[r bs + i] = sum_k sum_j val[(browptr[r] + k) bs^2 + i bs + j] x[col(k) bs + j].  y is overwritten (NaN in y on entry
+ *   does not survive); x is read only.  One launch of mat_mult (mat_ops.hpp): a sub-group of 8, 16 or 32 lanes or one wavefront per row, by
+ *   the longest row; val is read once in 16-byte accesses; no atomics, the lanes of a row add in a fixed tree: bitwise repeatable, and a row's
+ *   result depends on that row's values and the x it reads alone.  The column of an entry comes from the per-axis tables (the default
+ *   where a sub-group takes a row) or from bcolidx (the default where a wavefront does); IGX_MATMULT_INDEX=0 / =1 in the environment when the IGX is created picks the tables /
+ *   bcolidx for every block size (both give the same bits; profiles/matmult.txt has their times).  IGXGetKernelName starts with "mat_mult";
+ *   IGXGetLastTiming reports one launch.
+ * IGXMatGetDiagonal: d[r bs + i] = A[r][r][i][i].  IGXMatGetBlockDiagonal: nb = bs vectors, B[j][r bs + i] = A[r][r][i][j] -- the layout of
+ *   IGXCompute*BlockDiagonal, so IGXBlockDiagonalInvert / IGXBlockDiagonalApply take them unchanged.  Copies, bit for bit, one launch each.
+ * IGXMatSolve: IGXSolve's loop (the same code) with A(in, out) = IGXMatMult.  Of the spec it reads method, pc, rtol, atol and maxit; op, a, t,
+ *   V and U are IGNORED (the matrix is what it is).  The preconditioner: none; IGX_PC_JACOBI from IGXMatGetDiagonal; IGX_PC_PBJACOBI from
+ *   IGXMatGetBlockDiagonal and IGXBlockDiagonalInvert's kernel; IGX_PC_FASTDIAG, the state of the caller's IGXFastDiagSetUp on the matrix's
+ *   IGX (without it: IGX_ERR_ORDER).  Stop test, outcomes, b = 0, maxit = 0, history, info and bit-repeatability are IGXSolve's.
+ *   IGXGetKernelName gives "krylov(<method>, pc=<..>, mat_mult(...), <k> iterations)".  The work vectors are IGXSolve's store on the IGX,
+ *   replaced under the same rule: a matrix-free solve before or after a matrix solve is unaffected.
+ * Refusals, in this order, each decided before any HIP call:
+ *   1. a null A, x or y (d; B; spec, b or x): IGX_ERR_ARG_WRONG.  IGXMatGetBlockDiagonal then: nb != bs, a null entry of B: IGX_ERR_ARG_WRONG
+ *   2. a vector of another IGX than A's; a matrix made before the last IGXSetUp of its IGX (its pattern is that set-up's, whether or not the
+ *      sizes changed); a vector whose size is not that of the IGX's present space: IGX_ERR_ARG_WRONG
+ *   3. x == y (IGXMatSolve: x == b; IGXMatGetBlockDiagonal: an entry of B given twice): IGX_ERR_ARG_WRONG
+ *   4. more than one rank on an axis: IGX_ERR_SUP with a reason that names the call and says "one rank"
+ *   5. IGXMatSolve alone, with IGXSolve's codes: a negative or NaN tolerance, maxit < 0, an unknown method or preconditioner:
+ *      IGX_ERR_ARG_OUTOFRANGE; IGX_PC_FASTDIAG without IGXFastDiagSetUp: IGX_ERR_ORDER; then whatever fast diagonalisation refuses, with its
+ *      reason under the solve's name.
+ * Out of scope: several ranks, the transposed product, y += A x, the stored matrix as the operator of the other solve loops. */
+int IGXMatMult(IGXMat A,IGXVec x,IGXVec y);
+int IGXMatGetDiagonal(IGXMat A,IGXVec d);
+int IGXMatGetBlockDiagonal(IGXMat A,int nb,IGXVec B[]);
+int IGXMatSolve(IGXMat A,const IGXSolveSpec *spec,IGXVec b,IGXVec x,IGXSolveInfo *info,double *history /* NULL or [maxit+1]: |r_k|_2 */);
+
 /* The Newton loop on the matrix-free operators, resident on the device: G(x) = 0 from the guess x holds on entry, for the nonlinear forms
  * (Bratu, Cahn-Hilliard, NS-VMS, Bratu as IFunction).  op = IGX_OP_JACOBIAN: G(U) = IGXComputeFunction(U), dG/dU the Jacobian at U.
  * op = IGX_OP_IJACOBIAN: G(U) = IGXComputeIFunction(a, a U + W, t, U), dG/dU = IGXComputeIJacobian(a, a U + W, t, U) -- with a = 1/dt and

@@ -216,6 +216,8 @@ def lib(build_if_needed=False):
         "IGXCommLoopbackTest": [V, C.c_int64, _dp], "IGXCommGetRanks": [V, C.POINTER(C.c_int), C.POINTER(C.c_int)], "IGXCommGetEarlyPhases": [V, C.POINTER(C.c_int)],
         "IGXCommGetLinkRate": [V, _dp, _ip, _dp, _ip], "IGXGetFacePasses": [V, _ip], "IGXCommAllSum": [V, C.c_int, _dp],
         "IGXKrylovSweepTime": [V, C.c_int, C.c_int, C.c_int, _dp],
+        "IGXMatMult": [V, V, V], "IGXMatGetDiagonal": [V, V], "IGXMatGetBlockDiagonal": [V, C.c_int, C.POINTER(V)],
+        "IGXMatSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
         "IGXGetDeviceInfo": [C.c_char_p, C.c_int], "IGXCreateFromTables": [V, C.POINTER(V)],
     }
     missing = []
@@ -570,6 +572,28 @@ class Mat:
         return pi.value, pj.value
 
     def free_coo(self): _ck(lib().IGXMatFreeCOO(self.h))
+
+    # the stored matrix as an operator (one rank on every axis): the product, the diagonals, IGXSolve's loop on it
+    def mult(self, x, y): _ck(lib().IGXMatMult(self.h, x.h if x is not None else None, y.h if y is not None else None))      # y = A x
+    def diagonal(self, d): _ck(lib().IGXMatGetDiagonal(self.h, d.h if d is not None else None))
+
+    def block_diagonal(self, B):
+        """IGXMatGetBlockDiagonal: column j of every node's bs x bs diagonal block into B[j] (the layout of compute_*_block_diagonal)."""
+        _ck(lib().IGXMatGetBlockDiagonal(self.h, len(B), (C.c_void_p * max(len(B), 1))(*[b.h.value if b is not None else None for b in B])))
+
+    def solve(self, b, x, method="cg", pc="none", rtol=1e-10, atol=0.0, maxit=1000, history=False):
+        """IGXMatSolve: A x = b on the device with A this matrix (y = A x by mult), from the guess x holds.  Returns what IGX.solve returns."""
+        code = lambda table, v: table[v] if isinstance(v, str) else int(v)
+        spec = IGXSolveSpec(code(SOLVE_METHODS, method), 0, code(SOLVE_PCS, pc), 0.0, 0.0, None, None, float(rtol), float(atol), int(maxit))
+        info = IGXSolveInfo()
+        hist = np.zeros(max(int(maxit), 0) + 1) if history else None
+        _ck(lib().IGXMatSolve(self.h, C.byref(spec), b.h if b is not None else None, x.h if x is not None else None, C.byref(info),
+                              hist.ctypes.data_as(_dp) if history else None))
+        out = dict(iterations=info.iterations, reason=info.reason, reason_name=SOLVE_REASONS.get(info.reason, str(info.reason)),
+                   rnorm0=info.rnorm0, rnorm=info.rnorm, bnorm=info.bnorm)
+        if history:
+            out["history"] = hist[:info.iterations + 1].copy()
+        return out
 
     def layout(self):
         nrow, ncol = (C.c_int * 3)(), (C.c_int * 3)()

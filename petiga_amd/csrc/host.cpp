@@ -36,6 +36,7 @@ EnvSwitches read_env_switches() {
   e.patch_state = num("IGX_PATCH_STATE", 0);
   e.patch3 = num("IGX_PATCH3", 1);
   e.small_wpb = num("IGX_SMALL_WPB", 1);
+  e.matmult_index = num("IGX_MATMULT_INDEX", -1); if (e.matmult_index < 0 || e.matmult_index > 1) e.matmult_index = -1;
   e.band_prio = num("IGX_BAND_PRIO", 0); e.band_rmw_prio = num("IGX_BAND_RMW_PRIO", 0);
   if (kDebug) { e.debug_feature = num("IGX_DEBUG_FEATURE", 0); e.debug_noflush = num("IGX_DEBUG_NOFLUSH", 0); e.debug_timing = getenv("IGX_DEBUG_TIMING") != nullptr; e.debug_noprio = num("IGX_DEBUG_NOPRIO", 0); }
   return e;

@@ -55,6 +55,9 @@ struct EnvSwitches {
                              // Residual's own pass 2.1 ms per launch
   int gram_sumfact = 1;      // IGX_GRAM_SUMFACT=0: the p = 3 Gram walk on the identity geometry keeps its 480 MFMAs per element (pencil_mfma) instead of
                              // the sum-factorised walk-axis contraction (pencil_mfma_sf)
+  int matmult_index = -1;    // IGX_MATMULT_INDEX: where IGXMatMult takes the column of an entry from -- 0 the per-axis tables (the closed form of k_bcolidx),
+                             // 1 the matrix's bcolidx; unset (-1): the faster one as measured (profiles/matmult.txt) -- the tables where a sub-group takes a
+                             // row (at most 128 doubles), bcolidx where a wavefront does (mat_ops.hpp)
   int combine = -1;          // IGX_COMBINE: element bricks of the feature kernel (-1 = automatic, 0 = one element per workgroup)
   int debug_feature = 0, debug_noflush = 0, debug_timing = 0, debug_noprio = 0;   // only honoured by -DIGX_DEBUG builds
 };
