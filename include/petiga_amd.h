@@ -1086,6 +1086,12 @@ int IGXCommGetEarlyPhases(IGX iga,int *n);
  * nominal 2400 MHz peak; this figure says what the chip actually sustained while the kernel ran. */
 int IGXGetClockProbe(IGX iga,double *shader_mhz,int64_t *elements);
 
+/* The p = 3 patch walk's ticket order, host side (no device is touched).  For a mesh of n1 x n2 elements on axes 1 and 2 walked in nseg
+ * segments, colour (cx, cy) of the patches has *nitems items (segment, patch), item = segment x patches + patch; 0: the colour has no
+ * patch.  With cap > 0, items[t] is the item that ticket t walks and faces[t] whether its patch lies on a face of axis 1 or 2, for
+ * t < min(*nitems, cap); order 0 is the natural order, 1 the faces first (IGX_PATCH3_ORDER). */
+int IGXPatch3TicketOrder(int n1,int n2,int nseg,int cx,int cy,int order,int cap,int *nitems,int *items,int *faces);
+
 /* library / device info for logs */
 int IGXGetDeviceInfo(char *buf,int len);
 

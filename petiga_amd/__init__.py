@@ -219,6 +219,7 @@ def lib(build_if_needed=False):
         "IGXMatMult": [V, V, V], "IGXMatGetDiagonal": [V, V], "IGXMatGetBlockDiagonal": [V, C.c_int, C.POINTER(V)],
         "IGXMatSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
         "IGXGetDeviceInfo": [C.c_char_p, C.c_int], "IGXCreateFromTables": [V, C.POINTER(V)],
+        "IGXPatch3TicketOrder": [C.c_int] * 7 + [_ip, _ip, _ip],
     }
     missing = []
     for name, args in sig.items():
@@ -1088,3 +1089,13 @@ def device_info():
     buf = C.create_string_buffer(256)
     lib().IGXGetDeviceInfo(buf, 256)
     return buf.value.decode()
+
+
+def patch3_ticket_order(n1, n2, nseg, cx, cy, order=1):
+    """The p = 3 patch walk's ticket -> item map of colour (cx, cy) on a mesh of n1 x n2 elements (axes 1, 2) in nseg segments, from the
+    library's own helper (host side, no device): (items, faces) as int arrays over the tickets; empty when the colour has no patch."""
+    n = C.c_int(0)
+    _ck(lib().IGXPatch3TicketOrder(n1, n2, nseg, cx, cy, order, 0, C.byref(n), None, None))
+    items, faces = np.zeros(max(n.value, 1), dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.int32)
+    _ck(lib().IGXPatch3TicketOrder(n1, n2, nseg, cx, cy, order, n.value, C.byref(n), items.ctypes.data_as(_ip), faces.ctypes.data_as(_ip)))
+    return items[:n.value], faces[:n.value]

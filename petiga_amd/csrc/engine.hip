@@ -104,6 +104,7 @@ struct _p_IGX {
   std::function<void()> slab_done;     // set during an assembly with a communicator: marks "upper face of axis 2 assembled" on the engine stream
   DevBuf partials, dbgbuf, clkbuf;   // IGXComputeScalar: per-element partial sums + reduction stages
   DevBuf nsingular;                  // IGXBlockDiagonalInvert: the count of singular blocks
+  DevBuf patch3_counters;            // the p = 3 patch walk's ticket counters, one per colour launch; zeroed on `stream` ahead of every assembly's launches (pencil_launch.hpp)
   DomInfo dom;
   int64_t nbrows = 0, nblocks = 0;
   std::shared_ptr<IgxComm> comm;   // transport of the ghost-row exchange (comm.hpp)
@@ -1048,6 +1049,7 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
   out.debug = s.env.debug_feature;
   if (kDebug && (out.debug & 8)) { if (!g->dbgbuf.p) g->dbgbuf.alloc(32 * sizeof(long long)); HIPCK(hipMemsetAsync(g->dbgbuf.p, 0, 32 * sizeof(long long), g->stream)); out.dbg = g->dbgbuf.as<long long>(); }
   if (s.env.clock_probe) { if (!g->clkbuf.p) { if (g->clkbuf.alloc(4 * sizeof(long long))) return fail(IGX_ERR_MEM, "clock probe buffer"); HIPCK(hipMemsetAsync(g->clkbuf.p, 0, 4 * sizeof(long long), g->stream)); } out.clk = g->clkbuf.as<long long>(); }
+  if (s.env.patch3_persist && s.dim == 3 && s.axis[0].p == 3 && !g->patch3_counters.p && g->patch3_counters.alloc(patch3_counter_bytes<PATCH3_MX, PATCH3_MY>())) return fail(IGX_ERR_MEM, "ticket counters of the patch walk");
   if (hasM) { out.browptr = A->browptr.as<int64_t>(); out.val = A->val.as<double>(); }
   if (hasV) out.vec = b->a.as<double>();
   out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;
@@ -1073,7 +1075,7 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
     // (asked for by name, a Tangent on a mapped geometry at another degree is refused with the reason; the automatic choice goes on to the feature kernel)
     if ((op == OP_JACOBIAN || op == OP_IJACOBIAN) && s.dim == 3 && s.nsd == 3 && s.axis[0].p != 2 && g->kernel_choice == 2 && (s.form == IGX_FORM_CAHNHILLIARD || s.form == IGX_FORM_BRATU))
       return fail(IGX_ERR_SUP, "a Tangent on a mapped geometry takes the walk at p = 2 only (state_pencil_geo); the feature kernel covers the other degrees");
-    rc = try_gram_mfma(g->s, S, out, g->stream, g->kernel_choice == 2, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix, slab_done, tangent ? &st : nullptr, face_done);
+    rc = try_gram_mfma(g->s, S, out, g->stream, g->kernel_choice == 2, g->last_kernel, g->last_launches, g_err, done, g->dom, zero_matrix, slab_done, tangent ? &st : nullptr, face_done, g->patch3_counters.as<int>());
     g->face_done = nullptr;
     if (rc) return rc;
   }
@@ -1505,6 +1507,20 @@ extern "C" int IGXGetClockProbe(IGX g, double *shader_mhz, int64_t *elements) {
   *shader_mhz = 100.0 * (double)h[0] / (double)h[1];
   if (elements) *elements = h[2];
   HIPCK(hipMemsetAsync(g->clkbuf.p, 0, 4 * sizeof(long long), g->stream));   // the sums start again
+  return 0;
+}
+
+// the host side of patch3_ticket_item (gram_patch3.hpp), on the colour's arguments as patch_colour_args fills them
+extern "C" int IGXPatch3TicketOrder(int n1, int n2, int nseg, int cx, int cy, int order, int cap, int *nitems, int *items, int *faces) {
+  using G = Patch3<PATCH3_MX, PATCH3_MY>;
+  if (!nitems || n1 < 1 || n2 < 1 || nseg < 1 || cx < 0 || cx >= G::SX || cy < 0 || cy >= G::SY || (cap > 0 && (!items || !faces))) return fail(IGX_ERR_ARG_WRONG, "IGXPatch3TicketOrder: sizes, colour or result arrays");
+  const int npx = (n1 + G::MX - 1) / G::MX, npy = (n2 + G::MY - 1) / G::MY;
+  PatchArgs A; memset(&A, 0, sizeof(A));
+  A.px_start = cx; A.px_step = G::SX; A.px_count = (npx - cx + G::SX - 1) / G::SX;
+  A.py_start = cy; A.py_step = G::SY; A.py_count = (npy - cy + G::SY - 1) / G::SY;
+  A.pa.nelx = n1; A.pa.nely = n2; A.pa.nseg = nseg;
+  *nitems = (A.px_count <= 0 || A.py_count <= 0) ? 0 : A.px_count * A.py_count * nseg;
+  for (int t = 0; t < std::min(*nitems, cap); ++t) { bool f = false; items[t] = patch3_ticket_item<G>(A, order, t, &f); faces[t] = f ? 1 : 0; }
   return 0;
 }
 

@@ -46,7 +46,7 @@ gram_patch_p2(SpaceDev S, OutDev out, PatchArgs A) {
   const PencilArgs &pa = A.pa;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const PatchWalk D = patch_decode<G>(S, A, wave);
+  const PatchWalk D = patch_decode<G>(S, A, wave, (int)blockIdx.x);
   const int seg = D.seg, ex0 = D.ex0, ey0 = D.ey0, mxv = D.mxv, myv = D.myv, wi = D.wi, wj = D.wj, elx = D.elx, ely = D.ely, wh = D.wh, ne = D.ne, nl = D.nl;
   const bool valid = D.valid;
   const AxisDev &AW = S.ax[0], &AX = S.ax[1], &AY = S.ax[2];
@@ -282,7 +282,7 @@ state_patch_p2(SpaceDev S, OutDev out, PatchArgs A, ParamsDev prm) {
   const PencilArgs &pa = A.pa;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const PatchWalk D = patch_decode<G>(S, A, wave);
+  const PatchWalk D = patch_decode<G>(S, A, wave, (int)blockIdx.x);
   const int seg = D.seg, ex0 = D.ex0, ey0 = D.ey0, mxv = D.mxv, myv = D.myv, wi = D.wi, wj = D.wj, elx = D.elx, ely = D.ely, wh = D.wh, ne = D.ne, nl = D.nl;
   const bool valid = D.valid;
   const AxisDev &AW = S.ax[0], &AX = S.ax[1], &AY = S.ax[2];

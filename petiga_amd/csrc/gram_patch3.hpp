@@ -75,9 +75,54 @@ __host__ __device__ static inline size_t patch3_lds_bytes(int ne_max) {
          (size_t)G::PAIR_INTS * 4 + 64;
 }
 
-template <bool SYSTEM, int MX, int MY>
+// ---- tickets (round 12).  A colour's ITEMS are its (segment, patch) pairs, item = segment x patches + patch as blockIdx.x used to
+// count them.  With a counter, the launch is as many workgroups as the device holds at once; each walks item after item: its first
+// TICKET is its index in the grid, every later one gridDim.x + what a relaxed atomicAdd on the colour's counter returns (the counter
+// starts at zero: the launcher zeroes all of an assembly's counters ahead of its first launch), until a ticket is at or past the item
+// count.  Nobody waits for anybody: no flag, no grid barrier, no spin; the one shared object is the counter, and the loop ends after at
+// most items + grid increments.  Without tickets (TICKETS = false: IGX_PATCH3_PERSIST=0, or a colour whose items the device holds at
+// once) a workgroup walks item blockIdx.x and leaves.
+struct Patch3Tickets {
+  int *counter;      // this launch's counter in device memory (null without tickets)
+  int order;         // patch3_ticket_item's order
+};
+// Ticket -> item, a permutation of the colour's items.  order 0: the identity.  order 1, heavy first: the patches on a face of axis 1 or
+// 2 (where a Dirichlet fix-up runs in every layer) before the interior ones, as list scheduling would have it; within either class
+// segment-major and then in the patches' own order, so that neighbours in memory are still walked at about the same time.
+// *face: whether the ticket's patch lies on such a face.
+template <class G>
+__host__ __device__ inline int patch3_ticket_item(const PatchArgs &A, int order, int t, bool *face = nullptr) {
+  const int px = A.px_count, py = A.py_count, npx = (A.pa.nelx + G::MX - 1) / G::MX, npy = (A.pa.nely + G::MY - 1) / G::MY;
+  const bool x0 = A.px_start == 0, x1 = A.px_start + (px - 1) * A.px_step == npx - 1;
+  const bool y0 = A.py_start == 0, y1 = A.py_start + (py - 1) * A.py_step == npy - 1;
+  if (!order) {
+    if (face) { const int patch = t % (px * py), tx = patch % px, ty = patch / px; *face = (x0 && tx == 0) || (x1 && tx == px - 1) || (y0 && ty == 0) || (y1 && ty == py - 1); }
+    return t;
+  }
+  // columns and rows with the face ones in front: nfx, nfy of them (the low face first), the others behind in their own order
+  const int nfx = (x0 ? 1 : 0) + ((x1 && !(x0 && px == 1)) ? 1 : 0), nfy = (y0 ? 1 : 0) + ((y1 && !(y0 && py == 1)) ? 1 : 0);
+  const int nface = nfy * px + (py - nfy) * nfx, nfi = nface * A.pa.nseg;
+  int seg, tx, ty;
+  if (t < nfi) {
+    seg = t / nface;
+    const int k = t - seg * nface;
+    if (k < nfy * px) { const int r = k / px; ty = (y0 && r == 0) ? 0 : py - 1; tx = k - r * px; }      // a face row, whole
+    else { const int k2 = k - nfy * px, r = k2 / nfx, c = k2 - r * nfx; ty = r + (y0 ? 1 : 0); tx = (x0 && c == 0) ? 0 : px - 1; }      // the face columns of another row
+  } else {
+    const int wd = px - nfx, nin = (py - nfy) * wd, u = t - nfi;
+    seg = u / nin;
+    const int k = u - seg * nin, r = k / wd;
+    ty = r + (y0 ? 1 : 0); tx = k - r * wd + (x0 ? 1 : 0);
+  }
+  if (face) *face = t < nfi;
+  return seg * (px * py) + ty * px + tx;
+}
+
+// TICKETS = false is the launch of one workgroup per item with nothing of the loop compiled in (K is not read): the kernel of the rounds
+// before, which small meshes keep -- the loop's instantiation carries more across an item and took 5 us longer per launch there.
+template <bool SYSTEM, int MX, int MY, bool TICKETS>
 __global__ void __launch_bounds__(MX * MY * 64, 1)
-gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
+gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A, Patch3Tickets K) {
   using G = Patch3<MX, MY>;
   constexpr int P = G::P, NB = 4, BW = G::BW, W = G::W, NX = G::NX, NY = G::NY, BLK = G::BLK, NTHR = W * 64;
   static_assert(patch3_ticks_once_each<G>(patch3_ticks<G>()), "a wavefront adds each block of its completed row once in a step");
@@ -85,10 +130,25 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
   extern __shared__ __attribute__((aligned(16))) double pencil_sm[];
   const PencilArgs &pa = A.pa;
   const bool stamped = kDebug && pa.debug_buf;
-  const long long st_wall0 = stamped ? wall_clock64() : 0;
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int nitems = pa.blocks_per_seg * pa.nseg;
+  // Everything an item leaves behind is built again inside the loop: every table in LDS, the window's zeroes, each register the walk
+  // keeps (the ten open blocks, the F sums, the old values requested ahead, the Dirichlet data) is declared in the loop's body.  The
+  // barrier at its end follows the last read of the trailing layers (leave_f: Fp, corr, the pair tables, the layer table).
+  int ticket = blockIdx.x;
+  if (TICKETS && ticket >= nitems) return;      // (a workgroup beyond the items: IGX_PATCH3_GRID)
+  do {
+  // (the thread's index is made opaque once per item: what depends on it alone is then computed again in every item instead of being
+  //  carried in registers across the whole walk, which took the System instantiation past its 256 VGPRs)
+  int tid = threadIdx.x;
+  if constexpr (TICKETS) asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const PatchWalk D = patch_decode<G>(S, A, wave);
+  const long long st_wall0 = stamped ? wall_clock64() : 0;
+  // the next ticket, asked for at the head of this item: its latency passes under the walk
+  int next_ticket = 0;
+  if (TICKETS && tid == 0) next_ticket = (int)gridDim.x + __hip_atomic_fetch_add(K.counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int item = TICKETS ? patch3_ticket_item<G>(A, K.order, ticket) : ticket;
+  const PatchWalk D = patch_decode<G>(S, A, wave, item);
   const int seg = D.seg, ex0 = D.ex0, ey0 = D.ey0, mxv = D.mxv, myv = D.myv, wi = D.wi, wj = D.wj, elx = D.elx, ely = D.ely, wh = D.wh, ne = D.ne, nl = D.nl;
   const bool valid = D.valid;
   const AxisDev &AW = S.ax[0], &AX = S.ax[1], &AY = S.ax[2];
@@ -383,18 +443,26 @@ gram_pencil_patch3(SpaceDev S, OutDev out, PatchArgs A) {
   }
   if (stamped && lane == 0) {
     // -DIGX_DEBUG: per wavefront, the five parts of a step summed over the walk, its elements, and on the 100 MHz clock the set-up before
-    // the walk and the trailing layers behind it; behind them the workgroup's record {entry, exit, HW_ID, XCC_ID}
-    long long *d = pa.debug_buf + ((size_t)blockIdx.x * W + wave) * 8;
+    // the walk and the trailing layers behind it; behind them the item's record {entry, exit, HW_ID, XCC_ID} (one per item: a workgroup
+    // that walks several leaves several, and the report's gaps are those between two items on a CU)
+    long long *d = pa.debug_buf + ((size_t)item * W + wave) * 8;
     const long long st_wall3 = wall_clock64();
     d[0] = st[0]; d[1] = st[1]; d[2] = st[2]; d[3] = st[3]; d[4] = st[4]; d[5] = ne; d[6] = st_wall1 - st_wall0; d[7] = st_wall3 - st_wall2;
-    if (wave == 0) { long long *w = pa.debug_buf + (size_t)gridDim.x * W * 8 + (size_t)blockIdx.x * 4; w[0] = st_wall0; w[1] = st_wall3; w[2] = __builtin_amdgcn_s_getreg((16 - 1) << 11 | 4); w[3] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20); }
+    if (wave == 0) { long long *w = pa.debug_buf + (size_t)nitems * W * 8 + (size_t)item * 4; w[0] = st_wall0; w[1] = st_wall3; w[2] = __builtin_amdgcn_s_getreg((16 - 1) << 11 | 4); w[3] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20); }
   }
-  if (out.clk && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && tid == 0) {
-    // IGX_CLOCK_PROBE: s_memtime against the 100 MHz s_memrealtime over the walk, first and last workgroup of every launch (as gram_pencil_body)
+  if (out.clk && (item == 0 || item == nitems - 1) && tid == 0) {
+    // IGX_CLOCK_PROBE: s_memtime against the 100 MHz s_memrealtime over the walk, first and last item of every launch (as gram_pencil_body's
+    // first and last workgroup), by whoever walks them
     atomicAdd(reinterpret_cast<unsigned long long *>(out.clk), (unsigned long long)(__builtin_readcyclecounter() - tk0));
     atomicAdd(reinterpret_cast<unsigned long long *>(out.clk) + 1, (unsigned long long)(wall_clock64() - tw0));
     atomicAdd(reinterpret_cast<unsigned long long *>(out.clk) + 2, (unsigned long long)ne);
   }
+  if constexpr (!TICKETS) break;
+  // the workgroup learns its next ticket through LDS; the barrier also closes the item: nothing of it is read after this
+  if (tid == 0) cntp[4] = next_ticket;
+  __syncthreads();
+  ticket = __builtin_amdgcn_readfirstlane(cntp[4]);
+  } while (ticket < nitems);
 }
 
 

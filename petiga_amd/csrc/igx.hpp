@@ -49,6 +49,10 @@ struct EnvSwitches {
   int small_wpb = 1;         // IGX_SMALL_WPB=0: launches that fill less than half the CUs keep eight-wavefront workgroups (pencil_launch.hpp, round 6)
   int patch3 = 1;            // IGX_PATCH3: the p = 3 Gram walk on the identity geometry -- 0 the pencil walk, 1 the patch walk where it pays (default),
                              // 2 the patch walk wherever it covers the configuration (gram_patch3.hpp, round 8)
+  int patch3_persist = 1;    // IGX_PATCH3_PERSIST=0: the p = 3 patch walk launches one workgroup per (segment, patch) item, as before round 12; 1 (default):
+                             // resident workgroups take their items from a counter by ticket (gram_patch3.hpp)
+  int patch3_grid = 0;       // IGX_PATCH3_GRID=n: the ticket launch is n workgroups (test and experiment knob); 0: as many as the device holds, at most the items
+  int patch3_order = 1;      // IGX_PATCH3_ORDER=0: tickets take the items in their natural order; 1 (default): the patches on a face of axis 1 or 2 first
   int patch_state = 0;       // IGX_PATCH_STATE=1: the Tangent of a p = 2 state form walks patches of 4 x 2 pencils (state_patch_p2) instead of state_pencil_k
   int fuse_resid = 0;        // IGX_FUSE_RESID=1: IGXComputeIFunctionIJacobian takes the fused walk (state_pencil_kr) where it exists; default: the two
                              // drivers one after the other -- measured in round 6: the fused launch costs 2.5 ms more than the Tangent's, the

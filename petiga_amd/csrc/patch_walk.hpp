@@ -34,7 +34,8 @@ struct PatchArgs {
   int py_start, py_step, py_count;       // ... and on axis 2
 };
 
-// ---- a workgroup's patch, segment and this wavefront's pencil, from blockIdx.x
+// ---- a workgroup's patch, segment and this wavefront's pencil, from the index of its item (segment, patch) of the colour: blockIdx.x
+// where a workgroup walks one item, the ticket's item where resident workgroups take theirs from a counter (gram_patch3.hpp)
 struct PatchWalk {
   int seg, ppx, ppy;       // segment of the walk axis, patch indices on axes 1, 2
   int ex0, ey0, mxv, myv;  // first element of the patch, elements of the patch inside the mesh
@@ -43,11 +44,11 @@ struct PatchWalk {
   bool valid;
 };
 template <class G>
-__device__ __forceinline__ PatchWalk patch_decode(const SpaceDev &S, const PatchArgs &A, int wave) {
+__device__ __forceinline__ PatchWalk patch_decode(const SpaceDev &S, const PatchArgs &A, int wave, int item) {
   const PencilArgs &pa = A.pa;
   PatchWalk D;
-  D.seg = blockIdx.x / pa.blocks_per_seg;
-  const int patch = blockIdx.x - D.seg * pa.blocks_per_seg;
+  D.seg = item / pa.blocks_per_seg;
+  const int patch = item - D.seg * pa.blocks_per_seg;
   const int tx = patch % A.px_count, ty = patch / A.px_count;
   D.ppx = A.px_start + tx * A.px_step; D.ppy = A.py_start + ty * A.py_step;
   D.ex0 = D.ppx * G::MX; D.ey0 = D.ppy * G::MY;

@@ -12,8 +12,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include "gram_mfma.hpp"
 #include "gram_patch.hpp"
 #include "gram_patch3.hpp"
@@ -344,17 +346,50 @@ static void launch_state_patches_p2(const Space &s, const SpaceDev &S, const Out
                                      [&](int, int, PatchArgs &A, size_t lds, dim3 grid, dim3 block) { hipLaunchKernelGGL(kern, grid, block, lds, stream, S, out, A, prm); });
 }
 // gram_patch3.hpp (round 8): the p = 3 walk of MX x MY patches of pencils
+// ... its ticket counters (round 12): one per colour launch, each on a 128-byte line of its own, in memory the engine owns.  All of an
+// assembly's counters are zeroed by one memset on the engine's stream ahead of its first launch that takes tickets: stream order puts
+// it behind the previous assembly's last launch and before this one's, and a counter belongs to one engine -- a ticket of an earlier assembly,
+// or of another engine, cannot be met.
+constexpr int PATCH3_COUNTER_INTS = 32;
+template <int MX, int MY> constexpr size_t patch3_counter_bytes() { return (size_t)Patch3<MX, MY>::SX * Patch3<MX, MY>::SY * PATCH3_COUNTER_INTS * sizeof(int); }
+// workgroups of the kernel the device holds at once: the occupancy of its block and LDS size times the CUs
+// (asked once per kernel and LDS size: the six launches of an assembly, and the assemblies of a run, share the answer)
+static int patch3_resident(const void *kern, int block, size_t lds) {
+  static thread_local std::map<std::pair<const void *, size_t>, int> known;
+  int &per_cu = known[{kern, lds}];
+  if (per_cu < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, lds) != hipSuccess || per_cu < 1)) { (void)hipGetLastError(); per_cu = 1; }
+  return per_cu * pencil_cus();
+}
+// The launch of a colour: IGX_PATCH3_PERSIST=1 (default) min(items, resident workgroups) workgroups that take their items by ticket --
+// where the device holds every item at once a ticket has nothing to hand out, and the launch is the one below; IGX_PATCH3_GRID=n: n
+// workgroups with tickets whatever the items (tests, experiments).  IGX_PATCH3_PERSIST=0: one workgroup per item.
 template <int MX, int MY>
-static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch) {
+static void launch_patches_p3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, bool first_touch, int *counters) {
   using G = Patch3<MX, MY>;
-  auto kern = out.op == OP_SYSTEM ? gram_pencil_patch3<true, MX, MY> : gram_pencil_patch3<false, MX, MY>;
+  auto kern = out.op == OP_SYSTEM ? gram_pencil_patch3<true, MX, MY, false> : gram_pencil_patch3<false, MX, MY, false>;      // one workgroup per item
+  auto kern_t = out.op == OP_SYSTEM ? gram_pencil_patch3<true, MX, MY, true> : gram_pencil_patch3<false, MX, MY, true>;      // tickets
+  const bool persist = s.env.patch3_persist != 0;
+  if (persist && !counters) { pencil_launch_error() = "the p = 3 patch walk's ticket counters are missing"; return; }
+  bool zeroed = false;      // (the memset goes ahead of the first launch that takes tickets: an assembly without one makes none)
   launch_patch_colours<G>(s, forcing, first_touch, patch3_lds_bytes<MX, MY>, "the p = 3 patch walk's tables do not fit the LDS", reinterpret_cast<const void *>(kern), launches,
                           [&](int cx, int cy, PatchArgs &A, size_t lds, dim3 grid, dim3 block) {
     static StampGate gate;      // -DIGX_DEBUG, IGX_DEBUG_TIMING=n: the n-th launch of the process is stamped (as launch_patches_p2)
     const bool dbg_t = gate.due(s);
     const size_t dbg_n = patch3_stamp_count(A.pa, G::W);
     if (dbg_t) stamps_alloc(A.pa, dbg_n);
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, S, out, A);
+    Patch3Tickets K{nullptr, s.env.patch3_order};
+    if (persist) {
+      const long long items = grid.x, resident = patch3_resident(reinterpret_cast<const void *>(kern_t), (int)block.x, lds);
+      if (s.env.patch3_grid > 0 || items > resident) {
+        if (!zeroed) { (void)hipMemsetAsync(counters, 0, patch3_counter_bytes<MX, MY>(), stream); zeroed = true; }
+        K.counter = counters + (cy * G::SX + cx) * PATCH3_COUNTER_INTS;
+        grid.x = (unsigned)(s.env.patch3_grid > 0 ? s.env.patch3_grid : std::min(items, resident));
+      }
+    }
+    if (K.counter) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern_t), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kern_t, grid, block, lds, stream, S, out, A, K);
+    } else hipLaunchKernelGGL(kern, grid, block, lds, stream, S, out, A, K);
     if (dbg_t) report_patch3_stamps(stamps_fetch(stream, A.pa, dbg_n), A.pa, G::W, cx, cy);
   });
 }
@@ -548,12 +583,13 @@ static int run_patch_walk(const Space &s, hipStream_t stream, const WalkInfo &w,
 
 // ------------------------------------------------------------------ dispatch
 // zero_matrix: MatZeroEntries of the caller; called before the first launch unless the axis-0 walk stores first touches
+// patch3_counters: the engine's ticket counters of the p = 3 patch walk (patch3_counter_bytes of device memory; launch_patches_p3)
 // slab_done (may be empty): called between the two passes of an assembly that forms the elements next to the upper face of axis
 // 2 first -- the ghost rows of that face are complete then and their exchange can run under the rest of the launches
 static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, bool forced,
                          std::string &kname, int &launches, std::string &err, bool &done, DomInfo &dom, const std::function<void()> &zero_matrix,
                          const std::function<void()> &slab_done = std::function<void()>(), const PencilModule *mod = nullptr,
-                         const std::function<void(int)> &face_done = std::function<void(int)>()) {
+                         const std::function<void(int)> &face_done = std::function<void(int)>(), int *patch3_counters = nullptr) {
   done = false;
   auto no = [&](const char *why) { if (forced) { err = std::string("MFMA kernel does not cover this configuration: ") + why; return (int)IGX_ERR_SUP; } return 0; };
   if (!mod && s.form != IGX_FORM_POISSON && s.form != IGX_FORM_POISSON_F) return no("form is not a scalar gradient-Gram form");
@@ -604,7 +640,7 @@ static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, h
   // It reports itself as a Gram pencil walk: the same element phase, bit-repeatable like it.
   if (deg == 3 && s.env.gram_sumfact != 0 && gram_patch_ok() && (s.env.patch3 == 2 || (s.env.patch3 == 1 && patch3_pays(s)))) {
     info.kind = WalkInfo::PATCH_P3;
-    return run_patch_walk(s, stream, info, "gram_pencil_patch3 kernel launch failed", [&] { launch_patches_p3<PATCH3_MX, PATCH3_MY>(s, S, out, stream, launches, ga.forcing, first_touch); }, kname, launches, err, done, dom);
+    return run_patch_walk(s, stream, info, "gram_pencil_patch3 kernel launch failed", [&] { launch_patches_p3<PATCH3_MX, PATCH3_MY>(s, S, out, stream, launches, ga.forcing, first_touch, patch3_counters); }, kname, launches, err, done, dom);
   }
   // p = 2, a Tangent (IGX_PATCH_STATE=1): 4 x 2 pencils per workgroup, state_patch_p2
   if (deg == 2 && walk_axis == 0 && s.env.patch_state && state && !geo && mod->patch_kfn && patch_walk_covers(s)) {
