@@ -104,7 +104,7 @@ struct _p_IGX {
   std::function<void()> slab_done;     // set during an assembly with a communicator: marks "upper face of axis 2 assembled" on the engine stream
   DevBuf partials, dbgbuf, clkbuf;   // IGXComputeScalar: per-element partial sums + reduction stages
   DevBuf nsingular;                  // IGXBlockDiagonalInvert: the count of singular blocks
-  DevBuf patch3_counters;            // the p = 3 patch walk's ticket counters, one per colour launch; zeroed on `stream` ahead of every assembly's launches (pencil_launch.hpp)
+  DevBuf patch3_counters;            // the p = 3 patch walk's ticket counters, one per colour launch (the rows walk, gram_rows3.hpp, takes the first); zeroed on `stream` ahead of every assembly's launches (pencil_launch.hpp)
   DomInfo dom;
   int64_t nbrows = 0, nblocks = 0;
   std::shared_ptr<IgxComm> comm;   // transport of the ghost-row exchange (comm.hpp)
@@ -1049,7 +1049,7 @@ static int compute(IGX g, int op, IGXMat A, IGXVec b, IGXVec U, IGXVec V, double
   out.debug = s.env.debug_feature;
   if (kDebug && (out.debug & 8)) { if (!g->dbgbuf.p) g->dbgbuf.alloc(32 * sizeof(long long)); HIPCK(hipMemsetAsync(g->dbgbuf.p, 0, 32 * sizeof(long long), g->stream)); out.dbg = g->dbgbuf.as<long long>(); }
   if (s.env.clock_probe) { if (!g->clkbuf.p) { if (g->clkbuf.alloc(4 * sizeof(long long))) return fail(IGX_ERR_MEM, "clock probe buffer"); HIPCK(hipMemsetAsync(g->clkbuf.p, 0, 4 * sizeof(long long), g->stream)); } out.clk = g->clkbuf.as<long long>(); }
-  if (s.env.patch3_persist && s.dim == 3 && s.axis[0].p == 3 && !g->patch3_counters.p && g->patch3_counters.alloc(patch3_counter_bytes<PATCH3_MX, PATCH3_MY>())) return fail(IGX_ERR_MEM, "ticket counters of the patch walk");
+  if ((s.env.patch3_persist || s.env.rows3) && s.dim == 3 && s.axis[0].p == 3 && !g->patch3_counters.p && g->patch3_counters.alloc(patch3_counter_bytes<PATCH3_MX, PATCH3_MY>())) return fail(IGX_ERR_MEM, "ticket counters of the patch walk");
   if (hasM) { out.browptr = A->browptr.as<int64_t>(); out.val = A->val.as<double>(); }
   if (hasV) out.vec = b->a.as<double>();
   out.U = U ? U->a.as<double>() : nullptr; out.V = V ? V->a.as<double>() : nullptr;

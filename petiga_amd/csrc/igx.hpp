@@ -35,7 +35,8 @@ struct EnvSwitches {
   int overlap = -1;          // IGX_OVERLAP: 0 = no face-first passes, the ghost-row exchange starts after the last launch; 1 = always; 2 = the face of axis 2
                              // alone (round 3); unset (-1): the pencil walk decides by cost against the size of the faces, the other kernels make their pass
   int fuse_groups = 1;       // IGX_FUSE_GROUPS=0: one launch per group of row fields again (NS-VMS p=3; experiment switch)
-  int no_first_touch = 0;    // IGX_NO_FIRST_TOUCH: MatZeroEntries + read-modify-write everywhere
+  int no_first_touch = 0;    // IGX_NO_FIRST_TOUCH: MatZeroEntries + read-modify-write everywhere (no meaning for the p = 3 rows walk, gram_rows3.hpp:
+                             // it stores every entry once and reads none)
   int feature_lds_kb = 0;    // IGX_FEATURE_LDS_KB: LDS target of the feature kernel
   int block_pencil = 1;      // IGX_BLOCK_PENCIL=0: constant-coefficient multi-field forms stay on the feature kernel (block_pencil.hpp)
   int no_vec_pairs = 0;      // IGX_NO_VEC_PAIRS=1: vec_sumfact keeps one element per wavefront at p <= 2
@@ -53,6 +54,9 @@ struct EnvSwitches {
                              // resident workgroups take their items from a counter by ticket (gram_patch3.hpp)
   int patch3_grid = 0;       // IGX_PATCH3_GRID=n: the ticket launch is n workgroups (test and experiment knob); 0: as many as the device holds, at most the items
   int patch3_order = 1;      // IGX_PATCH3_ORDER=0: tickets take the items in their natural order; 1 (default): the patches on a face of axis 1 or 2 first
+  int rows3 = 1;             // IGX_ROWS3: the p = 3 Gram matrix gathered by rows, each entry stored once (gram_rows3.hpp, round 13) -- 0 never, 1 where it pays
+                             // (default), 2 wherever it covers the configuration.  Chosen under IGX_PATCH3=1 only: IGX_PATCH3=0 is the pencil walk, 2 the patch walk
+  int rows3_grid = 0;        // IGX_ROWS3_GRID=n: the rows walk is a ticket launch of n workgroups (test and experiment knob); 0: as many as the device holds
   int patch_state = 0;       // IGX_PATCH_STATE=1: the Tangent of a p = 2 state form walks patches of 4 x 2 pencils (state_patch_p2) instead of state_pencil_k
   int fuse_resid = 0;        // IGX_FUSE_RESID=1: IGXComputeIFunctionIJacobian takes the fused walk (state_pencil_kr) where it exists; default: the two
                              // drivers one after the other -- measured in round 6: the fused launch costs 2.5 ms more than the Tangent's, the

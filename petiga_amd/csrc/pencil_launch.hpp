@@ -19,6 +19,7 @@
 #include "gram_mfma.hpp"
 #include "gram_patch.hpp"
 #include "gram_patch3.hpp"
+#include "gram_rows3.hpp"
 #include "boundary_loads.hpp"
 #include "pencil_stamps.hpp"
 #include "module_launch.hpp"
@@ -412,6 +413,63 @@ static bool patch3_pays(const Space &s) {
   return (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] >= PATCH3_MIN_ELEMENTS;
 }
 
+// gram_rows3.hpp (round 13): the p = 3 matrix gathered by rows.  It covers what the patch walk covers, on axes that are not periodic and
+// bring one new node per element, axis 0 included (a node's elements are then the four below it on every axis).
+static bool rows3_covers(const Space &s) {
+  if (!patch_walk_covers(s)) return false;
+  for (int d = 0; d < 3; ++d) {
+    if (s.axis[d].periodic || s.lay[d].gwidth != s.elem_width[d] + 3 || s.lay[d].nrow != s.lay[d].gwidth) return false;
+    for (int e = 0; e + 1 < s.elem_width[d]; ++e) if (s.basis[d].offset[s.elem_start[d] + e + 1] != s.basis[d].offset[s.elem_start[d] + e] + 1) return false;
+  }
+  return true;
+}
+// ... where it is the automatic choice (IGX_ROWS3=1): the smallest measured cube at which both alternated pairs were faster than the
+// patch walk (profiles/r13_rows3.txt)
+constexpr long long ROWS3_MIN_ELEMENTS = 48LL * 48 * 48;
+static bool rows3_pays(const Space &s) {
+  return (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] >= ROWS3_MIN_ELEMENTS;
+}
+// Segments of node layers: as long as possible (an item stages its tables and forms its planes once: about two layers' worth of
+// time), at most ROWS3_SEG_MAX layers, and shorter down to eight layers while the items are fewer than two per resident workgroup.
+// IGX_NSEG forces the count (down to one layer per segment).
+constexpr int ROWS3_SEG_MAX = 64;
+static void rows3_segments(const Space &s, int nl0, long long tiles, long long resident, int &seg_len, int &nseg) {
+  int n = (nl0 + ROWS3_SEG_MAX - 1) / ROWS3_SEG_MAX;
+  while (tiles * n < 2 * resident && (nl0 + n) / (n + 1) >= 8) ++n;
+  if (s.env.nseg > 0) n = std::max((nl0 + ROWS3_SEG_MAX - 1) / ROWS3_SEG_MAX, std::min(s.env.nseg, nl0));
+  seg_len = (nl0 + n - 1) / n; nseg = (nl0 + seg_len - 1) / seg_len;
+}
+// One launch per assembly.  Where the items outnumber the resident workgroups (or IGX_ROWS3_GRID=n asks for n workgroups) they are
+// taken by ticket from the first of the engine's counters, zeroed on the stream ahead of the launch; else one workgroup per item.
+static void launch_rows3(const Space &s, const SpaceDev &S, const OutDev &out, hipStream_t stream, int &launches, double forcing, int *counters) {
+  using R = Rows3;
+  const bool sys = out.op == OP_SYSTEM;
+  auto kern = sys ? gram_pencil_rows3<true, false> : gram_pencil_rows3<false, false>;
+  auto kern_t = sys ? gram_pencil_rows3<true, true> : gram_pencil_rows3<false, true>;
+  Rows3Args A; memset(&A, 0, sizeof(A));
+  A.forcing = forcing;
+  A.nel0 = s.elem_width[0]; A.nelx = s.elem_width[1]; A.nely = s.elem_width[2];
+  A.nl0 = A.nel0 + 3; A.nnx = A.nelx + 3; A.nny = A.nely + 3;
+  A.ntx = (A.nnx + R::TX - 1) / R::TX; A.nty = (A.nny + R::TY - 1) / R::TY;
+  const long long tiles = (long long)A.ntx * A.nty;
+  const long long resident = patch3_resident(reinterpret_cast<const void *>(kern_t), R::NTHR, rows3_lds_bytes(ROWS3_SEG_MAX));
+  rows3_segments(s, A.nl0, tiles, resident, A.seg_len, A.nseg);
+  const size_t lds = rows3_lds_bytes(A.seg_len);
+  const long long items = tiles * A.nseg;
+  if (lds > LDS_MAX || items > INT_MAX) { pencil_launch_error() = "the p = 3 rows walk's items or tables are beyond the launch's limits"; return; }
+  unsigned grid = (unsigned)items;
+  if (s.env.rows3_grid > 0 || items > resident) {
+    if (!counters) { pencil_launch_error() = "the p = 3 rows walk's ticket counter is missing"; return; }
+    (void)hipMemsetAsync(counters, 0, patch3_counter_bytes<PATCH3_MX, PATCH3_MY>(), stream);
+    A.counter = counters;
+    grid = (unsigned)(s.env.rows3_grid > 0 ? s.env.rows3_grid : resident);
+  }
+  const auto k = A.counter ? kern_t : kern;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(k, dim3(grid), dim3(R::NTHR), lds, stream, S, out, A);
+  launches++;
+}
+
 // ------------------------------------------------------------------ the Tangent's module
 // the walk's instantiation for the Tangent of a built-in state form: no geometry (state_pencil; p = 2 with packed tiles state_pencil_k,
 // with the Residual on the same MFMAs state_pencil_kr, and state_patch_p2 for the patch walk), a mapped geometry at p = 2
@@ -517,7 +575,7 @@ static WalkPasses assembly_passes(const Space &s, const PencilWalk &pw, const Bo
 
 // ------------------------------------------------------------------ reporting
 struct WalkInfo {
-  enum Kind { PATCH_P2, PATCH_P3, STATE_PATCH_P2, ELEMENTS, PENCILS } kind;
+  enum Kind { PATCH_P2, PATCH_P3, ROWS_P3, STATE_PATCH_P2, ELEMENTS, PENCILS } kind;
   int deg = 3, walk_axis = 0; bool geo = false, fixt = false; const PencilModule *mod = nullptr;
   bool state() const { return mod && mod->state; }
 };
@@ -525,6 +583,7 @@ static std::string walk_dom_name(const WalkInfo &w) {
   switch (w.kind) {
   case WalkInfo::PATCH_P2: return "gram_patch<p=2>";
   case WalkInfo::PATCH_P3: return "gram_pencil<walk=0,p=3,patch>";
+  case WalkInfo::ROWS_P3: return "gram_pencil<walk=0,p=3,rows>";
   case WalkInfo::STATE_PATCH_P2: return "state_patch<p=2>";
   case WalkInfo::ELEMENTS: return "gram_p3_element";
   default: return std::string(w.state() ? "state_pencil<walk=" : w.mod ? "form_pencil<hiprtc,walk=" : "gram_pencil<walk=") + char('0' + w.walk_axis) + ",p=" + char('0' + w.deg) + (w.geo ? ",geometry" : "") + ">";
@@ -535,6 +594,9 @@ static double walk_flop_per_element(const Space &s, const WalkInfo &w) {
   switch (w.kind) {
   case WalkInfo::PATCH_P2: return 2048.0 * 21 * 3;
   case WalkInfo::PATCH_P3: return 2.0 * 2 * 4 * 64 * 10;      // (the element phase of the sum-factorised walk: pencil_mfma_sf on 10 tiles)
+  // the rows walk: per layer of a tile of nine rows, wavefront dy runs (4 - |dy|) x 4 pencils x 16 (ta, tb) x 2 v_fma_f64 on 64 lanes (16 pencil
+  // rows over the seven wavefronts), on the vector pipe; a mesh has one row per element up to its faces
+  case WalkInfo::ROWS_P3: return 2.0 * 2 * 16 * 4 * 16 * 64 / Rows3::COLS;
   case WalkInfo::STATE_PATCH_P2: return w.mod->flop_per_element;
   case WalkInfo::ELEMENTS: return 2048.0 * 48 * 16;
   default: break;
@@ -550,6 +612,7 @@ static std::string walk_kname(const Space &s, const WalkInfo &w) {
   switch (w.kind) {
   case WalkInfo::PATCH_P2: return "gram_patch(mfma_f64_16x16x4,p=2,walk=0,packed tiles,4x3 pencils per workgroup,one window)";
   case WalkInfo::PATCH_P3: return "gram_pencil(mfma_f64_16x16x4,p=3,walk=0," + std::to_string(PATCH3_MX) + "x" + std::to_string(PATCH3_MY) + " pencils per workgroup,one window)";
+  case WalkInfo::ROWS_P3: return "gram_pencil(fp64 fma,p=3,walk=0,rows gathered by their owner,each entry stored once)";
   case WalkInfo::STATE_PATCH_P2: return "state_patch<" + w.mod->name + ">(mfma_f64_16x16x4,p=2,walk=0,packed tiles,4x2 pencils per workgroup,one window)";
   case WalkInfo::ELEMENTS: return "gram_p3_element(mfma_f64_16x16x4)";
   default: break;
@@ -622,13 +685,23 @@ static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, h
   Box all; for (int d = 0; d < 3; ++d) { all.lo[d] = 0; all.hi[d] = s.elem_width[d]; }
   if (!walk && deg != 3) return no("p=2 needs a walkable axis 0");
   const bool first_touch = walk_axis == 0 && !s.env.no_first_touch && out.val && axis_first_touch_ok(s, 1) && axis_first_touch_ok(s, 2);
-  if (!first_touch) zero_matrix();
+  // (round 13: IGX_ROWS3) p = 3 where the patch walk applies, one new node per element on axis 0 too: the rows walk (gram_rows3.hpp) stores
+  // every entry once and reads none -- no MatZeroEntries, no first touch, one launch.  Chosen under IGX_PATCH3=1 only.
+  const bool patch_ok = walk_axis == 0 && !geo && !mod && !fixt && (out.op == OP_MATRIX || out.op == OP_SYSTEM) && patch_walk_covers(s);
+  const bool rows3 = deg == 3 && s.env.gram_sumfact != 0 && patch_ok && out.val && s.env.patch3 == 1 && rows3_covers(s) &&
+                     (s.env.rows3 == 2 || (s.env.rows3 == 1 && rows3_pays(s)));
+  if (rows3) { /* nothing to zero */ }
+  else if (!first_touch) zero_matrix();
   else if (s.proc_sizes[0] * s.proc_sizes[1] * s.proc_sizes[2] > 1) zero_neighbour_rows(s, out, stream);   // the only entries no local element reaches
   // boundary loads first: F is zeroed and only added to, so the order is free -- and the ghost rows of the upper face of axis 2
   // must be complete when the first pass of a multi-rank assembly ends (slab_done below)
   if (sys) { if (int rc = launch_boundary_loads(s, S, out, stream, err)) return rc; }
   WalkInfo info; info.deg = deg; info.walk_axis = walk_axis; info.geo = geo; info.fixt = fixt; info.mod = mod;
-  auto gram_patch_ok = [&] { return walk_axis == 0 && !geo && !mod && !fixt && (out.op == OP_MATRIX || out.op == OP_SYSTEM) && patch_walk_covers(s); };
+  auto gram_patch_ok = [&] { return patch_ok; };
+  if (rows3) {
+    info.kind = WalkInfo::ROWS_P3;
+    return run_patch_walk(s, stream, info, "gram_pencil_rows3 kernel launch failed", [&] { launch_rows3(s, S, out, stream, launches, ga.forcing, patch3_counters); }, kname, launches, err, done, dom);
+  }
   // (round 6: IGX_PATCH=1) p = 2 on the identity geometry, one rank: the walk of 4 x 3 patches of pencils whose band rows leave through the whole
   // workgroup (gram_patch.hpp): 4 colours, 190 instead of 405 entries per element read-add-written
   if (deg == 2 && s.env.patch && gram_patch_ok()) {
