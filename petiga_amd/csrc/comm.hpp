@@ -392,7 +392,7 @@ static int comm_rank_sum_ready(IGX g) {
   if (c.gather.bytes != bytes) {
     HIPCK(hipStreamSynchronize(c.xs));
     if (c.gather.alloc(bytes)) return fail(IGX_ERR_MEM, "device allocation of the rank sum's gather buffer failed");
-    HIPCK(hipMemset(c.gather.p, 0, bytes));
+    HIPCK(hipMemsetAsync(c.gather.p, 0, bytes, c.xs));      // on the exchange stream, where every user of the buffer runs: xs does not wait for the null stream, and a zeroing there could land on this rank's row after IGXCommAllSum's copy
   }
   if (!c.sum_ready) HIPCK(hipEventCreateWithFlags(&c.sum_ready, hipEventDisableTiming));
   if (!c.sum_done) HIPCK(hipEventCreateWithFlags(&c.sum_done, hipEventDisableTiming));

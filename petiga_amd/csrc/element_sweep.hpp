@@ -1,5 +1,5 @@
 // element_sweep.hpp -- host side shared by the launchers of the two element kernels, the point-form kernel (generic_assemble,
-// generic_kernel.hpp) and the feature-GEMM kernel (feature_assemble, feature_mfma.hpp), for built-in forms (engine.hip:
+// generic_kernel.hpp) and the feature-GEMM kernel (feature_assemble, feature_mfma.hpp), for built-in forms (dispatch_unit.hip:
 // launch_generic, launch_feature_plan) and run-time forms (rtc.hpp: rtc_generic_launch, launch_feature_rtc) alike:
 //   FormFacts       what a launcher must know about a form, by name: from the traits of a built-in form, from igx_user_meta[16] of a module
 //   matfree_refusal where the matrix-free operators run, and why not: the one rule table of vec_sumfact's callers
@@ -279,7 +279,7 @@ static FeatureCarve carve_feature(const FormFacts &f, const Space &s, int op, in
 }
 
 // ------------------------------------------------------------------ sweep drivers
-// Engine is the IGX handle (engine.hip): its space, stream, scratch buffer, timing marks and the hooks of the running assembly.
+// Engine is the IGX handle (engine_objects.hpp): its space, stream, scratch buffer, timing marks and the hooks of the running assembly.
 
 // generic_assemble over the rank: the coloured interior sweep (functionals: one sweep), then one pass per visited face on this rank.
 // Every colour or face layer is split along axis 2 so that no launch needs more than 2 GiB of HBM scratch for Phi (gc.phi_in_lds false);

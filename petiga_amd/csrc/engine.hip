@@ -1,4 +1,6 @@
-// engine.hip -- device side of libpetiga_amd: table upload, sparsity pattern, kernel dispatch, C ABI.
+// engine.hip -- the main unit of libpetiga_amd's device side: the C ABI, table upload, sparsity pattern, the drivers, the Gram walks and,
+// from solve_loops.hpp on, the loops.  One translation unit on purpose ("The units"): a kernel's machine code here depends on
+// what else is in its unit.  The element kernels are instantiated in the dispatch units (dispatch_unit.hip).
 // Reference citations are file:line of dalcinl/PetIGA @ 2025-04-04.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -16,141 +18,15 @@
 #include "feature_mfma.hpp"
 #include "first_touch.hpp"
 #include "element_sweep.hpp"
-#if defined(IGX_TU_DISPATCH) && IGX_TU_DIM == 3
-#include "vec_sumfact.hpp"
-#define IGX_HAVE_VEC_SUMFACT 1
-#endif
-#ifndef IGX_TU_DISPATCH
 #include "block_diag.hpp"
 #include "fast_diag.hpp"
 #include "pencil_launch.hpp"      // (the Gram walks: gram_mfma.hpp, gram_patch.hpp, gram_patch3.hpp, boundary_loads.hpp, pencil_stamps.hpp and their host side)
 #include "block_pencil.hpp"      // (the host launcher, for run-time forms: rtc.hpp; no kernel of it is instantiated in this unit)
 #include "band_pt.hpp"           // (likewise: band_pt_run)
-#elif IGX_TU_DIM == 3 && (IGX_TU_GROUP < 0 || IGX_TU_GROUP == 1)
-#include "band_pt.hpp"           // (includes block_pencil.hpp; the constant-coefficient multi-field forms take band_pt on a mapped geometry)
-#define IGX_HAVE_BLOCK_PENCIL 1
-#define IGX_HAVE_BAND_PT 1
-#elif IGX_TU_DIM == 3 && IGX_TU_GROUP == 2
-#include "band_pt.hpp"
-#define IGX_HAVE_BAND_PT 1
-#endif
+#include "engine_objects.hpp"
 
-using namespace igx;
-
-// The library is built from several translation units of this one source (see petiga_amd/build.py): the main unit
-// (C ABI, set-up, drivers; the Gram walks with their host side, pencil_launch.hpp) and, compiled with -DIGX_TU_DISPATCH -DIGX_TU_DIM=d -DIGX_TU_GROUP=g, units that hold only
-// the kernel instantiations of one dimension / form group.  The last-error text is one object for all of them.
-inline std::string &igx_err_slot() { static thread_local std::string e; return e; }
-#define g_err igx_err_slot()
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-constexpr int IGX_NOT_MINE = -12345;    // a dispatch unit's answer for a form of another group
-#ifndef IGX_TU_GROUP
-#define IGX_TU_GROUP -1
-#endif
-#define HIPCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(IGX_ERR_LIB, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
-
-// ------------------------------------------------------------------ objects
-struct DevBuf {
-  void *p = nullptr; size_t bytes = 0;
-  DevBuf() = default;
-  // owns its allocation: movable, not copyable (a std::vector<DevBuf> that grows must MOVE its elements -- copied, the old elements'
-  // destructors freed the memory the new ones pointed to: the exchange buffers of a rank whose refresh and reduction lists differ in
-  // length, i.e. 4 and 8 ranks with a nonlinear form, before round 4)
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
-  DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { if (p) (void)hipFree(p); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) { if (p) { (void)hipFree(p); p = nullptr; } bytes = n; if (!n) return 0; return hipMalloc(&p, n) == hipSuccess ? 0 : 1; }
-  template <class T> int upload(const std::vector<T> &v) {
-    if (alloc(v.size() * sizeof(T))) return 1;
-    if (v.empty()) return 0;
-    return hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : 1;
-  }
-  template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
-struct AxisBufs { DevBuf tab, w, J, pt, off, rowmap, rcnt, P, rcol, prefix, bnd, knots, elof; };   // knots, elof: the knot vector and the element of every knot span (probe.hpp)
-
-
-struct IgxComm;
-struct RtcForm;
-struct KrylovState;
-struct NewtonState;
-struct TimeStepState;
-struct BlockVecState;
-struct EigenState;
-// IGXFastDiagSetUp's host result and the device copies IGXFastDiagApply makes of it at its first call
-struct FastDiagState {
-  FastDiag h;
-  bool on_device = false;
-  DevBuf tf[3][4], tb[3][4], s[3][4], count[3];     // [axis][combo]: forward table T[j][i] = U[j - first][i], backward T[i][j], beta lambda; [axis]: elements per function
-  DevBuf work[2];                                   // two ping-pong buffers of the local vector's size
-};
-struct _p_IGX {
-  Space s;
-  bool on_device = false;
-  AxisBufs ab[3];
-  DevBuf X, W, A, fixtable, errflag, scratch;
-  hipStream_t stream = nullptr;
-  int kernel_choice = 0;
-  _p_IGX() { s.env = read_env_switches(); kernel_choice = s.env.kernel; }   // environment switches are read here, once per IGX
-  std::string last_kernel = "none";
-  std::string rtc_note;           // why a run-time form was kept off a kernel it asked for (appended to the kernel name)
-  bool timing = false;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // step begin, kernels begin/end, step end, dominant kernel begin/end
-  double last_total_ms = 0, last_kernel_ms = 0; int last_launches = 0;
-  std::function<void()> zero_matrix;   // MatZeroEntries of the running IGXCompute*, called by the kernel path that needs it
-  std::function<void()> slab_done;     // set during an assembly with a communicator: marks "upper face of axis 2 assembled" on the engine stream
-  DevBuf partials, dbgbuf, clkbuf;   // IGXComputeScalar: per-element partial sums + reduction stages
-  DevBuf nsingular;                  // IGXBlockDiagonalInvert: the count of singular blocks
-  DevBuf patch3_counters;            // the p = 3 patch walk's ticket counters, one per colour launch (the rows walk, gram_rows3.hpp, takes the first); zeroed on `stream` ahead of every assembly's launches (pencil_launch.hpp)
-  DomInfo dom;
-  int64_t nbrows = 0, nblocks = 0;
-  std::shared_ptr<IgxComm> comm;   // transport of the ghost-row exchange (comm.hpp)
-  // recorded on the engine stream when the elements next to the upper face of axis 2 have been assembled (pencil kernel, several
-  // ranks): IGXReduceGhostRows starts the messages of that face behind it, under the launches of the other elements
-  // slab_valid: bit 0 = the mark of axis 2 (slab_ev), bit 1 = axis 1, bit 2 = axis 0 (face_ev[1], face_ev[0]: the pencil walk's three passes)
-  hipEvent_t slab_ev = nullptr; int slab_valid = 0; IGXMat slab_A = nullptr; IGXVec slab_b = nullptr;
-  hipEvent_t face_ev[2] = {nullptr, nullptr};
-  std::function<void(int)> face_done;  // marks "upper face of axis 1 / 0 assembled" (pencil_launch.hpp)
-  std::shared_ptr<RtcForm> rtc; std::string rtc_source, rtc_name;   // run-time compiled user form (rtc.hpp)
-  std::shared_ptr<RtcForm> rtc_scalar;                              // ... and the last user functional (IGXComputeScalarSource)
-  std::shared_ptr<FastDiagState> fd;                                // fast diagonalisation (IGXFastDiagSetUp; fast_diag.hpp)
-  DevBuf krscal;                                                    // IGXVecDot / IGXSolve: the slabs of partial sums, the record and the device scalars (krylov.hpp)
-  std::shared_ptr<KrylovState> krylov;                              // IGXSolve's work vectors and preconditioner storage, kept between solves
-  std::shared_ptr<NewtonState> newton;                              // IGXSolveNonlinear's work vectors, kept between solves
-  std::shared_ptr<TimeStepState> timestep;                          // IGXTimeStep's work vectors, U_{n-1} and h_{n-1}, kept between calls
-  std::shared_ptr<BlockVecState> blockvec;                          // IGXVecMDot / IGXVecMAXPY: the slab of partial tiles, the coefficient ring and the record (block_vec.hpp)
-  std::shared_ptr<EigenState> eigen;                                // IGXEigenSolve's work vectors, kept between solves
-  std::string self_timed;                                           // the value of last_kernel for which the call itself stored last_total_ms / last_kernel_ms (a solve loop; a probe of no points): IGXGetLastTiming keeps them
-  int batched_actions = 0;                                          // IGXSetBatchedActions: IGXEigenSolve applies this IGX's action to its blocks in one call
-  unsigned long long setup_gen = 0;                               // counts IGXSetUp calls: a probe made before the last one is stale (IGXProbeCreate)
-  // STOPGAP for a defect of tests/test_multigrid_abi.py::test_refusals_in_the_pinned_order, to be removed with the fix of that test.  Its
-  // step 12 (lines 168-170) creates a multigrid from two temporary IGX objects; Python destroys them before IGXMultigridSetUp(hj) runs, so
-  // mg_stale reads s.setup and setup_gen of freed objects (undefined behaviour; the fix is to keep the level objects alive in the test,
-  // which this change may not edit).  sizeof(_p_IGX) is 8 modulo 16, here and in the commit before, so glibc's free() writes the freed
-  // chunk's footer over the object's last word unless the chunk merges into the heap's top: with setup_gen last, the test passed or
-  // answered "stale" (58 for 62) by the state of the heap -- run on its own the test file fails with the earlier commit's library too.
-  // This unused word takes the footer instead.  It relies on glibc's chunk layout and on nothing reusing the freed memory before the
-  // call; it makes no use after IGXDestroy valid.
-  unsigned long long tail = 0;
-};
-
-struct _p_IGXMat {
-  IGX iga; int bs; int64_t nbrows, nblocks;
-  DevBuf browptr, bcolidx, val;
-  DevBuf coo_i, coo_j;     // coordinate lists kept on the device for the hand-back (IGXMatGetCOODevice), or empty
-  unsigned long long gen = 0;   // the IGX's setup_gen at IGXCreateMat: the pattern is that set-up's (IGXMatMult and its kin refuse a matrix of an earlier one)
-};
-struct _p_IGXVec { IGX iga; int64_t n; DevBuf a; };
-// (KrylovState, NewtonState, TimeStepState, BlockVecState, EigenState: solve_loops.hpp, the main unit)
-
-#ifndef IGX_TU_DISPATCH
 extern "C" const char *IGXGetLastError(void) { return g_err.c_str(); }
-#endif
 
-#ifndef IGX_TU_DISPATCH
 // ------------------------------------------------------------------ set-up mirror
 extern "C" int IGXCreate(IGX *iga) { if (!iga) return fail(IGX_ERR_ARG_WRONG, "null pointer"); *iga = new _p_IGX(); igx_pool_acquire(); return 0; }
 extern "C" int IGXDestroy(IGX *iga) {
@@ -163,8 +39,6 @@ extern "C" int IGXDestroy(IGX *iga) {
   igx_pool_release();          // the last one out hands the launch-scoped pool back to the driver
   return 0;
 }
-#define NEEDIGA(g) do { if (!(g)) return fail(IGX_ERR_ARG_WRONG, "null IGX"); } while (0)
-#define AXISCK(g, i) do { NEEDIGA(g); if ((i) < 0 || (i) >= 3) return fail(IGX_ERR_ARG_OUTOFRANGE, "Index must be in range [0,2]"); } while (0)
 static void touch(IGX g) { g->s.setup = false; g->on_device = false; }
 static void drop_net(IGX g) { g->s.netX.clear(); g->s.netW.clear(); g->s.net_nsd = 0; g->s.netA.clear(); g->s.npd = 0; }
 
@@ -634,358 +508,6 @@ extern "C" int IGXGetDeviceInfo(char *buf, int len) {
   return 0;
 }
 
-#endif   // !IGX_TU_DISPATCH
-
-#ifdef IGX_TU_DISPATCH
-// ------------------------------------------------------------------ feature-GEMM kernel dispatch (feature_mfma.hpp)
-// one launch per group of DOFI row fields: I0 = 0, DOFI, 2*DOFI, ...
-template <class Form, int DIM, int TA, int NW, int DOFI, int I0, bool HASM, bool PENCIL = false>
-static void launch_feature_passes(IGX g, const SpaceDev &S, const ParamsDev &prm, const OutDev &out, const ColorRange &cr, const FCarve &cv, size_t nblocks, size_t lds_bytes, bool first, int &launches) {
-  if constexpr (HASM && !PENCIL && I0 == 0 && DOFI < Form::DOF) {
-    if (g->s.env.fuse_groups) {   // all groups of row fields in one launch: the element is tabulated once (feature_mfma.hpp, FUSE)
-      auto fused = feature_assemble<Form, DIM, TA, NW, 0, DOFI, true, false, true>;
-      if (first) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-      hipLaunchKernelGGL(fused, dim3((unsigned)nblocks), dim3(64 * NW), lds_bytes, g->stream, S, prm, out, cr, cv);
-      launches++;
-      return;
-    }
-  }
-  auto kern = feature_assemble<Form, DIM, TA, NW, I0, DOFI, HASM, PENCIL>;
-  if (first) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(64 * NW), lds_bytes, g->stream, S, prm, out, cr, cv);
-  launches++;
-  if constexpr (HASM && I0 + DOFI < Form::DOF) launch_feature_passes<Form, DIM, TA, NW, DOFI, I0 + DOFI, HASM, PENCIL>(g, S, prm, out, cr, cv, nblocks, lds_bytes, first, launches);
-}
-
-// executed v_mfma_f64_16x16x4 flops per element of the feature kernel's matrix phase (roofline accounting)
-template <class Form, int TA>
-static double feature_mfma_flop(int nq_padded) {
-  constexpr int NFS = (shape_order_of<Form>::v >= 2) ? 13 : 4;
-  return 2048.0 * fm_mfma_per_kstep<Form>(NFS) * TA * TA * (nq_padded / 4);
-}
-
-// Pencil mode of the feature kernel (combine before write along axis 0): 4x4x4 basis functions, one new node layer per element
-// on axis 0 (a periodic axis 0 wrapped inside the rank is walked too: the last elements add to the rows the first ones wrote,
-// inside the same workgroup; such an axis never has first-touch stores), no boundary-form passes, and enough pencils per
-// colour of axes 1, 2 to fill the CUs (a workgroup walks the whole local axis-0 range).  IGX_COMBINE=0 / 1 overrides the count.
-static bool feature_pencil_wanted(IGX g, int wgs_per_cu, bool pays) {
-  const Space &s = g->s;
-  if (s.dim != 3 || s.env.combine == 0) return false;
-  for (int d = 0; d < 3; ++d) if (s.basis[d].nen != 4) return false;
-  if (s.elem_width[0] < 4) return false;
-  for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) return false;
-  for (int e = 0; e + 1 < s.elem_width[0]; ++e) if (s.basis[0].offset[s.elem_start[0] + e + 1] != s.basis[0].offset[s.elem_start[0] + e] + 1) return false;
-  if (s.env.combine > 0) return true;
-  if (!pays) return false;
-  static const int ncu = [] { int dev = 0; hipDeviceProp_t pr; return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
-  const int nc1 = std::max(1, s.lay[1].ncolors), nc2 = std::max(1, s.lay[2].ncolors);
-  const long long per_colour = (long long)((s.elem_width[1] + nc1 - 1) / nc1) * ((s.elem_width[2] + nc2 - 1) / nc2);
-  return per_colour * 2 >= (long long)ncu * wgs_per_cu;   // too few pencils: one element per workgroup fills the chip better
-}
-
-// returns 0 and sets done when the feature kernel ran; done stays false when the case is not covered
-template <class Form, int DIM, int TA, int NW, int DOFI, bool HASM, bool PEN = false>
-static int launch_feature_plan(IGX g, const SpaceDev &S, const OutDev &out, bool &done) {
-  const Space &s = g->s;
-  constexpr int DOF = Form::DOF;
-  constexpr FormFacts facts = facts_of<Form>();
-  constexpr int NFS = (facts.shape_order >= 2) ? 1 + DIM + DIM * DIM : 1 + DIM;
-  constexpr int WGS = fm_min_waves<Form, TA, NW, DOFI, HASM, PEN>();
-  constexpr int NPS = fm_popcount((unsigned long long)(phi_mask_of<Form>::v & ((1u << NFS) - 1u)));   // features kept in LDS
-  // pencil mode parks the 7 leaving tiles of every (i,j) block of a launch in the Phi region before they are written out
-  constexpr unsigned long long PR = mat_pair_mask_of<Form>::v;
-  constexpr int stage_need = PEN ? 7 * 16 * 17 * (PR ? fm_popcount(fm_pairs_upper(PR)) : DOFI * DOF) : 0;   // the leaving tiles (feature_mfma.hpp)
-  const FeatureCarve fc = carve_feature(facts, s, out.op, TA, NW, HASM, WGS, NPS, stage_need);
-  if (!fc.fits) return 0;   // not covered: the generic kernel takes it
-  const FCarve &cv = fc.cv; const size_t lds_bytes = fc.lds_bytes;
-  const ParamsDev prm = params_of(s);
-  const bool fused = HASM && !PEN && DOFI < DOF && s.env.fuse_groups;   // one launch forms all groups of row fields of its elements
-  FeatureSweep fs;
-  fs.HASM = HASM; fs.pencil = PEN; fs.single = facts.nscalar > 0; fs.two_pass = true;
-  fs.dom_name = PEN ? "feature_assemble<pencil>" : "feature_assemble<element>";
-  fs.dom_groups = (HASM && !fused) ? (DOF / DOFI) : 1;
-  fs.flop_per_element = HASM ? feature_mfma_flop<Form, TA>(cv.QC * cv.nchunk) * (fused ? DOF : DOFI) / DOF : 0.0;
-  if (int rc = sweep_feature(g, out, fs, [&](const OutDev &o, const ColorRange &cr, size_t nblocks, bool first, int &launches) {
-        launch_feature_passes<Form, DIM, TA, NW, DOFI, 0, HASM, PEN>(g, S, prm, o, cr, cv, nblocks, lds_bytes, first, launches);
-        return 0;
-      })) return rc;
-  HIPCK(hipGetLastError());
-  if (HASM) g->last_kernel = std::string("feature_assemble(mfma_f64_16x16x4,tiles=") + std::to_string(TA) + "x" + std::to_string(TA) + ",waves=" + char('0' + NW) +
-                   ",rowfields/launch=" + char('0' + DOFI) + (fused ? std::string("x") + char('0' + DOF / DOFI) + " fused" : std::string()) +
-                   ",chunks=" + std::to_string(cv.nchunk) + (PEN ? ",pencil walk axis 0" : "") + ")";
-  else g->last_kernel = std::string("feature_assemble(vector only,waves=") + char('0' + NW) + ",chunks=" + std::to_string(cv.nchunk) + ")";
-  done = true;
-  return 0;
-}
-
-template <class Form, int DIM, int TA>
-static int launch_feature_ta(IGX g, const SpaceDev &S, const OutDev &out, bool &done) {
-  constexpr int DOF = Form::DOF;
-  constexpr int NW = (TA >= 4) ? 8 : 4;
-  // 4x4 tiles: 8 waves, <= 144 accumulator VGPRs per wave (dof 4: two launches of two row fields).  Measured on
-  // Elasticity3D p=3: one launch of all row fields with 8 waves 2.67 M elements/s (3.2 with Gram accumulators); three
-  // launches of one row field with 4-wave workgroups, two per CU, 1.63 M elements/s (tabulation repeated per launch).
-  if constexpr (nscalar_of<Form>::v > 0) return launch_feature_plan<Form, DIM, TA, NW, DOF, false>(g, S, out, done);
-  else {
-    const bool hasM = op_has_matrix(out.op);
-    if (!hasM) return launch_feature_plan<Form, DIM, TA, NW, DOF, false>(g, S, out, done);
-    // field Hessians on the fly live in the vector-only kernels unless the matrix callback reads them too (feature_mfma.hpp,
-    // HU_HERE): IGAComputeSystem of such a form (NS-VMS: nobody calls it) is left to the point-form kernel
-    constexpr bool HU_SPLIT = Form::ORDER >= 2 && shape_order_of<Form>::v < 2 && (Form::NEED & NEED_HU) != 0 && (mat_need_of<Form>::v & NEED_HU) == 0;
-    if (HU_SPLIT && out.op == OP_SYSTEM) return 0;
-    constexpr bool GRAM = mat_pair_mask_of<Form>::v != 0ull;   // all row fields from one set of Gram accumulators
-    // a scalar form at nen = 64 has 4 tiles per wave with 4-wave workgroups: small enough for 4 workgroups per CU
-    // (Poisson p=3 on a NURBS geometry: 11.9 vs 10.4 M elements/s with the 8-wave layout)
-    // 8x8 tiles (nen <= 128): a wave holds 8 tiles per accumulator set, so one row field per group (the groups are fused)
-    constexpr int DOFI = (TA >= 8 && !GRAM) ? 1 : ((TA == 4 && DOF == 4 && !GRAM) ? 2 : DOF);
-    if constexpr (TA == 4 && DIM == 3) {
-      // pencil mode: the same wave layouts as the element mode (scalar forms: 4 waves with 4 tiles each, 4 workgroups per CU)
-      constexpr int NWP = (DOF == 1) ? 4 : 8;
-      constexpr int WG = fm_min_waves<Form, 4, NWP, (DOF == 1 ? 1 : DOFI), true, true>();
-      // Measured (MI355X): Elasticity3D 128^3 3.35 -> 4.8 M elements/s; NavierStokesVMS 96^3 (two launches of 8 accumulator
-      // sets, 128 registers live through a heavy tabulation) 1.41 -> 0.78: the automatic choice keeps the walk for the
-      // constant-coefficient (Gram) multi-field forms.  Scalar forms lose as well (Poisson p=3 on a NURBS geometry, 128^3:
-      // 8.5 vs 12.5 M elements/s: their scatter is small next to the tabulation, and the walk runs fewer workgroups per CU).
-      constexpr bool PAYS = GRAM && DOF > 1;
-      if (feature_pencil_wanted(g, WG, PAYS)) {   // (not covered when the staging buffers do not fit the LDS next to a mapped geometry's arrays)
-        if (int rc = launch_feature_plan<Form, DIM, 4, NWP, (DOF == 1 ? 1 : DOFI), true, true>(g, S, out, done)) return rc;
-        if (done) return 0;
-      }
-    }
-    if constexpr (TA == 4 && DOF == 1) return launch_feature_plan<Form, DIM, 4, 4, 1, true>(g, S, out, done);
-    else
-    return launch_feature_plan<Form, DIM, TA, NW, DOFI, true>(g, S, out, done);
-  }
-}
-
-template <class Form, int DIM>
-static int launch_feature(IGX g, const SpaceDev &S, const OutDev &out, bool &done) {
-  done = false;
-  if constexpr (DIM < 2) return 0;
-  else {
-    const Space &s = g->s;
-    constexpr bool fields = (Form::NEED & (NEED_U | NEED_UT | NEED_GU | NEED_HU)) != 0;
-    if (s.dof != Form::DOF && (nscalar_of<Form>::v == 0 || fields)) return 0;
-    int NE = 1; for (int d = 0; d < 3; ++d) NE *= s.basis[d].nen;
-    if (NE > 256) return 0;
-    if (NE > 128) {  // 16 tile rows x two panels of 8 tile columns (p = 5 in 3-D: nen = 216): one accumulator set of 16 tiles per wave
-      constexpr unsigned long long PR = mat_pair_mask_of<Form>::v;
-      constexpr int NACC16 = PR ? fm_popcount(PR) : Form::DOF;
-      if constexpr (DIM == 3 && nscalar_of<Form>::v == 0 && !has_boundary_of<Form>::v) {
-        for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) return 0;
-        if constexpr (NACC16 == 1) return launch_feature_ta<Form, DIM, 16>(g, S, out, done);
-        else {
-          const bool hasM = op_has_matrix(out.op);
-          if (hasM) return 0;
-          return launch_feature_plan<Form, DIM, 16, 8, Form::DOF, false>(g, S, out, done);
-        }
-      } else return 0;
-    }
-    if (NE > 64) {   // 8x8 tiles (p = 4 in 3-D: nen = 125) while the accumulators fit: <= 2 sets of 8 tiles per wave
-      constexpr unsigned long long PR = mat_pair_mask_of<Form>::v;
-      constexpr int NACC8 = PR ? fm_popcount(PR) : Form::DOF;      // Gram pairs, or the dof blocks of one row field
-      if constexpr (DIM == 3 && nscalar_of<Form>::v == 0 && !has_boundary_of<Form>::v) {
-        for (int a = 0; a < 3; ++a) for (int sd = 0; sd < 2; ++sd) if (s.visit[a][sd]) return 0;
-        if constexpr (NACC8 <= 2) return launch_feature_ta<Form, DIM, 8>(g, S, out, done);
-        else {   // more accumulator sets than a wave holds at 8 tiles each: the vector-only drivers still take the kernel
-          const bool hasM = op_has_matrix(out.op);
-          if (hasM) return 0;
-          return launch_feature_plan<Form, DIM, 8, 8, Form::DOF, false>(g, S, out, done);
-        }
-      } else return 0;
-    }
-    if (NE <= 16) return launch_feature_ta<Form, DIM, 1>(g, S, out, done);
-    if (NE <= 32) return launch_feature_ta<Form, DIM, 2>(g, S, out, done);
-    return launch_feature_ta<Form, DIM, 4>(g, S, out, done);
-  }
-}
-
-// ------------------------------------------------------------------ matrix-free dispatch
-// The matrix-free operators of a built-in form (IGXCompute*Action, *ActionBlock, *Diagonal, *BlockDiagonal): vec_sumfact in the mode's
-// instantiation, or the refusal matfree_refusal names (element_sweep.hpp) -- no other kernel forms them.  cols: ACTION_BATCH's columns.
-template <class Form, int DIM>
-static int launch_matfree(IGX g, const SpaceDev &S, const OutDev &out, VsMode mode, const ActionCols *cols) {
-  const Space &s = g->s;
-  constexpr FormFacts facts = facts_of<Form>();
-  if (const MfRefusal r = matfree_refusal(s, g->kernel_choice, mode, &facts, MfCaller::FORM)) return fail(r.code, r.msg);
-#ifdef IGX_HAVE_VEC_SUMFACT
-  if constexpr (DIM == 3 && !general_only_of<Form>::v && nscalar_of<Form>::v == 0 && !has_boundary_of<Form>::v) {
-    const ParamsDev prm = params_of(s);
-    const VsTraits t = vs_traits(mode);
-    bool done = false;
-    auto run = [&](auto m) { return try_vec_sumfact<Form, decltype(m)::value>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done, cols); };
-    int rc = IGX_ERR_PLIB;
-    if (mode == VsMode::ACTION) rc = run(std::integral_constant<VsMode, VsMode::ACTION>());
-    else if (mode == VsMode::ACTION_BATCH) rc = run(std::integral_constant<VsMode, VsMode::ACTION_BATCH>());
-    else if constexpr (shape_order_of<Form>::v < 2) rc = t.block ? run(std::integral_constant<VsMode, VsMode::BLOCK_DIAGONAL>()) : run(std::integral_constant<VsMode, VsMode::DIAGONAL>());
-    if (rc) return fail(rc, "vec_sumfact kernel launch failed");
-    return done ? 0 : fail(IGX_ERR_PLIB, std::string("vec_sumfact did not take a ") + (t.block ? "matrix block diagonal" : t.diagonal ? "matrix diagonal" : "matrix action") + " it covers");
-  }
-#endif
-  return fail(IGX_ERR_PLIB, "matfree_refusal let a case pass that vec_sumfact does not hold");
-}
-
-// ------------------------------------------------------------------ generic kernel dispatch
-template <class Form, int DIM>
-static int launch_generic(IGX g, const SpaceDev &S, const OutDev &out) {
-  const Space &s = g->s;
-  constexpr int DOF = Form::DOF;
-  constexpr bool THIRD = Form::ORDER >= 3;
-  constexpr int NS = nscalar_of<Form>::v;
-  // third-order tabulation, the property array and the point's shape table exist in the general kernel only
-  constexpr bool GENERAL = general_only_of<Form>::v;
-  const ParamsDev prm = params_of(s);
-  if (GENERAL && g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a form of order 3 or one that reads the property array runs on the general kernel only");
-  if ((Form::NEED & NEED_PROP) && !S.npd) return fail(IGX_ERR_ARG_WRONGSTATE, "No property set");      // src/petigaelem.c:300
-  // a geometry of another dimension than the parametric one: tabulated by the general kernel only (no inverse map: src/petigaelem.c:966)
-  const bool emb = s.nsd && s.nsd != DIM;
-  if (emb && g->kernel_choice != 0 && g->kernel_choice != 1) return fail(IGX_ERR_SUP, "a geometry with nsd != dim runs on the general kernel only");
-  if ((Form::NEED & NEED_MAPX) && !s.nsd) return fail(IGX_ERR_ARG_WRONGSTATE, "No geometry set");
-  if (THIRD && s.order < 3) return fail(IGX_ERR_ARG_WRONGSTATE, "the form reads third derivatives (p->shape[3]): call IGASetOrder(iga,3) first");
-#ifdef IGX_HAVE_VEC_SUMFACT
-  if constexpr (DIM == 3 && !GENERAL) if (g->kernel_choice == 0 && !emb) {   // vector-only drivers: sum factorisation both ways (vec_sumfact.hpp)
-    bool done = false;
-    if (int rc = try_vec_sumfact<Form>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, done)) return fail(rc, "vec_sumfact kernel launch failed");
-    if (done) return 0;
-  }
-#endif
-#ifdef IGX_HAVE_BLOCK_PENCIL
-  if constexpr (DIM == 3 && !GENERAL) if ((g->kernel_choice == 0 || g->kernel_choice == 4) && !emb) {   // band rows by node layer (block_pencil.hpp)
-    bool done = false;
-    if (int rc = try_block_pencil<Form>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, g_err, done, g->dom, g->zero_matrix, g->slab_done)) return rc;
-    if (done) return 0;
-  }
-#endif
-#ifdef IGX_HAVE_BAND_PT
-  // (p = 2 only on request: the 27-function element in 4 x 4 x 4 tile slots wastes two thirds of the MFMAs there -- NS-VMS 48^3: 7.7 M el/s, the
-  //  feature kernel's 2 x 2 tiles are as fast -- so the automatic choice keeps the feature kernel at p = 2)
-  if constexpr (DIM == 3 && !GENERAL) if ((g->kernel_choice == 0 && s.axis[0].p == 3) || g->kernel_choice == 4) {   // band rows by node layer, point-dependent coefficients (band_pt.hpp)
-    bool done = false;
-    if (int rc = try_band_pt<Form>(s, S, prm, out, g->stream, g->last_kernel, g->last_launches, g_err, done, g->dom, g->zero_matrix, g->slab_done)) return rc;
-    if (done) return 0;
-  }
-#endif
-  if (g->kernel_choice == 4) return fail(IGX_ERR_SUP, "the band-row kernels do not cover this case (block_pencil: 3-D, p = 3, identity geometry, System / Matrix driver of a constant-coefficient form with 2 or 3 fields; band_pt: 3-D, p = 2 or 3, any geometry: matrix-only driver of a 4-field form with separated point coefficients, System / Matrix driver of a constant-coefficient form with 2 or 3 fields without boundary loads)");
-  if constexpr (!GENERAL) if (g->kernel_choice != 1 && !emb) {   // matrix-producing ops: the dense contraction goes to the matrix cores when covered
-    bool done = false;
-    if (int rc = launch_feature<Form, DIM>(g, S, out, done)) return rc;
-    if (done) return 0;
-    if (g->kernel_choice == 3) return fail(IGX_ERR_SUP, "the feature-GEMM kernel does not cover this case (needs dim >= 2 and nen <= 64; in 3-D nen <= 128 / 256 for forms with at most two / one accumulator set)");
-  }
-  if (g->zero_matrix) g->zero_matrix();
-  const bool fields = (Form::NEED & (NEED_U | NEED_UT | NEED_GU | NEED_HU | NEED_D3U)) != 0;
-  if (s.dof != DOF && (NS == 0 || fields)) return fail(IGX_ERR_ARG_WRONG, "form does not match the number of fields (dof)");
-  // Phi in LDS up to 64 KiB per workgroup, in an HBM slice beyond: a 131 KiB Phi (p = 3) in LDS leaves one workgroup per CU and
-  // measured slower than the HBM slice with two (Poisson p=3 48^3: 0.91 vs 1.71 M elements/s, Elasticity 0.80 vs 1.28)
-  const size_t lds_limit = 160 * 1024 - 512, phi_limit = 64 * 1024;
-  const GenericCarve gc = carve_generic(facts_of<Form>(), s, S.npd, out.op, phi_limit);
-  const size_t lds_bytes = gc.lds_bytes;
-  if (lds_bytes > lds_limit) return fail(IGX_ERR_SUP, "element work set exceeds the 160 KiB LDS");
-  auto kern = generic_assemble<Form, DIM>;
-  HIPCK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  if (int rc = sweep_generic(g, g_err, gc, NS > 0, [&](const ColorRange &cr, int bid, int64_t elem_base, size_t nblocks) {
-        OutDev o = out; o.bid = bid; o.elem_base = elem_base;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(256), lds_bytes, g->stream, S, prm, o, cr, gc.cv, g->scratch.template as<double>(), gc.phi_doubles);
-        return 0;
-      })) return rc;
-  HIPCK(hipGetLastError());
-  g->last_kernel = std::string("generic_assemble(") + (gc.phi_in_lds ? "phi=LDS" : "phi=HBM") + ")";
-  return 0;
-}
-
-// GROUP < 0: every form; else only the forms of that group (0 scalar second-order-free forms, 1 multi-field
-// constant-coefficient forms, 2 the nonlinear demos), IGX_NOT_MINE for the others
-// launch(form_tag<Form>()): the launcher of the entry -- the element kernels' (launch_generic) or the matrix-free operators' (launch_matfree)
-template <class Form> struct form_tag { using type = Form; };
-template <int DIM, int GROUP, class Launch>
-static int dispatch_dim(IGX g, Launch &&launch) {
-  const Space &s = g->s;
-#define IGX_GROUP(gid, ...) do { if constexpr (GROUP < 0 || GROUP == (gid)) return launch(form_tag<__VA_ARGS__>()); else return IGX_NOT_MINE; } while (0)
-  switch (s.form) {
-  case IGX_FORM_POISSON:   IGX_GROUP(0, FormPoisson<DIM>);
-  case IGX_FORM_POISSON_F: IGX_GROUP(0, FormPoissonF<DIM>);
-  case IGX_FORM_L2PROJ_X2: IGX_GROUP(0, FormL2ProjX2<DIM>);
-  case IGX_FORM_BOUNDARYINTEGRAL: IGX_GROUP(0, FormBoundaryIntegral<DIM>);
-  case IGX_FORM_NITSCHE:          IGX_GROUP(0, FormNitsche<DIM>);
-  case IGX_FORM_DER3:      IGX_GROUP(0, FormDer3<DIM>);
-  case IGX_FORM_PROPERTY:  IGX_GROUP(0, FormProperty<DIM>);
-  case IGX_FORM_SURFACE:
-    if constexpr (GROUP < 0 || GROUP == 0) {
-      if constexpr (DIM <= 2) return launch(form_tag<FormSurface<DIM>>());
-      else return fail(IGX_ERR_ARG_WRONG, "the surface form needs dim = 1 or 2 (a curve or a surface in space)");
-    } else return IGX_NOT_MINE;
-  case IGX_FORM_ERRNORM:   IGX_GROUP(1, FormErrNorm<DIM>);
-  case IGX_FORM_MASS:
-    if constexpr (GROUP < 0 || GROUP == 1) {
-      switch (s.dof) {
-      case 1: return launch(form_tag<FormMass<DIM, 1>>());
-      case 2: return launch(form_tag<FormMass<DIM, 2>>());
-      case 3: return launch(form_tag<FormMass<DIM, 3>>());
-      case 4: return launch(form_tag<FormMass<DIM, 4>>());
-      default: return fail(IGX_ERR_SUP, "mass form is instantiated for dof 1..4");
-      }
-    } else return IGX_NOT_MINE;
-  case IGX_FORM_ELASTICITY:
-    if constexpr (GROUP < 0 || GROUP == 1) {
-      if constexpr (DIM == 3) return launch(form_tag<FormElasticity>());
-      else return fail(IGX_ERR_ARG_WRONG, "Elasticity3D form needs dim = 3");
-    } else return IGX_NOT_MINE;
-  case IGX_FORM_ELASTICITY_F:
-    if constexpr (GROUP < 0 || GROUP == 1) {
-      if constexpr (DIM == 3) return launch(form_tag<FormElasticityF>());
-      else return fail(IGX_ERR_ARG_WRONG, "Elasticity3D form needs dim = 3");
-    } else return IGX_NOT_MINE;
-  case IGX_FORM_CAHNHILLIARD:
-    if constexpr (GROUP < 0 || GROUP == 2) {
-      if constexpr (DIM >= 2) return launch(form_tag<FormCahnHilliard<DIM>>());
-      else return fail(IGX_ERR_ARG_WRONG, "Cahn-Hilliard form needs dim = 2 or 3");
-    } else return IGX_NOT_MINE;
-  case IGX_FORM_BRATU:     IGX_GROUP(2, FormBratu<DIM>);
-  case IGX_FORM_NSVMS:
-    if constexpr (GROUP < 0 || GROUP == 2) {
-      if constexpr (DIM == 3) return launch(form_tag<FormNSVMS>());
-      else return fail(IGX_ERR_ARG_WRONG, "NavierStokesVMS form needs dim = 3");
-    } else return IGX_NOT_MINE;
-  default: return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() first");   // IGACheckFormOp, include/petiga.h:925-936
-  }
-#undef IGX_GROUP
-}
-
-// IGAComputeScalar (src/petigacomp.c:35-98): the functionals of one dimension
-template <int DIM>
-static int dispatch_scalar(IGX g, int kind, const SpaceDev &S, const OutDev &out, int order) {
-  switch (kind) {
-  case IGX_SCALAR_VOLUME:  return launch_generic<ScalarVolume<DIM>, DIM>(g, S, out);
-  case IGX_SCALAR_X2ERR:   return launch_generic<ScalarX2Err<DIM>, DIM>(g, S, out);
-  case IGX_SCALAR_ERRNORM: return order >= 2 ? launch_generic<ScalarErrNorm<DIM, true>, DIM>(g, S, out) : launch_generic<ScalarErrNorm<DIM, false>, DIM>(g, S, out);
-  default: return fail(IGX_ERR_ARG_OUTOFRANGE, "unknown scalar functional");
-  }
-}
-
-// the entry points of this unit
-int igx_tu_dispatch(std::integral_constant<int, IGX_TU_DIM>, std::integral_constant<int, IGX_TU_GROUP>, IGX g, const SpaceDev &S, const OutDev &out) {
-  return dispatch_dim<IGX_TU_DIM, IGX_TU_GROUP>(g, [&](auto form) { return launch_generic<typename decltype(form)::type, IGX_TU_DIM>(g, S, out); });
-}
-int igx_tu_matfree(std::integral_constant<int, IGX_TU_DIM>, std::integral_constant<int, IGX_TU_GROUP>, IGX g, const SpaceDev &S, const OutDev &out, VsMode mode, const ActionCols *cols) {
-  return dispatch_dim<IGX_TU_DIM, IGX_TU_GROUP>(g, [&](auto form) { return launch_matfree<typename decltype(form)::type, IGX_TU_DIM>(g, S, out, mode, cols); });
-}
-#if IGX_TU_GROUP < 0 || IGX_TU_GROUP == 2
-int igx_tu_scalar(std::integral_constant<int, IGX_TU_DIM>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order) {
-  return dispatch_scalar<IGX_TU_DIM>(g, kind, S, out, order);
-}
-#endif
-#endif   // IGX_TU_DISPATCH
-
-#ifndef IGX_TU_DISPATCH
-// kernel instantiations live in the dispatch units (one per dimension; three form groups for dim 3)
-#define IGX_TU_ENTRIES(d, gr) \
-  int igx_tu_dispatch(std::integral_constant<int, d>, std::integral_constant<int, gr>, IGX g, const SpaceDev &S, const OutDev &out); \
-  int igx_tu_matfree(std::integral_constant<int, d>, std::integral_constant<int, gr>, IGX g, const SpaceDev &S, const OutDev &out, VsMode mode, const ActionCols *cols);
-IGX_TU_ENTRIES(1, -1) IGX_TU_ENTRIES(2, -1) IGX_TU_ENTRIES(3, 0) IGX_TU_ENTRIES(3, 1) IGX_TU_ENTRIES(3, 2)
-#undef IGX_TU_ENTRIES
-int igx_tu_scalar(std::integral_constant<int, 1>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order);
-int igx_tu_scalar(std::integral_constant<int, 2>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order);
-int igx_tu_scalar(std::integral_constant<int, 3>, IGX g, int kind, const SpaceDev &S, const OutDev &out, int order);
 static int launch_generic_rtc(IGX g, const SpaceDev &S, const OutDev &out, VsMode mode = VsMode::VECTOR);
 // entry(dimension, form group) of the unit that holds the space's dimension (dim 3: the three form groups in turn)
 template <class Entry>
@@ -1532,914 +1054,11 @@ extern "C" int IGXPatch3TicketOrder(int n1, int n2, int nseg, int cx, int cy, in
 #include "rtc.hpp"
 
 // ------------------------------------------------------------------ vector algebra on IGXVec, IGXSolve, IGXSolveNonlinear, IGXTimeStep
-// (host code and, through it, krylov.hpp, newton.hpp and timestep.hpp: the last kernels but the probe's in the unit, so every kernel above is
-// compiled as it was before these existed)
+// (host code and, through it, krylov.hpp, block_vec.hpp, newton.hpp, timestep.hpp and multigrid.hpp).  From here on every subsystem is a host
+// header that includes its kernels; each came last when it was added, so every kernel above it is compiled as it was before it existed.
+// Keep the order (scripts/kernel_digest.py shows what a change of it does).
 #include "solve_loops.hpp"
-// ------------------------------------------------------------------ point evaluation of a discrete field (probe.hpp)
-#include "probe.hpp"
-// IGXProbe: IGAProbe (src/petigaprobe.c) for many points at once.  The points are located on the device once, at IGXProbeCreate; every
-// refusal is decided on the host before the first HIP call.  A probe of no points never touches the device.
-struct _p_IGXProbe {
-  IGX iga; unsigned long long gen; int order, dim; int64_t npts, nlocal;
-  DevBuf pts, span, local, out;
-  std::vector<double> hpts; std::vector<unsigned char> hlocal;
-};
-static int probe_stale(_p_IGXProbe *q, const char *fn) {
-  if (!q) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null probe");
-  if (!q->iga->s.setup || q->gen != q->iga->setup_gen) return fail(IGX_ERR_ORDER, std::string(fn) + ": the probe is stale: IGXSetUp() ran on its IGX after IGXProbeCreate(); make a new probe");
-  return 0;
-}
-static ProbeDev make_probedev(IGX g) {
-  ProbeDev L; memset(&L, 0, sizeof(L));
-  const Space &s = g->s; L.dim = s.dim; L.namax = 1;
-  for (int d = 0; d < s.dim; ++d) {
-    const Axis &ax = s.axis[d]; ProbeAxisDev &A = L.ax[d];
-    A.U = g->ab[d].knots.as<double>(); A.elof = g->ab[d].elof.as<int>(); A.p = ax.p; A.n = (int)ax.U.size() - 1 - ax.p - 1;
-    A.estart = s.elem_start[d]; A.ewidth = s.elem_width[d];
-    if (ax.p + 1 > L.namax) L.namax = ax.p + 1;
-  }
-  return L;
-}
-static int probe_grid(int64_t n) { const int64_t b = (n + PROBE_T - 1) / PROBE_T; return (int)(b < 1 ? 1 : (b > PROBE_G ? PROBE_G : b)); }
-static const char *probe_geometry_kind(const Space &s) {
-  const bool map = s.nsd == s.dim;
-  if (!s.nsd) return "identity";
-  if (map) return s.rational ? "rational" : "polynomial";
-  return s.rational ? "rational, parametric (nsd != dim)" : "polynomial, parametric (nsd != dim)";
-}
-static std::string probe_name(const Space &s, int order, int64_t npts) {
-  std::string p = std::to_string(s.axis[0].p);
-  bool same = true; for (int d = 1; d < s.dim; ++d) same = same && s.axis[d].p == s.axis[0].p;
-  if (!same) for (int d = 1; d < s.dim; ++d) p += "x" + std::to_string(s.axis[d].p);
-  return "probe(" + std::to_string(s.dim) + "d, p=" + p + ", order=" + std::to_string(order) + ", " + probe_geometry_kind(s) + ", " + std::to_string((long long)npts) + " points)";
-}
-#define PROBE_ARGS int grid, size_t lds, hipStream_t st, const SpaceDev &S, const ProbeDev &L, const double *pts, const int *span, const unsigned char *local, const double *U, double *out, long long n
-#define PROBE_PASS grid, lds, st, S, L, pts, span, local, U, out, n
-#define PROBE_GO(R, M) hipLaunchKernelGGL((probe_eval<DIM, DER, R, M>), dim3(grid), dim3(PROBE_T), lds, st, S, L, pts, span, local, U, out, n)
-template <int DIM, int DER> static void probe_launch_kind(bool rat, bool map, PROBE_ARGS) {
-  if constexpr (DER == 0) { if (rat) PROBE_GO(true, false); else PROBE_GO(false, false); }      // a value needs no map
-  else { if (rat && map) PROBE_GO(true, true); else if (rat) PROBE_GO(true, false); else if (map) PROBE_GO(false, true); else PROBE_GO(false, false); }
-}
-template <int DIM> static void probe_launch_der(int der, bool rat, bool map, PROBE_ARGS) {
-  switch (der) {
-    case 0: probe_launch_kind<DIM, 0>(rat, map, PROBE_PASS); break;
-    case 1: probe_launch_kind<DIM, 1>(rat, map, PROBE_PASS); break;
-    case 2: probe_launch_kind<DIM, 2>(rat, map, PROBE_PASS); break;
-    default: probe_launch_kind<DIM, 3>(rat, map, PROBE_PASS); break;
-  }
-}
-template <int DIM> static void probe_launch_geom(bool rat, int grid, size_t lds, hipStream_t st, const SpaceDev &S, const ProbeDev &L, const double *pts, const int *span, const unsigned char *local, double *out, long long n) {
-  if (rat) hipLaunchKernelGGL((probe_geom<DIM, true>), dim3(grid), dim3(PROBE_T), lds, st, S, L, pts, span, local, out, n);
-  else hipLaunchKernelGGL((probe_geom<DIM, false>), dim3(grid), dim3(PROBE_T), lds, st, S, L, pts, span, local, out, n);
-}
-
-extern "C" int IGXProbeCreate(IGX g, int order, int64_t npts, const double *u, IGXProbe *prb) {
-  if (!g) return fail(IGX_ERR_ARG_WRONG, "IGXProbeCreate: null IGX: a probe belongs to one");
-  if (!prb) return fail(IGX_ERR_ARG_WRONG, "IGXProbeCreate: null pointer for the probe");
-  if (order == 4) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXProbeCreate: the probe's order 4 is not covered: the device keeps derivative slots 0..3");
-  if (order < 0 || order > 3) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXProbeCreate: the probe's order must be in range [0,3]");
-  if (npts < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXProbeCreate: the probe's number of points must not be negative");
-  const Space &s = g->s;
-  if (!s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() before IGXProbeCreate(): the probe locates its points in the set-up knot vectors");
-  for (int d = 0; d < s.dim; ++d) if (s.axis[d].p > 7) return fail(IGX_ERR_SUP, "IGXProbeCreate: the probe covers degrees up to 7, axis " + std::to_string(d) + " has degree " + std::to_string(s.axis[d].p));
-  if (npts > 0 && !u) return fail(IGX_ERR_ARG_WRONG, "IGXProbeCreate: null points for a probe of " + std::to_string((long long)npts) + " points");
-  for (int64_t i = 0; i < npts; ++i) for (int d = 0; d < s.dim; ++d) {
-    const Axis &ax = s.axis[d]; const double v = u[i * s.dim + d];
-    const double lo = ax.U[ax.p], hi = ax.U[ax.U.size() - 1 - ax.p];
-    if (!(v >= lo && v <= hi)) {
-      char buf[256]; snprintf(buf, sizeof(buf), "IGXProbeCreate: point %lld of the probe has u[%d] = %g outside the axis [%g, %g]", (long long)i, d, v, lo, hi);
-      return fail(IGX_ERR_ARG_OUTOFRANGE, buf);
-    }
-  }
-  std::unique_ptr<_p_IGXProbe> q(new _p_IGXProbe());
-  q->iga = g; q->gen = g->setup_gen; q->order = order; q->dim = s.dim; q->npts = npts; q->nlocal = 0;
-  if (npts > 0) {
-    if (int rc = ensure_device(g)) return rc;
-    q->hpts.assign(u, u + npts * s.dim); q->hlocal.assign((size_t)npts, 0);
-    if (q->pts.upload(q->hpts) || q->span.alloc((size_t)npts * 3 * sizeof(int)) || q->local.alloc((size_t)npts))
-      return fail(IGX_ERR_MEM, "device allocation of the probe's points failed");
-    const ProbeDev L = make_probedev(g);
-    const int64_t nb = (npts + 255) / 256;
-    const bool timing = g->timing && g->ev[0];
-    if (timing) { HIPCK(hipEventRecord(g->ev[0], g->stream)); HIPCK(hipEventRecord(g->ev[1], g->stream)); }
-    hipLaunchKernelGGL(probe_locate, dim3((unsigned)(nb > PROBE_G ? PROBE_G : nb)), dim3(256), 0, g->stream, L, q->pts.as<double>(), (long long)npts, q->span.as<int>(), q->local.as<unsigned char>());
-    if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "probe_locate: kernel launch failed");
-    if (timing) HIPCK(hipEventRecord(g->ev[2], g->stream));
-    HIPCK(hipMemcpyAsync(q->hlocal.data(), q->local.p, (size_t)npts, hipMemcpyDeviceToHost, g->stream));
-    if (timing) HIPCK(hipEventRecord(g->ev[3], g->stream));
-    HIPCK(hipStreamSynchronize(g->stream));
-    for (unsigned char f : q->hlocal) q->nlocal += f ? 1 : 0;
-    g->last_kernel = "probe_locate(" + std::to_string(s.dim) + "d, " + std::to_string((long long)npts) + " points)"; g->last_launches = 1;
-  }
-  *prb = reinterpret_cast<IGXProbe>(q.release());
-  return 0;
-}
-extern "C" int IGXProbeDestroy(IGXProbe *prb) { if (prb && *prb) { delete reinterpret_cast<_p_IGXProbe *>(*prb); *prb = nullptr; } return 0; }
-extern "C" int IGXProbeGetLocal(IGXProbe prb, int64_t *nlocal, unsigned char *local) {
-  _p_IGXProbe *q = reinterpret_cast<_p_IGXProbe *>(prb);
-  if (int rc = probe_stale(q, "IGXProbeGetLocal")) return rc;
-  if (nlocal) *nlocal = q->nlocal;
-  if (local && q->npts > 0) memcpy(local, q->hlocal.data(), (size_t)q->npts);
-  return 0;
-}
-extern "C" int IGXProbeGetInfo(IGXProbe prb, int64_t *npts, int *order, int *nsd, int64_t *points_per_turn) {
-  _p_IGXProbe *q = reinterpret_cast<_p_IGXProbe *>(prb);
-  if (int rc = probe_stale(q, "IGXProbeGetInfo")) return rc;
-  if (npts) *npts = q->npts;
-  if (order) *order = q->order;
-  if (nsd) *nsd = q->iga->s.nsd ? q->iga->s.nsd : q->iga->s.dim;
-  if (points_per_turn) *points_per_turn = (int64_t)PROBE_G * PROBE_T;
-  return 0;
-}
-extern "C" int IGXProbeGeomMap(IGXProbe prb, double *x) {
-  _p_IGXProbe *q = reinterpret_cast<_p_IGXProbe *>(prb);
-  if (int rc = probe_stale(q, "IGXProbeGeomMap")) return rc;
-  if (q->npts == 0) return 0;
-  if (!x) return fail(IGX_ERR_ARG_WRONG, "IGXProbeGeomMap: null array for the probe's points in space");
-  IGX g = q->iga; const Space &s = g->s;
-  if (!s.nsd) {      // no geometry: x = u (mapX[0] = point, src/petigaprobe.c:360-363); a point of another rank: zeros
-    for (int64_t i = 0; i < q->npts; ++i) for (int d = 0; d < s.dim; ++d) x[i * s.dim + d] = q->hlocal[i] ? q->hpts[i * s.dim + d] : 0.0;
-    return 0;
-  }
-  if (int rc = ensure_device(g)) return rc;
-  const size_t bytes = (size_t)q->npts * s.nsd * sizeof(double);
-  if (q->out.bytes < bytes && q->out.alloc(bytes)) return fail(IGX_ERR_MEM, "device allocation of the probe's result failed");
-  const SpaceDev S = make_spacedev(g); const ProbeDev L = make_probedev(g);
-  const size_t lds = (size_t)3 * L.namax * PROBE_T * sizeof(double);
-  const int grid = probe_grid(q->npts);
-  const bool timing = g->timing && g->ev[0];
-  if (timing) { HIPCK(hipEventRecord(g->ev[0], g->stream)); HIPCK(hipEventRecord(g->ev[1], g->stream)); }
-  switch (s.dim) {
-    case 1: probe_launch_geom<1>(s.rational != 0, grid, lds, g->stream, S, L, q->pts.as<double>(), q->span.as<int>(), q->local.as<unsigned char>(), q->out.as<double>(), (long long)q->npts); break;
-    case 2: probe_launch_geom<2>(s.rational != 0, grid, lds, g->stream, S, L, q->pts.as<double>(), q->span.as<int>(), q->local.as<unsigned char>(), q->out.as<double>(), (long long)q->npts); break;
-    default: probe_launch_geom<3>(s.rational != 0, grid, lds, g->stream, S, L, q->pts.as<double>(), q->span.as<int>(), q->local.as<unsigned char>(), q->out.as<double>(), (long long)q->npts); break;
-  }
-  if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "probe_geom: kernel launch failed");
-  if (timing) HIPCK(hipEventRecord(g->ev[2], g->stream));
-  HIPCK(hipMemcpyAsync(x, q->out.p, bytes, hipMemcpyDeviceToHost, g->stream));
-  if (timing) HIPCK(hipEventRecord(g->ev[3], g->stream));
-  HIPCK(hipStreamSynchronize(g->stream));
-  g->last_kernel = "probe_geom(" + std::to_string(s.dim) + "d, " + probe_geometry_kind(s) + ", " + std::to_string((long long)q->npts) + " points)"; g->last_launches = 1;
-  return 0;
-}
-extern "C" int IGXProbeEvaluate(IGXProbe prb, IGXVec U, int der, double *out) {
-  _p_IGXProbe *q = reinterpret_cast<_p_IGXProbe *>(prb);
-  if (int rc = probe_stale(q, "IGXProbeEvaluate")) return rc;
-  if (der < 0 || der > q->order) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXProbeEvaluate: expecting 0 <= der <= " + std::to_string(q->order) + " (the probe's order), got der = " + std::to_string(der));
-  IGX g = q->iga; const Space &s = g->s;
-  if (!U) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: null vector: the probe evaluates the field an IGXVec holds");
-  if (U->iga != g) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: the vector was created by another IGX than the probe's");
-  if (U->n != (int64_t)s.lay[0].nrow * s.lay[1].nrow * s.lay[2].nrow * s.dof) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: the vector is of another size than the probe's space");
-  if (q->npts == 0) { g->last_kernel = g->self_timed = probe_name(s, der, 0); g->last_launches = 0; g->last_total_ms = g->last_kernel_ms = 0; return 0; }
-  if (!out) return fail(IGX_ERR_ARG_WRONG, "IGXProbeEvaluate: null array for the probe's result");
-  if (int rc = ensure_device(g)) return rc;
-  int no = 1; for (int k = 0; k < der; ++k) no *= s.dim;
-  const size_t bytes = (size_t)q->npts * s.dof * no * sizeof(double);
-  if (q->out.bytes < bytes && q->out.alloc(bytes)) return fail(IGX_ERR_MEM, "device allocation of the probe's result failed");
-  const SpaceDev S = make_spacedev(g); const ProbeDev L = make_probedev(g);
-  const size_t lds = (size_t)3 * L.namax * (der + 1) * PROBE_T * sizeof(double);
-  const int grid = probe_grid(q->npts);
-  const bool rat = s.rational != 0, map = s.nsd != 0 && s.nsd == s.dim;
-  const bool timing = g->timing && g->ev[0];
-  if (timing) { HIPCK(hipEventRecord(g->ev[0], g->stream)); HIPCK(hipEventRecord(g->ev[1], g->stream)); }
-  const double *pts = q->pts.as<double>(); const int *span = q->span.as<int>(); const unsigned char *local = q->local.as<unsigned char>();
-  const double *Ud = U->a.as<double>(); double *od = q->out.as<double>(); const long long n = (long long)q->npts; hipStream_t st = g->stream;
-  switch (s.dim) {
-    case 1: probe_launch_der<1>(der, rat, map, grid, lds, st, S, L, pts, span, local, Ud, od, n); break;
-    case 2: probe_launch_der<2>(der, rat, map, grid, lds, st, S, L, pts, span, local, Ud, od, n); break;
-    default: probe_launch_der<3>(der, rat, map, grid, lds, st, S, L, pts, span, local, Ud, od, n); break;
-  }
-  if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "probe_eval: kernel launch failed");
-  if (timing) HIPCK(hipEventRecord(g->ev[2], g->stream));
-  HIPCK(hipMemcpyAsync(out, q->out.p, bytes, hipMemcpyDeviceToHost, g->stream));
-  if (timing) HIPCK(hipEventRecord(g->ev[3], g->stream));
-  HIPCK(hipStreamSynchronize(g->stream));
-  g->last_kernel = probe_name(s, der, q->npts); g->last_launches = 1;
-  return 0;
-}
-
-// ------------------------------------------------------------------ transfer between nested spline spaces (transfer.hpp)
-#include "transfer.hpp"
-// IGXTransfer: prolongation xf = P xc and restriction rc = P^T rf between two set-up IGX on nested knot vectors.  The tables are built on
-// the host at IGXTransferCreate (transfer_axis_setup, host.cpp), which touches no device; the first Prolong / Restrict uploads them.  Every
-// refusal is decided on the host before the first HIP call.  The clock is the loops' (LoopState's two events, LoopClock): the call stores
-// its own figures on the FINE IGX under the self_timed rule.
-struct TransferAxisBufs { DevBuf ufirst, count, T, boxlo, boxlen, pptr, pidx, pval, rptr, ridx, rval; };
-struct _p_IGXTransfer : LoopState {
-  IGX coarse = nullptr, fine = nullptr; unsigned long long cgen = 0, fgen = 0;
-  int dim = 0, dof = 0, path = 0;                       // path: 0 automatic, 1 fused, 2 axis passes (IGXTransferSetPath)
-  TransferAxis ax[3];
-  int F[3] = {1, 1, 1}, nbox[3] = {1, 1, 1};            // the fused kernel's boxes: fine rows per box, boxes per axis
-  std::vector<int> boxlo[3], boxlen[3];                 // a box's coarse footprint per axis (columns before folding)
-  size_t sizeA = 0, sizeB = 0;                          // doubles of the fused kernel's two LDS buffers
-  bool fits = false;                                    // the footprints fit TR_LDS_MAX: the fused kernel can run
-  int64_t ntmp = 0;                                     // doubles of the largest intermediate of the axis passes
-  bool on_device = false;
-  TransferAxisBufs ab[3]; DevBuf tmp[2];
-};
-static const SolverWords kTransferWords = {"IGXTransferCreate", "the transfer needs one rank on every axis of both spaces: its boxes and gathers have no exchange across ranks", nullptr, nullptr};
-static int transfer_stale(_p_IGXTransfer *q, const char *fn) {
-  if (!q) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null transfer");
-  if (!q->coarse->s.setup || q->cgen != q->coarse->setup_gen || !q->fine->s.setup || q->fgen != q->fine->setup_gen)
-    return fail(IGX_ERR_ORDER, std::string(fn) + ": the transfer is stale: IGXSetUp() ran on one of its IGX after IGXTransferCreate(); make a new transfer");
-  return 0;
-}
-static void transfer_axis_unit(TransferAxis &t) {      // an axis beyond dim: one function on both sides
-  t = TransferAxis(); t.first = {0}; t.count = {1}; t.ufirst = {0}; t.T = {1.0};
-  t.pptr = {0, 1}; t.pidx = {0}; t.pval = {1.0}; t.rptr = {0, 1}; t.ridx = {0}; t.rval = {1.0};
-}
-static std::string transfer_name(const _p_IGXTransfer *q, bool down, bool fused) {      // down: the restriction, fine -> coarse
-  std::string p, nc, nf;
-  for (int d = 0; d < q->dim; ++d) {
-    p += (d ? "," : "") + std::to_string(q->ax[d].p); nc += (d ? "x" : "") + std::to_string(q->ax[d].nc); nf += (d ? "x" : "") + std::to_string(q->ax[d].nf);
-  }
-  return std::string(down ? "transfer_restrict" : "transfer_prolong") + "(" + std::to_string(q->dim) + "d, p=" + p + ", " + (down ? nf : nc) + " -> " + (down ? nc : nf) + ", dof " + std::to_string(q->dof) + ", " + (fused ? "fused" : "axis passes") + ")";
-}
-
-extern "C" int IGXTransferCreate(IGX coarse, IGX fine, IGXTransfer *tr) {
-  const SolverWords &words = kTransferWords;
-  if (!coarse || !fine) return fail(IGX_ERR_ARG_WRONG, "IGXTransferCreate: null IGX: a transfer joins a coarse and a fine one");
-  if (!tr) return fail(IGX_ERR_ARG_WRONG, "IGXTransferCreate: null pointer for the transfer");
-  const Space &c = coarse->s, &f = fine->s;
-  if (!c.setup || !f.setup) return fail(IGX_ERR_ORDER, std::string("Must call IGXSetUp() on both IGX before ") + words.call + "(): the transfer is built from the set-up knot vectors");
-  if (c.dim != f.dim) return fail(IGX_ERR_ARG_WRONG, "IGXTransferCreate: the transfer needs the same dim on both sides, got " + std::to_string(c.dim) + " and " + std::to_string(f.dim));
-  if (c.dof != f.dof) return fail(IGX_ERR_ARG_WRONG, "IGXTransferCreate: the transfer needs the same dof on both sides, got " + std::to_string(c.dof) + " and " + std::to_string(f.dof));
-  for (int d = 0; d < f.dim; ++d) {
-    if (c.axis[d].p != f.axis[d].p) return fail(IGX_ERR_ARG_WRONG, "IGXTransferCreate: the transfer needs the same degree on axis " + std::to_string(d) + " (degree elevation is not covered), got " + std::to_string(c.axis[d].p) + " and " + std::to_string(f.axis[d].p));
-    if ((c.axis[d].periodic != 0) != (f.axis[d].periodic != 0)) return fail(IGX_ERR_ARG_WRONG, "IGXTransferCreate: the transfer needs the same periodicity on axis " + std::to_string(d));
-  }
-  if (coarse->stream != fine->stream) return fail(IGX_ERR_ARG_WRONG, "IGXTransferCreate: the transfer needs the same stream on both IGX (IGXSetStream): its work is enqueued on the fine one's");
-  for (int d = 0; d < f.dim; ++d) if (c.proc_sizes[d] != 1 || f.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, words.one_rank);
-  for (int d = 0; d < f.dim; ++d) if (f.axis[d].p > 7) return fail(IGX_ERR_SUP, "IGXTransferCreate: the transfer covers degrees up to 7, axis " + std::to_string(d) + " has degree " + std::to_string(f.axis[d].p));
-  for (int d = 0; d < f.dim; ++d) for (const Axis *ax : {&c.axis[d], &f.axis[d]}) {
-    const int p = ax->p, m = ax->m;
-    if ((int)ax->U.size() != m + 1 || m < 2 * p + 1) return fail(IGX_ERR_SUP, "IGXTransferCreate: the transfer needs the knot vectors, axis " + std::to_string(d) + " has none");
-    if (!ax->periodic) for (int k = 0; k < p; ++k) if (ax->U[k] != ax->U[k + 1] || ax->U[m - k] != ax->U[m - k - 1])
-      return fail(IGX_ERR_SUP, "IGXTransferCreate: the transfer covers clamped and periodic axes, axis " + std::to_string(d) + " is neither");
-  }
-  std::unique_ptr<_p_IGXTransfer> q(new _p_IGXTransfer());
-  q->coarse = coarse; q->fine = fine; q->cgen = coarse->setup_gen; q->fgen = fine->setup_gen; q->dim = f.dim; q->dof = f.dof;
-  for (int d = 0; d < 3; ++d) {
-    if (d >= f.dim) { transfer_axis_unit(q->ax[d]); continue; }
-    std::string e;
-    if (int rc = transfer_axis_setup(c.axis[d], f.axis[d], d, q->ax[d], e)) return fail(rc, "IGXTransferCreate: the transfer refuses " + e);
-    if (q->ax[d].nf != f.lay[d].nrow || q->ax[d].nc != c.lay[d].nrow) return fail(IGX_ERR_PLIB, "IGXTransferCreate: the transfer's tables and the vectors' row boxes differ on axis " + std::to_string(d));
-  }
-  // the fused kernel's boxes and their coarse footprints, from the tables themselves
-  const int Fmax[3] = {TR_FX, TR_FY, TR_FZ};
-  int cmax[3];
-  for (int d = 0; d < 3; ++d) {
-    const TransferAxis &t = q->ax[d];
-    const int F = std::min(Fmax[d], t.nf), nb = (t.nf + F - 1) / F;
-    q->F[d] = F; q->nbox[d] = nb; q->boxlo[d].resize(nb); q->boxlen[d].resize(nb); cmax[d] = 1;
-    for (int b = 0; b < nb; ++b) {
-      int lo = INT_MAX, hi = 0;
-      for (int i = b * F; i < std::min(t.nf, (b + 1) * F); ++i) { lo = std::min(lo, t.ufirst[i]); hi = std::max(hi, t.ufirst[i] + t.count[i]); }
-      q->boxlo[d][b] = lo; q->boxlen[d][b] = hi - lo; cmax[d] = std::max(cmax[d], hi - lo);
-    }
-  }
-  q->sizeA = (size_t)q->dof * cmax[2] * std::max((size_t)cmax[1] * cmax[0], (size_t)q->F[1] * q->F[0]);
-  q->sizeB = (size_t)q->dof * cmax[2] * cmax[1] * q->F[0];
-  q->fits = (q->sizeA + q->sizeB) * sizeof(double) <= (size_t)TR_LDS_MAX && (int64_t)q->nbox[0] * q->nbox[1] * q->nbox[2] < (int64_t)INT_MAX;
-  {   // the axis passes' intermediates: prolongation 0, 1, 2 and restriction 2, 1, 0
-    const int64_t nf0 = q->ax[0].nf, nf1 = q->ax[1].nf, nc1 = q->ax[1].nc, nc2 = q->ax[2].nc;
-    q->ntmp = q->dof * std::max(nc2 * std::max(nc1, nf1) * nf0, nc2 * nf1 * nf0);
-    if ((int64_t)q->ax[2].nf * nf1 * nf0 * q->dof >= ((int64_t)1 << 32)) return fail(IGX_ERR_SUP, "IGXTransferCreate: the transfer covers fine vectors below 2^32 entries");
-  }
-  *tr = reinterpret_cast<IGXTransfer>(q.release());
-  return 0;
-}
-extern "C" int IGXTransferDestroy(IGXTransfer *tr) { if (tr && *tr) { delete reinterpret_cast<_p_IGXTransfer *>(*tr); *tr = nullptr; } return 0; }
-extern "C" int IGXTransferGetAxis(IGXTransfer tr, int axis, int *nf, int *nc, int *width, int first[], int count[], double T[]) {
-  _p_IGXTransfer *q = reinterpret_cast<_p_IGXTransfer *>(tr);
-  if (int rc = transfer_stale(q, "IGXTransferGetAxis")) return rc;
-  if (axis < 0 || axis > 2) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTransferGetAxis: the transfer's axis must be in range [0,2]");
-  const TransferAxis &t = q->ax[axis];
-  if (nf) *nf = t.nf; if (nc) *nc = t.nc; if (width) *width = t.width;
-  if (first) memcpy(first, t.first.data(), t.first.size() * sizeof(int));
-  if (count) memcpy(count, t.count.data(), t.count.size() * sizeof(int));
-  if (T) memcpy(T, t.T.data(), t.T.size() * sizeof(double));
-  return 0;
-}
-extern "C" int IGXTransferSetPath(IGXTransfer tr, int path) {
-  _p_IGXTransfer *q = reinterpret_cast<_p_IGXTransfer *>(tr);
-  if (int rc = transfer_stale(q, "IGXTransferSetPath")) return rc;
-  if (path < 0 || path > 2) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXTransferSetPath: the transfer's path must be 0 (automatic), 1 (fused) or 2 (axis passes)");
-  if (path == 1 && !q->fits) return fail(IGX_ERR_SUP, "IGXTransferSetPath: the transfer's fused kernel needs " + std::to_string((q->sizeA + q->sizeB) * sizeof(double)) + " bytes of LDS for a box's coarse footprint, the budget is " + std::to_string(TR_LDS_MAX));
-  q->path = path;
-  return 0;
-}
-extern "C" int IGXTransferGetInfo(IGXTransfer tr, int box[3], int64_t *lds_bytes, int *fused) {
-  _p_IGXTransfer *q = reinterpret_cast<_p_IGXTransfer *>(tr);
-  if (int rc = transfer_stale(q, "IGXTransferGetInfo")) return rc;
-  if (box) for (int d = 0; d < 3; ++d) box[d] = q->F[d];
-  if (lds_bytes) *lds_bytes = (int64_t)((q->sizeA + q->sizeB) * sizeof(double));
-  if (fused) *fused = q->fits && q->path != 2 ? 1 : 0;
-  return 0;
-}
-static int transfer_upload(_p_IGXTransfer *q) {
-  if (int rc = ensure_device(q->coarse)) return rc;
-  if (int rc = ensure_device(q->fine)) return rc;
-  if (q->on_device) return 0;
-  for (int d = 0; d < 3; ++d) {
-    const TransferAxis &t = q->ax[d]; TransferAxisBufs &B = q->ab[d];
-    if (B.ufirst.upload(t.ufirst) || B.count.upload(t.count) || B.T.upload(t.T) || B.boxlo.upload(q->boxlo[d]) || B.boxlen.upload(q->boxlen[d]) || B.pptr.upload(t.pptr) ||
-        B.pidx.upload(t.pidx) || B.pval.upload(t.pval) || B.rptr.upload(t.rptr) || B.ridx.upload(t.ridx) || B.rval.upload(t.rval))
-      return fail(IGX_ERR_MEM, "device allocation of the transfer's tables failed");
-  }
-  for (auto &b : q->tmp) if (b.alloc((size_t)q->ntmp * sizeof(double))) return fail(IGX_ERR_MEM, "device allocation of the transfer's intermediates failed");
-  q->on_device = true;
-  return 0;
-}
-// the checks of Prolong and Restrict: vc lives on the coarse IGX, vf on the fine one
-static int transfer_vec_args(_p_IGXTransfer *q, const char *fn, IGXVec vc, IGXVec vf) {
-  if (int rc = transfer_stale(q, fn)) return rc;
-  if (!vc || !vf) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null vector: the transfer carries an IGXVec of the coarse IGX and one of the fine IGX");
-  if (vc->iga != q->coarse) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the coarse vector was created by another IGX than the transfer's coarse one");
-  if (vf->iga != q->fine) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the fine vector was created by another IGX than the transfer's fine one");
-  if (vc->n != (int64_t)q->ax[0].nc * q->ax[1].nc * q->ax[2].nc * q->dof) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the coarse vector is of another size than the transfer's coarse space");
-  if (vf->n != (int64_t)q->ax[0].nf * q->ax[1].nf * q->ax[2].nf * q->dof) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the fine vector is of another size than the transfer's fine space");
-  if (vc == vf) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the transfer needs two vectors, got the same one twice");
-  if (q->coarse->stream != q->fine->stream) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the transfer needs the same stream on both IGX (IGXSetStream)");
-  return 0;
-}
-// the axis passes src -> dst in the order given, identity axes skipped (their rows multiply by 1.0: an exact copy); the last pass stores
-// into dst, with add if asked; an all-identity transfer makes one pass, on the first axis of the order
-static int transfer_passes(_p_IGXTransfer *q, bool down, const double *src, double *dst, int add, int *launches) {
-  IGX g = q->fine;
-  int order[3], n = 0;
-  for (int k = 0; k < 3; ++k) { const int d = down ? 2 - k : k; if (!q->ax[d].identity) order[n++] = d; }
-  if (!n) order[n++] = down ? 2 : 0;
-  int64_t cur[3];
-  for (int d = 0; d < 3; ++d) cur[d] = down ? q->ax[d].nf : q->ax[d].nc;
-  const double *from = src;
-  for (int k = 0; k < n; ++k) {
-    const int d = order[k]; const TransferAxis &t = q->ax[d]; const TransferAxisBufs &B = q->ab[d];
-    TrPassDev P;
-    P.ptr = (down ? B.rptr : B.pptr).as<int>(); P.idx = (down ? B.ridx : B.pidx).as<int>(); P.val = (down ? B.rval : B.pval).as<double>();
-    int64_t inner = q->dof, outer = 1;
-    for (int e = 0; e < d; ++e) inner *= cur[e];
-    for (int e = d + 1; e < 3; ++e) outer *= cur[e];
-    const int64_t nout = down ? t.nc : t.nf, line = nout * inner, nblk = outer * ((line + TR_T - 1) / TR_T);
-    if (line >= ((int64_t)1 << 32) || nblk >= ((int64_t)1 << 32)) return fail(IGX_ERR_SUP, "the transfer's axis pass covers lines and block counts below 2^32");
-    P.nout = (unsigned)nout; P.nin = (unsigned)cur[d]; P.inner = (unsigned)inner; P.outer = (unsigned)outer;
-    const bool last = k == n - 1;
-    double *to = last ? dst : q->tmp[k & 1].as<double>();
-    hipLaunchKernelGGL(transfer_axis_pass, dim3((unsigned)std::min<int64_t>(nblk, TR_G)), dim3(TR_T), 0, g->stream, P, from, to, last ? add : 0);
-    if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "transfer_axis_pass: kernel launch failed");
-    cur[d] = nout; from = to;
-  }
-  *launches = n;
-  return 0;
-}
-extern "C" int IGXTransferProlong(IGXTransfer tr, IGXVec xc, IGXVec xf, int add) {
-  _p_IGXTransfer *q = reinterpret_cast<_p_IGXTransfer *>(tr);
-  if (int rc = transfer_vec_args(q, "IGXTransferProlong", xc, xf)) return rc;
-  if (int rc = transfer_upload(q)) return rc;
-  IGX g = q->fine; g->slab_valid = 0;
-  const bool fused = q->fits && q->path != 2;
-  LoopClock clock(g, *q);
-  if (int rc = clock.begin(g)) return rc;
-  if (fused) {
-    TrFusedDev P; memset(&P, 0, sizeof(P));
-    for (int d = 0; d < 3; ++d) {
-      const TransferAxis &t = q->ax[d]; const TransferAxisBufs &B = q->ab[d]; TrAxisDev &A = P.ax[d];
-      A.ufirst = B.ufirst.as<int>(); A.count = B.count.as<int>(); A.T = B.T.as<double>(); A.boxlo = B.boxlo.as<int>(); A.boxlen = B.boxlen.as<int>();
-      A.nf = t.nf; A.nc = t.nc; A.width = t.width; A.F = q->F[d]; A.nbox = q->nbox[d]; A.wrap = t.periodic ? t.nc : INT_MAX;
-    }
-    P.dof = q->dof; P.sizeA = (int)q->sizeA;
-    hipLaunchKernelGGL(transfer_prolong_fused, dim3((unsigned)(q->nbox[0] * q->nbox[1] * q->nbox[2])), dim3(TR_T), (q->sizeA + q->sizeB) * sizeof(double), g->stream, P, xc->a.as<double>(), xf->a.as<double>(), add ? 1 : 0);
-    if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "transfer_prolong_fused: kernel launch failed");
-    clock.own(1);
-  } else {
-    int n = 0;
-    if (int rc = transfer_passes(q, false, xc->a.as<double>(), xf->a.as<double>(), add ? 1 : 0, &n)) return rc;
-    clock.own(n);
-  }
-  if (int rc = clock.finish(g, transfer_name(q, false, fused))) return rc;
-  if (clock.timing) g->last_kernel_ms = g->last_total_ms;      // the call is its kernels
-  return 0;
-}
-extern "C" int IGXTransferRestrict(IGXTransfer tr, IGXVec rf, IGXVec rc_) {
-  _p_IGXTransfer *q = reinterpret_cast<_p_IGXTransfer *>(tr);
-  if (int rc = transfer_vec_args(q, "IGXTransferRestrict", rc_, rf)) return rc;
-  if (int rc = transfer_upload(q)) return rc;
-  IGX g = q->fine; g->slab_valid = 0; q->coarse->slab_valid = 0;
-  LoopClock clock(g, *q);
-  if (int rc = clock.begin(g)) return rc;
-  int n = 0;
-  if (int rc = transfer_passes(q, true, rf->a.as<double>(), rc_->a.as<double>(), 0, &n)) return rc;
-  clock.own(n);
-  if (int rc = clock.finish(g, transfer_name(q, true, false))) return rc;
-  if (clock.timing) g->last_kernel_ms = g->last_total_ms;
-  return 0;
-}
-// ------------------------------------------------------------------ the multigrid cycle (multigrid.hpp)
-// IGXMultigrid: one V-cycle over a hierarchy of set-up IGX as a preconditioner application, and IGXSolve's loop preconditioned by it.  The
-// cycle is the one the header states line by line; between two operator calls a Chebyshev step is one sweep of multigrid.hpp, everything
-// else is the drivers above: compute_matfree, block_diagonal_run, IGXFastDiagApply, the transfer and IGXSolve.  IGXMultigridCreate touches
-// no device; IGXMultigridSetUp allocates the work vectors of every level, forms the diagonals and estimates lambda.  The clock is the
-// loops': the figures of a call are stored on the FINEST IGX.
-enum { MG_X = 0, MG_B, MG_R, MG_D, MG_W, MG_Z, MG_NWORK };
-struct MgLevel {
-  IGX g = nullptr; unsigned long long gen = 0;
-  IGXVec U = nullptr, V = nullptr;                       // the state of the level's operator (IGXMultigridSetState)
-  int64_t n = 0; int kind = IGX_PC_JACOBI;               // kind: what D is, the diagonal or the inverted point blocks
-  double lambda = 0, theta = 0, delta = 0;
-  std::vector<double> c1, c2;                            // the constants of Chebyshev step j: rho_j rho_{j-1} and 2 rho_j / delta
-  std::vector<std::unique_ptr<_p_IGXVec>> work, dv;      // x b r d w z; the diagonal or the dof block columns
-  std::vector<IGXVec> cols;
-  MgFaces faces; int face_nodes = 0;
-  int launches = 0;                                      // of the last cycle, on this level
-};
-struct _p_IGXMultigrid : LoopState {
-  IGXMultigridSpec spec; int L = 0;
-  std::vector<MgLevel> lv; std::vector<IGXTransfer> tr;
-  bool ready = false;
-  std::shared_ptr<KrylovState> krylov;                   // IGXMultigridSolve's work vectors, on the finest IGX
-  std::string action;                                    // the finest action's kernel name
-  ~_p_IGXMultigrid() { for (auto &t : tr) IGXTransferDestroy(&t); }
-};
-static const SolverWords kMultigridWords = {"IGXMultigridSetUp", "the multigrid needs one rank on every axis of every level",
-                                            "the multigrid runs where its actions, its diagonals and its coarse solve run, and ", nullptr};
-static const char *const kMgPcNames[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
-static int mg_stale(_p_IGXMultigrid *q, const char *fn) {
-  if (!q) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null multigrid");
-  for (const MgLevel &l : q->lv) if (!l.g->s.setup || l.gen != l.g->setup_gen)
-    return fail(IGX_ERR_ORDER, std::string(fn) + ": the multigrid is stale: IGXSetUp() ran on one of its levels after IGXMultigridCreate(); make a new multigrid");
-  return 0;
-}
-static std::string mg_name(const _p_IGXMultigrid *q) {
-  const IGXMultigridSpec &sp = q->spec;
-  std::string coarse = sp.coarse_maxit == 0 ? std::string(kMgPcNames[sp.coarse_pc]) + " x1" : std::string(sp.coarse_method == IGX_SOLVE_CG ? "cg" : "bicgstab") + "+" + kMgPcNames[sp.coarse_pc];
-  return "multigrid(" + std::to_string(q->L) + " levels, chebyshev-" + kMgPcNames[sp.smoother_pc] + " " + std::to_string(sp.degree) + ", coarse " + coarse + ", " + q->action + ")";
-}
-// the figures of a driver call, and of a call that stored its own (the transfer, IGXSolve), on a level's IGX
-static int mg_driver(LoopClock &clk, IGX gl) {
-  clk.launches += gl->last_launches;
-  if (clk.timing && gl->timing) { float ms = 0; HIPCK(hipEventSynchronize(gl->ev[2])); HIPCK(hipEventElapsedTime(&ms, gl->ev[1], gl->ev[2])); clk.op_ms += ms; }
-  return 0;
-}
-static void mg_stored(LoopClock &clk, IGX gl) { clk.launches += gl->last_launches; if (clk.timing && gl->timing) clk.op_ms += gl->last_kernel_ms; }
-static int mg_refused(int rc) { return solver_refused(kMultigridWords, rc); }
-
-extern "C" int IGXMultigridCreate(int nlevels, IGX levels[], const IGXMultigridSpec *sp, IGXMultigrid *mg) {
-  if (!levels || !sp || !mg) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridCreate: null pointer: the multigrid takes its levels, a specification and a place for the handle");
-  for (int k = 0; k < nlevels; ++k) if (!levels[k]) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridCreate: the multigrid's level " + std::to_string(k) + " is a null IGX");
-  if (nlevels < 2) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridCreate: the multigrid needs two levels at the least, got " + std::to_string(nlevels));
-  auto range = [](const char *what) { return fail(IGX_ERR_ARG_OUTOFRANGE, std::string("IGXMultigridCreate: the multigrid's specification: ") + what); };
-  if (sp->op < IGX_OP_MATRIX || sp->op > IGX_OP_IJACOBIAN) return range("unknown operator");
-  if (sp->smoother_pc != IGX_PC_JACOBI && sp->smoother_pc != IGX_PC_PBJACOBI) return range("smoother_pc must be IGX_PC_JACOBI or IGX_PC_PBJACOBI");
-  if (sp->degree < 1) return range("degree must be 1 at the least");
-  if (!(sp->lo > 0) || !(sp->hi > sp->lo) || !std::isfinite(sp->lo) || !std::isfinite(sp->hi)) return range("lo and hi must be finite with 0 < lo < hi");
-  if (sp->power_its < 1) return range("power_its must be 1 at the least");
-  if (sp->coarse_method != IGX_SOLVE_CG && sp->coarse_method != IGX_SOLVE_BICGSTAB) return range("unknown coarse method");
-  if (sp->coarse_pc < IGX_PC_NONE || sp->coarse_pc > IGX_PC_FASTDIAG) return range("unknown coarse preconditioner");
-  if (sp->coarse_maxit < 0) return range("coarse_maxit must not be negative");
-  if (!(sp->coarse_rtol >= 0)) return range("coarse_rtol must not be negative");
-  if (sp->coarse_maxit == 0 && sp->coarse_pc == IGX_PC_NONE) return range("coarse_maxit == 0 is one application of coarse_pc, which must not be IGX_PC_NONE");
-  for (int k = 0; k < nlevels; ++k) if (!levels[k]->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() on every level before IGXMultigridCreate(): the multigrid's level " + std::to_string(k) + " is not set up");
-  for (int k = 0; k < nlevels; ++k) if (levels[k]->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() on every level first: the multigrid's level " + std::to_string(k) + " has no form");
-  bool faces0[3][2][MAXFD];
-  fast_diag_fixed_faces(levels[0]->s, faces0);
-  for (int k = 1; k < nlevels; ++k) {
-    const Space &a = levels[0]->s, &b = levels[k]->s;
-    if (a.form != b.form || a.params != b.params || levels[0]->rtc_source != levels[k]->rtc_source || levels[0]->rtc_name != levels[k]->rtc_name)
-      return fail(IGX_ERR_ARG_WRONG, "IGXMultigridCreate: the multigrid needs the same form with the same parameters on every level, level " + std::to_string(k) + " differs from level 0");
-    bool faces[3][2][MAXFD];
-    fast_diag_fixed_faces(b, faces);
-    if (a.dof != b.dof || memcmp(faces, faces0, sizeof(faces)) != 0)
-      return fail(IGX_ERR_ARG_WRONG, "IGXMultigridCreate: the multigrid needs the same Dirichlet faces per field on every level, level " + std::to_string(k) + " differs from level 0");
-  }
-  for (int k = 0; k < nlevels; ++k) if (levels[k]->fixtable.p) return fail(IGX_ERR_SUP, "IGXMultigridCreate: the multigrid does not cover a fix table (IGXSetFixTable, level " + std::to_string(k) + "): its fixed rows are not a union of faces");
-  for (int k = 1; k < nlevels; ++k) if (levels[k]->stream != levels[0]->stream) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridCreate: the multigrid needs the same stream on every level (IGXSetStream), level " + std::to_string(k) + " differs from level 0");
-  std::unique_ptr<_p_IGXMultigrid> q(new _p_IGXMultigrid());
-  q->spec = *sp; q->L = nlevels; q->lv.resize(nlevels);
-  for (int k = 0; k < nlevels; ++k) {
-    MgLevel &l = q->lv[k]; IGX g = levels[k]; const Space &s = g->s;
-    l.g = g; l.gen = g->setup_gen;
-    l.kind = (k == 0 && sp->coarse_maxit == 0 && (sp->coarse_pc == IGX_PC_JACOBI || sp->coarse_pc == IGX_PC_PBJACOBI)) ? sp->coarse_pc : sp->smoother_pc;
-    int64_t nodes = 1;
-    MgFaces &F = l.faces; memset(&F, 0, sizeof(F));
-    F.dof = s.dof;
-    for (int d = 0; d < 3; ++d) { F.n[d] = d < s.dim ? s.lay[d].nrow : 1; nodes *= F.n[d]; }
-    l.n = nodes * s.dof;
-    for (int d = 0; d < s.dim; ++d) for (int sd = 0; sd < 2; ++sd) {
-      unsigned mask = 0;
-      for (int f = 0; f < s.dof; ++f) if (faces0[d][sd][f]) mask |= 1u << f;
-      if (!mask) continue;
-      F.axis[F.nface] = d; F.at[F.nface] = sd ? F.n[d] - 1 : 0; F.mask[F.nface] = mask; ++F.nface;
-      l.face_nodes = std::max<int64_t>(l.face_nodes, nodes / F.n[d]);
-    }
-  }
-  for (int k = 1; k < nlevels; ++k) {
-    IGXTransfer t = nullptr;
-    if (int rc = IGXTransferCreate(levels[k - 1], levels[k], &t)) return fail(rc, "IGXMultigridCreate: the multigrid's levels " + std::to_string(k - 1) + " and " + std::to_string(k) + ": " + std::string(g_err));
-    q->tr.push_back(t);
-  }
-  *mg = reinterpret_cast<IGXMultigrid>(q.release());
-  return 0;
-}
-extern "C" int IGXMultigridDestroy(IGXMultigrid *mg) { if (mg && *mg) { delete reinterpret_cast<_p_IGXMultigrid *>(*mg); *mg = nullptr; } return 0; }
-extern "C" int IGXMultigridSetState(IGXMultigrid mg, int level, IGXVec V, IGXVec U) {
-  _p_IGXMultigrid *q = reinterpret_cast<_p_IGXMultigrid *>(mg);
-  if (int rc = mg_stale(q, "IGXMultigridSetState")) return rc;
-  if (level < 0 || level >= q->L) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridSetState: the multigrid's level must be in range [0," + std::to_string(q->L - 1) + "]");
-  MgLevel &l = q->lv[level];
-  if ((U && U->iga != l.g) || (V && V->iga != l.g)) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridSetState: the multigrid's state vector was created by another IGX than level " + std::to_string(level));
-  if ((U && U->n != l.n) || (V && V->n != l.n)) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridSetState: the multigrid's state vector is of another size than the level's space");
-  l.U = U; l.V = V; q->ready = false;
-  return 0;
-}
-extern "C" int IGXMultigridGetInfo(IGXMultigrid mg, int level, double *lambda, int64_t *n, int *launches_per_cycle) {
-  _p_IGXMultigrid *q = reinterpret_cast<_p_IGXMultigrid *>(mg);
-  if (int rc = mg_stale(q, "IGXMultigridGetInfo")) return rc;
-  if (level < 0 || level >= q->L) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridGetInfo: the multigrid's level must be in range [0," + std::to_string(q->L - 1) + "]");
-  if (lambda) *lambda = q->lv[level].lambda;
-  if (n) *n = q->lv[level].n;
-  if (launches_per_cycle) *launches_per_cycle = q->lv[level].launches;
-  return 0;
-}
-// the level's action at its state, and z = D^-1 in
-static int mg_action(_p_IGXMultigrid *q, int k, IGXVec in, IGXVec out, LoopClock *clk) {
-  MgLevel &l = q->lv[k]; const IGXMultigridSpec &sp = q->spec;
-  const bool ij = sp.op == IGX_OP_IJACOBIAN;
-  if (int rc = compute_matfree(l.g, VsMode::ACTION, sp.op, sp.op == IGX_OP_MATRIX ? nullptr : l.U, ij ? l.V : nullptr, 1, &in, 1, &out, ij ? sp.a : 0.0, ij ? sp.t : 0.0)) return mg_refused(rc);
-  if (k == q->L - 1) q->action = l.g->last_kernel;
-  return clk ? mg_driver(*clk, l.g) : 0;
-}
-static int mg_blocks(MgLevel &l, IGXVec in, IGXVec out, LoopClock *clk) {
-  if (int rc = block_diagonal_run(l.g, (int)l.cols.size(), l.cols.data(), in, out, nullptr, false)) return mg_refused(rc);
-  return clk ? mg_driver(*clk, l.g) : 0;
-}
-extern "C" int IGXMultigridSetUp(IGXMultigrid mg) {
-  _p_IGXMultigrid *q = reinterpret_cast<_p_IGXMultigrid *>(mg);
-  if (int rc = mg_stale(q, "IGXMultigridSetUp")) return rc;
-  const IGXMultigridSpec &sp = q->spec;
-  q->ready = false;
-  if (sp.coarse_pc == IGX_PC_FASTDIAG && !q->lv[0].g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() on level 0 before IGXMultigridSetUp(): the multigrid's coarse preconditioner is IGX_PC_FASTDIAG");
-  for (int k = 0; k < q->L; ++k) {
-    const MgLevel &l = q->lv[k];
-    if (sp.op != IGX_OP_MATRIX && !l.U) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridSetUp: the multigrid's level " + std::to_string(k) + " has no state vector U (IGXMultigridSetState)");
-    if (sp.op == IGX_OP_IJACOBIAN && !l.V) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridSetUp: the multigrid's level " + std::to_string(k) + " has no state vector V (IGXMultigridSetState)");
-  }
-  for (const MgLevel &l : q->lv) if (int rc = solver_runs_here(l.g, kMultigridWords)) return rc;
-  const bool ij = sp.op == IGX_OP_IJACOBIAN;
-  for (int k = 0; k < q->L; ++k) {
-    MgLevel &l = q->lv[k]; IGX g = l.g;
-    if (int rc = ensure_device(g)) return rc;
-    if ((int64_t)g->nbrows * g->s.dof != l.n) return fail(IGX_ERR_PLIB, "IGXMultigridSetUp: the multigrid's vectors and the level's row box differ");
-    if (int rc = kr_scalars(g)) return rc;
-    const bool pb = l.kind == IGX_PC_PBJACOBI;
-    if (l.work.empty()) if (int rc = add_vecs(g, l.n, pb ? MG_NWORK : MG_NWORK - 1, l.work, "device allocation of the multigrid's work vectors failed")) return rc;
-    if (l.dv.empty()) {
-      if (int rc = add_vecs(g, l.n, pb ? g->s.dof : 1, l.dv, "device allocation of the multigrid's diagonals failed")) return rc;
-      for (auto &v : l.dv) l.cols.push_back(v.get());
-    }
-    IGXVec U = sp.op == IGX_OP_MATRIX ? nullptr : l.U, V = ij ? l.V : nullptr;
-    if (int rc = compute_matfree(g, pb ? VsMode::BLOCK_DIAGONAL : VsMode::DIAGONAL, sp.op, U, V, 0, nullptr, (int)l.cols.size(), l.cols.data(), ij ? sp.a : 0.0, ij ? sp.t : 0.0)) return mg_refused(rc);
-    if (pb) if (int rc = block_diagonal_run(g, g->s.dof, l.cols.data(), nullptr, nullptr, nullptr, true)) return mg_refused(rc);
-    // lambda: power_its steps on D^-1 A from v_i = sin(1 + i); after each step lambda = |D^-1 A v| / |v|, and v <- D^-1 A v / |D^-1 A v|
-    IGXVec v = l.work[MG_X].get(), w = l.work[MG_W].get(), z = l.work[MG_D].get();
-    {
-      std::vector<double> h((size_t)l.n);
-      for (int64_t i = 0; i < l.n; ++i) h[(size_t)i] = std::sin(1.0 + (double)i);
-      HIPCK(hipMemcpy(v->a.p, h.data(), v->a.bytes, hipMemcpyHostToDevice));
-    }
-    double nv = 0, nz = 0;
-    for (int it = 0; it < sp.power_its; ++it) {
-      if (int rc = IGXVecNorm2(v, &nv)) return rc;
-      if (int rc = mg_action(q, k, v, w, nullptr)) return rc;
-      if (pb) { if (int rc = mg_blocks(l, w, z, nullptr)) return rc; }
-      else KR_LAUNCH(kr_pdiv, kr_grid(l.n), KR_T, g, z->a.as<double>(), w->a.as<double>(), l.cols[0]->a.as<double>(), (long long)l.n);
-      if (int rc = IGXVecNorm2(z, &nz)) return rc;
-      l.lambda = nz / nv;
-      if (!(l.lambda > 0) || !std::isfinite(l.lambda)) return fail(IGX_ERR_ARG_WRONGSTATE, "IGXMultigridSetUp: the multigrid's estimate of lambda on level " + std::to_string(k) + " is not positive and finite: the operator or its diagonal is singular at this state");
-      KR_LAUNCH(kr_axpby, kr_grid(l.n), KR_T, g, v->a.as<double>(), 1.0 / nz, z->a.as<double>(), 0.0, (long long)l.n);
-    }
-    // theta = (hi + lo) lambda / 2, delta = (hi - lo) lambda / 2, sigma = theta / delta, rho_1 = 1 / sigma, rho_j = 1 / (2 sigma - rho_{j-1})
-    l.theta = (sp.hi + sp.lo) * l.lambda / 2; l.delta = (sp.hi - sp.lo) * l.lambda / 2;
-    const double sigma = l.theta / l.delta;
-    double rho = 1.0 / sigma;
-    l.c1.assign(sp.degree + 1, 0.0); l.c2.assign(sp.degree + 1, 0.0);
-    for (int j = 2; j <= sp.degree; ++j) { const double rn = 1.0 / (2 * sigma - rho); l.c1[j] = rn * rho; l.c2[j] = 2 * rn / l.delta; rho = rn; }
-    l.launches = 0;
-  }
-  for (IGXTransfer t : q->tr) if (int rc = transfer_upload(reinterpret_cast<_p_IGXTransfer *>(t))) return rc;
-  HIPCK(hipStreamSynchronize(q->lv[q->L - 1].g->stream));
-  q->ready = true;
-  return 0;
-}
-// Smooth(l, b, x, zero guess): degree Chebyshev steps; on return r holds the residual BEFORE the last step's correction d
-static int mg_smooth(_p_IGXMultigrid *q, int k, IGXVec b, IGXVec x, bool zero, LoopClock &clk) {
-  MgLevel &l = q->lv[k]; IGX g = l.g; const long long n = (long long)l.n;
-  const bool pb = l.kind == IGX_PC_PBJACOBI;
-  IGXVec r = l.work[MG_R].get(), d = l.work[MG_D].get(), w = l.work[MG_W].get(), z = pb ? l.work[MG_Z].get() : nullptr;
-  double *xd = x->a.as<double>(), *dd = d->a.as<double>(), *rd = r->a.as<double>(), *wd = w->a.as<double>();
-  const double *bd = b->a.as<double>(), *Dz = pb ? z->a.as<double>() : l.cols[0]->a.as<double>();
-  const double c = 1.0 / l.theta;
-  const unsigned grid = kr_grid(n);
-  if (!zero) {
-    if (int rc = mg_action(q, k, x, w, &clk)) return rc;
-    KR_LAUNCH(mg_resid<true>, grid, KR_T, g, rd, bd, wd, n); clk.own(1);
-  }
-  if (pb) if (int rc = mg_blocks(l, zero ? b : r, z, &clk)) return rc;
-  void (*mg_cheb_first_k)(double *, double *, double *, const double *, const double *, double, long long) =
-      zero ? (pb ? mg_cheb_first<true, true> : mg_cheb_first<true, false>) : (pb ? mg_cheb_first<false, true> : mg_cheb_first<false, false>);
-  KR_LAUNCH(mg_cheb_first_k, grid, KR_T, g, xd, dd, rd, bd, Dz, c, n);
-  clk.own(1);
-  for (int j = 2; j <= q->spec.degree; ++j) {
-    if (int rc = mg_action(q, k, d, w, &clk)) return rc;
-    if (pb) {
-      KR_LAUNCH(mg_resid<false>, grid, KR_T, g, rd, bd, wd, n); clk.own(1);
-      if (int rc = mg_blocks(l, r, z, &clk)) return rc;
-      KR_LAUNCH(mg_cheb_step<true>, grid, KR_T, g, xd, dd, rd, wd, Dz, l.c1[j], l.c2[j], n);
-    } else KR_LAUNCH(mg_cheb_step<false>, grid, KR_T, g, xd, dd, rd, wd, Dz, l.c1[j], l.c2[j], n);
-    clk.own(1);
-  }
-  return 0;
-}
-// x = V(k, b) from a zero guess
-static int mg_cycle(_p_IGXMultigrid *q, int k, IGXVec b, IGXVec x, LoopClock &clk) {
-  MgLevel &l = q->lv[k]; IGX g = l.g; const long long n = (long long)l.n;
-  const IGXMultigridSpec &sp = q->spec;
-  const int at_entry = clk.launches;
-  g->slab_valid = 0;
-  if (k == 0) {
-    if (sp.coarse_maxit == 0) {
-      if (sp.coarse_pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, x->a.as<double>(), b->a.as<double>(), l.cols[0]->a.as<double>(), n); clk.own(1); }
-      else if (sp.coarse_pc == IGX_PC_PBJACOBI) { if (int rc = mg_blocks(l, b, x, &clk)) return rc; }
-      else { if (int rc = IGXFastDiagApply(g, b, x)) return mg_refused(rc); if (int rc = mg_driver(clk, g)) return rc; }
-    } else {
-      KR_LAUNCH(kr_set, kr_grid(n), KR_T, g, x->a.as<double>(), 0.0, n); clk.own(1);
-      IGXSolveSpec cs; memset(&cs, 0, sizeof(cs));
-      cs.method = sp.coarse_method; cs.op = sp.op; cs.pc = sp.coarse_pc; cs.a = sp.a; cs.t = sp.t; cs.V = l.V; cs.U = l.U; cs.rtol = sp.coarse_rtol; cs.atol = 0.0; cs.maxit = sp.coarse_maxit;
-      IGXSolveInfo ci; memset(&ci, 0, sizeof(ci));
-      if (int rc = IGXSolve(g, &cs, b, x, &ci, nullptr)) return mg_refused(rc);
-      mg_stored(clk, g);
-    }
-    l.launches = clk.launches - at_entry;
-    return 0;
-  }
-  MgLevel &c = q->lv[k - 1];
-  IGXVec r = l.work[MG_R].get(), d = l.work[MG_D].get(), w = l.work[MG_W].get(), bc = c.work[MG_B].get(), xc = c.work[MG_X].get();
-  if (int rc = mg_smooth(q, k, b, x, true, clk)) return rc;
-  if (int rc = mg_action(q, k, d, w, &clk)) return rc;
-  KR_LAUNCH(mg_resid<false>, kr_grid(n), KR_T, g, r->a.as<double>(), b->a.as<double>(), w->a.as<double>(), n); clk.own(1);
-  if (int rc = IGXTransferRestrict(q->tr[k - 1], r, bc)) return rc;
-  mg_stored(clk, g);
-  if (c.faces.nface) {
-    hipLaunchKernelGGL(mg_zero_fixed, dim3((unsigned)std::min(256, (c.face_nodes + MG_FACE_T - 1) / MG_FACE_T), (unsigned)c.faces.nface), dim3(MG_FACE_T), 0, g->stream, bc->a.as<double>(), c.faces);
-    if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "mg_zero_fixed: kernel launch failed");
-    clk.own(1);
-  }
-  const int before = clk.launches;
-  if (int rc = mg_cycle(q, k - 1, bc, xc, clk)) return rc;
-  const int below = clk.launches - before;
-  if (int rc = IGXTransferProlong(q->tr[k - 1], xc, x, 1)) return rc;
-  mg_stored(clk, g);
-  if (int rc = mg_smooth(q, k, b, x, false, clk)) return rc;
-  l.launches = clk.launches - at_entry - below;
-  return 0;
-}
-static int mg_vec_args(_p_IGXMultigrid *q, const char *fn, IGXVec a, IGXVec b) {
-  const MgLevel &l = q->lv[q->L - 1];
-  if (!a || !b) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": null vector: the multigrid takes two vectors of its finest IGX");
-  if (a->iga != l.g || b->iga != l.g) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": vector created by another IGX than the multigrid's finest level");
-  if (a->n != l.n || b->n != l.n) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": vector of another size than the multigrid's finest space");
-  if (a == b) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the multigrid needs two different vectors, got the same one twice");
-  return 0;
-}
-extern "C" int IGXMultigridApply(IGXMultigrid mg, IGXVec r, IGXVec z) {
-  _p_IGXMultigrid *q = reinterpret_cast<_p_IGXMultigrid *>(mg);
-  if (int rc = mg_stale(q, "IGXMultigridApply")) return rc;
-  if (!q->ready) return fail(IGX_ERR_ORDER, "Must call IGXMultigridSetUp() before IGXMultigridApply(): the multigrid has no diagonals and no lambda yet (or a state changed since)");
-  if (int rc = mg_vec_args(q, "IGXMultigridApply", r, z)) return rc;
-  IGX g = q->lv[q->L - 1].g;
-  LoopClock clk(g, *q);
-  if (int rc = clk.begin(g)) return rc;
-  if (int rc = mg_cycle(q, q->L - 1, r, z, clk)) return rc;
-  return clk.finish(g, mg_name(q));
-}
-extern "C" int IGXMultigridSolve(IGXMultigrid mg, int method, double rtol, double atol, int maxit, IGXVec b, IGXVec x, IGXSolveInfo *info, double *history) {
-  _p_IGXMultigrid *q = reinterpret_cast<_p_IGXMultigrid *>(mg);
-  if (int rc = mg_stale(q, "IGXMultigridSolve")) return rc;
-  if (method != IGX_SOLVE_CG && method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridSolve: unknown method");
-  if (maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridSolve: maxit must not be negative");
-  if (!(rtol >= 0) || !(atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridSolve: the tolerances must not be negative");
-  if (!q->ready) return fail(IGX_ERR_ORDER, "Must call IGXMultigridSetUp() before IGXMultigridSolve(): the multigrid has no diagonals and no lambda yet (or a state changed since)");
-  if (int rc = mg_vec_args(q, "IGXMultigridSolve", b, x)) return rc;
-  const int fine = q->L - 1;
-  MgLevel &l = q->lv[fine]; IGX g = l.g;
-  if ((l.U && l.U == x) || (l.V && l.V == x)) return fail(IGX_ERR_ARG_WRONG, "IGXMultigridSolve: the solution must not be a state vector of the multigrid");
-  const bool cg = method == IGX_SOLVE_CG;
-  if (!q->krylov || q->krylov->method != method) {
-    q->krylov.reset();
-    std::shared_ptr<KrylovState> ks(new KrylovState());
-    if (int rc = ks->ensure(g, l.n, cg ? 4 : 8, "device allocation of the multigrid solve's work vectors failed")) return rc;
-    ks->method = method; ks->pc = -1; ks->dof = g->s.dof;
-    q->krylov = ks;
-  }
-  KrylovState &st = *q->krylov;
-  LoopClock clk(g, st);
-  if (int rc = clk.begin(g)) return rc;
-  auto A = [&](IGXVec in, IGXVec out) -> int { return mg_action(q, fine, in, out, &clk); };
-  auto M = [&](IGXVec in, IGXVec out) -> int { return mg_cycle(q, fine, in, out, clk); };
-  const KrylovPlan kp = {method, rtol, atol, maxit, false, nullptr};
-  int its = 0;
-  if (int rc = krylov_loop(g, st, clk, kp, A, M, b, x, info, &its, history)) return rc;
-  return clk.finish(g, std::string("krylov(") + (cg ? "cg" : "bicgstab") + ", pc=" + mg_name(q) + ", " + q->action + ", " + std::to_string(its) + " iterations)");
-}
-// One fused Chebyshev step against the four IGXVec kernels it replaces (r = r - w by kr_axpby, z = r / D by kr_pdiv, d = c1 d + c2 z and
-// x = x + d by kr_axpby), on the work vectors of a level, for scripts/multigrid_rate.py: per round `reps` launches of each version between
-// two events, the versions alternating; fused_ms / split_ms receive the time of ONE step per round.  w is zeroed first, so r keeps its
-// values; x and d are overwritten (every cycle starts from a zero guess: nothing depends on them).
-extern "C" int IGXMultigridMeasureStep(IGXMultigrid mg, int level, int reps, int rounds, double *fused_ms, double *split_ms) {
-  _p_IGXMultigrid *q = reinterpret_cast<_p_IGXMultigrid *>(mg);
-  if (int rc = mg_stale(q, "IGXMultigridMeasureStep")) return rc;
-  if (level < 0 || level >= q->L) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridMeasureStep: the multigrid's level must be in range [0," + std::to_string(q->L - 1) + "]");
-  if (reps < 1 || rounds < 1 || !fused_ms || !split_ms) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMultigridMeasureStep: the multigrid's measurement needs reps >= 1, rounds >= 1 and two arrays of rounds doubles");
-  if (!q->ready) return fail(IGX_ERR_ORDER, "Must call IGXMultigridSetUp() before IGXMultigridMeasureStep()");
-  MgLevel &l = q->lv[level]; IGX g = l.g; const long long n = (long long)l.n;
-  if (l.kind != IGX_PC_JACOBI) return fail(IGX_ERR_SUP, "IGXMultigridMeasureStep: the multigrid's fused step exists for the diagonal alone; with point blocks a step is three launches");
-  double *x = l.work[MG_X]->a.as<double>(), *d = l.work[MG_D]->a.as<double>(), *r = l.work[MG_R]->a.as<double>(), *w = l.work[MG_W]->a.as<double>(), *z = l.work[MG_B]->a.as<double>();
-  const double *D = l.cols[0]->a.as<double>();
-  const double c1 = 0.25, c2 = 0.5;
-  const unsigned grid = kr_grid(n);
-  for (auto &e : q->ev) if (!e) HIPCK(hipEventCreate(&e));
-  HIPCK(hipMemsetAsync(w, 0, (size_t)n * sizeof(double), g->stream));
-  auto fused = [&]() -> int { KR_LAUNCH(mg_cheb_step<false>, grid, KR_T, g, x, d, r, w, D, c1, c2, n); return 0; };
-  auto split = [&]() -> int {
-    KR_LAUNCH(kr_axpby, grid, KR_T, g, r, -1.0, w, 1.0, n);
-    KR_LAUNCH(kr_pdiv, grid, KR_T, g, z, r, D, n);
-    KR_LAUNCH(kr_axpby, grid, KR_T, g, d, c2, z, c1, n);
-    KR_LAUNCH(kr_axpby, grid, KR_T, g, x, 1.0, d, 1.0, n);
-    return 0;
-  };
-  for (int k = 0; k < 3; ++k) { if (int rc = fused()) return rc; if (int rc = split()) return rc; }      // warm-up: both code objects, both access patterns
-  for (int round = 0; round < rounds; ++round) for (int version = 0; version < 2; ++version) {
-    float ms = 0;
-    HIPCK(hipEventRecord(q->ev[0], g->stream));
-    for (int k = 0; k < reps; ++k) if (int rc = version ? split() : fused()) return rc;
-    HIPCK(hipEventRecord(q->ev[1], g->stream)); HIPCK(hipEventSynchronize(q->ev[1])); HIPCK(hipEventElapsedTime(&ms, q->ev[0], q->ev[1]));
-    (version ? split_ms : fused_ms)[round] = (double)ms / reps;
-  }
-  return 0;
-}
-
-// ------------------------------------------------------------------ the stored matrix as an operator (mat_ops.hpp)
-// IGXMatMult, IGXMatGetDiagonal, IGXMatGetBlockDiagonal and IGXMatSolve: what a caller without PETSc does with an assembled IGXMat.  The last
-// kernels of the unit, so every kernel above is compiled as it was before these existed.  One rank on every axis; the refusals are decided in
-// the header's order before the first HIP call.
-#include "mat_ops.hpp"
-// 2. the vectors are the matrix's IGX's, and the matrix and the vectors have the sizes of its present space
-static int mat_current(const char *fn, IGXMat A, int nv, const IGXVec *v) {
-  IGX g = A->iga; const Space &s = g->s;
-  for (int k = 0; k < nv; ++k) if (v[k]->iga != g) return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": vector created by another IGX than the matrix's");
-  int64_t rows = 1, blocks = 1;
-  if (s.setup) for (int d = 0; d < 3; ++d) { int64_t t = 0; for (int r = 0; r < s.lay[d].nrow; ++r) t += s.lay[d].rcnt[r]; rows *= s.lay[d].nrow; blocks *= t; }
-  // (the set-up's count as well as the sizes: a set-up that keeps the three counts may still move the pattern, and the kernels walk the
-  // matrix's browptr with the IGX's present axis tables)
-  if (!s.setup || A->gen != g->setup_gen || A->bs != s.dof || A->nbrows != rows || A->nblocks != blocks)
-    return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": the matrix was made before the last IGXSetUp() of its IGX (its pattern and size are that set-up's): create it again");
-  for (int k = 0; k < nv; ++k) if (v[k]->n != rows * s.dof)
-    return fail(IGX_ERR_ARG_WRONG, std::string(fn) + ": vector of another size than its IGX's space (made before the last IGXSetUp()): create it again");
-  return 0;
-}
-// 4. one rank on every axis; with it, a column node index is a row index of x: checked here, not assumed
-static int mat_one_rank(const char *fn, IGX g) {
-  const Space &s = g->s;
-  for (int d = 0; d < s.dim; ++d) if (s.proc_sizes[d] != 1)
-    return fail(IGX_ERR_SUP, std::string(fn) + ": the stored matrix as an operator needs one rank on every axis: its columns are then the rows of x, and there is no ghost refresh in the product");
-  for (int d = 0; d < 3; ++d) if (s.lay[d].nrow != s.lay[d].ncol || s.lay[d].rownode != s.lay[d].colnode)
-    return fail(IGX_ERR_PLIB, std::string(fn) + ": the column box of an axis is not its row box");
-  return 0;
-}
-static MatPat make_matpat(IGX g) {
-  MatPat P;
-  for (int d = 0; d < 3; ++d) {
-    P.nrow[d] = g->s.lay[d].nrow; P.ncol[d] = g->s.lay[d].ncol; P.W[d] = 2 * g->s.lay[d].p + 1;
-    P.rcnt[d] = g->ab[d].rcnt.as<int>(); P.rcol[d] = g->ab[d].rcol.as<int>();
-  }
-  return P;
-}
-// y = A x, the arguments checked: one launch on the engine's stream
-static int mat_mult_run(IGXMat A, IGXVec x, IGXVec y) {
-  IGX g = A->iga;
-  if (int rc = ensure_device(g)) return rc;
-  long long longest = (long long)A->bs * A->bs;
-  for (int d = 0; d < 3; ++d) longest *= *std::max_element(g->s.lay[d].rcnt.begin(), g->s.lay[d].rcnt.end());
-  const int lanes = mat_mult_lanes(longest);
-  // unset: the faster one as measured (profiles/matmult.txt) -- the tables where rows are short enough for sub-groups (dof 1 at p <= 2: by 1 to
-  // 8 %), bcolidx where a wavefront takes a row (p = 3: by 1 to 5 %; bs = 3: level)
-  bool tables = g->s.env.matmult_index < 0 ? lanes < 64 : g->s.env.matmult_index == 0;
-  for (int d = 0; d < 3; ++d) if (2 * g->s.lay[d].p + 1 > MM_MAXW) tables = false;      // beyond the range mm_div is exact in (no degree the library takes today: p <= 7)
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[0], g->stream)); HIPCK(hipEventRecord(g->ev[1], g->stream)); }
-  g->slab_valid = 0;
-  if (!mat_mult_launch(A->bs, lanes, tables, make_matpat(g), (long long)A->nbrows, A->browptr.as<int64_t>(), A->bcolidx.as<int32_t>(), A->val.as<double>(), x->a.as<double>(), y->a.as<double>(), g->stream))
-    return fail(IGX_ERR_SUP, "IGXMatMult: the block size must be 1 to 8");
-  if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "mat_mult: kernel launch failed");
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
-  g->last_launches = 1;
-  char name[160];
-  snprintf(name, sizeof(name), "mat_mult(bs=%d, %s, columns from %s)", A->bs, lanes == 64 ? "one wavefront per row" : (std::to_string(lanes) + " lanes per row").c_str(), tables ? "the axis tables" : "bcolidx");
-  g->last_kernel = name;
-  return 0;
-}
-// the diagonal (nb = 0: into B[0]) or the nb = bs block columns, the arguments checked: one launch
-static int mat_diag_run(IGXMat A, int nb, IGXVec *B) {
-  IGX g = A->iga;
-  if (int rc = ensure_device(g)) return rc;
-  MatCols cols; memset(&cols, 0, sizeof(cols));
-  for (int j = 0; j < std::max(nb, 1); ++j) cols.col[j] = B[j]->a.as<double>();
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[0], g->stream)); HIPCK(hipEventRecord(g->ev[1], g->stream)); }
-  g->slab_valid = 0;
-  mat_get_diag_launch(nb > 0, make_matpat(g), (long long)A->nbrows, A->bs, A->browptr.as<int64_t>(), A->val.as<double>(), cols, g->stream);
-  if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "mat_get_diag: kernel launch failed");
-  if (g->timing) { HIPCK(hipEventRecord(g->ev[2], g->stream)); HIPCK(hipEventRecord(g->ev[3], g->stream)); }
-  g->last_launches = 1;
-  g->last_kernel = nb > 0 ? "mat_get_block_diagonal(one thread per scalar, the block's place from the axis tables)" : "mat_get_diagonal(one thread per scalar, the block's place from the axis tables)";
-  return 0;
-}
-extern "C" int IGXMatMult(IGXMat A, IGXVec x, IGXVec y) {
-  if (!A || !x || !y) return fail(IGX_ERR_ARG_WRONG, "IGXMatMult: null matrix or vector");
-  const IGXVec v[2] = {x, y};
-  if (int rc = mat_current("IGXMatMult", A, 2, v)) return rc;
-  if (x == y) return fail(IGX_ERR_ARG_WRONG, "IGXMatMult: x and y must be different vectors");
-  if (int rc = mat_one_rank("IGXMatMult", A->iga)) return rc;
-  return mat_mult_run(A, x, y);
-}
-extern "C" int IGXMatGetDiagonal(IGXMat A, IGXVec d) {
-  if (!A || !d) return fail(IGX_ERR_ARG_WRONG, "IGXMatGetDiagonal: null matrix or vector");
-  if (int rc = mat_current("IGXMatGetDiagonal", A, 1, &d)) return rc;
-  if (int rc = mat_one_rank("IGXMatGetDiagonal", A->iga)) return rc;
-  return mat_diag_run(A, 0, &d);
-}
-extern "C" int IGXMatGetBlockDiagonal(IGXMat A, int nb, IGXVec B[]) {
-  if (!A || !B) return fail(IGX_ERR_ARG_WRONG, "IGXMatGetBlockDiagonal: null matrix or array of block columns");
-  if (nb != A->bs || nb < 1 || nb > MAXBC) return fail(IGX_ERR_ARG_WRONG, "IGXMatGetBlockDiagonal: the block diagonal has bs columns: nb must equal the matrix's block size");
-  for (int j = 0; j < nb; ++j) if (!B[j]) return fail(IGX_ERR_ARG_WRONG, "IGXMatGetBlockDiagonal: null block column");
-  if (int rc = mat_current("IGXMatGetBlockDiagonal", A, nb, B)) return rc;
-  for (int j = 0; j < nb; ++j) for (int k = 0; k < j; ++k) if (B[k] == B[j]) return fail(IGX_ERR_ARG_WRONG, "IGXMatGetBlockDiagonal: the same vector given for two block columns");
-  if (int rc = mat_one_rank("IGXMatGetBlockDiagonal", A->iga)) return rc;
-  return mat_diag_run(A, nb, B);
-}
-// IGXSolve's loop (krylov_loop) with A(in, out) = the product above and the preconditioners read out of the matrix; the work vectors are
-// IGXSolve's own store on the IGX, replaced under the same rule, so the two solves may follow each other in any order.
-extern "C" int IGXMatSolve(IGXMat A, const IGXSolveSpec *sp, IGXVec b, IGXVec x, IGXSolveInfo *info, double *history) {
-  if (!A || !sp || !b || !x) return fail(IGX_ERR_ARG_WRONG, "IGXMatSolve: null matrix, specification, right-hand side or solution vector");
-  const IGXVec v[2] = {b, x};
-  if (int rc = mat_current("IGXMatSolve", A, 2, v)) return rc;
-  if (x == b) return fail(IGX_ERR_ARG_WRONG, "IGXMatSolve: the solution and the right-hand side must be different vectors");
-  IGX g = A->iga;
-  if (int rc = mat_one_rank("IGXMatSolve", g)) return rc;
-  if (!(sp->rtol >= 0) || !(sp->atol >= 0)) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMatSolve: the tolerances must not be negative");
-  if (sp->maxit < 0) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMatSolve: maxit must not be negative");
-  if (sp->method != IGX_SOLVE_CG && sp->method != IGX_SOLVE_BICGSTAB) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMatSolve: unknown method");
-  if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return fail(IGX_ERR_ARG_OUTOFRANGE, "IGXMatSolve: unknown preconditioner");
-  static const SolverWords words = {"IGXMatSolve", "", "the Krylov solve on the stored matrix runs where its preconditioner runs, and ", nullptr};
-  if (int rc = solver_pc_ready(g, words, sp->pc)) return rc;
-  if (int rc = ensure_device(g)) return rc;
-  if (int rc = kr_scalars(g)) return rc;
-  const bool cg = sp->method == IGX_SOLVE_CG;
-  const int dof = A->bs, pc = sp->pc;
-  const long long n = (long long)b->n;
-  if (!g->krylov || g->krylov->method != sp->method || g->krylov->pc != pc || g->krylov->dof != dof || g->krylov->n != n) {
-    g->krylov.reset();
-    std::shared_ptr<KrylovState> ks(new KrylovState());
-    if (int rc = ks->ensure(g, n, cg ? 4 : 8, "device allocation of the Krylov work vectors failed")) return rc;
-    if (int rc = add_vecs(g, n, pc == IGX_PC_JACOBI ? 1 : pc == IGX_PC_PBJACOBI ? dof : 0, ks->pcv, "device allocation of the preconditioner's vectors failed")) return rc;
-    ks->method = sp->method; ks->pc = pc; ks->dof = dof;
-    g->krylov = ks;
-  }
-  KrylovState &st = *g->krylov;
-  LoopClock clk(g, st);
-  if (int rc = clk.begin(g)) return rc;
-  std::string opname;
-  auto Aop = [&](IGXVec in, IGXVec out) -> int {
-    if (int rc = mat_mult_run(A, in, out)) return rc;
-    if (opname.empty()) opname = g->last_kernel;
-    return clk.driver(g);
-  };
-  std::vector<IGXVec> cols; for (auto &c : st.pcv) cols.push_back(c.get());
-  if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
-    if (int rc = mat_diag_run(A, pc == IGX_PC_JACOBI ? 0 : dof, cols.data())) return rc;
-    if (int rc = clk.driver(g)) return rc;
-  }
-  if (pc == IGX_PC_PBJACOBI) {
-    if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return solver_refused(words, rc);
-    if (int rc = clk.driver(g)) return rc;
-  }
-  auto M = [&](IGXVec in, IGXVec out) -> int {
-    if (pc == IGX_PC_NONE) return 0;
-    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); clk.own(1); return 0; }
-    if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return solver_refused(words, rc);
-    return clk.driver(g);
-  };
-  const KrylovPlan kp = {sp->method, sp->rtol, sp->atol, sp->maxit, pc == IGX_PC_NONE, pc == IGX_PC_JACOBI ? cols[0]->a.as<double>() : nullptr};
-  int its = 0;
-  if (int rc = krylov_loop(g, st, clk, kp, Aop, M, b, x, info, &its, history)) return rc;
-  static const char *const methods[2] = {"cg", "bicgstab"}, *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
-  return clk.finish(g, std::string("krylov(") + methods[sp->method] + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)");
-}
-#endif   // !IGX_TU_DISPATCH
+#include "probe_host.hpp"        // point evaluation of a discrete field (probe.hpp)
+#include "transfer_host.hpp"     // transfer between nested spline spaces (transfer.hpp)
+#include "multigrid_host.hpp"    // the multigrid cycle (its sweeps: multigrid.hpp, above)
+#include "mat_ops_host.hpp"      // the stored matrix as an operator (mat_ops.hpp)

@@ -1,6 +1,6 @@
 // mat_ops.hpp -- the stored block-CSR matrix of IGXCreateMat as an operator: y = A x (IGXMatMult, and through it IGXMatSolve) and the copies
 // of its diagonal and of its bs x bs diagonal blocks (IGXMatGetDiagonal / IGXMatGetBlockDiagonal).  Included by the main unit only, behind
-// everything else; the host entries follow it in engine.hip.  One rank on every axis: the column node index is then the row index of x.
+// everything else; the host entries follow it in mat_ops_host.hpp.  One rank on every axis: the column node index is then the row index of x.
 // Layout (k_browptr, k_bcolidx): row r = (r0, r1, r2) owns c0 c1 c2 blocks, c_d = rcnt[d][r_d]; block k = k0 + c0 (k1 + c1 k2) lies at
 // val[(browptr[r] + k) bs^2], row-major inside, and its column node is rcol[0][r0 W0 + k0] + ncol0 (rcol[1][r1 W1 + k1] + ncol1 rcol[2][r2 W2 + k2]).
 // mat_mult: G lanes per row (G = 8, 16, 32: sub-groups of a wavefront, 64 / G rows per wavefront; G = 64: one wavefront per row), MM_T / G rows

@@ -1,4 +1,4 @@
-// multigrid.hpp -- the sweeps of the V-cycle (IGXMultigrid: engine.hip, behind the transfer it calls).  Included by the main unit only, after
+// multigrid.hpp -- the sweeps of the V-cycle (IGXMultigrid: multigrid_host.hpp, behind the transfer it calls).  Included by the main unit only, after
 // timestep.hpp, whose sweep discipline it keeps: KR_T threads per workgroup, a grid-stride loop of 16-byte accesses over a grid capped at KR_G
 // workgroups, the n & 1 tail in thread 0 of workgroup 0.  None of them emits a sum; no atomics: a cycle is bit-repeatable.
 // A Chebyshev step of the smoother between two operator calls is ONE sweep:

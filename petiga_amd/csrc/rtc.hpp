@@ -1,4 +1,4 @@
-// rtc.hpp -- run-time compiled user forms (included by engine.hip, main unit only).
+// rtc.hpp -- run-time compiled user forms (included by engine.hip, the main unit).
 //
 // PetIGA's point callbacks are arbitrary user functions (IGAFormSystem ... IGAFormIJacobian, include/petiga.h:153-197,
 // registered through IGASetForm*, src/petigaform.c:388-833).  Host function pointers cannot run on the GPU and the built-in
@@ -269,7 +269,7 @@ struct RtcArgs { SpaceDev S; ParamsDev prm; OutDev out; ColorRange cr; Carve cv;
 
 
 // ---- the feature-GEMM kernel (feature_mfma.hpp) for a run-time form: launch_feature / launch_feature_ta / launch_feature_plan of
-// engine.hip with the form's constants read from the module.  Element mode only (no pencil walk), matrix / vector drivers.
+// dispatch_unit.hip with the form's constants read from the module.  Element mode only (no pencil walk), matrix / vector drivers.
 struct RtcFeatArgs { SpaceDev S; ParamsDev prm; OutDev out; ColorRange cr; FCarve cv; };
 
 // feature_assemble<UserForm, dim, TA, NW, I0, DOFI, HASM> for one wave layout: one function per group of row fields
@@ -286,7 +286,7 @@ static int rtc_feature_module(RtcForm &F, int DIM, int DOF, int TA, int NW, int 
   return rtc_instance(F, P, load, out);
 }
 
-// wave layouts of launch_feature_ta (engine.hip): 8 waves at 4x4 tiles, except scalar matrix forms (4 waves with 4 tiles each);
+// wave layouts of launch_feature_ta (dispatch_unit.hip): 8 waves at 4x4 tiles, except scalar matrix forms (4 waves with 4 tiles each);
 // dof 4 at 4x4 tiles takes two launches of two row fields
 static void rtc_feature_layout(int NE, int DOF, bool GRAM, bool HASM, int &TA, int &NW, int &DOFI) {
   TA = NE <= 16 ? 1 : (NE <= 32 ? 2 : (NE <= 64 ? 4 : (NE <= 128 ? 8 : 16)));
@@ -479,7 +479,7 @@ static int launch_block_rtc(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &
 }
 
 static int rtc_generic_launch(IGX g, RtcForm &F, const SpaceDev &S, const OutDev &out);
-// launch_generic (engine.hip) with the form's constants read from the module instead of from a template parameter
+// launch_generic (dispatch_unit.hip) with the form's constants read from the module instead of from a template parameter
 // ---- band rows by node layer with point-dependent coefficients (band_pt.hpp) for a run-time struct: four fields, first order, the
 // point coefficients separated from the basis functions (NCOEF, point_coef, mat_c; optionally mat_unit / BAND_NFEAT / BAND_NACC with
 // their hooks, forms.hpp: FormNSVMS is the model); Matrix / Jacobian / IJacobian drivers.  The conditions of bpt_form_ok are checked

@@ -1,6 +1,6 @@
 // solve_loops.hpp -- the host side of the vector algebra on IGXVec and of the device-resident loops: IGXSolve (kernels: krylov.hpp),
 // IGXSolveNonlinear (newton.hpp), IGXTimeStep (timestep.hpp) and IGXEigenSolve (block_vec.hpp).  Host code only: it launches kernels and defines none.  Included by the
-// main unit of engine.hip as the last thing before the probe, so every kernel above is compiled as it was before these existed; the three
+// main unit (engine.hip) as the last thing before the probe (probe_host.hpp), so every kernel above is compiled as it was before these existed; the three
 // kernel headers are included here, where their loops begin, in that order, block_vec.hpp (IGXVecMDot / IGXVecMAXPY) behind the vector algebra,
 // and multigrid.hpp (the sweeps of IGXMultigrid's cycle) at the end, before IGXEigenSolve, which zeroes its start block's fixed rows with them.
 // What the loops share is written once, up front: the state kept between calls (LoopState), the accounting of launches and kernel time
@@ -862,7 +862,7 @@ extern "C" int IGXTimeStep(IGX g, const IGXTimeStepSpec *sp, IGXVec U, IGXVec V,
 
 // ------------------------------------------------------------------ the multigrid cycle's sweeps (multigrid.hpp)
 #include "multigrid.hpp"
-// IGXMultigrid's host side calls the transfer and so stands behind it, at the end of engine.hip; its outer loop is krylov_loop above.
+// IGXMultigrid's host side calls the transfer and so stands behind it (multigrid_host.hpp); its outer loop is krylov_loop above.
 
 // ------------------------------------------------------------------ the eigen solve (LOBPCG; its sweeps: block_vec.hpp)
 // IGXEigenSolve.  The two operators are the matrix-free driver's internal entry on stiff and on mass (both on stiff's vectors: the same

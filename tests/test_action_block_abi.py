@@ -31,7 +31,7 @@ CALLS = {"IGXComputeMatrixActionBlock": [V, C.c_int, PV, PV],
          "IGXComputeJacobianActionBlock": [V, V, C.c_int, PV, PV],
          "IGXComputeIJacobianActionBlock": [V, C.c_double, V, C.c_double, V, C.c_int, PV, PV],
          "IGXSetBatchedActions": [V, C.c_int]}
-# every built-in form the action covers in 3-D (engine.hip: dispatch_dim; order <= 2, no boundary branch, no functional)
+# every built-in form the action covers in 3-D (dispatch_unit.hip: dispatch_dim; order <= 2, no boundary branch, no functional)
 FORMS = ["FormPoisson<3>", "FormPoissonF<3>", "FormL2ProjX2<3>", "FormErrNorm<3>", "FormMass<3, 1>", "FormMass<3, 2>", "FormMass<3, 3>", "FormMass<3, 4>",
          "FormElasticity", "FormElasticityF", "FormCahnHilliard<3>", "FormBratu<3>", "FormNSVMS"]
 

@@ -165,10 +165,12 @@ def test_refusals_in_the_pinned_order():
     two = (C.c_double * 2)()
     assert L.IGXMultigridMeasureStep(h, 1, 10, 2, two, two) == ORDER and "IGXMultigridSetUp" in why()
     # 12. a missing state at SetUp
-    rc, msg, hj = _create([_bratu(2), _bratu(4)], _spec(op=1))
+    jc, jf = _bratu(2), _bratu(4)                           # (named: the levels outlive the multigrid made from them)
+    rc, msg, hj = _create([jc, jf], _spec(op=1))
     assert rc == 0, (rc, msg)
     assert L.IGXMultigridSetUp(hj) == ARG_WRONG and "state" in why() and "level 0" in why() and "multigrid" in why()
     assert L.IGXMultigridDestroy(C.byref(hj)) == 0
+    del jc, jf
     # GetInfo and SetState: the level's range
     n, lam, k = C.c_int64(), C.c_double(), C.c_int()
     assert L.IGXMultigridGetInfo(h, 1, C.byref(lam), C.byref(n), C.byref(k)) == 0 and (n.value, lam.value, k.value) == (6 ** 3, 0.0, 0)
