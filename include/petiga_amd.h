@@ -527,6 +527,39 @@ int IGXMatGetDiagonal(IGXMat A,IGXVec d);
 int IGXMatGetBlockDiagonal(IGXMat A,int nb,IGXVec B[]);
 int IGXMatSolve(IGXMat A,const IGXSolveSpec *spec,IGXVec b,IGXVec x,IGXSolveInfo *info,double *history /* NULL or [maxit+1]: |r_k|_2 */);
 
+/* The product on a block of vectors and the eigen solve on it.
+ * IGXMatMultBlock: Y[j] = A X[j] for j < nx, 1 <= nx <= 48 (the block-vector limit of IGXCompute*ActionBlock).  The block is cut into chunks
+ *   of NC columns, NC = 8 at bs <= 2, 4 at bs = 3 and 4, 2 at bs >= 5; what is left after the full chunks goes to the next narrower widths
+ *   (NC/2, NC/4, .. 2) and a last single column to IGXMatMult's own kernel.  One launch of mat_mult_block (mat_ops.hpp) per chunk reads val,
+ *   browptr, bcolidx and the axis tables once for all its columns.  IGXMatMultBlockPlan gives the widths of the launches of a (bs, nx) in
+ *   order (widths: NULL or [nx]); it touches no device.  Column j of the result is BIT FOR BIT what IGXMatMult(A, X[j], Y[j]) stores: it does
+ *   not depend on nx, on the column's place in the block, on the chunking or on the other columns (a NaN column of X makes its own column of Y
+ *   NaN and no other).  Y is overwritten and never read; no atomics.  A vector may appear twice in X.  IGXGetLastTiming reports the number of
+ *   chunk launches; IGXGetKernelName gives "mat_mult_block(bs=<bs>, <lanes per row>, columns from <the axis tables|bcolidx>, NC=<NC>)";
+ *   IGX_MATMULT_INDEX picks the index variant as for IGXMatMult.
+ *   Refusals, in this order, each decided before any launch: 1. a null A, X or Y: IGX_ERR_ARG_WRONG; 2. nx outside [1, 48]:
+ *   IGX_ERR_ARG_OUTOFRANGE; 3. a null entry: IGX_ERR_ARG_WRONG; 4. IGXMatMult's rule 2 on all 2 nx vectors (foreign, stale, wrong size):
+ *   IGX_ERR_ARG_WRONG; 5. a vector twice in Y; 6. a vector of X that is also in Y: IGX_ERR_ARG_WRONG; 7. more than one rank on an axis:
+ *   IGX_ERR_SUP, in IGXMatMult's words under this call's name; 8. a block size above 8: IGX_ERR_SUP.
+ * IGXMatEigenSolve: IGXEigenSolve's contract and loop (below, line by line: the same code) with A(block) and B(block) one IGXMatMultBlock
+ *   each on the stored K and M (M == NULL: B = I).  The vectors belong to K's IGX; M comes from the same IGX or from another one on the same
+ *   space.  T: none; IGX_PC_JACOBI / IGX_PC_PBJACOBI read out of K as in IGXMatSolve; IGX_PC_FASTDIAG the state of IGXFastDiagSetUp on K's
+ *   IGX.  The start block's fixed rows (the Dirichlet faces of K's IGX) are zeroed first and stay exactly zero because a fixed row of the
+ *   assembled K and M holds its diagonal alone (the element count) and a fixed column is zero in every other row.  Any dimension, degree and form the assembly takes: the loop needs nothing three-dimensional.
+ *   Both matrices must be symmetric: the caller's responsibility.  info->actions counts columns (2 m per iteration with M, m without);
+ *   IGXGetKernelName gives "eigen(lobpcg, block <m>, pc=<..>, mat_mult_block(...), <k> iterations)"; the work vectors are IGXEigenSolve's
+ *   store on K's IGX, replaced under the same rule.
+ *   Refusals, in this order, before the first HIP call: 1. a null K, spec, X, lambda or info: IGX_ERR_ARG_WRONG; 2. the spec's ranges
+ *   (IGX_ERR_ARG_OUTOFRANGE) and nx != block (IGX_ERR_ARG_WRONG), as in IGXEigenSolve; 3. a null entry of X, then IGXMatMult's rule 2 for K
+ *   and X, an entry of X given twice, then rule 2 for M: IGX_ERR_ARG_WRONG; 4. M's IGX differs from K's in dim, dof, then per axis degree,
+ *   knots, periodicity, then the Dirichlet faces per field, then the stream; then a block size or pattern that differs: IGX_ERR_ARG_WRONG;
+ *   5. more than one rank on an axis: IGX_ERR_SUP ("one rank"); 6. a fix table on either IGX: IGX_ERR_SUP; 7. a block size above 8:
+ *   IGX_ERR_SUP; 8. IGX_PC_FASTDIAG: what fast diagonalisation itself refuses (dim != 3 among it) with its reason under this call's name:
+ *   IGX_ERR_SUP; then no IGXFastDiagSetUp on K's IGX: IGX_ERR_ORDER.
+ * Out of scope: several ranks, the transposed product, Y += A X, the block product inside IGXMatSolve, locking, interior eigenvalues. */
+int IGXMatMultBlock(IGXMat A,int nx,IGXVec X[],IGXVec Y[]);
+int IGXMatMultBlockPlan(int bs,int nx,int *nchunks,int widths[] /* NULL or [nx] */);
+
 /* The Newton loop on the matrix-free operators, resident on the device: G(x) = 0 from the guess x holds on entry, for the nonlinear forms
  * (Bratu, Cahn-Hilliard, NS-VMS, Bratu as IFunction).  op = IGX_OP_JACOBIAN: G(U) = IGXComputeFunction(U), dG/dU the Jacobian at U.
  * op = IGX_OP_IJACOBIAN: G(U) = IGXComputeIFunction(a, a U + W, t, U), dG/dU = IGXComputeIJacobian(a, a U + W, t, U) -- with a = 1/dt and
@@ -912,6 +945,10 @@ typedef struct { int iterations, reason, nconverged, restarts, actions; } IGXEig
 int IGXEigenSolve(IGX stiff,IGX mass /* NULL: B = I */,const IGXEigenSpec *spec,int nx,IGXVec X[] /* [block], of stiff */,
                   double lambda[] /* [block] */,double resid[] /* [block], may be NULL */,IGXEigenInfo *info,
                   double *history /* NULL or [maxit+1][block]: |r_j|_2 */);
+/* the same loop on the stored matrices (stated with IGXMatMultBlock, above) */
+int IGXMatEigenSolve(IGXMat K,IGXMat M /* NULL: B = I */,const IGXEigenSpec *spec,int nx,IGXVec X[] /* [block], of K's IGX */,
+                     double lambda[] /* [block] */,double resid[] /* [block], may be NULL */,IGXEigenInfo *info,
+                     double *history /* NULL or [maxit+1][block]: |r_j|_2 */);
 
 /* Functionals of a discrete field: S[k] = sum over this rank's elements and points of JW * scalar_k(point)
  * (IGAComputeScalar, src/petigacomp.c:35-98, before its MPI_Allreduce: with several ranks the caller sums S over the

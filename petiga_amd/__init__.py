@@ -218,6 +218,8 @@ def lib(build_if_needed=False):
         "IGXKrylovSweepTime": [V, C.c_int, C.c_int, C.c_int, _dp],
         "IGXMatMult": [V, V, V], "IGXMatGetDiagonal": [V, V], "IGXMatGetBlockDiagonal": [V, C.c_int, C.POINTER(V)],
         "IGXMatSolve": [V, C.POINTER(IGXSolveSpec), V, V, C.POINTER(IGXSolveInfo), _dp],
+        "IGXMatMultBlock": [V, C.c_int, C.POINTER(V), C.POINTER(V)], "IGXMatMultBlockPlan": [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+        "IGXMatEigenSolve": [V, V, C.POINTER(IGXEigenSpec), C.c_int, C.POINTER(V), _dp, _dp, C.POINTER(IGXEigenInfo), _dp],
         "IGXGetDeviceInfo": [C.c_char_p, C.c_int], "IGXCreateFromTables": [V, C.POINTER(V)],
         "IGXPatch3TicketOrder": [C.c_int] * 7 + [_ip, _ip, _ip],
     }
@@ -529,6 +531,14 @@ Vec.mdot = staticmethod(_mdot)
 Vec.maxpy = staticmethod(_maxpy)
 
 
+def mat_mult_block_plan(bs, nx):
+    """IGXMatMultBlockPlan: the widths of the launches Mat.mult_block makes for nx columns at block size bs, in order (a width of 1 is Mat.mult's
+    own kernel); host only"""
+    n, w = C.c_int(0), (C.c_int * max(int(nx), 1))()
+    _ck(lib().IGXMatMultBlockPlan(int(bs), int(nx), C.byref(n), w))
+    return [int(w[k]) for k in range(n.value)]
+
+
 class Mat:
     def __init__(self, iga):
         self.iga = iga
@@ -594,6 +604,40 @@ class Mat:
                    rnorm0=info.rnorm0, rnorm=info.rnorm, bnorm=info.bnorm)
         if history:
             out["history"] = hist[:info.iterations + 1].copy()
+        return out
+
+    def mult_block(self, X, Y):
+        """IGXMatMultBlock: Y[j] = A X[j] for lists of Vecs of one length (1 .. 48); column j is bit for bit what mult(X[j], Y[j]) stores."""
+        if len(X) != len(Y):
+            raise ValueError("the block product takes as many results as vectors, got %d and %d" % (len(Y), len(X)))
+        _ck(lib().IGXMatMultBlock(self.h, len(X), _vec_array(X), _vec_array(Y)))
+
+    def eigen(self, nev, mass=None, block=None, pc="none", rtol=1e-8, atol=0.0, maxit=200, X0=None, history=False):
+        """IGXMatEigenSolve: the nev lowest eigenpairs of K x = lambda M x by LOBPCG on the device, K this matrix, M the Mat `mass` on the
+        same space (None: the identity).  X0: the start block, a list of block Vecs of this matrix's IGX (default: as IGX.eigen).  Returns
+        what IGX.eigen returns."""
+        nev = int(nev)
+        m = min(16, nev + 2) if block is None else int(block)
+        X = X0
+        if X is None:
+            X = []
+            if 1 <= nev <= m <= 16:      # (otherwise the call refuses the specification before it looks at the block)
+                rng = np.random.default_rng(0)
+                for _ in range(m):
+                    v = self.iga.create_vec()
+                    X.append(v.set(rng.standard_normal(v.n)))
+        X = list(X)
+        spec = IGXEigenSpec(nev, m, SOLVE_PCS[pc] if isinstance(pc, str) else int(pc), float(rtol), float(atol), int(maxit))
+        info = IGXEigenInfo()
+        lam, res = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        hist = np.zeros((max(int(maxit), 0) + 1, max(m, 1))) if history else None
+        _ck(lib().IGXMatEigenSolve(self.h, mass.h if mass is not None else None, C.byref(spec), len(X), _vec_array(X), lam.ctypes.data_as(_dp), res.ctypes.data_as(_dp),
+                                   C.byref(info), hist.ctypes.data_as(_dp) if history else None))
+        out = {k: getattr(info, k) for k, _ in IGXEigenInfo._fields_}
+        out["reason_name"] = EIGEN_REASONS.get(info.reason, str(info.reason))
+        out["lambda"], out["X"], out["resid"] = lam[:m].copy(), X, res[:m].copy()
+        if history:
+            out["history"] = hist[:info.iterations + 1, :m].copy()
         return out
 
     def layout(self):

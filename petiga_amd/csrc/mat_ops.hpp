@@ -100,6 +100,106 @@ __global__ void __launch_bounds__(MM_T) mat_mult(const MatPat P, long long nbrow
   }
 }
 
+// mat_mult_block: Y_c = A X_c for the NC columns of a chunk in one pass over val (IGXMatMultBlock).  mat_mult's lane mapping,
+// pairs, head and tail, entry rule and column rule, restated and not shared: mat_mult stays the code it is.  A lane keeps BS x NC sums; for
+// every value it loads once it gathers x_c[col bs + j] for the NC columns and does NC fmas.  Column c's products enter column c's sums in
+// mat_mult's order (the strided pairs in ascending q, x before y of a pair, then the head on lane 0 and the tail on lane G - 1), with the same
+// fma and the same xor butterfly: column c of the result is bit for bit what mat_mult stores for X_c, whatever NC is, wherever the column
+// stands in the chunk and whatever the other columns hold.  Nothing is read from Y; no atomics.  val, browptr, bcolidx and the tables are read
+// once per chunk.  The column pointers arrive by value.
+template <int NC> struct MatBlockCols { const double *x[NC]; double *y[NC]; };
+// columns of a full chunk by block size: BS NC sums in double are 2 BS NC VGPRs, 32 at the most here, so that nothing goes to scratch and four
+// waves per SIMD stay resident (the gathered x of an unrolled pair of pairs takes up to 8 NC more).  What is left of a block after its
+// full chunks goes to the next narrower widths (NC / 2, NC / 4, ... >= 2) and the last single column to mat_mult itself.
+constexpr int mat_block_nc(int bs) { return bs <= 2 ? 8 : bs <= 4 ? 4 : 2; }
+// the chunk plan of nx columns: widths[k] columns in launch k, in order; returns the number of launches (widths may be null).  Pure host code.
+inline int mat_block_plan(int bs, int nx, int *widths) {
+  int n = 0;
+  for (int w = mat_block_nc(bs), left = nx; left > 0;) {
+    while (w > left) w >>= 1;
+    if (widths) widths[n] = w;
+    ++n; left -= w;
+  }
+  return n;
+}
+
+template <int BS, int G, bool TABLES, int NC>
+__global__ void __launch_bounds__(MM_T) mat_mult_block(const MatPat P, long long nbrows, const int64_t *__restrict__ browptr, const int32_t *__restrict__ bcolidx,
+                                                       const double *__restrict__ val, const MatBlockCols<NC> V) {
+  constexpr int BB = BS * BS;
+  const int lane = threadIdx.x % G;
+  const long long r = (long long)blockIdx.x * (MM_T / G) + threadIdx.x / G;
+  if (r >= nbrows) return;
+  const long long b0 = browptr[r];
+  const int nblk = (int)(browptr[r + 1] - b0), len = nblk * BB;
+  int c0 = 1, c01 = 1;
+  float rc0 = 1.0f, rc01 = 1.0f;
+  const int *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
+  const int ncol0 = P.ncol[0], ncol1 = P.ncol[1];
+  bool run = false;
+  int first = 0;
+  if (TABLES) {
+    const unsigned ru = (unsigned)r, q = ru / (unsigned)P.nrow[0];
+    const int r0 = (int)(ru - q * (unsigned)P.nrow[0]), r2 = (int)(q / (unsigned)P.nrow[1]), r1 = (int)(q - (unsigned)r2 * (unsigned)P.nrow[1]);
+    const int c1 = P.rcnt[1][r1], c2 = P.rcnt[2][r2];
+    c0 = P.rcnt[0][r0]; c01 = c0 * c1;
+    rc0 = 1.0f / (float)c0; rc01 = 1.0f / (float)c01;
+    t0 = P.rcol[0] + r0 * P.W[0]; t1 = P.rcol[1] + r1 * P.W[1]; t2 = P.rcol[2] + r2 * P.W[2];
+    const int f0 = t0[0], f1 = t1[0], f2 = t2[0];
+    run = t0[c0 - 1] - f0 == c0 - 1 && t1[c1 - 1] - f1 == c1 - 1 && t2[c2 - 1] - f2 == c2 - 1;
+    first = f0 + ncol0 * (f1 + ncol1 * f2);
+  }
+  auto column = [&](int k) -> long long {
+    if (!TABLES) return (long long)bcolidx[b0 + k];
+    const int k2 = mm_div(k, rc01), w = k - k2 * c01, k1 = mm_div(w, rc0), k0 = w - k1 * c0;
+    if (run) return (long long)(first + k0 + ncol0 * (k1 + ncol1 * k2));
+    return (long long)(t0[k0] + ncol0 * (t1[k1] + ncol1 * t2[k2]));
+  };
+  double acc[BS][NC];
+#pragma unroll
+  for (int i = 0; i < BS; ++i)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[i][c] = 0.0;
+  auto add = [&](int e, double v) {
+    const int k = e / BB, w = e - k * BB, i = w / BS, j = w - i * BS;
+    const long long at = column(k) * BS + j;
+    double xv[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) xv[c] = V.x[c][at];
+#pragma unroll
+    for (int ii = 0; ii < BS; ++ii) if (ii == i) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc[ii][c] = fma(v, xv[c], acc[ii][c]);
+    }
+  };
+  const double *row = val + b0 * BB;
+  const int head = (int)((b0 * BB) & 1) & (len > 0 ? 1 : 0), npairs = (len - head) >> 1, tail = (len - head) & 1;
+  typedef double mm_d2 __attribute__((ext_vector_type(2)));
+  const mm_d2 *pairs = reinterpret_cast<const mm_d2 *>(row + head);
+#pragma unroll 2
+  for (int q = lane; q < npairs; q += G) {
+    const mm_d2 v = pairs[q];
+    add(head + 2 * q, v.x); add(head + 2 * q + 1, v.y);
+  }
+  if (head && lane == 0) add(0, row[0]);
+  if (tail && lane == G - 1) add(len - 1, row[len - 1]);
+#pragma unroll
+  for (int i = 0; i < BS; ++i)
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int o = G / 2; o > 0; o >>= 1) acc[i][c] += __shfl_xor(acc[i][c], o, G);
+  if (lane < BS) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      double out = acc[0][c];
+#pragma unroll
+      for (int i = 1; i < BS; ++i) if (lane == i) out = acc[i][c];
+      V.y[c][r * BS + lane] = out;
+    }
+  }
+}
+
 // The diagonal block of every row, copied: one thread per scalar.  BLOCK = false: out.col[0][r bs + i] = A[r][r][i][i]; BLOCK = true: column j of
 // the block goes to out.col[j][r bs + i] (the layout of IGXCompute*BlockDiagonal).  The block's position in the row comes from the per-axis
 // tables: on each axis the place of the row's own node among the row's sorted columns.

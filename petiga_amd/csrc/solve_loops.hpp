@@ -891,56 +891,40 @@ static int eig_rayleigh_ritz(int q, int m, int ld, const std::vector<double> &GA
   for (int j = 0; j < m; ++j) { theta[j] = E.lambda[j]; for (int i = 0; i < q; ++i) C[(size_t)i * m + j] = d[i] * E.U[(size_t)i + (size_t)q * j]; }
   return 0;
 }
-extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IGXVec X[], double lambda[], double resid[], IGXEigenInfo *info, double *history) {
-  const SolverWords &words = kEigenWords;
-  if (!g || !sp || !X || !lambda || !info) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: null pointer: the eigen solve takes the stiffness IGX, a specification, the block X, lambda and info");
-  auto range = [](const char *what) { return fail(IGX_ERR_ARG_OUTOFRANGE, std::string("IGXEigenSolve: the eigen solve's specification: ") + what); };
+// the specification's ranges and nx == block, under the caller's name
+static int eig_spec_refusal(const SolverWords &w, const IGXEigenSpec *sp, int nx) {
+  auto range = [&](const char *what) { return fail(IGX_ERR_ARG_OUTOFRANGE, std::string(w.call) + ": the eigen solve's specification: " + what); };
   if (sp->nev < 1) return range("nev must be 1 at the least");
   if (sp->block < sp->nev || sp->block > BV_EIG_MAX) return range("block must be in range [nev,16]");
   if (sp->pc < IGX_PC_NONE || sp->pc > IGX_PC_FASTDIAG) return range("unknown preconditioner");
   if (!(sp->rtol >= 0) || !(sp->atol >= 0)) return range("the tolerances must not be negative");
   if (sp->maxit < 0) return range("maxit must not be negative");
-  if (nx != sp->block) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve takes a start block of spec->block vectors, got " + std::to_string(nx));
-  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() on the stiffness IGX before IGXEigenSolve(): the eigen solve needs a set-up space");
-  if (mass && !mass->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() on the mass IGX before IGXEigenSolve(): the eigen solve needs a set-up space");
-  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() on the stiffness IGX first: the eigen solve has no operator A");
-  if (mass && mass->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() on the mass IGX first: the eigen solve has no operator B");
-  bool faces[3][2][MAXFD];
-  fast_diag_fixed_faces(g->s, faces);
-  if (mass) {
-    const Space &a = g->s, &b = mass->s;
-    auto differs = [](const std::string &what) { return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve needs the mass IGX on the space of the stiffness IGX: " + what + " differs"); };
-    if (a.dim != b.dim) return differs("dim");
-    if (a.dof != b.dof) return differs("dof");
-    for (int d = 0; d < a.dim; ++d) {
-      if (a.axis[d].p != b.axis[d].p) return differs("the degree of axis " + std::to_string(d));
-      if (a.axis[d].U != b.axis[d].U) return differs("the knot vector of axis " + std::to_string(d));
-      if (a.axis[d].periodic != b.axis[d].periodic) return differs("the periodicity of axis " + std::to_string(d));
-    }
-    bool fb[3][2][MAXFD];
-    fast_diag_fixed_faces(b, fb);
-    if (memcmp(faces, fb, sizeof(fb)) != 0) return differs("the set of Dirichlet faces per field");
-    if (g->stream != mass->stream) return differs("the stream (IGXSetStream)");
+  if (nx != sp->block) return fail(IGX_ERR_ARG_WRONG, std::string(w.call) + ": the eigen solve takes a start block of spec->block vectors, got " + std::to_string(nx));
+  return 0;
+}
+// the IGX of B on the space of the IGX of A (fa: A's Dirichlet faces per field): dim, dof, then per axis degree, knots, periodicity, then the
+// faces, then the stream; lead opens the refusal
+static int eig_same_space(const char *lead, IGX ga, IGX gb, const bool fa[3][2][MAXFD]) {
+  const Space &a = ga->s, &b = gb->s;
+  auto differs = [&](const std::string &what) { return fail(IGX_ERR_ARG_WRONG, lead + what + " differs"); };
+  if (a.dim != b.dim) return differs("dim");
+  if (a.dof != b.dof) return differs("dof");
+  for (int d = 0; d < a.dim; ++d) {
+    if (a.axis[d].p != b.axis[d].p) return differs("the degree of axis " + std::to_string(d));
+    if (a.axis[d].U != b.axis[d].U) return differs("the knot vector of axis " + std::to_string(d));
+    if (a.axis[d].periodic != b.axis[d].periodic) return differs("the periodicity of axis " + std::to_string(d));
   }
-  for (IGX h : {g, mass}) if (h) for (int d = 0; d < h->s.dim; ++d) if (h->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, words.one_rank);
-  for (IGX h : {g, mass}) if (h && h->fixtable.p) return fail(IGX_ERR_SUP, "IGXEigenSolve: the eigen solve does not cover a fix table (IGXSetFixTable): its fixed rows are not a union of faces");
-  const int m = sp->block, pc = sp->pc;
-  for (int j = 0; j < m; ++j) {
-    if (!X[j]) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a null vector");
-    if (X[j]->iga != g) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a vector created by another IGX than the stiffness IGX");
-    for (int k = 0; k < j; ++k) if (X[k] == X[j]) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a vector twice");
-  }
-  if (pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() on the stiffness IGX before IGXEigenSolve() with IGX_PC_FASTDIAG");
-  for (IGX h : {g, mass}) if (h) if (int rc = solver_runs_here(h, words)) return rc;
-  if (int rc = ensure_device(g)) return rc;
-  if (mass) if (int rc = ensure_device(mass)) return rc;
-  const long long n = (long long)g->nbrows * g->s.dof;
-  for (int j = 0; j < m; ++j) if (X[j]->n != n) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: vector of another size than the space's");
-  if (mass && (long long)mass->nbrows * mass->s.dof != n) return fail(IGX_ERR_PLIB, "IGXEigenSolve: the row boxes of the two IGX differ");
-  if (int rc = bv_state(g)) return rc;
-  const int dof = g->s.dof;
-  // work vectors, in blocks of m: X' ; AX AX' ; W AW ; P P' AP AP' ; with a preconditioner R ; with a mass BX BX' BW BP BP'
-  const int nblocks = 9 + (pc != IGX_PC_NONE ? 1 : 0) + (mass ? 5 : 0);
+  bool fb[3][2][MAXFD];
+  fast_diag_fixed_faces(b, fb);
+  if (memcmp(fa, fb, sizeof(fb)) != 0) return differs("the set of Dirichlet faces per field");
+  if (ga->stream != gb->stream) return differs("the stream (IGXSetStream)");
+  return 0;
+}
+// the eigen solve's work vectors on g for a block of m, in blocks of m: X' ; AX AX' ; W AW ; P P' AP AP' ; with a preconditioner R ; with a
+// mass BX BX' BW BP BP'.  Kept between calls, replaced when a figure differs (IGXEigenSolve and IGXMatEigenSolve share the store).
+typedef std::vector<IGXVec> EigBlock;
+static int eig_state(IGX g, int m, int pc, int dof, long long n, bool has_mass) {
+  const int nblocks = 9 + (pc != IGX_PC_NONE ? 1 : 0) + (has_mass ? 5 : 0);
   if (!g->eigen || g->eigen->m != m || g->eigen->pc != pc || g->eigen->dof != dof || g->eigen->n != n || g->eigen->nblocks != nblocks) {
     g->eigen.reset();
     std::shared_ptr<EigenState> es(new EigenState());
@@ -949,54 +933,31 @@ extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IG
     es->m = m; es->pc = pc; es->dof = dof; es->nblocks = nblocks;
     g->eigen = es;
   }
-  EigenState &st = *g->eigen;
+  return 0;
+}
+// The loop the header states for IGXEigenSolve, line by line, on whatever applies the operators: IGXEigenSolve (the matrix-free actions) and
+// IGXMatEigenSolve (the stored matrices) call it, as krylov_loop serves the Krylov solves.  The caller has checked its arguments, made the
+// state (eig_state, bv_state) and begun the clock; it names the solve and finishes the clock afterwards.
+//   act_block(in, aout, bout)   aout_j = A in_j and, with a mass, bout_j = B in_j for the block; it counts its launches on the clock
+//   prepare()                   what T needs before its first use (the diagonal, the inverted point blocks): after the start block's fixed
+//                               rows are zeroed and before the first action, the order the launches have always had
+//   T(in, out)                  out = T in for one column; never called with pc none
+//   faces                       the Dirichlet faces per field whose rows of the start block are zeroed (fast_diag_fixed_faces)
+template <class FA, class FP, class FT>
+static int eigen_loop(IGX g, EigenState &st, LoopClock &clk, const SolverWords &words, const IGXEigenSpec *sp, bool has_mass, const bool faces[3][2][MAXFD],
+                      FA &&act_block, FP &&prepare, FT &&T, IGXVec X[], double lambda[], double resid[], IGXEigenInfo *info, double *history, const int &actions) {
+  typedef EigBlock Block;
+  const int m = sp->block, pc = sp->pc, dof = g->s.dof;
+  const long long n = (long long)st.n;
   BlockVecState &bv = *g->blockvec;
-  typedef std::vector<IGXVec> Block;
   int next_block = 0;
   auto block = [&]() { Block b(m); for (int j = 0; j < m; ++j) b[j] = st.work[(size_t)next_block * m + j].get(); ++next_block; return b; };
   Block Xb[2] = {Block(X, X + m), block()}, AX[2] = {block(), block()}, W = block(), AW = block(), P[2] = {block(), block()}, AP[2] = {block(), block()};
   Block R = pc != IGX_PC_NONE ? block() : W;
   Block BX[2] = {Xb[0], Xb[1]}, BW = W, BP[2] = {P[0], P[1]};
-  if (mass) { BX[0] = block(); BX[1] = block(); BW = block(); BP[0] = block(); BP[1] = block(); }
-  LoopClock clk(g, st);
-  if (int rc = clk.begin(g)) return rc;
+  if (has_mass) { BX[0] = block(); BX[1] = block(); BW = block(); BP[0] = block(); BP[1] = block(); }
   g->slab_valid = 0;
-  std::string opname;
-  int actions = 0;
-  auto actA = [&](IGXVec in, IGXVec out) -> int {
-    if (int rc = compute_matfree(g, VsMode::ACTION, IGX_OP_MATRIX, nullptr, nullptr, 1, &in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
-    if (opname.empty()) opname = g->last_kernel;
-    ++actions;
-    return clk.driver(g);
-  };
-  auto actB = [&](IGXVec in, IGXVec out) -> int {      // the mass IGX's figures: its own launches and, where it is timed too, its own events
-    if (int rc = compute_matfree(mass, VsMode::ACTION, IGX_OP_MATRIX, nullptr, nullptr, 1, &in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
-    ++actions;
-    clk.launches += mass->last_launches;
-    if (clk.timing && mass->timing) { float ms = 0; HIPCK(hipEventSynchronize(mass->ev[2])); HIPCK(hipEventElapsedTime(&ms, mass->ev[1], mass->ev[2])); clk.op_ms += ms; }
-    return 0;
-  };
-  // IGXSetBatchedActions(stiff, 1): one call of the action on a block per operator (compute_matfree, ACTION_BATCH) in place of m single actions;
-  // the figures are taken as above, the block call's in place of the m calls'
-  static_assert(BV_EIG_MAX <= IGX_ACTION_MAXCOLS && ACTION_BLOCK_MAX == BV_MAX, "the eigen solve's block is one chunk of the block action; a block call takes a block vector");
-  auto act_block = [&](const Block &in, const Block &aout, const Block &bout) -> int {
-    if (g->batched_actions) {
-      if (int rc = compute_matfree(g, VsMode::ACTION_BATCH, IGX_OP_MATRIX, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), m, const_cast<IGXVec *>(aout.data()), 0.0, 0.0)) return solver_refused(words, rc);
-      if (opname.empty()) opname = g->last_kernel;
-      actions += m;
-      if (int rc = clk.driver(g)) return rc;
-      if (!mass) return 0;
-      if (int rc = compute_matfree(mass, VsMode::ACTION_BATCH, IGX_OP_MATRIX, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), m, const_cast<IGXVec *>(bout.data()), 0.0, 0.0)) return solver_refused(words, rc);
-      actions += m;
-      clk.launches += mass->last_launches;
-      if (clk.timing && mass->timing) { float ms = 0; HIPCK(hipEventSynchronize(mass->ev[2])); HIPCK(hipEventElapsedTime(&ms, mass->ev[1], mass->ev[2])); clk.op_ms += ms; }
-      return 0;
-    }
-    for (int j = 0; j < m; ++j) if (int rc = actA(in[j], aout[j])) return rc;
-    if (mass) for (int j = 0; j < m; ++j) if (int rc = actB(in[j], bout[j])) return rc;
-    return 0;
-  };
-  auto mdot = [&](Block &S, Block &T, std::vector<double> &G) -> int { clk.own(2); return bv_mdot_run(g, (int)S.size(), S.data(), (int)T.size(), T.data(), G.data()); };
+  auto mdot = [&](Block &S, Block &T_, std::vector<double> &G) -> int { clk.own(2); return bv_mdot_run(g, (int)S.size(), S.data(), (int)T_.size(), T_.data(), G.data()); };
   auto maxpy = [&](Block &Y, Block &S, const double *C) -> int { clk.own(1); return bv_maxpy_run(g, (int)Y.size(), Y.data(), (int)S.size(), S.data(), C, 0.0); };
   auto join = [](std::initializer_list<const Block *> parts) { Block b; for (const Block *p : parts) b.insert(b.end(), p->begin(), p->end()); return b; };
   // the fixed rows of the start block
@@ -1012,28 +973,14 @@ extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IG
       F.axis[F.nface] = d; F.at[F.nface] = sd ? F.n[d] - 1 : 0; F.mask[F.nface] = mask; ++F.nface;
       face_nodes = std::max(face_nodes, nodes / F.n[d]);
     }
-    if (nodes * dof != n) return fail(IGX_ERR_PLIB, "IGXEigenSolve: the eigen solve's vectors and the row box differ");
+    if (nodes * dof != n) return fail(IGX_ERR_PLIB, std::string(words.call) + ": the eigen solve's vectors and the row box differ");
     if (F.nface) for (int j = 0; j < m; ++j) {
       hipLaunchKernelGGL(mg_zero_fixed, dim3((unsigned)std::min<long long>(256, (face_nodes + MG_FACE_T - 1) / MG_FACE_T), (unsigned)F.nface), dim3(MG_FACE_T), 0, g->stream, X[j]->a.as<double>(), F);
       if (hipGetLastError() != hipSuccess) return fail(IGX_ERR_LIB, "mg_zero_fixed: kernel launch failed");
       clk.own(1);
     }
   }
-  // the preconditioner T of stiff: its diagonal, or its inverted point blocks
-  std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
-  if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
-    if (int rc = compute_matfree(g, pc == IGX_PC_JACOBI ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL, IGX_OP_MATRIX, nullptr, nullptr, 0, nullptr, (int)cols.size(), cols.data(), 0.0, 0.0)) return solver_refused(words, rc);
-    if (int rc = clk.driver(g)) return rc;
-  }
-  if (pc == IGX_PC_PBJACOBI) {
-    if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return solver_refused(words, rc);
-    if (int rc = clk.driver(g)) return rc;
-  }
-  auto T = [&](IGXVec in, IGXVec out) -> int {
-    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); clk.own(1); return 0; }
-    if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return solver_refused(words, rc);
-    return clk.driver(g);
-  };
+  if (int rc = prepare()) return rc;
   int c = 0, its = 0, reason = 0, restarts = 0, nconv = 0;
   bool haveP = false;
   std::vector<double> GA((size_t)9 * m * m), GB((size_t)9 * m * m), C, theta(m, 0.0), rec((size_t)2 * m, 0.0), rn(m, 0.0);
@@ -1046,7 +993,7 @@ extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IG
   else {
     if (int rc = maxpy(Xb[1], Xb[0], C.data())) return rc;
     if (int rc = maxpy(AX[1], AX[0], C.data())) return rc;
-    if (mass) if (int rc = maxpy(BX[1], BX[0], C.data())) return rc;
+    if (has_mass) if (int rc = maxpy(BX[1], BX[0], C.data())) return rc;
     c = 1;
   }
   while (!reason) {
@@ -1096,7 +1043,7 @@ extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IG
     if (int rc = maxpy(Xb[1 - c], XP, CX.data())) return rc;
     if (int rc = maxpy(AP[1 - c], AWP, CWP)) return rc;
     if (int rc = maxpy(AX[1 - c], AXP, CX.data())) return rc;
-    if (mass) {
+    if (has_mass) {
       if (int rc = maxpy(BP[1 - c], BWP, CWP)) return rc;
       if (int rc = maxpy(BX[1 - c], BXP, CX.data())) return rc;
     }
@@ -1107,6 +1054,95 @@ extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IG
   HIPCK(hipStreamSynchronize(g->stream));
   for (int j = 0; j < m; ++j) { lambda[j] = theta[j]; if (resid) resid[j] = rn[j]; }
   info->iterations = its; info->reason = reason; info->nconverged = nconv; info->restarts = restarts; info->actions = actions;
+  return 0;
+}
+extern "C" int IGXEigenSolve(IGX g, IGX mass, const IGXEigenSpec *sp, int nx, IGXVec X[], double lambda[], double resid[], IGXEigenInfo *info, double *history) {
+  const SolverWords &words = kEigenWords;
+  if (!g || !sp || !X || !lambda || !info) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: null pointer: the eigen solve takes the stiffness IGX, a specification, the block X, lambda and info");
+  if (int rc = eig_spec_refusal(words, sp, nx)) return rc;
+  if (!g->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() on the stiffness IGX before IGXEigenSolve(): the eigen solve needs a set-up space");
+  if (mass && !mass->s.setup) return fail(IGX_ERR_ORDER, "Must call IGXSetUp() on the mass IGX before IGXEigenSolve(): the eigen solve needs a set-up space");
+  if (g->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() on the stiffness IGX first: the eigen solve has no operator A");
+  if (mass && mass->s.form == IGX_FORM_NONE) return fail(IGX_ERR_ARG_WRONGSTATE, "Must call IGASetForm...() on the mass IGX first: the eigen solve has no operator B");
+  bool faces[3][2][MAXFD];
+  fast_diag_fixed_faces(g->s, faces);
+  if (mass) if (int rc = eig_same_space("IGXEigenSolve: the eigen solve needs the mass IGX on the space of the stiffness IGX: ", g, mass, faces)) return rc;
+  for (IGX h : {g, mass}) if (h) for (int d = 0; d < h->s.dim; ++d) if (h->s.proc_sizes[d] != 1) return fail(IGX_ERR_SUP, words.one_rank);
+  for (IGX h : {g, mass}) if (h && h->fixtable.p) return fail(IGX_ERR_SUP, "IGXEigenSolve: the eigen solve does not cover a fix table (IGXSetFixTable): its fixed rows are not a union of faces");
+  const int m = sp->block, pc = sp->pc;
+  for (int j = 0; j < m; ++j) {
+    if (!X[j]) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a null vector");
+    if (X[j]->iga != g) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a vector created by another IGX than the stiffness IGX");
+    for (int k = 0; k < j; ++k) if (X[k] == X[j]) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: the eigen solve's start block holds a vector twice");
+  }
+  if (pc == IGX_PC_FASTDIAG && !g->fd) return fail(IGX_ERR_ORDER, "Must call IGXFastDiagSetUp() on the stiffness IGX before IGXEigenSolve() with IGX_PC_FASTDIAG");
+  for (IGX h : {g, mass}) if (h) if (int rc = solver_runs_here(h, words)) return rc;
+  if (int rc = ensure_device(g)) return rc;
+  if (mass) if (int rc = ensure_device(mass)) return rc;
+  const long long n = (long long)g->nbrows * g->s.dof;
+  for (int j = 0; j < m; ++j) if (X[j]->n != n) return fail(IGX_ERR_ARG_WRONG, "IGXEigenSolve: vector of another size than the space's");
+  if (mass && (long long)mass->nbrows * mass->s.dof != n) return fail(IGX_ERR_PLIB, "IGXEigenSolve: the row boxes of the two IGX differ");
+  if (int rc = bv_state(g)) return rc;
+  const int dof = g->s.dof;
+  if (int rc = eig_state(g, m, pc, dof, n, mass != nullptr)) return rc;
+  EigenState &st = *g->eigen;
+  typedef EigBlock Block;
+  LoopClock clk(g, st);
+  if (int rc = clk.begin(g)) return rc;
+  std::string opname;
+  int actions = 0;
+  auto actA = [&](IGXVec in, IGXVec out) -> int {
+    if (int rc = compute_matfree(g, VsMode::ACTION, IGX_OP_MATRIX, nullptr, nullptr, 1, &in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
+    if (opname.empty()) opname = g->last_kernel;
+    ++actions;
+    return clk.driver(g);
+  };
+  auto actB = [&](IGXVec in, IGXVec out) -> int {      // the mass IGX's figures: its own launches and, where it is timed too, its own events
+    if (int rc = compute_matfree(mass, VsMode::ACTION, IGX_OP_MATRIX, nullptr, nullptr, 1, &in, 1, &out, 0.0, 0.0)) return solver_refused(words, rc);
+    ++actions;
+    clk.launches += mass->last_launches;
+    if (clk.timing && mass->timing) { float ms = 0; HIPCK(hipEventSynchronize(mass->ev[2])); HIPCK(hipEventElapsedTime(&ms, mass->ev[1], mass->ev[2])); clk.op_ms += ms; }
+    return 0;
+  };
+  // IGXSetBatchedActions(stiff, 1): one call of the action on a block per operator (compute_matfree, ACTION_BATCH) in place of m single actions;
+  // the figures are taken as above, the block call's in place of the m calls'
+  static_assert(BV_EIG_MAX <= IGX_ACTION_MAXCOLS && ACTION_BLOCK_MAX == BV_MAX, "the eigen solve's block is one chunk of the block action; a block call takes a block vector");
+  auto act_block = [&](const Block &in, const Block &aout, const Block &bout) -> int {
+    if (g->batched_actions) {
+      if (int rc = compute_matfree(g, VsMode::ACTION_BATCH, IGX_OP_MATRIX, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), m, const_cast<IGXVec *>(aout.data()), 0.0, 0.0)) return solver_refused(words, rc);
+      if (opname.empty()) opname = g->last_kernel;
+      actions += m;
+      if (int rc = clk.driver(g)) return rc;
+      if (!mass) return 0;
+      if (int rc = compute_matfree(mass, VsMode::ACTION_BATCH, IGX_OP_MATRIX, nullptr, nullptr, m, const_cast<IGXVec *>(in.data()), m, const_cast<IGXVec *>(bout.data()), 0.0, 0.0)) return solver_refused(words, rc);
+      actions += m;
+      clk.launches += mass->last_launches;
+      if (clk.timing && mass->timing) { float ms = 0; HIPCK(hipEventSynchronize(mass->ev[2])); HIPCK(hipEventElapsedTime(&ms, mass->ev[1], mass->ev[2])); clk.op_ms += ms; }
+      return 0;
+    }
+    for (int j = 0; j < m; ++j) if (int rc = actA(in[j], aout[j])) return rc;
+    if (mass) for (int j = 0; j < m; ++j) if (int rc = actB(in[j], bout[j])) return rc;
+    return 0;
+  };
+  // the preconditioner T of stiff: its diagonal, or its inverted point blocks
+  std::vector<IGXVec> cols; for (auto &v : st.pcv) cols.push_back(v.get());
+  auto prepare = [&]() -> int {
+    if (pc == IGX_PC_JACOBI || pc == IGX_PC_PBJACOBI) {
+      if (int rc = compute_matfree(g, pc == IGX_PC_JACOBI ? VsMode::DIAGONAL : VsMode::BLOCK_DIAGONAL, IGX_OP_MATRIX, nullptr, nullptr, 0, nullptr, (int)cols.size(), cols.data(), 0.0, 0.0)) return solver_refused(words, rc);
+      if (int rc = clk.driver(g)) return rc;
+    }
+    if (pc == IGX_PC_PBJACOBI) {
+      if (int rc = block_diagonal_run(g, dof, cols.data(), nullptr, nullptr, nullptr, true)) return solver_refused(words, rc);
+      if (int rc = clk.driver(g)) return rc;
+    }
+    return 0;
+  };
+  auto T = [&](IGXVec in, IGXVec out) -> int {
+    if (pc == IGX_PC_JACOBI) { KR_LAUNCH(kr_pdiv, kr_grid(n), KR_T, g, out->a.as<double>(), in->a.as<double>(), cols[0]->a.as<double>(), n); clk.own(1); return 0; }
+    if (int rc = pc == IGX_PC_PBJACOBI ? block_diagonal_run(g, dof, cols.data(), in, out, nullptr, false) : IGXFastDiagApply(g, in, out)) return solver_refused(words, rc);
+    return clk.driver(g);
+  };
+  if (int rc = eigen_loop(g, st, clk, words, sp, mass != nullptr, faces, act_block, prepare, T, X, lambda, resid, info, history, actions)) return rc;
   static const char *const pcs[4] = {"none", "jacobi", "pbjacobi", "fastdiag"};
-  return clk.finish(g, "eigen(lobpcg, block " + std::to_string(m) + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(its) + " iterations)");
+  return clk.finish(g, "eigen(lobpcg, block " + std::to_string(m) + ", pc=" + pcs[pc] + ", " + opname + ", " + std::to_string(info->iterations) + " iterations)");
 }
