@@ -1129,6 +1129,11 @@ int IGXGetClockProbe(IGX iga,double *shader_mhz,int64_t *elements);
  * t < min(*nitems, cap); order 0 is the natural order, 1 the faces first (IGX_PATCH3_ORDER). */
 int IGXPatch3TicketOrder(int n1,int n2,int nseg,int cx,int cy,int order,int cap,int *nitems,int *items,int *faces);
 
+/* The p = 3 rows walk's staged tile-layer, host side (no device is touched).  On a full layer of a regular tile of 3 x 3 node columns the
+ * nine finished rows are staged in a buffer of *doubles doubles in memory order before they are stored (IGX_ROWS3_STAGE); *offset is
+ * where the entry (node column col = 0 .. 8 of the tile, column offsets dy, dx, d = -3 .. 3 on axes 2, 1, 0) lies in it. */
+int IGXRows3StageOffset(int col,int dy,int dx,int d,int *offset,int *doubles);
+
 /* library / device info for logs */
 int IGXGetDeviceInfo(char *buf,int len);
 

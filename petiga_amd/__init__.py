@@ -222,6 +222,7 @@ def lib(build_if_needed=False):
         "IGXMatEigenSolve": [V, V, C.POINTER(IGXEigenSpec), C.c_int, C.POINTER(V), _dp, _dp, C.POINTER(IGXEigenInfo), _dp],
         "IGXGetDeviceInfo": [C.c_char_p, C.c_int], "IGXCreateFromTables": [V, C.POINTER(V)],
         "IGXPatch3TicketOrder": [C.c_int] * 7 + [_ip, _ip, _ip],
+        "IGXRows3StageOffset": [C.c_int] * 4 + [_ip, _ip],
     }
     missing = []
     for name, args in sig.items():
@@ -1143,3 +1144,11 @@ def patch3_ticket_order(n1, n2, nseg, cx, cy, order=1):
     items, faces = np.zeros(max(n.value, 1), dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.int32)
     _ck(lib().IGXPatch3TicketOrder(n1, n2, nseg, cx, cy, order, n.value, C.byref(n), items.ctypes.data_as(_ip), faces.ctypes.data_as(_ip)))
     return items[:n.value], faces[:n.value]
+
+
+def rows3_stage_offset(col, dy, dx, d):
+    """Where the entry (node column col of the tile, dy, dx, d) lies in the p = 3 rows walk's staged tile-layer, and the buffer's doubles,
+    from the function the kernel itself calls (host side, no device)."""
+    off, n = C.c_int(0), C.c_int(0)
+    _ck(lib().IGXRows3StageOffset(col, dy, dx, d, C.byref(off), C.byref(n)))
+    return off.value, n.value

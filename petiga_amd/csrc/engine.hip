@@ -1046,6 +1046,16 @@ extern "C" int IGXPatch3TicketOrder(int n1, int n2, int nseg, int cx, int cy, in
   return 0;
 }
 
+// the rows walk's staged tile-layer (gram_rows3.hpp): where the entry (node column col of the tile, dy, dx, d) lies in the buffer --
+// rows3_stage_offset, the function the kernel calls -- and the buffer's doubles
+extern "C" int IGXRows3StageOffset(int col, int dy, int dx, int d, int *offset, int *doubles) {
+  using R = Rows3;
+  if (!offset || col < 0 || col >= R::COLS || std::abs(dy) > R::P || std::abs(dx) > R::P || std::abs(d) > R::P) return fail(IGX_ERR_ARG_WRONG, "IGXRows3StageOffset: column, offsets or result");
+  *offset = rows3_stage_offset(col, dy, dx, d);
+  if (doubles) *doubles = R::STG;
+  return 0;
+}
+
 // ------------------------------------------------------------------ multi-GPU ghost rows (filled in by exchange.hpp)
 #include "exchange.hpp"
 #include "comm.hpp"

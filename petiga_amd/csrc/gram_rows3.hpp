@@ -19,6 +19,13 @@
 // and the seven wavefronts the row's 343.  Placed round-robin, the wavefronts load every SIMD with four pencil-rows.  Wavefront 7 owns
 // the F rows of the nine columns and gathers the liftings of the Dirichlet rows.
 //
+// Staged stores (round 14, Rows3Args::stage): on a FULL layer (seven band positions on the walk axis) of a REGULAR tile (every node column
+// at least three nodes from both ends of axes 1 and 2) a column's row is 343 consecutive doubles in the order (dy, dx, d) and the next
+// layer's row follows it directly.  There the run lanes write their finished runs to one of two LDS buffers in memory order, and after one
+// barrier all eight wavefronts copy the nine rows out, consecutive lanes storing consecutive doubles: a store instruction covers 512
+// contiguous bytes of a row where a run lane's covers 63 pieces at a 56-byte stride.  Same values from the same adder; every other layer
+// and tile keeps the per-run stores.
+//
 // Degree 3, identity geometry, one rank, no wrapped axis, one new node per element on every axis; System and Matrix drivers,
 // Dirichlet values on any face.  Boundary loads: the per-face launch that runs first (F is added to).
 #pragma once
@@ -30,8 +37,18 @@ struct Rows3 {
   static constexpr int P = 3, BW = 7, TX = 3, TY = 3, COLS = TX * TY, RUNW = BW, W = RUNW + 1, NTHR = W * 64;
   static constexpr int ES = TX + P;            // elements of an axis that hold a node of the tile (TX = TY)
   static constexpr int RUNS = BW * BW;         // runs of a row
+  static constexpr int ROW = RUNS * BW;        // entries of a full row of a regular tile
+  static constexpr int STG = COLS * ROW;       // doubles of a staged tile-layer
+  static constexpr int NCOPY = (STG + NTHR - 1) / NTHR;      // doubles a thread copies per staged layer
   static_assert(COLS * BW <= 64 && TX == TY, "a wavefront holds the runs (column, dx) of one dy");
+  static_assert((NCOPY - 1) * NTHR <= STG, "only a thread's last copy can lie beyond the buffer");
 };
+// where the entry (node column col of the tile, dy, dx, d) of a full layer of a regular tile lies in the staged tile-layer: the column's
+// row, in memory order -- RC 7 + P0[d] of patch_run_address and the layer table
+__host__ __device__ static inline int rows3_stage_offset(int col, int dy, int dx, int d) {
+  using R = Rows3;
+  return col * R::ROW + ((dy + R::P) * R::BW + dx + R::P) * R::BW + d + R::P;
+}
 
 struct Rows3Args {
   double forcing;
@@ -40,14 +57,16 @@ struct Rows3Args {
   int ntx, nty;              // tiles of node columns
   int seg_len, nseg;         // node layers per segment, segments: item = tile * nseg + segment (a column's rows follow each other in memory)
   int *counter;              // the assembly's ticket counter (null: one workgroup per item)
+  int stage;                 // full layers of regular tiles leave through LDS as contiguous spans (the launch's LDS holds the buffers)
 };
 
 // LDS: G [seg_len + 3 elements][4 ta][4 tb][2], wq [seg_len + 3][4], X and Y [ES][2][16], the F factors of axes 1, 2, the liftings of a layer's
-// runs, the layer table, the ticket
-__host__ __device__ static inline size_t rows3_lds_bytes(int seg_len) {
+// runs, the two buffers of a staged tile-layer (stage only), the nine column bases, a layer's prefix where it is full, the layer table,
+// the ticket
+__host__ __device__ static inline size_t rows3_lds_bytes(int seg_len, bool stage) {
   using R = Rows3;
-  const size_t doubles = (size_t)(seg_len + 3) * 36 + 2 * R::ES * 32 + 2 * R::ES * 4 + 2 * 8 + ((R::COLS * R::RUNS + 7) & ~7);
-  return doubles * 8 + (size_t)seg_len * 8 + (size_t)seg_len * 4 * 10 + 64;
+  const size_t doubles = (size_t)(seg_len + 3) * 36 + 2 * R::ES * 32 + 2 * R::ES * 4 + 2 * 8 + ((R::COLS * R::RUNS + 7) & ~7) + (stage ? 2 * ((R::STG + 1) & ~1) : 0);
+  return doubles * 8 + (size_t)(R::COLS + 1) * 8 + (size_t)seg_len * 8 + (size_t)seg_len * 8 + (size_t)seg_len * 4 * 10 + 64;
 }
 
 // elements that hold node n of an axis of nel elements
@@ -63,9 +82,12 @@ gram_pencil_rows3(SpaceDev S, OutDev out, Rows3Args A) {
   const int sl = A.seg_len, net = sl + 3, nitems = A.ntx * A.nty * A.nseg;
   double *G = pencil_sm, *wq = G + net * 32, *Xt = wq + net * 4, *Yt = Xt + ES * 32, *sxl = Yt + ES * 32, *syl = sxl + ES * 4, *Jxl = syl + ES * 4, *Jyl = Jxl + 8;
   double *corr = Jyl + 8;      // [column][dy][dx]: the lifting sum_k K_ik v_k of the run's row over its fixed columns
+  double *stg = corr + ((R::COLS * R::RUNS + 7) & ~7);      // [2][column][dy][dx][d]: the finished rows of a staged tile-layer, in memory order
+  long long *colbase = reinterpret_cast<long long *>(stg + (A.stage ? 2 * ((R::STG + 1) & ~1) : 0));      // a regular tile's columns: where the row of prefix 0 begins
+  long long *lrow = colbase + R::COLS + 1;      // the layer's prefix where it is full (T.cnt = 7, band positions 0 .. 6), else -1: all a layer's stores ask
   PencilLds T;
   T.zt = G; T.wq = wq; T.Jz = nullptr;
-  T.pre = reinterpret_cast<long long *>(corr + ((R::COLS * R::RUNS + 7) & ~7));
+  T.pre = lrow + sl;
   T.cnt = reinterpret_cast<int *>(T.pre + sl); T.rho = T.cnt + sl; T.P = T.rho + sl;
   int *tick = T.P + sl * 8;
 
@@ -86,6 +108,8 @@ gram_pencil_rows3(SpaceDev S, OutDev out, Rows3Args A) {
   const int ty = tile / A.ntx, tx = tile - ty * A.ntx;
   const int ax0 = tx * R::TX, ay0 = ty * R::TY;
   const int l_lo = seg * sl, nlay = min(l_lo + sl, A.nl0) - l_lo;      // the segment's node layers [l_lo, l_lo + nlay), counted from the axis' first
+  // (workgroup-uniform) a regular tile: each of its rows has 7 x 7 column pairs on axes 1, 2
+  const bool regular = A.stage && ax0 >= P && ax0 + R::TX - 1 <= A.nnx - 1 - P && ay0 >= P && ay0 + R::TY - 1 <= A.nny - 1 - P;
 
   {   // ---- the tables of the item.  Element slot i of G and wq is element l_lo - 3 + i of the walk axis, slot i of the others element
       // ax0 - 3 + i (ay0 - 3 + i); an element outside the mesh leaves zeroes: the loops below have no branches
@@ -110,6 +134,12 @@ gram_pencil_rows3(SpaceDev S, OutDev out, Rows3Args A) {
     }
     T.lay0 = AW.off[0] + l_lo;
     patch_stage_layers<BW>(T, AW, nlay, tid, NTHR);
+    for (int i = tid; i < nlay; i += NTHR) lrow[i] = (T.cnt[i] == BW && patch_layer_full<BW>(T.P + i * 8)) ? T.pre[i] : -1;      // (the thread that staged the layer)
+    if (regular && tid < R::COLS) {
+      long long ca = 0; int cb = 0, cc = 0;
+      patch_run_address<P>(S, 0, 0, ax0 + tid % R::TX, -P, ay0 + tid / R::TX, -P, ca, cb, cc);
+      colbase[tid] = ca + (long long)cc * BW;
+    }
     for (int i = tid; i < 2 * ES * 32; i += NTHR) {      // X, then Y: [slot][k][ia][ib]
       const bool isy = i >= ES * 32;
       const int j = isy ? i - ES * 32 : i, slot = j >> 5, k = (j >> 4) & 1, ia = (j >> 2) & 3, ib = j & 3;
@@ -153,6 +183,16 @@ gram_pencil_rows3(SpaceDev S, OutDev out, Rows3Args A) {
   if (active) active = AX.P[(AX.off[0] + ax) * BW + dxi] >= 0 && AY.P[(AY.off[0] + ay) * BW + dy + P] >= 0;      // (the column node lies inside the mesh)
   long long RA = 0; int RB = 0, RC = 0;
   if (active) patch_run_address<P>(S, 0, 0, ax, dx, ay, dy, RA, RB, RC);
+  const long long RA7 = RA + (long long)RC * BW;      // ... on a full layer: pos = RA7 + RB prefix0(layer) + d
+  // what this thread copies of a staged tile-layer: doubles tid + k NTHR of the buffer, to their places in the rows of prefix 0
+  double *cdst[R::NCOPY];
+#pragma unroll
+  for (int k = 0; k < R::NCOPY; ++k) {
+    const int i = min(tid + k * NTHR, R::STG - 1), c = i / R::ROW;
+    cdst[k] = regular ? out.val + colbase[c] + (i - c * R::ROW) : nullptr;
+  }
+  const int sgo = rows3_stage_offset(col, dy, dx, -P);
+  int sb = 0;      // the buffer of the next staged layer: two, so one barrier per layer is enough
   // its planes: pencil (ja, ia) is the element (ay - ja, ax - ia); jj counts the wavefront's 4 - |dy| pencils in y from ja_lo
   const int ja_lo = max(0, -dy), nj = runw ? NB - abs(dy) : 0;
   double mw[NB][NB], mxy[NB][NB];
@@ -201,6 +241,8 @@ gram_pencil_rows3(SpaceDev S, OutDev out, Rows3Args A) {
     const int lay = T.lay0 + li;
     // (workgroup-uniform: the rows of this layer of the tile that the fix-up can reach)
     const bool bcl = SYSTEM && fx.any && (tile_reach || (lay >= fx.wlo - P && lay <= fx.wlo + P) || (lay >= fx.whi - P && lay <= fx.whi + P));
+    const long long lr = lrow[li];
+    const bool staged = regular && lr >= 0;      // (workgroup-uniform)
     if (runw) {
       // the Gram sums of the four elements L - ta that hold the layer: slot li + 3 - ta
       double g0[NB][NB], g1[NB][NB];
@@ -238,11 +280,28 @@ gram_pencil_rows3(SpaceDev S, OutDev out, Rows3Args A) {
           if (lane < R::COLS * BW) corr[col * R::RUNS + (dy + P) * BW + dxi] = c;
         }
       }
-      if (active && T.cnt[li] > 0) {
+      const double zero[BW] = {0, 0, 0, 0, 0, 0, 0};
+      if (staged) {
+        if (lane < R::COLS * BW) {      // (a regular tile: every run is active)
+          double *sg = stg + sb * ((R::STG + 1) & ~1) + sgo;
+#pragma unroll
+          for (int d = 0; d < BW; ++d) sg[d] = zero[d] + v[d];
+        }
+      } else if (active && lr >= 0) {
+        patch_run_add_store<BW>(out.val, RA7 + (long long)RB * lr, T.P + li * 8, true, zero, v);
+      } else if (active && T.cnt[li] > 0) {
         const int *p0 = T.P + li * 8;
-        const double zero[BW] = {0, 0, 0, 0, 0, 0, 0};
         patch_run_add_store<BW>(out.val, RA + (long long)RB * T.pre[li] + (long long)RC * T.cnt[li], p0, patch_layer_full<BW>(p0), zero, v);
       }
+    }
+    if (staged) {
+      __syncthreads();      // the tile-layer is staged; the other buffer's readers passed the barrier of the layer before
+      const double *src = stg + sb * ((R::STG + 1) & ~1);
+      const long long adv = (long long)R::RUNS * lr;
+#pragma unroll
+      for (int k = 0; k < R::NCOPY; ++k)
+        if (k + 1 < R::NCOPY || tid + k * NTHR < R::STG) cdst[k][adv] = src[tid + k * NTHR];
+      sb ^= 1;
     }
     if constexpr (SYSTEM) {
       if (bcl) __syncthreads();      // the liftings of the layer's runs are staged

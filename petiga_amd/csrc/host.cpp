@@ -40,6 +40,7 @@ EnvSwitches read_env_switches() {
   e.patch3_order = num("IGX_PATCH3_ORDER", 1) != 0;
   e.rows3 = num("IGX_ROWS3", 1); if (e.rows3 < 0 || e.rows3 > 2) e.rows3 = 1;
   e.rows3_grid = std::max(0, std::min(num("IGX_ROWS3_GRID", 0), 1 << 16));
+  e.rows3_stage = num("IGX_ROWS3_STAGE", 1); if (e.rows3_stage < 0 || e.rows3_stage > 2) e.rows3_stage = 1;
   e.small_wpb = num("IGX_SMALL_WPB", 1);
   e.matmult_index = num("IGX_MATMULT_INDEX", -1); if (e.matmult_index < 0 || e.matmult_index > 1) e.matmult_index = -1;
   e.band_prio = num("IGX_BAND_PRIO", 0); e.band_rmw_prio = num("IGX_BAND_RMW_PRIO", 0);

@@ -57,6 +57,8 @@ struct EnvSwitches {
   int rows3 = 1;             // IGX_ROWS3: the p = 3 Gram matrix gathered by rows, each entry stored once (gram_rows3.hpp, round 13) -- 0 never, 1 where it pays
                              // (default), 2 wherever it covers the configuration.  Chosen under IGX_PATCH3=1 only: IGX_PATCH3=0 is the pencil walk, 2 the patch walk
   int rows3_grid = 0;        // IGX_ROWS3_GRID=n: the rows walk is a ticket launch of n workgroups (test and experiment knob); 0: as many as the device holds
+  int rows3_stage = 1;       // IGX_ROWS3_STAGE: the rows walk's full layers of regular tiles leave through LDS as contiguous spans (round 14) -- 0 never (a run
+                             // lane stores its run), 1 where it pays (default), 2 wherever the rows walk runs
   int patch_state = 0;       // IGX_PATCH_STATE=1: the Tangent of a p = 2 state form walks patches of 4 x 2 pencils (state_patch_p2) instead of state_pencil_k
   int fuse_resid = 0;        // IGX_FUSE_RESID=1: IGXComputeIFunctionIJacobian takes the fused walk (state_pencil_kr) where it exists; default: the two
                              // drivers one after the other -- measured in round 6: the fused launch costs 2.5 ms more than the Tangent's, the

@@ -429,6 +429,16 @@ constexpr long long ROWS3_MIN_ELEMENTS = 48LL * 48 * 48;
 static bool rows3_pays(const Space &s) {
   return (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] >= ROWS3_MIN_ELEMENTS;
 }
+// ... and where its full layers of regular tiles are staged in LDS and stored as contiguous spans (IGX_ROWS3_STAGE=1; 2: wherever the
+// walk runs, 0: nowhere).  Never where the mesh has nothing to stage: a regular tile needs six elements on axes 1 and 2, a full layer four
+// on axis 0.  The default: from the smallest measured cube at which staging was faster in both alternated pairs
+// (profiles/r14_rows3_stores.txt: slower at 48^3 and 64^3, one pair each way at 96^3, 4-5 % faster at 128^3, 13 % at 256^3).  Only cubes
+// were measured; the count of elements stands in for them, and a slab or a bar of as many elements was not.
+constexpr long long ROWS3_STAGE_MIN_ELEMENTS = 128LL * 128 * 128;
+static bool rows3_stages(const Space &s) {
+  if (s.env.rows3_stage == 0 || s.elem_width[0] < 4 || s.elem_width[1] < 6 || s.elem_width[2] < 6) return false;
+  return s.env.rows3_stage == 2 || (long long)s.elem_width[0] * s.elem_width[1] * s.elem_width[2] >= ROWS3_STAGE_MIN_ELEMENTS;
+}
 // Segments of node layers: as long as possible (an item stages its tables and forms its planes once: about two layers' worth of
 // time), at most ROWS3_SEG_MAX layers, and shorter down to eight layers while the items are fewer than two per resident workgroup.
 // IGX_NSEG forces the count (down to one layer per segment).
@@ -452,9 +462,11 @@ static void launch_rows3(const Space &s, const SpaceDev &S, const OutDev &out, h
   A.nl0 = A.nel0 + 3; A.nnx = A.nelx + 3; A.nny = A.nely + 3;
   A.ntx = (A.nnx + R::TX - 1) / R::TX; A.nty = (A.nny + R::TY - 1) / R::TY;
   const long long tiles = (long long)A.ntx * A.nty;
-  const long long resident = patch3_resident(reinterpret_cast<const void *>(kern_t), R::NTHR, rows3_lds_bytes(ROWS3_SEG_MAX));
+  A.stage = rows3_stages(s) ? 1 : 0;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern_t), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows3_lds_bytes(ROWS3_SEG_MAX, A.stage != 0));
+  const long long resident = patch3_resident(reinterpret_cast<const void *>(kern_t), R::NTHR, rows3_lds_bytes(ROWS3_SEG_MAX, A.stage != 0));
   rows3_segments(s, A.nl0, tiles, resident, A.seg_len, A.nseg);
-  const size_t lds = rows3_lds_bytes(A.seg_len);
+  const size_t lds = rows3_lds_bytes(A.seg_len, A.stage != 0);
   const long long items = tiles * A.nseg;
   if (lds > LDS_MAX || items > INT_MAX) { pencil_launch_error() = "the p = 3 rows walk's items or tables are beyond the launch's limits"; return; }
   unsigned grid = (unsigned)items;
@@ -577,6 +589,7 @@ static WalkPasses assembly_passes(const Space &s, const PencilWalk &pw, const Bo
 struct WalkInfo {
   enum Kind { PATCH_P2, PATCH_P3, ROWS_P3, STATE_PATCH_P2, ELEMENTS, PENCILS } kind;
   int deg = 3, walk_axis = 0; bool geo = false, fixt = false; const PencilModule *mod = nullptr;
+  bool staged = false;      // ROWS_P3: full layers of regular tiles leave through LDS (rows3_stages)
   bool state() const { return mod && mod->state; }
 };
 static std::string walk_dom_name(const WalkInfo &w) {
@@ -612,7 +625,7 @@ static std::string walk_kname(const Space &s, const WalkInfo &w) {
   switch (w.kind) {
   case WalkInfo::PATCH_P2: return "gram_patch(mfma_f64_16x16x4,p=2,walk=0,packed tiles,4x3 pencils per workgroup,one window)";
   case WalkInfo::PATCH_P3: return "gram_pencil(mfma_f64_16x16x4,p=3,walk=0," + std::to_string(PATCH3_MX) + "x" + std::to_string(PATCH3_MY) + " pencils per workgroup,one window)";
-  case WalkInfo::ROWS_P3: return "gram_pencil(fp64 fma,p=3,walk=0,rows gathered by their owner,each entry stored once)";
+  case WalkInfo::ROWS_P3: return "gram_pencil(fp64 fma,p=3,walk=0,rows gathered by their owner,each entry stored once" + std::string(w.staged ? ",full rows staged in LDS" : "") + ")";
   case WalkInfo::STATE_PATCH_P2: return "state_patch<" + w.mod->name + ">(mfma_f64_16x16x4,p=2,walk=0,packed tiles,4x2 pencils per workgroup,one window)";
   case WalkInfo::ELEMENTS: return "gram_p3_element(mfma_f64_16x16x4)";
   default: break;
@@ -699,7 +712,7 @@ static int try_gram_mfma(const Space &s, const SpaceDev &S, const OutDev &out, h
   WalkInfo info; info.deg = deg; info.walk_axis = walk_axis; info.geo = geo; info.fixt = fixt; info.mod = mod;
   auto gram_patch_ok = [&] { return patch_ok; };
   if (rows3) {
-    info.kind = WalkInfo::ROWS_P3;
+    info.kind = WalkInfo::ROWS_P3; info.staged = rows3_stages(s);
     return run_patch_walk(s, stream, info, "gram_pencil_rows3 kernel launch failed", [&] { launch_rows3(s, S, out, stream, launches, ga.forcing, patch3_counters); }, kname, launches, err, done, dom);
   }
   // (round 6: IGX_PATCH=1) p = 2 on the identity geometry, one rank: the walk of 4 x 3 patches of pencils whose band rows leave through the whole
